@@ -2,6 +2,7 @@
 """Benchmark of the hot path: images/s of the TT-small forward on MI355X.
 
     python bench.py [--gpus N --steps K --warmup W] [--batch B] [--variant small|xsmall|full|valexnet]
+                    [--dump-outputs DIR] [--full]
 
 A step is one forward of ``--batch`` (default 256, BASELINE.json configs[1]) synthetic
 224x224 images per GPU, already resident in HBM, plus -- for N > 1 -- the all-gather of the
@@ -9,7 +10,14 @@ logits (RCCL).  One process per GPU, batch sharded by image, weak scaling (per-G
 ``--gpus N`` with N > 1 works both under ``torch.distributed.run`` (RANK / WORLD_SIZE in the
 environment) and as a plain ``python bench.py --gpus N``: in the second case this process -- before
 it touches the GPU -- starts the N ranks itself (scale_imagenet_amd/launch.py) and relays rank 0's
-line.  Rank 0 prints ONE JSON line with the driver's contract fields plus
+line.
+
+A plain run sets up, warms up (W steps, then WARM_UP_S more), times exactly K steps (one window,
+unless --windows asks for more) and prints ONE JSON line on rank 0 with the contract fields (metric,
+value, unit, higher_is_better, dtype, ms_per_step = the milliseconds of one timed step).  ``--dump-outputs DIR`` then also writes
+the logits of the last timed step as DIR/logits.npy (float32; the inputs are the same synthetic
+images on every run).  ``--full`` adds everything else, as the line always carried it: the median
+of 3 windows of K steps (9 when K <= 50), the serial pass, and
 
   roofline          the dominant kernel by device time: algorithmic flops (or bytes) per
                     launch / its average launch duration, measured with HIP events on the
@@ -42,6 +50,8 @@ F32_PEAK_TFLOPS = 157.3      # fp32 matrix == fp32 vector peak; exact-f32 MFMA
 F16_PEAK_TFLOPS = 2500.0     # dense fp16/bf16 MFMA; stem and lin1 issue 3 fp16 products per f32 product (fp16 x 2 split)
 F64_PEAK_TFLOPS = 78.6       # AMD's MI355X datasheet figure for FP64 (vector = matrix); the guide lists none
 
+WARM_UP_S = 0.5              # least device-busy time between the W warm-up steps and the first timed window (see timed)
+
 # algorithmic work per image of TT-small; MACs -> 2 flops
 GATE_BYTES_PER_IMAGE, GATE_TABLE_BYTES = 74_592, 14_155_776
 
@@ -54,7 +64,7 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=None, help="images per GPU per step (default: the variant's BASELINE batch)")
     ap.add_argument("--inflight", type=int, default=2,
                     help="batches kept in flight (model lanes on separate HIP streams, as evaluate.py runs the "
-                         "eval loop); 1 = one batch at a time. The serial figure is reported alongside.")
+                         "eval loop); 1 = one batch at a time. With --full the serial figure is reported alongside.")
     ap.add_argument("--input", default="f32", choices=["f32", "u8"],
                     help="f32 = the reference's contract (normalised float32 NCHW, the headline); u8 = uint8 HWC images "
                          "with ToTensor + Normalize fused into the stem (SURVEY 8f N1)")
@@ -63,11 +73,18 @@ def parse_args(argv=None):
                          "float32 at batch 256, more than the 256 MiB Infinity Cache, so the stem's input stream really "
                          "comes from HBM; 1 = the same buffer every step)")
     ap.add_argument("--windows", type=int, default=0,
-                    help="timed windows of --steps steps each (0 = 9 when --steps <= 50 -- a 20-step window is 3 ms, and the clock is still "
-                         "settling during the first ones --, else 3); value = the median window, min / max beside it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="timed windows of --steps steps each (0 = one window in a plain run; with --full 9 when --steps <= 50 -- a "
+                         "20-step window is 3 ms, and the clock is still settling during the first ones --, else 3); value = the "
+                         "median window, min / max beside it")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: serial pass, per-kernel rooflines (a second "
+                         "pass with HIP events), B = 2048 gate path, uint8 leg, golden-image parity, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the logits of the last timed step as DIR/logits.npy (float32, at most 64 MB: a fixed "
+                         "sample of rows beyond that, their indices in DIR/logits_rows.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the B = 2048 gate-path pass and the golden-image parity check (profiling runs)")
+                    help="--full without the B = 2048 gate-path pass and the golden-image parity check (profiling runs)")
     ap.add_argument("--verify-gather", action="store_true",
                     help="N > 1: rank 0 also runs every rank's shard itself and requires the gathered logits to be identical")
     ap.add_argument("--variant", default="small", choices=["small", "xsmall", "full", "valexnet"],
@@ -317,7 +334,7 @@ def main():
            "full": ttnet.TT_vf_19lv3_imgnet, "valexnet": ttnet.TT_FHE_XSMALL_vAlexnet}[args.variant]
     model = cls(Namespace(layers=1, groups=[1, None, 4, None], **vargs))
     model.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in st.items()}, strict=True)
-    extras = args.variant == "small" and world == 1 and not args.no_extras
+    extras = args.full and args.variant == "small" and world == 1 and not args.no_extras
     model = model.to(dev).eval().reserve(max(B, 2048) if extras else B)
 
     n_total = B * world
@@ -362,36 +379,54 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    n_windows = args.windows if args.windows > 0 else (9 if args.steps <= 50 else 3)
+    n_windows = args.windows if args.windows > 0 else ((9 if args.steps <= 50 else 3) if args.full else 1)
+
+    def all_ranks_max(v: float) -> float:
+        if world == 1:
+            return v
+        t = torch.tensor([v], device="cpu" if dist.get_backend() == "gloo" else dev, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        return float(t.item())
 
     def timed(lanes):
-        """W untimed warm-up steps, then n_windows windows of EXACTLY K steps, each bracketed by a barrier +
-        device synchronisation on both sides, MAX over ranks; returns the windows' times."""
-        for i in range(max(args.warmup, 3 * lanes * (NX if lanes > 1 else 1))):     # (3 calls per lane: two plain, then the graph capture)
+        """W untimed warm-up steps (at least 3 per lane and input buffer), then more for WARM_UP_S, then n_windows
+        windows of EXACTLY K steps, each bracketed by a barrier +
+        device synchronisation on both sides, MAX over ranks; returns the windows' times and the output of the
+        last step (complete: the window's closing fence waited for it)."""
+        chunk = 3 * lanes * (NX if lanes > 1 else 1)            # (3 calls per lane: two plain, then the graph capture)
+        for i in range(max(args.warmup, chunk)):
             step(i, lanes)
+        # then chunks until the device has been busy for WARM_UP_S: a first window on a chip that sat idle through the
+        # set-up also times its clock ramp (~20 % of a 20-step window).  Every rank runs the same number of chunks.
+        fence()
+        t0 = time.perf_counter()
+        while all_ranks_max(WARM_UP_S - (time.perf_counter() - t0)) > 0:
+            for i in range(chunk):
+                step(i, lanes)
+            fence()
         els = []
+        y = None
         for _ in range(n_windows):
             fence()
             t0 = time.perf_counter()
             for i in range(args.steps):
-                step(i, lanes)
+                y = step(i, lanes)
             fence()
-            el = time.perf_counter() - t0
-            if world > 1:
-                gloo = dist.get_backend() == "gloo"
-                t = torch.tensor([el], device="cpu" if gloo else dev, dtype=torch.float64)
-                dist.all_reduce(t, op=dist.ReduceOp.MAX)
-                el = float(t.item())
-            els.append(el)
-        return els
+            els.append(all_ranks_max(time.perf_counter() - t0))
+        return els, y
 
     def median(v):
         v = sorted(v)
         return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
 
-    serial_windows = timed(1)
-    windows = timed(R) if R > 1 else serial_windows
-    elapsed_serial, elapsed = median(serial_windows), median(windows)
+    # --full keeps the order it always had: the serial pass first, then the headline configuration
+    serial_windows = timed(1)[0] if args.full and R > 1 else None
+    windows, y_last = timed(R)
+    elapsed = median(windows)
+    elapsed_serial = median(serial_windows) if serial_windows else elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, y_last)
+    del y_last
 
     gather_ok = None
     if world > 1 and args.verify_gather:
@@ -420,12 +455,12 @@ def main():
         return {k: v / steps for k, v in acc.items()}
 
     prof_steps = min(args.steps, 30)
-    avg_ms = profile(x, prof_steps)
+    avg_ms = profile(x, prof_steps) if args.full else None
     # With two or more lanes the plan runs its float32 stem on 128 of the 256 CUs (csrc/stem.hip: the other batch's kernels use the
     # rest).  The per-kernel figures of the roofline are one forward at a time on the whole chip, as in every earlier round: a twin
     # model with a single lane; the stem's time in the in-flight configuration is kept beside them.
     stem_ms_lanes = None
-    if R > 1 and args.variant in ("small", "xsmall") and args.input == "f32":
+    if args.full and R > 1 and args.variant in ("small", "xsmall") and args.input == "f32":
         stem_ms_lanes = avg_ms.get("stem")
         twin = cls(Namespace(layers=1, groups=[1, None, 4, None], **vargs))
         twin.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in st.items()}, strict=True)
@@ -440,19 +475,30 @@ def main():
         del twin
 
     if rank == 0:
-        models = kernel_models(args.variant, spec, B)
-        traffic, traffic_src = measured_traffic(args.variant, B)
-        kernels = roofline_records(avg_ms, models, traffic, 2.0 if args.input == "u8" else 3.0)
-        gate = gate_path_record(avg_ms, B) if args.variant == "small" else None
-        dom = max(kernels, key=lambda r: r["ms"])
-        roofline = {k: dom[k] for k in dom if k not in ("kernel", "ms")}
-        roofline["kernel"] = dom["kernel"]
-        roofline["ms"] = dom["ms"]
-        if stem_ms_lanes is not None:
-            roofline["note"] = ("kernel times: one forward at a time on the whole chip (a single-lane twin of the model); in the timed "
-                                "configuration (two batches in flight) the stem runs on 128 of the 256 CUs while the other batch's "
-                                "kernels use the rest: see stem_ms_128_cus")
-            roofline["stem_ms_128_cus"] = round(stem_ms_lanes, 5)
+        full_fields, gate = {}, None
+        if args.full:
+            models = kernel_models(args.variant, spec, B)
+            traffic, traffic_src = measured_traffic(args.variant, B)
+            kernels = roofline_records(avg_ms, models, traffic, 2.0 if args.input == "u8" else 3.0)
+            gate = gate_path_record(avg_ms, B) if args.variant == "small" else None
+            dom = max(kernels, key=lambda r: r["ms"])
+            roofline = {k: dom[k] for k in dom if k not in ("kernel", "ms")}
+            roofline["kernel"] = dom["kernel"]
+            roofline["ms"] = dom["ms"]
+            if stem_ms_lanes is not None:
+                roofline["note"] = ("kernel times: one forward at a time on the whole chip (a single-lane twin of the model); in the timed "
+                                    "configuration (two batches in flight) the stem runs on 128 of the 256 CUs while the other batch's "
+                                    "kernels use the rest: see stem_ms_128_cus")
+                roofline["stem_ms_128_cus"] = round(stem_ms_lanes, 5)
+            full_fields = {
+                "serial": {"value": round(n_total * args.steps / elapsed_serial, 2),
+                           "ms_per_step": round(1e3 * elapsed_serial / args.steps, 4),
+                           "note": "the same K steps with one batch in flight (every step waits for the previous one), on the same plan: with lanes >= 2 its float32 stem runs on 128 CUs, which costs a forward that runs alone ~4 %"},
+                "roofline": roofline,
+                "roofline_kernels": kernels + ([gate] if gate else []),
+                "traffic_source": traffic_src,
+                "kernel_ms_sum": round(sum(avg_ms.values()), 5),
+            }
         metric = {"small": "images/sec ImageNet 224x224, TT-small, MI355X; top-1 exact-match",
                   "xsmall": "images/sec ImageNet 224x224, TT-xsmall, MI355X; top-1 exact-match",
                   "full": "images/sec ImageNet 224x224, TT-full (p=60), MI355X; top-1 exact-match",
@@ -485,13 +531,7 @@ def main():
             "input_buffers": {"n": NX, "bytes_each": int(x.numel() * x.element_size()),
                               "note": "rotated step by step; more than the 256 MiB Infinity Cache in total when n >= 2 at "
                                       "batch 256 float32" if NX > 1 else "one buffer: the input may be served from the Infinity Cache"},
-            "serial": {"value": round(n_total * args.steps / elapsed_serial, 2),
-                       "ms_per_step": round(1e3 * elapsed_serial / args.steps, 4),
-                       "note": "the same K steps with one batch in flight (every step waits for the previous one), on the same plan: with lanes >= 2 its float32 stem runs on 128 CUs, which costs a forward that runs alone ~4 %"},
-            "roofline": roofline,
-            "roofline_kernels": kernels + ([gate] if gate else []),
-            "traffic_source": traffic_src,
-            "kernel_ms_sum": round(sum(avg_ms.values()), 5),
+            **full_fields,
         }
         if gather_ok is not None:
             out["gather_verified"] = gather_ok
@@ -533,9 +573,9 @@ def main():
                                       "note": "median of three windows of 200 steps; not the headline: the reference's API takes the "
                                               "normalised float32 tensor"}
                 del xu, xu0
-            if world == 1 and not args.no_extras:
+            if args.full and world == 1 and not args.no_extras:
                 out["parity"] = golden_parity(args.variant, spec, model, dev)
-            if args.variant == "full" and os.environ.get("TTNET_FULL_EXACT") != "1":
+            if args.full and args.variant == "full" and os.environ.get("TTNET_FULL_EXACT") != "1":
                 # share of the blocks' outputs the fast evaluation could not vouch for and sent through float64;
                 # counters of the plan's current lane since it was created
                 plan = model._any_plan()
@@ -546,7 +586,7 @@ def main():
         except Exception as e:                      # noqa: BLE001 - reported, not swallowed
             out["extras_error"] = f"{type(e).__name__}: {e}"
         try:
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline(args.variant, spec, st, B)
                 out["gpu_over_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
         except Exception as e:                      # noqa: BLE001
@@ -556,6 +596,27 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, y) -> None:
+    """DIR/logits.npy: the logits the timed path handed its caller in its last step (all ranks' rows when N > 1),
+    float32.  Beyond 64 MB a fixed (seeded) sample of rows is kept, in ascending order, with their indices in
+    DIR/logits_rows.npy (float64)."""
+    import numpy as np
+    a = y.detach().float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    rows_path = os.path.join(out_dir, "logits_rows.npy")
+    if os.path.exists(rows_path):
+        os.remove(rows_path)
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - 4096) // (a.nbytes // a.shape[0] + 8)
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+        a = a[rows]
+        np.save(rows_path, rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "logits.npy"), np.ascontiguousarray(a))
 
 
 def golden_parity(variant, spec, model, dev):

@@ -10,7 +10,7 @@ export COUNTERS_BATCH=$batch
 out=gpurun_out/${tag}
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-args="--steps 5 --warmup 1 --no-cpu-baseline --no-extras --inflight 1 --variant $variant ${BENCH_EXTRA}"
+args="--full --steps 5 --warmup 1 --no-cpu-baseline --no-extras --inflight 1 --variant $variant ${BENCH_EXTRA}"
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVES SQ_WAVE_CYCLES \
   --output-format csv -d $out/pmc_sq1_$variant -o c -- python bench.py $args > /dev/null 2> $out/pmc_sq1_$variant.err || exit 1
 rocprofv3 --kernel-trace --pmc SQ_INSTS_MFMA SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_IDX_ACTIVE \

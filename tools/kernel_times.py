@@ -3,7 +3,7 @@ import sys, os, json, subprocess
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 variant = os.environ.get("VARIANT", "small")
 for b in (sys.argv[1:] or ["256", "2048"]):
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--batch", b, "--steps", "20",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline", "--batch", b, "--steps", "20",
                           "--variant", variant],
                          capture_output=True, text=True)
     try:

@@ -1,5 +1,5 @@
 """profiles/<tag>_traffic_b<B>.json from two rocprofv3 PMC passes of bench.py:
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d <fetch_dir> -o f -- python bench.py --steps 5 --warmup 1 --no-cpu-baseline --inflight 1
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d <fetch_dir> -o f -- python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --inflight 1
     rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d <write_dir> -o w -- python bench.py ... (same)
 usage: python tools/make_traffic_profile.py <fetch_dir> <write_dir> <batch> <out.json>
 

@@ -3,7 +3,7 @@
 #   bash tools/power_sample.sh [bench args]   -> stdout
 smi() { rocm-smi --showpower --showclocks --showuse 2>/dev/null | grep -E "Power|sclk|GPU use" | sed 's/^GPU\[0\]\s*: //' | tr '\n' ';'; echo; }
 echo "idle: $(smi)"
-python bench.py --steps 150000 --windows 1 --no-cpu-baseline --no-extras "$@" > /tmp/power_bench.json 2>/dev/null &
+python bench.py --full --steps 150000 --windows 1 --no-cpu-baseline --no-extras "$@" > /tmp/power_bench.json 2>/dev/null &
 pid=$!
 for i in $(seq 1 200); do
   use=$(rocm-smi --showuse 2>/dev/null | grep -oE "GPU use \(%\): [0-9]+" | grep -oE "[0-9]+$")

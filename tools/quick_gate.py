@@ -2,7 +2,7 @@
 import json, os, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for b in (sys.argv[1:] or ["256"]):
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--no-extras", "--batch", b,
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline", "--no-extras", "--batch", b,
                           "--steps", "30", "--warmup", "5"], capture_output=True, text=True)
     try:
         d = json.loads(out.stdout.strip().splitlines()[-1])
