@@ -160,9 +160,38 @@ int ttnet_forward_u8(ttnet_plan *plan, int lane, const uint8_t *x_nhwc_dev, int6
  * geometry uploads its coefficient tables synchronously and keeps them for the life of the process).  src must be 16-byte
  * aligned, dst 4-byte aligned, crop * 3 a multiple of 4, n <= 65535.  Byte-identical to Pillow 12.x on the committed fixture tests/golden/ref_resize.npz
  * (Pillow's own outputs for seeded images of nine geometries); torchvision is not importable where this is
- * built, so its output-size and crop-offset rules are restated. */
+ * built, so its output-size and crop-offset rules are restated.
+ * Size bound: a workgroup keeps the intermediate rows of its 16 output rows in LDS, so large images are refused
+ * (TTNET_E_UNSUPPORTED, beyond about 2650 px on the shorter side at resize 256 / crop 224: 2592 x 3888 is accepted,
+ * 2848 x 4288 is not).  ttnet_resize_center_crop_u8_ragged has no such bound below 8192 px. */
 int ttnet_resize_center_crop_u8(const uint8_t *src_hwc_dev, int64_t n, int h, int w, int resize, int crop,
                                 uint8_t *dst_hwc_dev, void *stream);
+
+/* Image i of a ragged batch: uint8 HWC [h][w][3] at byte `offset` of the source buffer (no alignment asked). */
+typedef struct ttnet_image_desc {
+  int64_t offset;
+  int32_t h, w;
+} ttnet_image_desc;                                   /* 16 bytes */
+
+/* The same Resize(resize) + CenterCrop(crop), byte for byte, on a RAGGED batch: n images of any mix of sizes in one
+ * buffer [src_dev, src_dev + src_bytes), described by n descriptors in DEVICE memory -> uint8 [n][crop][crop][3] in
+ * descriptor order.  One kernel launch, asynchronous on `stream`; nothing is allocated, uploaded or waited for on the
+ * host, and nothing is cached per geometry: every workgroup reads its image's descriptor and computes the output
+ * size, the crop offsets and Pillow's coefficient tables itself (float64, in the order Pillow computes them), so the
+ * call can be captured into a graph and replayed with new buffer contents, new geometries included.
+ *   - src_dev 16-byte aligned, desc_dev 8-byte aligned, dst_dev 4-byte aligned, crop * 3 a multiple of 4,
+ *     resize >= crop (no image can then fall short of the crop), 1 <= n <= 65535.
+ *   - max_h / max_w bound every image's h / w; they size the LDS of a workgroup (which does not grow with the
+ *     scale factor beyond the coefficient tables: about 100 KB at 8192 x 8192, resize 256 / crop 224).  Bounds
+ *     the kernel cannot serve are refused here with TTNET_E_UNSUPPORTED (at 256 / 224: beyond about 9200 px on
+ *     the shorter of max_h, max_w); an image is never refused on its own.
+ *   - a descriptor with h outside [1, max_h], w outside [1, max_w], a negative offset or bytes ending past
+ *     src_bytes yields a zero crop and is counted in *bad_dev (int32, device memory, added to, never cleared) when
+ *     bad_dev is not NULL.  Whatever the descriptors hold, the kernel reads nothing outside the source buffer and
+ *     writes nothing outside dst. */
+int ttnet_resize_center_crop_u8_ragged(const uint8_t *src_dev, int64_t src_bytes, const ttnet_image_desc *desc_dev,
+                                       int64_t n, int max_h, int max_w, int resize, int crop, uint8_t *dst_dev,
+                                       int32_t *bad_dev, void *stream);
 
 /* Same, starting from the binarised stem output (features[3], netbin.py:193) given as
  * row-packed bits uint64 [n][p][56]; used by the parity tests to separate the integer

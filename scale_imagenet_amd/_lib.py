@@ -23,6 +23,11 @@ class NetDesc(C.Structure):
                 ("max_batch", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ImageDesc(C.Structure):
+    """ttnet_image_desc: image i of a ragged batch is uint8 HWC [h][w][3] at byte ``offset`` of the source buffer."""
+    _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32)]
+
+
 class TTNetError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"libttnet status {status}: {message}")
@@ -41,6 +46,8 @@ SYMBOLS: List[Tuple[str, object, list]] = [
     ("ttnet_plan_set_input_norm", C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("ttnet_forward_u8", C.c_int, [_P, C.c_int, _P, C.c_int64, _P, _P]),
     ("ttnet_resize_center_crop_u8", C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    ("ttnet_resize_center_crop_u8_ragged", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                     _P, _P, _P]),
     ("ttnet_forward_from_stem_bits", C.c_int, [_P, _P, C.c_int64, _P, _P]),
     ("ttnet_read_stage", C.c_int, [_P, C.c_char_p, C.c_int64, _P, C.c_size_t, C.c_int, _P]),
     ("ttnet_plan_get_table", C.c_int, [_P, C.c_char_p, _P, C.c_size_t]),

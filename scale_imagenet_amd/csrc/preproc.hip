@@ -321,3 +321,315 @@ extern "C" int ttnet_resize_center_crop_u8(const uint8_t *src_dev, int64_t n, in
   TT_HIP(hipGetLastError());
   return TTNET_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Ragged batches (ttnet_resize_center_crop_u8_ragged): images of any mix of sizes in one buffer, one launch, nothing on
+// the host per call.  A workgroup makes up to RG_TY output rows of one image, as resize_crop_kernel does, but
+//   - it reads its image's descriptor and computes the geometry and the coefficient tables it needs itself, in float64
+//     and in the order precompute() computes them (the library builds with -ffp-contract=off and double division is
+//     correctly rounded, so the tables are the same integers);
+//   - its LDS does not grow with the scale factor beyond the tables: after the horizontal pass of a staged chunk, the
+//     chunk's intermediate rows are folded into the vertical sums at once (int32, in registers, four output bytes per
+//     item), so only one chunk of intermediate rows is ever kept.  Integer sums do not depend on their order: the
+//     result is the byte of the two-pass form.
+// The next chunk's global loads are issued before the fold of the current one.
+namespace ttnet {
+namespace {
+
+constexpr int RG_TY = 16, RG_THREADS = 256, RG_ITEMS = 16, RG_CHUNK = 16, RG_STAGE_LOADS = 6,
+              RG_STAGE_Q = RG_STAGE_LOADS * RG_THREADS;        // items: (output row, dword column) sums per thread
+
+struct RaggedArgs {
+  const uint8_t *src;
+  int64_t src_bytes;
+  const ttnet_image_desc *desc;
+  uint8_t *dst;
+  int32_t *bad;
+  int max_h, max_w, resize, crop;
+  int ty;          // output rows per workgroup: RG_ITEMS / ceil(crop * 3 / 4 / RG_THREADS)
+  int kmax;        // most taps per window any image within max_h x max_w can need (stride room of the tables)
+  int stage_q;     // 16-byte pieces of the staged-input area
+};
+
+// One axis of Pillow's resampling, as precompute() sets it up; `ident`: a pass Pillow skips (size unchanged).
+struct Axis {
+  double scale, support, ss;
+  int in, ksize;
+  bool ident;
+};
+
+__device__ inline Axis make_axis(int in, int out) {
+  Axis a;
+  a.in = in;
+  a.ident = in == out;
+  a.scale = (double)((float)in - 0.0f) / out;
+  const double filterscale = a.scale < 1.0 ? 1.0 : a.scale;
+  a.support = 1.0 * filterscale;
+  a.ss = 1.0 / filterscale;
+  a.ksize = a.ident ? 1 : (int)ceil(a.support) * 2 + 1;
+  return a;
+}
+
+// first input index and tap count of output index xx
+__device__ inline void axis_window(const Axis &a, int xx, double &center, int &xmin, int &cnt) {
+  if (a.ident) { center = 0.0; xmin = xx; cnt = 1; return; }
+  center = 0.0 + (xx + 0.5) * a.scale;
+  xmin = (int)(center - a.support + 0.5);
+  if (xmin < 0) xmin = 0;
+  int xmax = (int)(center + a.support + 0.5);
+  if (xmax > a.in) xmax = a.in;
+  cnt = min(xmax - xmin, a.ksize);
+}
+
+// k[0 .. ksize): the window's fixed-point coefficients, zeros beyond its count (precompute + normalize_coeffs_8bpc)
+__device__ inline void axis_coeffs(const Axis &a, int xx, int *k) {
+  if (a.ident) { k[0] = 1 << kPrecisionBits; return; }
+  double center;
+  int xmin, cnt;
+  axis_window(a, xx, center, xmin, cnt);
+  double ww = 0.0;
+  for (int x = 0; x < cnt; ++x) {
+    double t = (x + xmin - center + 0.5) * a.ss;
+    if (t < 0.0) t = -t;
+    ww += t < 1.0 ? 1.0 - t : 0.0;
+  }
+  for (int x = 0; x < cnt; ++x) {
+    double t = (x + xmin - center + 0.5) * a.ss;
+    if (t < 0.0) t = -t;
+    double w = t < 1.0 ? 1.0 - t : 0.0;
+    if (ww != 0.0) w /= ww;
+    k[x] = w < 0 ? (int)(-0.5 + w * (1 << kPrecisionBits)) : (int)(0.5 + w * (1 << kPrecisionBits));
+  }
+  for (int x = cnt; x < a.ksize; ++x) k[x] = 0;
+}
+
+// horizontal pass of a staged chunk: one intermediate pixel per thread and step, as in resize_crop_kernel
+template <int KSH>
+__device__ inline void ragged_hpass(const uint8_t *s_in, uint8_t *s_mid, const int *s_xb, const int *s_kh, int ksh, int nr,
+                                    int crop, uint32_t row_bytes, uint32_t al0, uint32_t pitch) {
+  const float inv_crop = 1.0f / (float)crop;
+  const int ow = crop * 3;
+  for (int i = threadIdx.x; i < nr * crop; i += RG_THREADS) {
+    const int rr = (int)(((float)i + 0.5f) * inv_crop), xc = i - rr * crop;
+    const uint8_t *p = s_in + (uint32_t)rr * row_bytes + ((al0 + (uint32_t)rr * pitch) & 15u) + s_xb[xc];
+    const int *k = s_kh + xc * ksh;
+    int a0 = 1 << (kPrecisionBits - 1), a1 = a0, a2 = a0;
+    if constexpr (KSH != 0) {
+#pragma unroll
+      for (int x = 0; x < KSH; ++x) {
+        const int kx = k[x];
+        a0 += __mul24((int)p[3 * x], kx);
+        a1 += __mul24((int)p[3 * x + 1], kx);
+        a2 += __mul24((int)p[3 * x + 2], kx);
+      }
+    } else {
+#pragma nounroll
+      for (int x = 0; x < ksh; ++x) {
+        const int kx = k[x];
+        a0 += __mul24((int)p[3 * x], kx);
+        a1 += __mul24((int)p[3 * x + 1], kx);
+        a2 += __mul24((int)p[3 * x + 2], kx);
+      }
+    }
+    uint8_t *o = s_mid + (size_t)rr * ow + 3 * xc;
+    o[0] = (uint8_t)clip8(a0);
+    o[1] = (uint8_t)clip8(a1);
+    o[2] = (uint8_t)clip8(a2);
+  }
+}
+
+// WIDE: crop * 3 / 4 > RG_THREADS, several dword columns per thread (fewer rows per tile); otherwise item e is row e, column tid
+template <bool WIDE>
+__global__ __launch_bounds__(RG_THREADS) void resize_crop_ragged_kernel(RaggedArgs a) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  const int im = blockIdx.y, tid = threadIdx.x, crop = a.crop, ow = crop * 3, owq = ow >> 2;
+  const int y_lo = blockIdx.x * a.ty, rows_out = min(a.ty, crop - y_lo), items = rows_out * owq;
+  const int ncol = (owq + RG_THREADS - 1) / RG_THREADS;
+  uint32_t *dst = (uint32_t *)(a.dst + ((size_t)im * crop + y_lo) * ow);      // this tile's rows, contiguous
+  const ttnet_image_desc d = a.desc[im];
+  const int h = d.h, w = d.w;
+  bool ok = h >= 1 && h <= a.max_h && w >= 1 && w <= a.max_w && d.offset >= 0 && d.offset <= a.src_bytes &&
+            (int64_t)h * w * 3 <= a.src_bytes - d.offset;
+  // torchvision: the shorter side becomes `resize`, the longer int(resize * long / short); kept if the shorter side matches
+  int nw = w, nh = h;
+  if (ok && !((w <= h && w == a.resize) || (h <= w && h == a.resize))) {
+    if (w <= h) { nw = a.resize; nh = (int)((double)a.resize * h / w); }
+    else { nh = a.resize; nw = (int)((double)a.resize * w / h); }
+  }
+  const int x0 = (int)nearbyint((nw - crop) / 2.0), y0 = (int)nearbyint((nh - crop) / 2.0);     // Python's round()
+  const Axis ax = make_axis(w, nw), ay = make_axis(h, nh);
+  const int ksh = ax.ksize, ksv = ay.ksize;
+  double c;
+  int c0, cl, nl, r0, rl, rn;
+  axis_window(ax, x0, c, c0, nl);
+  axis_window(ax, x0 + crop - 1, c, cl, nl);
+  const int cw = cl + nl - c0, row_q = (cw * 3 + 15 + 15) / 16;
+  axis_window(ay, y0 + y_lo, c, r0, rn);
+  axis_window(ay, y0 + y_lo + rows_out - 1, c, rl, rn);
+  const int R = rl + rn - r0;
+  // (the host sized kmax and stage_q for every image within max_h x max_w; this only keeps LDS safe if that were wrong)
+  ok = ok && ksh <= a.kmax && ksv <= a.kmax && row_q <= a.stage_q;
+  if (!ok) {
+    for (int i = tid; i < items; i += RG_THREADS) dst[i] = 0u;
+    if (blockIdx.x == 0 && tid == 0 && a.bad) atomicAdd(a.bad, 1);
+    return;
+  }
+  const int chunk = min(RG_CHUNK, a.stage_q / row_q);
+  // LDS: [staged input][one chunk of intermediate rows][pad: taps past a row's end][tables]
+  uint8_t *s_in = lds;
+  uint8_t *s_mid = lds + (size_t)a.stage_q * 16;                                        // [RG_CHUNK][ow]
+  int *s_xb = (int *)(s_mid + (size_t)RG_CHUNK * ow + ((3 * a.kmax + 31) & ~15));       // [crop]
+  int *s_kh = s_xb + crop;                                                              // [crop][ksh]
+  int *s_bv = s_kh + (size_t)crop * a.kmax;                                             // [RG_TY][2]: first row (tile-relative), count
+  int *s_kv = s_bv + 2 * RG_TY;                                                         // [RG_TY][ksv]
+  for (int xc = tid; xc < crop; xc += RG_THREADS) {
+    int xmin, cnt;
+    axis_window(ax, x0 + xc, c, xmin, cnt);
+    s_xb[xc] = (xmin - c0) * 3;
+    axis_coeffs(ax, x0 + xc, s_kh + xc * ksh);
+  }
+  const int yc_t = RG_THREADS - 1 - tid;                   // the vertical rows on the last threads (idle above at crop 224)
+  if (yc_t < rows_out) {
+    int ymin, cnt;
+    axis_window(ay, y0 + y_lo + yc_t, c, ymin, cnt);
+    s_bv[2 * yc_t] = ymin - r0;
+    s_bv[2 * yc_t + 1] = cnt;
+    axis_coeffs(ay, y0 + y_lo + yc_t, s_kv + yc_t * ksv);
+  }
+  const size_t whole_q = (size_t)a.src_bytes >> 4;
+  const uint32_t pitch = (uint32_t)w * 3u, row_bytes = (uint32_t)row_q * 16u;
+  const float inv_rowq = 1.0f / (float)row_q;
+  auto first_byte = [&](int rc) { return (size_t)d.offset + ((size_t)(r0 + rc) * w + c0) * 3; };
+  uint4 v[RG_STAGE_LOADS];
+  // stage: the 16-byte pieces of the buffer from the one that holds byte (row, c0), never past src_bytes
+  auto load = [&](int rc) {
+    const int nr = min(chunk, R - rc);
+    const size_t first0 = first_byte(rc);
+#pragma unroll
+    for (int u = 0; u < RG_STAGE_LOADS; ++u) {
+      const int i = tid + RG_THREADS * u;
+      v[u] = make_uint4(0u, 0u, 0u, 0u);
+      if (i < nr * row_q) {
+        const int rr = (int)(((float)i + 0.5f) * inv_rowq), dq = i - rr * row_q;
+        const size_t q = ((first0 + (size_t)rr * pitch) >> 4) + dq;
+        if (q < whole_q) v[u] = ((const uint4 *)a.src)[q];
+        else if (q == whole_q) {                            // the last, partial piece byte by byte
+          uint32_t t[4] = {0u, 0u, 0u, 0u};
+          for (size_t b = 16 * whole_q; b < (size_t)a.src_bytes; ++b) t[(b & 15) >> 2] |= (uint32_t)a.src[b] << (8 * (b & 3));
+          v[u] = make_uint4(t[0], t[1], t[2], t[3]);
+        }
+      }
+    }
+  };
+  // the vertical sums: a thread owns dword column q = tid + RG_THREADS * c of output rows yc; item e = c * ty + yc
+  int acc[RG_ITEMS][4];
+#pragma unroll
+  for (int e = 0; e < RG_ITEMS; ++e) acc[e][0] = acc[e][1] = acc[e][2] = acc[e][3] = 1 << (kPrecisionBits - 1);
+  load(0);
+  for (int rc = 0; rc < R; rc += chunk) {
+    const int nr = min(chunk, R - rc);
+    const uint32_t al0 = (uint32_t)(first_byte(rc) & 15);
+    __syncthreads();                                       // the previous chunk has been consumed (and the tables are in place)
+#pragma unroll
+    for (int u = 0; u < RG_STAGE_LOADS; ++u) {
+      const int i = tid + RG_THREADS * u;
+      if (i < nr * row_q) ((uint4 *)s_in)[i] = v[u];
+    }
+    __syncthreads();
+    switch (ksh) {
+      case 1: ragged_hpass<1>(s_in, s_mid, s_xb, s_kh, ksh, nr, crop, row_bytes, al0, pitch); break;
+      case 3: ragged_hpass<3>(s_in, s_mid, s_xb, s_kh, ksh, nr, crop, row_bytes, al0, pitch); break;
+      case 5: ragged_hpass<5>(s_in, s_mid, s_xb, s_kh, ksh, nr, crop, row_bytes, al0, pitch); break;
+      case 7: ragged_hpass<7>(s_in, s_mid, s_xb, s_kh, ksh, nr, crop, row_bytes, al0, pitch); break;
+      case 9: ragged_hpass<9>(s_in, s_mid, s_xb, s_kh, ksh, nr, crop, row_bytes, al0, pitch); break;
+      default: ragged_hpass<0>(s_in, s_mid, s_xb, s_kh, ksh, nr, crop, row_bytes, al0, pitch); break;
+    }
+    __syncthreads();
+    if (rc + chunk < R) load(rc + chunk);                  // in flight during the fold
+    // fold the chunk's rows [rc, rc + nr) into the sums of the output rows whose windows meet them (row bounds and
+    // coefficients are uniform over the workgroup: LDS broadcasts, uniform loops)
+#pragma unroll
+    for (int e = 0; e < RG_ITEMS; ++e) {
+      const int yc = WIDE ? e % a.ty : e, q = WIDE ? tid + RG_THREADS * (e / a.ty) : tid;
+      if (e < ncol * a.ty && yc < rows_out) {
+        const int ymin = s_bv[2 * yc], lo = max(ymin, rc), hi = min(ymin + s_bv[2 * yc + 1], rc + nr);
+        if (q < owq && lo < hi) {
+          const int *k = s_kv + yc * ksv - ymin;
+          const uint32_t *m = (const uint32_t *)s_mid + q - rc * owq;
+#pragma nounroll
+          for (int y = lo; y < hi; ++y) {
+            const uint32_t wv = m[y * owq];
+            const int ky = k[y];
+            acc[e][0] += __mul24((int)(wv & 255u), ky);
+            acc[e][1] += __mul24((int)((wv >> 8) & 255u), ky);
+            acc[e][2] += __mul24((int)((wv >> 16) & 255u), ky);
+            acc[e][3] += __mul24((int)(wv >> 24), ky);
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < RG_ITEMS; ++e) {
+    const int yc = WIDE ? e % a.ty : e, q = WIDE ? tid + RG_THREADS * (e / a.ty) : tid;
+    if (e < ncol * a.ty && yc < rows_out && q < owq)
+      dst[yc * owq + q] = clip8(acc[e][0]) | (clip8(acc[e][1]) << 8) | (clip8(acc[e][2]) << 16) | (clip8(acc[e][3]) << 24);
+  }
+}
+
+}  // namespace
+}  // namespace ttnet
+
+extern "C" int ttnet_resize_center_crop_u8_ragged(const uint8_t *src_dev, int64_t src_bytes, const ttnet_image_desc *desc_dev,
+                                                  int64_t n, int max_h, int max_w, int resize, int crop, uint8_t *dst_dev,
+                                                  int32_t *bad_dev, void *stream) {
+  if (!src_dev || !desc_dev || !dst_dev || src_bytes < 1 || n < 1 || n > 65535 || max_h < 1 || max_w < 1 || crop < 1 ||
+      resize < crop) {
+    set_error("resize_center_crop_ragged: bad argument (n %lld, src_bytes %lld, max %dx%d, resize %d, crop %d; "
+              "resize must be >= crop)", (long long)n, (long long)src_bytes, max_w, max_h, resize, crop);
+    return TTNET_E_INVALID;
+  }
+  if (((uintptr_t)src_dev & 15) || ((uintptr_t)desc_dev & 7) || ((uintptr_t)dst_dev & 3) || (crop * 3) % 4) {
+    set_error("resize_center_crop_ragged: the input must be 16-byte aligned, the descriptors 8-byte aligned, the output "
+              "4-byte aligned and crop * 3 a multiple of 4");
+    return TTNET_E_INVALID;
+  }
+  // Bounds over every image within max_h x max_w.  Scale of an axis (w / nw or h / nh): the shorter side s goes to
+  // `resize` (scale s / resize), the longer side l to int(resize * l / s) > resize * l / s - 1 (scale < s / (resize - 1));
+  // s <= min(max_h, max_w).  Taps 2 * ceil(max(scale, 1)) + 1; input columns of the crop < (crop + 1) * max(scale, 1) + 3.
+  const int ow = crop * 3, owq = ow / 4;
+  const int ty = std::min(RG_TY, RG_ITEMS / ((owq + RG_THREADS - 1) / RG_THREADS));
+  const double smax = std::max(1.0, (double)std::min(max_h, max_w) / (resize > 1 ? resize - 1.0 : 1.0));
+  if (ty < 1 || smax > 1e4 || max_h > 65536 || max_w > 65536 || resize > 65536) {
+    set_error("resize_center_crop_ragged: crop %d or images up to %dx%d at resize %d are beyond this kernel", crop, max_w,
+              max_h, resize);
+    return TTNET_E_UNSUPPORTED;
+  }
+  RaggedArgs a{};
+  a.src = src_dev; a.src_bytes = src_bytes; a.desc = desc_dev; a.dst = dst_dev; a.bad = bad_dev;
+  a.max_h = max_h; a.max_w = max_w; a.resize = resize; a.crop = crop; a.ty = ty;
+  a.kmax = 2 * (int)ceil(smax) + 3;                                  // (+2: slack over the rounding of the bound)
+  const int64_t cw_max = (int64_t)ceil((crop + 1) * smax) + 4, row_q_max = (cw_max * 3 + 30) / 16;
+  if (row_q_max > RG_STAGE_Q) {
+    set_error("resize_center_crop_ragged: images up to %dx%d at resize %d / crop %d need %lld input bytes per row, more than "
+              "the %d a workgroup stages", max_w, max_h, resize, crop, (long long)(cw_max * 3), RG_STAGE_Q * 16);
+    return TTNET_E_UNSUPPORTED;
+  }
+  a.stage_q = (int)std::min<int64_t>((int64_t)RG_CHUNK * row_q_max, RG_STAGE_Q);
+  const size_t lds = (size_t)a.stage_q * 16 + (size_t)RG_CHUNK * ow + ((3 * a.kmax + 31) & ~15) +
+                     ((size_t)crop + (size_t)crop * a.kmax + 2 * RG_TY + (size_t)RG_TY * a.kmax) * sizeof(int);
+  if (lds > 160 * 1024) {
+    set_error("resize_center_crop_ragged: images up to %dx%d at resize %d / crop %d need %zu bytes of LDS per workgroup",
+              max_w, max_h, resize, crop, lds);
+    return TTNET_E_UNSUPPORTED;
+  }
+  auto launch = [&](auto kernel) -> int {
+    TT_TRY(ensure_dynamic_lds((const void *)kernel, lds));
+    hipLaunchKernelGGL(kernel, dim3((crop + ty - 1) / ty, (unsigned)n), dim3(RG_THREADS), lds, (hipStream_t)stream, a);
+    return TTNET_OK;
+  };
+  if (owq <= RG_THREADS) TT_TRY(launch(resize_crop_ragged_kernel<false>));
+  else TT_TRY(launch(resize_crop_ragged_kernel<true>));
+  TT_HIP(hipGetLastError());
+  return TTNET_OK;
+}

@@ -5,14 +5,156 @@
 ``resize_center_crop_u8`` does the first two on decoded uint8 HWC images already on the device
 (libttnet: ttnet_resize_center_crop_u8, csrc/preproc.hip); the last two are fused into the stem by
 ``model.forward_u8``.  JPEG decoding stays on the host (out of scope).
+
+A decoder batch of ImageNet images has many sizes.  ``pack_u8`` / ``collate_u8`` put such a batch into one flat
+buffer plus descriptors (``RaggedU8``), and ``resize_center_crop_u8_ragged`` resizes and crops all of it in one
+launch (ttnet_resize_center_crop_u8_ragged), in input order.
 """
 from __future__ import annotations
 
 import ctypes as C
+from typing import Dict, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib
+
+# the largest image side pack_u8 accepts (ttnet_resize_center_crop_u8_ragged serves it at resize 256 / crop 224)
+MAX_SIDE = 8192
+# ttnet_image_desc (include/ttnet.h): int64 offset, int32 h, int32 w -- 16 bytes, viewed as int64 [n, 2] in torch
+DESC_DTYPE = np.dtype([("offset", "<i8"), ("h", "<i4"), ("w", "<i4")])
+assert DESC_DTYPE.itemsize == C.sizeof(_lib.ImageDesc) == 16
+
+
+class RaggedU8:
+    """A batch of decoded uint8 HWC images of mixed sizes: ``data`` (uint8 [bytes], image i at byte offset
+    ``desc[i]``), ``desc`` (int64 [n, 2]: the 16-byte ttnet_image_desc records), and the largest height and
+    width in the batch.  Move it with ``.to(device, non_blocking=True)``; ``DataLoader(pin_memory=True)`` calls
+    ``.pin_memory()``."""
+
+    def __init__(self, data: torch.Tensor, desc: torch.Tensor, max_h: int, max_w: int):
+        if data.dtype != torch.uint8 or data.dim() != 1 or desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != 2:
+            raise RuntimeError(f"RaggedU8: expected uint8 [bytes] and int64 [n,2], got {data.dtype} {tuple(data.shape)}, "
+                               f"{desc.dtype} {tuple(desc.shape)}")
+        if data.device != desc.device:
+            raise RuntimeError(f"RaggedU8: data on {data.device}, descriptors on {desc.device}")
+        self.data, self.desc, self.max_h, self.max_w = data, desc, int(max_h), int(max_w)
+
+    def __len__(self) -> int:
+        return self.desc.shape[0]
+
+    @property
+    def device(self) -> torch.device:
+        return self.data.device
+
+    def to(self, device, non_blocking: bool = False) -> "RaggedU8":
+        return RaggedU8(self.data.to(device, non_blocking=non_blocking), self.desc.to(device, non_blocking=non_blocking),
+                        self.max_h, self.max_w)
+
+    def pin_memory(self) -> "RaggedU8":
+        return RaggedU8(self.data.pin_memory(), self.desc.pin_memory(), self.max_h, self.max_w)
+
+    def descriptors(self) -> np.ndarray:
+        """The descriptors as a numpy record array (offset, h, w)."""
+        return self.desc.cpu().numpy().view(DESC_DTYPE).reshape(-1)
+
+
+def pack_u8(images: Sequence) -> RaggedU8:
+    """HWC uint8 images (numpy arrays or CPU tensors) of any sizes -> one host ``RaggedU8``, images back to back
+    in order.  Raises RuntimeError naming the first image that is not uint8 [h, w, 3] with 1 <= h, w <= MAX_SIDE."""
+    n = len(images)
+    if n < 1 or n > 65535:
+        raise RuntimeError(f"pack_u8: expected 1 to 65535 images, got {n}")
+    arrays = []
+    for i, im in enumerate(images):
+        if isinstance(im, torch.Tensor):
+            if im.is_cuda:
+                raise RuntimeError(f"pack_u8: image {i} is on {im.device}; pack decoded host images")
+            im = im.numpy()
+        if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+            desc = f"{im.dtype} {tuple(im.shape)}" if isinstance(im, np.ndarray) else type(im).__name__
+            raise RuntimeError(f"pack_u8: image {i} must be uint8 HWC [h, w, 3], got {desc}")
+        if not (1 <= im.shape[0] <= MAX_SIDE and 1 <= im.shape[1] <= MAX_SIDE):
+            raise RuntimeError(f"pack_u8: image {i} is {im.shape[1]}x{im.shape[0]}; sides must lie in [1, {MAX_SIDE}]")
+        arrays.append(im)
+    desc = np.zeros(n, dtype=DESC_DTYPE)
+    sizes = np.array([a.size for a in arrays], dtype=np.int64)
+    desc["offset"][1:] = np.cumsum(sizes)[:-1]
+    desc["h"] = [a.shape[0] for a in arrays]
+    desc["w"] = [a.shape[1] for a in arrays]
+    data = torch.empty(int(sizes.sum()), dtype=torch.uint8)
+    flat = data.numpy()
+    for a, off, sz in zip(arrays, desc["offset"], sizes):
+        flat[off:off + sz] = a.reshape(-1)           # (copies a non-contiguous view too)
+    return RaggedU8(data, torch.from_numpy(desc.view(np.int64).reshape(n, 2)), int(desc["h"].max()), int(desc["w"].max()))
+
+
+def collate_u8(batch):
+    """``DataLoader`` ``collate_fn`` for ``(image, target)`` pairs of decoded uint8 HWC images of any sizes:
+    returns ``(RaggedU8, targets)`` with the targets collated as the default collate does."""
+    images, targets = zip(*batch)
+    return pack_u8(images), torch.utils.data.default_collate(list(targets))
+
+
+# per device: a running count of bad descriptors (device int32) and its host mirror, copied after each call
+_bad: Dict[torch.device, tuple] = {}
+
+
+def _bad_counter(device: torch.device):
+    if device not in _bad:
+        _bad[device] = (torch.zeros(1, dtype=torch.int32, device=device), torch.zeros(1, dtype=torch.int32).pin_memory())
+    return _bad[device]
+
+
+def _raise_bad(count: int):
+    raise RuntimeError(f"resize_center_crop_u8_ragged: {count} image descriptor(s) of an earlier batch were out of "
+                       "bounds (h, w beyond max_h / max_w or bytes past the buffer): their crops are zero")
+
+
+def check_ragged(device=None):
+    """Synchronise ``device`` and raise if any ragged call on it met a bad descriptor (then clear the count).
+    ``resize_center_crop_u8_ragged`` reports one on a later call without synchronising; call this after the
+    last batch of a loop."""
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if device in _bad:
+        dev_count, host = _bad[device]
+        torch.cuda.synchronize(device)
+        count = int(dev_count.item())
+        if count:
+            dev_count.zero_()
+            host.zero_()
+            _raise_bad(count)
+
+
+def resize_center_crop_u8_ragged(r: RaggedU8, resize: int = 256, crop: int = 224) -> torch.Tensor:
+    """A ragged batch on a HIP device -> uint8 [n, crop, crop, 3] in input order, one asynchronous kernel launch
+    (capturable in a graph).  A bad descriptor gives a zero crop and makes a later call raise (the device count is
+    copied to the host after each call, without a synchronisation); ``check_ragged`` checks at once."""
+    if not isinstance(r, RaggedU8):
+        raise RuntimeError(f"expected a RaggedU8 (pack_u8 / collate_u8), got {type(r).__name__}")
+    if not r.data.is_cuda:
+        raise RuntimeError(f"the ragged batch is on {r.device}: move it with .to(device, non_blocking=True)")
+    dev = r.data.device
+    dev_count, host = _bad_counter(dev)
+    capturing = torch.cuda.is_current_stream_capturing()
+    if not capturing and int(host[0]):
+        count = int(host[0])
+        dev_count.zero_()
+        host.zero_()
+        _raise_bad(count)
+    data = r.data if r.data.data_ptr() % 16 == 0 else r.data.clone()
+    desc = r.desc.contiguous()
+    n = len(r)
+    out = torch.empty((n, crop, crop, 3), device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.load().ttnet_resize_center_crop_u8_ragged(
+            C.c_void_p(data.data_ptr()), data.numel(), C.c_void_p(desc.data_ptr()), n, r.max_h, r.max_w, int(resize),
+            int(crop), C.c_void_p(out.data_ptr()), C.c_void_p(dev_count.data_ptr()), C.c_void_p(stream)))
+        if not capturing:
+            host.copy_(dev_count, non_blocking=True)
+    return out
 
 
 def resize_center_crop_u8(x_u8: torch.Tensor, resize: int = 256, crop: int = 224) -> torch.Tensor:
@@ -30,6 +172,9 @@ def resize_center_crop_u8(x_u8: torch.Tensor, resize: int = 256, crop: int = 224
     return out
 
 
-def imgnet_eval_forward(model, x_u8: torch.Tensor, lane: int = 0) -> torch.Tensor:
-    """``model(imgnet_transform(False)(image))`` for a batch of decoded images of one size."""
+def imgnet_eval_forward(model, x_u8, lane: int = 0) -> torch.Tensor:
+    """``model(imgnet_transform(False)(image))`` for a batch of decoded images: of one size (uint8 [N,H,W,3]), or
+    of mixed sizes (``RaggedU8`` on the device, from ``collate_u8``)."""
+    if isinstance(x_u8, RaggedU8):
+        return model.forward_u8(resize_center_crop_u8_ragged(x_u8), lane=lane)
     return model.forward_u8(resize_center_crop_u8(x_u8), lane=lane)

@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import os
 from collections import OrderedDict
-from typing import Dict, Tuple
+from typing import Dict, List, Tuple
 
 import numpy as np
 
@@ -156,4 +156,26 @@ def synth_state_dict(spec, weight_seed: int = 0, calibrated: bool = True) -> "Or
             for leaf in ("running_mean", "running_var"):
                 assert z[leaf].shape == out[f"{head}.{leaf}"].shape
                 out[f"{head}.{leaf}"] = z[leaf].astype(np.float32)
+    return out
+
+
+def imagenet_like_sizes(n: int, seed: int = 0) -> List[Tuple[int, int]]:
+    """``n`` seeded (h, w) pairs shaped like a decoded ImageNet validation batch: mostly 500 x 375 / 375 x 500 /
+    500 x 333 in either orientation with some jitter, a few small ones and a few camera-sized ones up to
+    3000 x 4000 (for the ragged resize tools and tests)."""
+    rng = np.random.default_rng(seed)
+    common = [(375, 500), (500, 375), (333, 500), (500, 333), (500, 500), (400, 500), (500, 400)]
+    large = [(3000, 4000), (4000, 3000), (2848, 4288), (1600, 1200), (1200, 1600), (2592, 3888)]
+    out = []
+    for _ in range(n):
+        u = rng.random()
+        if u < 0.80:
+            h, w = common[int(rng.integers(len(common)))]
+            if rng.random() < 0.3:
+                h, w = h - int(rng.integers(0, 40)), w - int(rng.integers(0, 40))
+        elif u < 0.99:
+            h, w = int(rng.integers(100, 900)), int(rng.integers(100, 900))
+        else:
+            h, w = large[int(rng.integers(len(large)))]
+        out.append((h, w))
     return out
