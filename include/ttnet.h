@@ -193,6 +193,65 @@ int ttnet_resize_center_crop_u8_ragged(const uint8_t *src_dev, int64_t src_bytes
                                        int64_t n, int max_h, int max_w, int resize, int crop, uint8_t *dst_dev,
                                        int32_t *bad_dev, void *stream);
 
+/* JPEG decoding in front of the ragged resize: PIL.Image.open(path).convert("RGB"), the default loader of
+ * torchvision.datasets.ImageFolder (main.py:208) that feeds the eval transform (utils/preprocess.py:104), on a batch of
+ * compressed files.  Decoded on the device: Huffman-coded sequential 8-bit JPEG (SOF0, SOF1) with one scan holding
+ * every component -- YCbCr (3 components, luma sampling 1x1 / 2x1 / 2x2, chroma 1x1) or greyscale (1 component,
+ * replicated to RGB) -- with or without restart intervals, 1 <= h, w <= 8192.  The output is byte for byte what Pillow
+ * 12.x with libjpeg-turbo 3.x decodes (islow integer IDCT, fancy upsampling, SCALEBITS 16 colour tables; the fixtures
+ * under tests/golden/jpeg pin it).  Any other file is decoded on the host and carried as raw pixels (kind 1) that the
+ * device copies through.
+ *
+ * Image i of the batch, built on the host from the markers before SOS (scale_imagenet_amd/jpeg.py, pack_jpeg); 80
+ * bytes, the array 16-byte aligned.  kind 0 (decoded on the device): [data_offset, + data_bytes) of the source buffer is
+ * the entropy-coded data after the SOS header, up to the end of the file; table_offset is a 2048-byte table block:
+ * uint16 quant[3][64] (per frame component, zig-zag order as in DQT) at 0, then for component c = 0..2 the DC and
+ * then the AC Huffman table of its scan as DHT holds them, counts[16] + symbols[256] (272 bytes each) at
+ * 384 + 272 * (2c + ac).  comp[c] = {id, h_samp << 4 | v_samp, quant table, dc << 4 | ac table} (informative: the
+ * block already holds the selected tables).  block_offset: first of this image's coefficient blocks (MCU columns x MCU
+ * rows x blocks per MCU) in the decoder's workspace.  kind 1: data_offset holds uint8 HWC [h][w][3].  Both: the
+ * decoded image goes to [out_offset, + h * w * 3) of dst. */
+typedef struct ttnet_jpeg_desc {
+  int64_t data_offset, data_bytes;
+  int64_t table_offset;
+  int64_t out_offset;
+  int64_t block_offset;
+  int32_t h, w;
+  int32_t kind;              /* 0: JPEG decoded on the device, 1: raw pixels copied */
+  int32_t ncomp;             /* 1 or 3 */
+  int32_t restart_interval;  /* MCUs per restart segment, 0: none */
+  uint8_t comp[3][4];
+  int32_t reserved[2];
+} ttnet_jpeg_desc;
+
+typedef struct ttnet_jpeg_ctx ttnet_jpeg_ctx;
+
+/* A decoder context on `device`; its workspace is sized by ttnet_jpeg_ctx_reserve (the only calls that allocate). */
+int ttnet_jpeg_ctx_create(int device, ttnet_jpeg_ctx **out);
+/* Sizes the workspace for batches of up to max_images images, max_blocks coefficient blocks in all and max_bytes bytes of
+ * source buffer (about 128 bytes per block + 19 bytes per source byte).  Replaces (and frees) the previous workspace:
+ * call it outside graph capture, with no decode in flight on the context. */
+int ttnet_jpeg_ctx_reserve(ttnet_jpeg_ctx *ctx, int64_t max_images, int64_t max_blocks, int64_t max_bytes);
+/* Decodes n images described by jdesc_dev (device memory) from [src_dev, src_dev + src_bytes) into dst_dev, back to back
+ * at each descriptor's out_offset, and writes their ttnet_image_desc records (out_offset, h, w) to dst_desc_dev: the
+ * input of ttnet_resize_center_crop_u8_ragged.  n_blocks is the descriptors' total of coefficient blocks.  Three kernel
+ * launches on `stream`; nothing is allocated, copied or waited for, nothing is cached per image, so the call can be
+ * captured into a graph and replayed with new images within the same reservation.  TTNET_E_INVALID when n, n_blocks or
+ * src_bytes exceed the reservation.  src_dev and jdesc_dev 16-byte aligned, dst_desc_dev 8-byte aligned.
+ *   - corrupt entropy-coded data (truncated, a bad Huffman code, a coefficient index past 63, a missing or misnumbered
+ *     RST) makes that image all zero and adds 1 to stats_dev[0]; a descriptor outside the buffers or the reservation
+ *     does too, and its output record gets h = w = 0.  The kernels read nothing outside the source buffer and write
+ *     nothing outside the workspace and each image's own output span, whatever the bitstream holds.
+ *   - stats_dev[1] (int32, added to) counts restart segments whose subsequence synchronisation was still changing after
+ *     its round bound and that were then walked sequentially (per segment; the settled segments of the same image are
+ *     not).  TTNET_JPEG_SEQUENTIAL=1 walks every segment so and counts them all (diagnostic: the result is the same).
+ *   - the workspace (ttnet_jpeg_ctx_reserve) is baked into a captured graph: it must not be re-reserved while such a
+ *     graph may still be replayed. */
+int ttnet_jpeg_decode_ragged(ttnet_jpeg_ctx *ctx, const uint8_t *src_dev, int64_t src_bytes,
+                             const ttnet_jpeg_desc *jdesc_dev, int64_t n, int64_t n_blocks, uint8_t *dst_dev,
+                             int64_t dst_bytes, ttnet_image_desc *dst_desc_dev, int32_t *stats_dev, void *stream);
+void ttnet_jpeg_ctx_destroy(ttnet_jpeg_ctx *ctx);
+
 /* Same, starting from the binarised stem output (features[3], netbin.py:193) given as
  * row-packed bits uint64 [n][p][56]; used by the parity tests to separate the integer
  * gate path (bit exact) from the float stem (exact except at near ties). */

@@ -28,6 +28,14 @@ class ImageDesc(C.Structure):
     _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32)]
 
 
+class JpegDesc(C.Structure):
+    """ttnet_jpeg_desc: one image of a JPEG batch (include/ttnet.h), 80 bytes."""
+    _fields_ = [("data_offset", C.c_int64), ("data_bytes", C.c_int64), ("table_offset", C.c_int64),
+                ("out_offset", C.c_int64), ("block_offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32),
+                ("kind", C.c_int32), ("ncomp", C.c_int32), ("restart_interval", C.c_int32),
+                ("comp", (C.c_uint8 * 4) * 3), ("reserved", C.c_int32 * 2)]
+
+
 class TTNetError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"libttnet status {status}: {message}")
@@ -48,6 +56,10 @@ SYMBOLS: List[Tuple[str, object, list]] = [
     ("ttnet_resize_center_crop_u8", C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     ("ttnet_resize_center_crop_u8_ragged", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                                      _P, _P, _P]),
+    ("ttnet_jpeg_ctx_create", C.c_int, [C.c_int, C.POINTER(_P)]),
+    ("ttnet_jpeg_ctx_reserve", C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64]),
+    ("ttnet_jpeg_decode_ragged", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, _P]),
+    ("ttnet_jpeg_ctx_destroy", None, [_P]),
     ("ttnet_forward_from_stem_bits", C.c_int, [_P, _P, C.c_int64, _P, _P]),
     ("ttnet_read_stage", C.c_int, [_P, C.c_char_p, C.c_int64, _P, C.c_size_t, C.c_int, _P]),
     ("ttnet_plan_get_table", C.c_int, [_P, C.c_char_p, _P, C.c_size_t]),

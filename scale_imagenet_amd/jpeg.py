@@ -1,0 +1,550 @@
+"""JPEG decoding on the device: the ``PIL.Image.open(path).convert("RGB")`` of ``ImageFolder``'s default loader
+(main.py:208) in front of the eval transform (utils/preprocess.py:104-108), from compressed file bytes.
+
+    file bytes --pack_jpeg (loader worker: header walk, tables)--> RaggedJpeg --H2D--> decode_ragged (libttnet,
+    csrc/jpeg.hip) --> RaggedU8 --> resize_center_crop_u8_ragged --> forward_u8
+
+``parse_header`` walks the markers in front of the first SOS in pure Python (no Pillow, no GPU).  Baseline and
+extended Huffman-coded sequential 8-bit files with one scan are decoded on the device: YCbCr with luma sampling 1x1,
+2x1 or 2x2 and chroma 1x1, and greyscale.  Everything else is decoded by Pillow in ``pack_jpeg`` (in the worker) and
+carried through the same batch as raw pixels that the device copies; nothing is dropped.  The device output is byte
+for byte Pillow's (libjpeg's islow IDCT, fancy upsampling, jdcolor.c's tables).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import io
+import os
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .preprocess import MAX_SIDE, RaggedU8, resize_center_crop_u8_ragged
+
+KIND_JPEG, KIND_RAW = 0, 1
+TABLE_BYTES = 2048        # per-image table block: uint16 quant[3][64] (zig-zag) + [3][dc, ac] x (counts[16], symbols[256])
+_HUFF_OFF = 384
+_HUFF_BYTES = 272
+# ttnet_jpeg_desc (include/ttnet.h), 80 bytes
+JDESC_DTYPE = np.dtype([("data_offset", "<i8"), ("data_bytes", "<i8"), ("table_offset", "<i8"), ("out_offset", "<i8"),
+                        ("block_offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("kind", "<i4"), ("ncomp", "<i4"),
+                        ("restart_interval", "<i4"), ("comp", "u1", (3, 4)), ("reserved", "<i4", (2,))])
+assert JDESC_DTYPE.itemsize == 80 == C.sizeof(_lib.JpegDesc)
+_JDESC_WORDS = JDESC_DTYPE.itemsize // 8
+
+_SOF_NAMES = {0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)", 0xC5: "differential sequential (SOF5)",
+              0xC6: "differential progressive (SOF6)", 0xC7: "differential lossless (SOF7)",
+              0xC9: "arithmetic-coded sequential (SOF9)", 0xCA: "arithmetic-coded progressive (SOF10)",
+              0xCB: "arithmetic-coded lossless (SOF11)", 0xCD: "arithmetic-coded differential (SOF13)",
+              0xCE: "arithmetic-coded differential progressive (SOF14)", 0xCF: "arithmetic-coded differential lossless (SOF15)"}
+
+
+@dataclass
+class Unsupported:
+    """A file the device does not decode, and why."""
+    reason: str
+
+
+@dataclass
+class JpegHeader:
+    """What the device decoder needs, from the markers before the first SOS."""
+    h: int
+    w: int
+    sof: int                                     # 0 or 1
+    comps: List[Tuple[int, int, int, int]]       # per frame component: (id, h_samp, v_samp, quant table)
+    scan_tables: List[Tuple[int, int]]           # per component, in frame order: (dc table, ac table)
+    qt: Dict[int, List[int]]                     # quant tables, zig-zag order, as in DQT
+    dht: Dict[Tuple[int, int], Tuple[List[int], List[int]]] = field(default_factory=dict)  # (class, id) -> counts, symbols
+    restart_interval: int = 0
+    scan_offset: int = 0                         # first byte of the entropy-coded data
+    jfif: bool = False
+    adobe_transform: Optional[int] = None
+
+    @property
+    def ncomp(self) -> int:
+        return len(self.comps)
+
+    @property
+    def sampling(self) -> List[Tuple[int, int]]:
+        return [(c[1], c[2]) for c in self.comps]
+
+    def mcus(self) -> Tuple[int, int, int]:
+        """(MCU columns, MCU rows, blocks per MCU)."""
+        if self.ncomp == 1:
+            return (self.w + 7) // 8, (self.h + 7) // 8, 1
+        hs, vs = self.comps[0][1], self.comps[0][2]
+        return (self.w + 8 * hs - 1) // (8 * hs), (self.h + 8 * vs - 1) // (8 * vs), hs * vs + 2
+
+    def blocks(self) -> int:
+        mx, my, b = self.mcus()
+        return mx * my * b
+
+    def segments(self) -> int:
+        mx, my, _ = self.mcus()
+        ri = self.restart_interval
+        return 1 if ri == 0 else (mx * my + ri - 1) // ri
+
+
+def _check_huffman(counts: List[int], symbols: List[int], dc: bool) -> Optional[str]:
+    """libjpeg's jpeg_make_d_derived_tbl checks: at most 256 symbols, no code overflows its length (the all-ones code
+    of a length is never assigned), DC symbols at most 15."""
+    if sum(counts) > 256 or sum(counts) != len(symbols):
+        return "Huffman table with more than 256 symbols"
+    code = 0
+    for l in range(1, 17):
+        code += counts[l - 1]
+        if code >= (1 << l):
+            return "Huffman table with an overfull code length"
+        code <<= 1
+    if dc and any(s > 15 for s in symbols):
+        return "DC Huffman table with a symbol above 15"
+    return None
+
+
+def parse_header(buf) -> "JpegHeader | Unsupported":
+    """Marker walk up to the first SOS.  Returns a JpegHeader if the device decodes the file, otherwise
+    Unsupported(reason).  Never reads outside ``buf``; a truncated or malformed header is Unsupported."""
+    b = bytes(buf)
+    n = len(b)
+    if n < 4 or b[0] != 0xFF or b[1] != 0xD8:
+        return Unsupported("not a JPEG file (no SOI marker)")
+    i = 2
+    qt: Dict[int, List[int]] = {}
+    dht: Dict[Tuple[int, int], Tuple[List[int], List[int]]] = {}
+    sof = None
+    ri = 0
+    jfif = False
+    adobe = None
+    while True:
+        if i >= n:
+            return Unsupported("header ends before the first SOS")
+        if b[i] != 0xFF:
+            return Unsupported(f"garbage between markers at byte {i}")
+        while i < n and b[i] == 0xFF:
+            i += 1
+        if i >= n:
+            return Unsupported("header ends before the first SOS")
+        m = b[i]
+        i += 1
+        if m == 0x01 or 0xD0 <= m <= 0xD7:
+            continue
+        if m == 0xD9:
+            return Unsupported("EOI before any scan")
+        if m == 0xD8 or m == 0x00:
+            return Unsupported(f"unexpected marker 0xFF{m:02X} in the header")
+        if i + 2 > n:
+            return Unsupported("header ends inside a marker length")
+        L = (b[i] << 8) | b[i + 1]
+        if L < 2 or i + L > n:
+            return Unsupported(f"marker 0xFF{m:02X} runs past the end of the file")
+        seg = b[i + 2:i + L]
+        nxt = i + L
+        if m == 0xE0 and seg[:5] == b"JFIF\0":
+            jfif = True
+        elif m == 0xEE and seg[:5] == b"Adobe" and len(seg) >= 12:
+            adobe = seg[11]
+        elif m == 0xDB:
+            j = 0
+            while j < len(seg):
+                pq, tq = seg[j] >> 4, seg[j] & 15
+                size = 64 * (pq + 1)
+                if pq > 1 or tq > 3 or j + 1 + size > len(seg):
+                    return Unsupported("malformed DQT")
+                vals = seg[j + 1:j + 1 + size]
+                qt[tq] = list(vals) if pq == 0 else [(vals[2 * k] << 8) | vals[2 * k + 1] for k in range(64)]
+                j += 1 + size
+        elif m == 0xC4:
+            j = 0
+            while j < len(seg):
+                if j + 17 > len(seg):
+                    return Unsupported("malformed DHT")
+                tc, th = seg[j] >> 4, seg[j] & 15
+                counts = list(seg[j + 1:j + 17])
+                total = sum(counts)
+                if tc > 1 or th > 3 or j + 17 + total > len(seg):
+                    return Unsupported("malformed DHT")
+                syms = list(seg[j + 17:j + 17 + total])
+                err = _check_huffman(counts, syms, tc == 0)
+                if err:
+                    return Unsupported(err)
+                dht[(tc, th)] = (counts, syms)
+                j += 17 + total
+        elif m == 0xCC:
+            return Unsupported("arithmetic coding (DAC)")
+        elif m in _SOF_NAMES:
+            return Unsupported(_SOF_NAMES[m])
+        elif m in (0xC0, 0xC1):
+            if sof is not None:
+                return Unsupported("more than one SOF")
+            if len(seg) < 6:
+                return Unsupported("malformed SOF")
+            p, h, w, nf = seg[0], (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4], seg[5]
+            if len(seg) < 6 + 3 * nf:
+                return Unsupported("malformed SOF")
+            if p != 8:
+                return Unsupported(f"{p}-bit samples")
+            comps = [(seg[6 + 3 * k], seg[7 + 3 * k] >> 4, seg[7 + 3 * k] & 15, seg[8 + 3 * k]) for k in range(nf)]
+            sof = (m - 0xC0, h, w, comps)
+        elif m == 0xDD:
+            if len(seg) < 2:
+                return Unsupported("malformed DRI")
+            ri = (seg[0] << 8) | seg[1]
+        elif m == 0xDA:
+            if sof is None:
+                return Unsupported("SOS before SOF")
+            if len(seg) < 1 or len(seg) < 1 + 2 * seg[0] + 3:
+                return Unsupported("malformed SOS")
+            ns = seg[0]
+            scomps = [(seg[1 + 2 * k], seg[2 + 2 * k] >> 4, seg[2 + 2 * k] & 15) for k in range(ns)]
+            ss, se, ahal = seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns]
+            return _classify(sof, scomps, (ss, se, ahal), qt, dht, ri, nxt, jfif, adobe)
+        i = nxt
+
+
+def _classify(sof, scomps, spectral, qt, dht, ri, scan_offset, jfif, adobe):
+    kind, h, w, comps = sof
+    nf = len(comps)
+    if h < 1 or w < 1:
+        return Unsupported("height given by a DNL marker" if h == 0 else "zero width")
+    if h > MAX_SIDE or w > MAX_SIDE:
+        return Unsupported(f"{w}x{h} is beyond {MAX_SIDE} px")
+    if nf == 4:
+        return Unsupported("4 components (CMYK / YCCK)")
+    if nf not in (1, 3):
+        return Unsupported(f"{nf} components")
+    if len(scomps) != nf:
+        return Unsupported("multi-scan sequential file (a scan without every component)")
+    if [c[0] for c in scomps] != [c[0] for c in comps]:
+        return Unsupported("scan components in another order than the frame's")
+    if spectral != (0, 63, 0):
+        return Unsupported("sequential scan with a spectral selection other than 0..63")
+    if nf == 3:
+        ids = tuple(c[0] for c in comps)
+        if adobe is not None and adobe != 1:
+            return Unsupported(f"Adobe colour transform {adobe} (not YCbCr)")
+        if adobe is None and not jfif and ids != (1, 2, 3):
+            return Unsupported(f"3 components with ids {ids} and no JFIF / Adobe marker (colour space unknown)")
+        ys = (comps[0][1], comps[0][2])
+        if ys not in ((1, 1), (2, 1), (2, 2)) or any((c[1], c[2]) != (1, 1) for c in comps[1:]):
+            return Unsupported(f"sampling {[(c[1], c[2]) for c in comps]}")
+    elif not (1 <= comps[0][1] <= 4 and 1 <= comps[0][2] <= 4):
+        return Unsupported("bad sampling factors")
+    for c in comps:
+        if c[3] not in qt:
+            return Unsupported(f"quantisation table {c[3]} is not defined")
+    tables = []
+    for (_, td, ta) in scomps:
+        if (0, td) not in dht or (1, ta) not in dht:
+            return Unsupported(f"Huffman table DC {td} / AC {ta} is not defined")
+        tables.append((td, ta))
+    return JpegHeader(h=h, w=w, sof=kind, comps=comps, scan_tables=tables, qt=qt, dht=dht, restart_interval=ri,
+                      scan_offset=scan_offset, jfif=jfif, adobe_transform=adobe)
+
+
+def table_block(hd: JpegHeader) -> np.ndarray:
+    """The TABLE_BYTES table block the device reads for one image (layout: include/ttnet.h, ttnet_jpeg_desc)."""
+    blk = np.zeros(TABLE_BYTES, dtype=np.uint8)
+    q = blk[:_HUFF_OFF].view("<u2").reshape(3, 64)
+    for k, c in enumerate(hd.comps):
+        q[k] = hd.qt[c[3]]
+    for k, (td, ta) in enumerate(hd.scan_tables):
+        for t, key in enumerate(((0, td), (1, ta))):
+            counts, syms = hd.dht[key]
+            o = _HUFF_OFF + (2 * k + t) * _HUFF_BYTES
+            blk[o:o + 16] = counts
+            blk[o + 16:o + 16 + len(syms)] = syms
+    return blk
+
+
+def _pillow_decode(item, name: str, reason: str) -> np.ndarray:
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise RuntimeError(f"pack_jpeg: {name} is not decoded on the device ({reason}) and Pillow, which decodes "
+                           f"such files on the host, is not importable: {e}") from None
+    try:
+        return np.asarray(Image.open(io.BytesIO(bytes(item))).convert("RGB"))
+    except Exception as e:        # noqa: BLE001 -- name the file
+        raise RuntimeError(f"pack_jpeg: {name} is not decoded on the device ({reason}) and Pillow fails on it: {e}") from e
+
+
+class RaggedJpeg:
+    """A batch of compressed images: ``data`` (uint8 [bytes]: per JPEG item a table block and its entropy-coded
+    data, per raw item its uint8 HWC pixels, every item 16-byte aligned), ``desc`` (int64 [n, 10]: the 80-byte
+    ttnet_jpeg_desc records) and the header totals the device call needs: coefficient blocks, output bytes, the
+    largest height and width.  Move it with ``.to(device, non_blocking=True)``; ``DataLoader(pin_memory=True)``
+    calls ``.pin_memory()``."""
+
+    def __init__(self, data: torch.Tensor, desc: torch.Tensor, n_blocks: int, out_bytes: int, max_h: int, max_w: int,
+                 reasons: Optional[List[Optional[str]]] = None):
+        if data.dtype != torch.uint8 or data.dim() != 1 or desc.dtype != torch.int64 or desc.dim() != 2 or \
+                desc.shape[1] != _JDESC_WORDS:
+            raise RuntimeError(f"RaggedJpeg: expected uint8 [bytes] and int64 [n,{_JDESC_WORDS}], got {data.dtype} "
+                               f"{tuple(data.shape)}, {desc.dtype} {tuple(desc.shape)}")
+        self.data, self.desc = data, desc
+        self.n_blocks, self.out_bytes, self.max_h, self.max_w = int(n_blocks), int(out_bytes), int(max_h), int(max_w)
+        self.reasons = reasons if reasons is not None else [None] * desc.shape[0]
+
+    def __len__(self) -> int:
+        return self.desc.shape[0]
+
+    @property
+    def device(self) -> torch.device:
+        return self.data.device
+
+    def _like(self, data, desc) -> "RaggedJpeg":
+        return RaggedJpeg(data, desc, self.n_blocks, self.out_bytes, self.max_h, self.max_w, self.reasons)
+
+    def to(self, device, non_blocking: bool = False) -> "RaggedJpeg":
+        return self._like(self.data.to(device, non_blocking=non_blocking), self.desc.to(device, non_blocking=non_blocking))
+
+    def pin_memory(self) -> "RaggedJpeg":
+        return self._like(self.data.pin_memory(), self.desc.pin_memory())
+
+    def descriptors(self) -> np.ndarray:
+        return self.desc.cpu().numpy().view(JDESC_DTYPE).reshape(-1)
+
+
+def _align16(x: int) -> int:
+    return (x + 15) & ~15
+
+
+def pack_jpeg(items: Sequence, names: Optional[Sequence[str]] = None) -> RaggedJpeg:
+    """Compressed files (bytes-like) and already-decoded images (uint8 HWC [h, w, 3] arrays) -> one host RaggedJpeg,
+    in order.  A file the device does not decode is decoded here with Pillow and packed raw; ``reasons[i]`` says why.
+    Raises RuntimeError naming the item if it can be neither decoded on the device nor by Pillow."""
+    n = len(items)
+    if n < 1 or n > 65535:
+        raise RuntimeError(f"pack_jpeg: expected 1 to 65535 items, got {n}")
+    names = list(names) if names is not None else [f"item {i}" for i in range(n)]
+    plan = []                      # (kind, header or array, payload bytes)
+    reasons: List[Optional[str]] = []
+    for i, it in enumerate(items):
+        if isinstance(it, torch.Tensor):
+            it = it.numpy()
+        if isinstance(it, np.ndarray):
+            if it.dtype != np.uint8 or it.ndim != 3 or it.shape[2] != 3 or not (
+                    1 <= it.shape[0] <= MAX_SIDE and 1 <= it.shape[1] <= MAX_SIDE):
+                raise RuntimeError(f"pack_jpeg: {names[i]} must be file bytes or uint8 HWC [h, w, 3] with sides in "
+                                   f"[1, {MAX_SIDE}], got {it.dtype} {tuple(it.shape)}")
+            plan.append((KIND_RAW, np.ascontiguousarray(it), None))
+            reasons.append("already decoded")
+            continue
+        if not isinstance(it, (bytes, bytearray, memoryview)):
+            raise RuntimeError(f"pack_jpeg: {names[i]} is a {type(it).__name__}, not file bytes or a uint8 array")
+        hd = parse_header(it)
+        if isinstance(hd, Unsupported):
+            a = _pillow_decode(it, names[i], hd.reason)
+            if not (1 <= a.shape[0] <= MAX_SIDE and 1 <= a.shape[1] <= MAX_SIDE):
+                raise RuntimeError(f"pack_jpeg: {names[i]} is {a.shape[1]}x{a.shape[0]}; sides must lie in [1, {MAX_SIDE}]")
+            plan.append((KIND_RAW, np.ascontiguousarray(a), None))
+            reasons.append(hd.reason)
+        else:
+            plan.append((KIND_JPEG, hd, memoryview(bytes(it))[hd.scan_offset:]))
+            reasons.append(None)
+    desc = np.zeros(n, dtype=JDESC_DTYPE)
+    size = 0
+    out = 0
+    blocks = 0
+    for i, (kind, obj, scan) in enumerate(plan):
+        d = desc[i]
+        d["kind"] = kind
+        if kind == KIND_RAW:
+            h, w = obj.shape[:2]
+            d["data_offset"], d["data_bytes"] = size, obj.size
+            size = _align16(size + obj.size)
+            d["ncomp"] = 3
+        else:
+            h, w = obj.h, obj.w
+            d["table_offset"] = size
+            d["data_offset"], d["data_bytes"] = size + TABLE_BYTES, len(scan)
+            size = _align16(size + TABLE_BYTES + len(scan))
+            d["block_offset"] = blocks
+            blocks += obj.blocks()
+            d["ncomp"] = obj.ncomp
+            d["restart_interval"] = obj.restart_interval
+            for k, c in enumerate(obj.comps):
+                d["comp"][k] = (c[0], (c[1] << 4) | c[2], c[3], (obj.scan_tables[k][0] << 4) | obj.scan_tables[k][1])
+        d["h"], d["w"] = h, w
+        d["out_offset"] = out
+        out += h * w * 3
+    data = torch.zeros(max(size, 16), dtype=torch.uint8)
+    flat = data.numpy()
+    for (kind, obj, scan), d in zip(plan, desc):
+        o = int(d["data_offset"])
+        if kind == KIND_RAW:
+            flat[o:o + obj.size] = obj.reshape(-1)
+        else:
+            t = int(d["table_offset"])
+            flat[t:t + TABLE_BYTES] = table_block(obj)
+            flat[o:o + len(scan)] = np.frombuffer(scan, dtype=np.uint8)
+    return RaggedJpeg(data, torch.from_numpy(desc.view(np.int64).reshape(n, _JDESC_WORDS)), blocks, out,
+                      int(desc["h"].max()), int(desc["w"].max()), reasons)
+
+
+def collate_jpeg(batch):
+    """``DataLoader`` ``collate_fn`` for ``(file_bytes, target)`` samples (``FileBytesFolder``): returns
+    ``(RaggedJpeg, targets)``, the targets collated as the default collate does."""
+    files, targets = zip(*batch)
+    return pack_jpeg(files), torch.utils.data.default_collate(list(targets))
+
+
+IMG_EXTENSIONS = (".jpg", ".jpeg", ".png", ".ppm", ".bmp", ".pgm", ".tif", ".tiff", ".webp")
+
+
+class FileBytesFolder(torch.utils.data.Dataset):
+    """``torchvision.datasets.ImageFolder``'s indexing (sorted class directories, their image files sorted, walked
+    recursively) returning ``(file bytes, class index)``: the decode happens in ``collate_jpeg`` and on the device."""
+
+    def __init__(self, root: str):
+        self.root = root
+        self.classes = sorted(e.name for e in os.scandir(root) if e.is_dir())
+        if not self.classes:
+            raise FileNotFoundError(f"FileBytesFolder: no class directories in {root}")
+        self.class_to_idx = {c: i for i, c in enumerate(self.classes)}
+        self.samples = []
+        for c in self.classes:
+            for base, _, files in sorted(os.walk(os.path.join(root, c), followlinks=True)):
+                for f in sorted(files):
+                    if f.lower().endswith(IMG_EXTENSIONS):
+                        self.samples.append((os.path.join(base, f), self.class_to_idx[c]))
+        self.targets = [t for _, t in self.samples]
+
+    def __len__(self) -> int:
+        return len(self.samples)
+
+    def __getitem__(self, i):
+        path, target = self.samples[i]
+        with open(path, "rb") as f:
+            return f.read(), target
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# device side
+
+class _Ctx:
+    def __init__(self, device: torch.device):
+        self.device = device
+        h = C.c_void_p()
+        _lib.check(_lib.load().ttnet_jpeg_ctx_create(device.index, C.byref(h)))
+        self.h = h
+        self.res = (0, 0, 0)
+        # int32 [2]: corrupt images, segments decoded sequentially (added to by the device); host mirror
+        self.stats = torch.zeros(2, dtype=torch.int32, device=device)
+        self.host = torch.zeros(2, dtype=torch.int32).pin_memory()
+        self.captured = False      # a graph captured a decode on this workspace: it must never be replaced
+
+    def reserve(self, images: int, blocks: int, nbytes: int):
+        if images <= self.res[0] and blocks <= self.res[1] and nbytes <= self.res[2]:
+            return
+        if images > MAX_IMAGES:
+            raise RuntimeError(f"decode_ragged: {images} images in one batch; at most {MAX_IMAGES}")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"decode_ragged: the batch ({images} images, {blocks} blocks, {nbytes} bytes) exceeds the "
+                               f"decoder's reservation {self.res} while a graph is being captured; call "
+                               "reserve_jpeg first")
+        if self.captured:
+            raise RuntimeError(f"decode_ragged: the batch ({images} images, {blocks} blocks, {nbytes} bytes) exceeds the "
+                               f"reservation {self.res} of a lane whose workspace a captured graph decodes into; growing "
+                               "it would free that workspace under the graph.  Use another lane, or reserve_jpeg enough "
+                               "before capturing")
+        grow = lambda need, have: max(need, have, int(need * 1.25) if have else need)   # noqa: E731
+        res = (min(grow(images, self.res[0]), MAX_IMAGES), grow(blocks, self.res[1]), grow(nbytes, self.res[2]))
+        _lib.check(_lib.load().ttnet_jpeg_ctx_reserve(self.h, res[0], res[1], res[2]))
+        self.res = res
+
+
+# one decoder context (workspace) per (device, lane): decodes on different lanes may be in flight together
+_ctx: Dict[Tuple[torch.device, int], _Ctx] = {}
+MAX_IMAGES = 65535          # ttnet_jpeg_ctx_reserve's bound
+
+
+def _context(device: torch.device, lane: int = 0) -> _Ctx:
+    key = (device, int(lane))
+    if key not in _ctx:
+        with torch.cuda.device(device):
+            _ctx[key] = _Ctx(device)
+    return _ctx[key]
+
+
+def reserve_jpeg(device, max_images: int, max_blocks: int, max_bytes: int, lane: int = 0):
+    """Size a lane's device decoder workspace ahead of time (e.g. before capturing a graph)."""
+    device = torch.device(device)
+    _context(device, lane).reserve(int(max_images), int(max_blocks), int(max_bytes))
+
+
+def jpeg_counters(device=None, clear: bool = True) -> Tuple[int, int]:
+    """Synchronise ``device`` and return (corrupt images, segments decoded by the sequential fallback) counted
+    since the last clear."""
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    torch.cuda.synchronize(device)
+    bad = seq = 0
+    for (dev, _), c in _ctx.items():
+        if dev == device:
+            v = c.stats.cpu().tolist()
+            bad, seq = bad + v[0], seq + v[1]
+            if clear:
+                c.stats.zero_()
+                c.host.zero_()
+    return int(bad), int(seq)
+
+
+def _raise_corrupt(count: int):
+    raise RuntimeError(f"decode_ragged: {count} image(s) of an earlier batch had corrupt entropy-coded data (truncated, "
+                       "a bad Huffman code, a coefficient index past 63 or a missing restart marker): they were "
+                       "decoded as all-zero images")
+
+
+def check_jpeg(device=None):
+    """Synchronise ``device`` and raise if any decode on it met a corrupt image (then clear the count)."""
+    bad, _ = jpeg_counters(device, clear=True)
+    if bad:
+        _raise_corrupt(bad)
+
+
+def decode_ragged(rj: RaggedJpeg, lane: int = 0) -> RaggedU8:
+    """A RaggedJpeg on a HIP device -> the decoded RGB images (a RaggedU8 on the device, in input order), with no host
+    synchronisation (capturable in a graph once the workspace is reserved).  Each ``lane`` has its own workspace:
+    batches in flight together on different streams use different lanes; a lane must not be reused before the
+    decode issued on it has finished or been ordered before the new one by its stream.  The workspace grows with the
+    batches, except on a lane that a captured graph decodes on: a larger batch there raises (use ``reserve_jpeg``
+    before capturing, or another lane), since growing would free memory the graph still uses.  A corrupt image decodes as zeros and
+    makes a later call raise (the device count is copied to the host after each call); ``check_jpeg`` checks at
+    once."""
+    if not isinstance(rj, RaggedJpeg):
+        raise RuntimeError(f"expected a RaggedJpeg (pack_jpeg / collate_jpeg), got {type(rj).__name__}")
+    if not rj.data.is_cuda:
+        raise RuntimeError(f"the JPEG batch is on {rj.device}: move it with .to(device, non_blocking=True)")
+    dev = rj.data.device
+    ctx = _context(dev, lane)
+    capturing = torch.cuda.is_current_stream_capturing()
+    ctx.captured = ctx.captured or capturing
+    if not capturing and int(ctx.host[0]):
+        count = int(ctx.host[0])
+        ctx.stats[0].zero_()
+        ctx.host[0] = 0
+        _raise_corrupt(count)
+    n = len(rj)
+    ctx.reserve(n, rj.n_blocks, rj.data.numel())
+    data = rj.data if rj.data.data_ptr() % 16 == 0 else rj.data.clone()
+    desc = rj.desc.contiguous()
+    out = torch.empty(_align16(max(rj.out_bytes, 16)), dtype=torch.uint8, device=dev)
+    odesc = torch.empty((n, 2), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.load().ttnet_jpeg_decode_ragged(
+            ctx.h, C.c_void_p(data.data_ptr()), data.numel(), C.c_void_p(desc.data_ptr()), n, rj.n_blocks,
+            C.c_void_p(out.data_ptr()), out.numel(), C.c_void_p(odesc.data_ptr()), C.c_void_p(ctx.stats.data_ptr()),
+            C.c_void_p(stream)))
+        if not capturing:
+            ctx.host.copy_(ctx.stats, non_blocking=True)
+    return RaggedU8(out, odesc, rj.max_h, rj.max_w)
+
+
+def jpeg_eval_forward(model, rj: RaggedJpeg, lane: int = 0) -> torch.Tensor:
+    """``model(imgnet_transform(False)(Image.open(f).convert("RGB")))`` for a batch of files: decode ->
+    resize_center_crop_u8_ragged -> forward_u8, all on the current stream, no host synchronisation."""
+    return model.forward_u8(resize_center_crop_u8_ragged(decode_ragged(rj, lane=lane)), lane=lane)

@@ -4,7 +4,8 @@
 
 ``resize_center_crop_u8`` does the first two on decoded uint8 HWC images already on the device
 (libttnet: ttnet_resize_center_crop_u8, csrc/preproc.hip); the last two are fused into the stem by
-``model.forward_u8``.  JPEG decoding stays on the host (out of scope).
+``model.forward_u8``.  JPEG decoding from file bytes runs on the device too (``jpeg.py``: ``decode_ragged``,
+``jpeg_eval_forward``).
 
 A decoder batch of ImageNet images has many sizes.  ``pack_u8`` / ``collate_u8`` put such a batch into one flat
 buffer plus descriptors (``RaggedU8``), and ``resize_center_crop_u8_ragged`` resizes and crops all of it in one
