@@ -136,7 +136,9 @@ int ttnet_forward(ttnet_plan *plan, const float *x_dev, int64_t n, float *logits
  * another's; this is how the eval loop of main.py:255-275 is pipelined, evaluate.py).  Calls on
  * one plan are still issued from one thread at a time; a lane must not be reused before the
  * forward issued on it has finished or been ordered before the new one by its stream.
- * ttnet_forward is lane 0; ttnet_read_stage reads the lane used last. */
+ * ttnet_forward is lane 0.  ttnet_read_stage, ttnet_forward_from_stem_bits and the
+ * "full_listed_*" queries of ttnet_plan_query work on the lane used last: the lane of the latest
+ * ttnet_forward / _lane / _u8 call that passed its argument checks (lane 0 before any). */
 int ttnet_plan_set_lanes(ttnet_plan *plan, int lanes);
 int ttnet_forward_lane(ttnet_plan *plan, int lane, const float *x_dev, int64_t n, float *logits_dev, void *stream);
 

@@ -63,13 +63,19 @@ struct BlockTT {
 struct MultiHead {
   std::string name;
   int C = 0, H = 0, W = 0, Ho = 0, Wo = 0, off34 = 0, stride = 2;
-  uint64_t *c3_tmp = nullptr;    // full variant: conv3 output at input resolution, before the majority pool
   bool last = false;
   BlockTT c1, c2, c3, cf;
-  uint16_t *o[4] = {nullptr, nullptr, nullptr, nullptr};
-  // block-fused path (gate_fused.hip): table images; the branch dwords of a last block
-  void *img_dw = nullptr, *img_c3 = nullptr;
-  uint32_t *idx = nullptr;
+  void *img_dw = nullptr, *img_c3 = nullptr;   // block-fused path (gate_fused.hip): table images
+};
+
+// How the blocks are evaluated, fixed when the geometry is built
+enum class GatePath {
+  TwoLaunch,   // TT-small: stage 1 + convf kernels of gate.hip, activations as rows and channel words
+  Fused,       // TT-small with stride-2 blocks only: one launch per block (gate_fused.hip), activations as
+               // compact rows; TTNET_GATE_UNFUSED=1 keeps TwoLaunch
+  XSmall,      // x-small variant: row-packed branch tensors, gate_xs.hip kernels
+  Full,        // full variant (fan-in 30): direct float64 evaluation, gate_full.hip
+  VAlexnet,    // CIFAR vAlexnet variant, gate_va.hip
 };
 
 struct Timing {
@@ -104,18 +110,11 @@ struct ttnet_plan {
   std::map<std::string, Tensor> tensors;
   std::vector<std::string> key_order;
   bool finalized = false;
-  bool xs = false;                  // x-small variant: row-packed branch tensors, gate_xs.hip kernels
-  bool full = false;                // full variant (fan-in 30): direct float64 evaluation, gate_full.hip
-  bool va = false;                  // CIFAR vAlexnet variant, gate_va.hip
-  bool fused = false;               // TT-small with stride-2 blocks only: one launch per block (gate_fused.hip), activations
-                                    // as compact rows; TTNET_GATE_UNFUSED=1 keeps the two-launch kernels of gate.hip
+  GatePath path = GatePath::TwoLaunch;
   uint32_t *tap = nullptr;          // fused path: branch dwords of a non-last block, filled on demand by ttnet_read_stage
   size_t tap_elems = 0;
-  uint64_t *va_y = nullptr;         // vAlexnet: the concatenated block output [n][256][11] rows
   float *va_scale = nullptr, *va_shift = nullptr;   // vAlexnet stem BatchNorm folded
-  float *last_float = nullptr;      // full variant: relu'd output of the last block before AvgPool2d
-  uint32_t *full_fix = nullptr;     // full variant: [64] counters + the pixel lists of one grouped 1x1 block (gate_full.hip)
-  size_t full_fix_cap = 0;          // list entries
+  size_t full_fix_cap = 0;          // full variant: list entries of Lane::full_fix
   float *full_gel = nullptr;        // full variant: GELU tables of the fast kernels (launch_full_gelu_tables), shared by all lanes
 
   // stem
@@ -125,20 +124,14 @@ struct ttnet_plan {
   uint16_t *stem_wt_u8 = nullptr;   // uint8 input: split weights with the normalisation folded in
   float *stem_init_u8 = nullptr;
   float in_mean[3] = {0.485f, 0.456f, 0.406f}, in_std[3] = {0.229f, 0.224f, 0.225f};   // utils/preprocess.py:107-108
-  // activations: x_rp[i] / x_cp[i] = input of block i
-  std::vector<uint64_t *> x_rp;
-  std::vector<uint16_t *> x_cp;
-  uint16_t *feat = nullptr;         // features as two fp16 planes in lin1 fragment order
   // head
   float *w1p = nullptr;             // scratch for the permuted lin1 weights (finalize only)
   uint16_t *w1f = nullptr;          // lin1 weights, two fp16 planes in fragment order
-  float *bn_scale = nullptr, *bn_shift = nullptr, *part = nullptr;
-  uint16_t *mid_frag = nullptr;     // lin2's A operand (head_mid_kernel), rows padded to 64
+  float *bn_scale = nullptr, *bn_shift = nullptr;
   uint16_t *w2f = nullptr;          // lin2 weights, split planes in fragment order, K padded to 16
   float lin2_inv = 1.f;             // 1 / (weight prescale x activation prescale)
   size_t part_elems = 0;
   size_t table_bytes = 0, workspace_bytes = 0;
-  int64_t last_n = 0;
 
   bool profiling = false;
   // captured forward per batch size (hipGraph): one launch instead of ~11 on the host side
@@ -156,24 +149,28 @@ struct ttnet_plan {
   };
   // A lane = one set of activation buffers (+ the graphs captured over them).  Lanes share the
   // weights and truth tables; forwards on different lanes may be in flight at the same time on
-  // different streams (ttnet_forward_lane).  The workspace pointers above always mirror the
-  // lane `cur`.
+  // different streams (ttnet_forward_lane).
   struct Lane {
-    std::vector<uint64_t *> x_rp;
+    struct Block {
+      uint16_t *o[4] = {nullptr, nullptr, nullptr, nullptr};   // branch outputs out1..out4
+      uint64_t *c3_tmp = nullptr;   // full variant: conv3 output at input resolution, before the majority pool
+      uint32_t *idx = nullptr;      // fused path: the branch dwords of a last block
+    };
+    std::vector<uint64_t *> x_rp;   // x_rp[i] / x_cp[i] = input of block i
     std::vector<uint16_t *> x_cp;
-    std::vector<std::array<uint16_t *, 4>> o;
-    std::vector<uint64_t *> c3_tmp;
-    std::vector<uint32_t *> idx;
-    uint64_t *va_y = nullptr;
-    float *last_float = nullptr, *part = nullptr;
-    uint32_t *full_fix = nullptr;
-    uint16_t *feat = nullptr, *mid_frag = nullptr;
+    std::vector<Block> blk;
+    uint64_t *va_y = nullptr;       // vAlexnet: the concatenated block output [n][256][11] rows
+    float *last_float = nullptr;    // full variant: relu'd output of the last block before AvgPool2d
+    uint32_t *full_fix = nullptr;   // full variant: [64] counters + the pixel lists of one grouped 1x1 block (gate_full.hip)
+    float *part = nullptr;          // lin1's partial sums
+    uint16_t *feat = nullptr;       // features as two fp16 planes in lin1 fragment order
+    uint16_t *mid_frag = nullptr;   // lin2's A operand (head_mid_kernel), rows padded to 64
     std::map<int64_t, GraphEntry> graphs;
     std::map<int64_t, int> eager_calls;
-    int64_t last_n = 0;
+    int64_t last_n = 0;             // images of the last forward on this lane
   };
   std::vector<Lane> lanes;
-  int cur = 0;
+  int last_lane = 0;                // lane of the latest forward: ttnet_read_stage, from_stem_bits, full_listed_*
   hipStream_t cap_stream = nullptr;
   bool graphs_ok = getenv("TTNET_NO_GRAPH") == nullptr;   // plain launches only when set (debugging)
   int64_t graph_replays = 0;
@@ -284,7 +281,7 @@ int build_geometry_valexnet(ttnet_plan *pl) {
     set_error("max_batch must be positive");
     return TTNET_E_INVALID;
   }
-  pl->va = true;
+  pl->path = GatePath::VAlexnet;
   pl->p = 64;
   pl->n_classes = 10; pl->inter = 100; pl->fcsize = 256 * 11 * 11;
   pl->head = "features.7";
@@ -318,12 +315,13 @@ int build_geometry(ttnet_plan *pl) {
   if (d.variant == TTNET_VALEXNET) return build_geometry_valexnet(pl);
   int kh = 4, kw = 4, pad = 2, gsize = 16;
   if (d.variant == TTNET_SMALL) {
+    pl->path = GatePath::TwoLaunch;    // (Fused below when every block allows it)
   } else if (d.variant == TTNET_XSMALL) {
     kh = kw = 2; pad = 1; gsize = 4;
-    pl->xs = true;
+    pl->path = GatePath::XSmall;
   } else if (d.variant == TTNET_FULL) {
     gsize = 30; pad = 3;               // kernels (6,5) / (5,6): set per branch below
-    pl->full = true;
+    pl->path = GatePath::Full;
   } else {
     set_error("unknown variant %d", d.variant);
     return TTNET_E_INVALID;
@@ -336,13 +334,14 @@ int build_geometry(ttnet_plan *pl) {
     set_error("nfilter, tfilter and max_batch must be positive");
     return TTNET_E_INVALID;
   }
+  const bool full_variant = pl->path == GatePath::Full;
   const int p = d.nfilter * d.tfilter;
   pl->p = p;
   // The reference constructs any p whose group counts divide its channel counts (TT_general_imagenet_v2_small.py:
   // 165-167, :28-76); a fan-in of 16 (the truth tables of the small variant) needs p % 16 == 0, and the depthwise
   // tables of both table variants are striped by 16 channels.  Built: p in {16, 32, .., 128} for the table variants
   // (one, two or four 32-channel M-tiles in the stem kernel), p <= 64 for the full variant; anything else is refused here.
-  if (p > 128 || (pl->full && p > 64) || (!pl->full && p % 16 != 0)) {
+  if (p > 128 || (full_variant && p > 64) || (!full_variant && p % 16 != 0)) {
     set_error("p = nfilter*tfilter = %d: built for p <= 128 with p %% 16 == 0 (fan-in 16 / tables striped by 16 channels; full variant: p <= 64)", p);
     return TTNET_E_UNSUPPORTED;
   }
@@ -361,7 +360,7 @@ int build_geometry(ttnet_plan *pl) {
       set_error("--layers %d: the reference defines 0..4", d.layers);
       return TTNET_E_UNSUPPORTED;
   }
-  if (d.layers >= 3 && (pl->xs || pl->full)) {
+  if (d.layers >= 3 && d.variant != TTNET_SMALL) {
     set_error("--layers %d (stride-1 blocks) is built for the small variant only", d.layers);
     return TTNET_E_UNSUPPORTED;
   }
@@ -379,7 +378,7 @@ int build_geometry(ttnet_plan *pl) {
     const int stride = strides[i];
     mh.stride = stride;
     int ho = (h + 2 * pad - kh) / stride + 1, wo = (w + 2 * pad - kw) / stride + 1;
-    if (pl->full) {
+    if (full_variant) {
       // models/TT_general_imagenet_v2.py:98-128: conv1 is (6,5), conv2 (5,6); at 29x29 they come
       // out 15x16 / 16x15 and are padded (bottom / right) to 16x16, out3/out4 by (0,2,0,2)
       if (w == 56) { mh.off34 = 1; ho = wo = 29; }
@@ -407,7 +406,7 @@ int build_geometry(ttnet_plan *pl) {
       set_error("in_channels must be divisible by groups (in_planes=%d, group size %d)", in_planes, gsize);
       return TTNET_E_INVALID;
     }
-    const int kh1 = pl->full ? 6 : kh, kw1 = pl->full ? 5 : kw, kh2 = pl->full ? 5 : kh, kw2 = pl->full ? 6 : kw;
+    const int kh1 = full_variant ? 6 : kh, kw1 = full_variant ? 5 : kw, kh2 = full_variant ? 5 : kh, kw2 = full_variant ? 6 : kw;
     mh.c1.g = make_geom(mh.name + ".Block_conv1", in_planes, in_planes, kh1, kw1, stride, pad, in_planes, false);
     mh.c2.g = make_geom(mh.name + ".Block_conv2", in_planes, in_planes, kh2, kw2, stride, pad, in_planes, false);
     mh.c3.g = make_geom(mh.name + ".Block_conv3", in_planes, in_planes, 1, 1, 1, 0, in_planes / gsize, false);
@@ -419,7 +418,7 @@ int build_geometry(ttnet_plan *pl) {
     add_tensor(pl, mh.name + ".act.grad_scale", {}, TTNET_F32, false);
     add_block_tt(pl, mh.cf.g);
     // internal index orders (table variants only)
-    if (!pl->full)
+    if (!full_variant)
     for (BlockTT *b : {&mh.c1, &mh.c2, &mh.c3}) {
       b->perm.resize(b->g.nbits());
       for (int q = 0; q < b->g.nbits(); ++q) b->perm[q] = (uint8_t)q;
@@ -427,7 +426,7 @@ int build_geometry(ttnet_plan *pl) {
     // convf group = gsize/4 channels x 4 branches; reference interleave is channel 4c+branch (:144-147),
     // internal index bit = (gsize/4)*branch + channel-in-group
     const int nch = gsize / 4;
-    if (!pl->full) {
+    if (!full_variant) {
       mh.cf.perm.resize(gsize);
       for (int br = 0; br < 4; ++br)
         for (int cl = 0; cl < nch; ++cl) mh.cf.perm[nch * br + cl] = (uint8_t)(4 * cl + br);
@@ -437,9 +436,10 @@ int build_geometry(ttnet_plan *pl) {
     in_planes = 2 * out_planes;
   }
   if (d.variant == TTNET_SMALL && getenv("TTNET_GATE_UNFUSED") == nullptr) {
-    pl->fused = true;
+    bool fusable = true;
     for (const MultiHead &mh : pl->blocks)
-      pl->fused = pl->fused && fused_block_supported(mh.C, mh.H, mh.Ho, mh.stride, mh.c1.g.pad, mh.c1.g.kh, mh.c1.g.kw);
+      fusable = fusable && fused_block_supported(mh.C, mh.H, mh.Ho, mh.stride, mh.c1.g.pad, mh.c1.g.kh, mh.c1.g.kw);
+    if (fusable) pl->path = GatePath::Fused;
   }
   const MultiHead &lb = pl->blocks.back();
   pl->featC = lb.cf.g.out_planes;
@@ -453,51 +453,52 @@ int build_geometry(ttnet_plan *pl) {
   return TTNET_OK;
 }
 
-// Activation workspace of one lane, into the plan's current workspace pointers.  Everything is
-// zeroed once: the branch-padding borders, the k padding of lin2's A operand and the rows of the
-// lin1 operand beyond the batch are never written again.
-int alloc_workspace(ttnet_plan *pl) {
+// Activation workspace of one lane.  Everything is zeroed once: the branch-padding borders, the
+// k padding of lin2's A operand and the rows of the lin1 operand beyond the batch are never
+// written again.
+int alloc_workspace(ttnet_plan *pl, ttnet_plan::Lane &L) {
   const int nb = pl->desc.max_batch;
   size_t *ws = &pl->workspace_bytes;
   const int kpad = (pl->inter + 15) / 16 * 16;
-  if (pl->va) {
-    pl->x_rp.assign(1, nullptr);
-    pl->x_cp.assign(1, nullptr);
-    TT_TRY(dev_alloc(pl, &pl->x_rp[0], (size_t)nb * 64 * 10, true, ws));
-    TT_TRY(dev_alloc(pl, &pl->va_y, (size_t)nb * 256 * 11, true, ws));
+  const GatePath path = pl->path;
+  L.x_rp.assign(pl->blocks.size(), nullptr);
+  L.x_cp.assign(pl->blocks.size(), nullptr);
+  L.blk.assign(pl->blocks.size(), {});
+  if (path == GatePath::VAlexnet) {
+    TT_TRY(dev_alloc(pl, &L.x_rp[0], (size_t)nb * 64 * 10, true, ws));
+    TT_TRY(dev_alloc(pl, &L.va_y, (size_t)nb * 256 * 11, true, ws));
   } else {
-    pl->x_rp.assign(pl->blocks.size(), nullptr);
-    pl->x_cp.assign(pl->blocks.size(), nullptr);
     for (size_t i = 0; i < pl->blocks.size(); ++i) {
-      MultiHead &mh = pl->blocks[i];
-      if (pl->fused) {
+      const MultiHead &mh = pl->blocks[i];
+      ttnet_plan::Lane::Block &bw = L.blk[i];
+      if (path == GatePath::Fused) {
         // one activation layout: rows of uint64 / uint32 / uint16 words by width (the stem's output stays uint64)
         const size_t bytes = (size_t)nb * mh.C * mh.H * (i == 0 ? 8 : row_bytes(mh.W));
-        TT_TRY(dev_alloc(pl, &pl->x_rp[i], (bytes + 7) / 8, true, ws));
-        TT_TRY(dev_alloc(pl, &pl->x_cp[i], 4, true, ws));
-        for (int b = 0; b < 4; ++b) TT_TRY(dev_alloc(pl, &mh.o[b], 8, true, ws));
-        mh.idx = nullptr;
-        if (mh.last) TT_TRY(dev_alloc(pl, &mh.idx, (size_t)nb * (mh.C / 8) * mh.Ho * mh.Wo, true, ws));
+        TT_TRY(dev_alloc(pl, &L.x_rp[i], (bytes + 7) / 8, true, ws));
+        // x_cp and the branch outputs are unused here: placeholders so that gate_args stays valid
+        TT_TRY(dev_alloc(pl, &L.x_cp[i], 4, true, ws));
+        for (int b = 0; b < 4; ++b) TT_TRY(dev_alloc(pl, &bw.o[b], 8, true, ws));
+        if (mh.last) TT_TRY(dev_alloc(pl, &bw.idx, (size_t)nb * (mh.C / 8) * mh.Ho * mh.Wo, true, ws));
         continue;
       }
-      TT_TRY(dev_alloc(pl, &pl->x_rp[i], (size_t)nb * mh.C * mh.H, true, ws));
-      TT_TRY(dev_alloc(pl, &pl->x_cp[i], pl->full ? 8 : (size_t)nb * mh.H * mh.W * (mh.C / 16), true, ws));
-      if (pl->full) TT_TRY(dev_alloc(pl, &mh.c3_tmp, (size_t)nb * mh.C * mh.H, true, ws));
+      TT_TRY(dev_alloc(pl, &L.x_rp[i], (size_t)nb * mh.C * mh.H, true, ws));
+      TT_TRY(dev_alloc(pl, &L.x_cp[i], path == GatePath::Full ? 8 : (size_t)nb * mh.H * mh.W * (mh.C / 16), true, ws));
+      if (path == GatePath::Full) TT_TRY(dev_alloc(pl, &bw.c3_tmp, (size_t)nb * mh.C * mh.H, true, ws));
       for (int b = 0; b < 4; ++b) {
         const size_t words16 = (size_t)nb * mh.Ho * mh.Wo * (mh.C / 16), rows64 = (size_t)nb * mh.C * mh.Ho;
-        TT_TRY(dev_alloc(pl, &mh.o[b], (pl->xs || pl->full) ? rows64 * 4 : words16, true, ws));
+        TT_TRY(dev_alloc(pl, &bw.o[b], (path == GatePath::XSmall || path == GatePath::Full) ? rows64 * 4 : words16, true, ws));
       }
     }
-    if (pl->full) {
+    if (path == GatePath::Full) {
       const MultiHead &lb = pl->blocks.back();
-      TT_TRY(dev_alloc(pl, &pl->last_float, (size_t)nb * lb.cf.g.out_planes * lb.Ho * lb.Wo, true, ws));
+      TT_TRY(dev_alloc(pl, &L.last_float, (size_t)nb * lb.cf.g.out_planes * lb.Ho * lb.Wo, true, ws));
       size_t cap = 0;                                  // pixels x groups of the largest binarised 1x1 block
       for (const MultiHead &mh : pl->blocks) {
         cap = std::max(cap, (size_t)mh.c3.g.groups * mh.H * mh.W);
         if (!mh.last) cap = std::max(cap, (size_t)mh.cf.g.groups * mh.Ho * mh.Wo);
       }
       pl->full_fix_cap = cap * (size_t)nb;
-      TT_TRY(dev_alloc(pl, &pl->full_fix, 64 + pl->full_fix_cap, true, ws));
+      TT_TRY(dev_alloc(pl, &L.full_fix, 64 + pl->full_fix_cap, true, ws));
       if (!pl->full_gel) {
         TT_TRY(dev_alloc(pl, &pl->full_gel, full_gelu_tables_elems(), false, ws));
         TT_TRY(launch_full_gelu_tables(pl->full_gel, nullptr));
@@ -506,55 +507,14 @@ int alloc_workspace(ttnet_plan *pl) {
     }
   }
   const int nb_pad = (nb + 255) / 256 * 256;          // the lin1 GEMM walks whole 256-row tiles
-  TT_TRY(dev_alloc(pl, &pl->feat, frag_elems(nb_pad, pl->fcsize), true, ws));
-  TT_TRY(dev_alloc(pl, &pl->mid_frag, frag_elems((nb + 63) / 64 * 64, kpad), true, ws));
+  TT_TRY(dev_alloc(pl, &L.feat, frag_elems(nb_pad, pl->fcsize), true, ws));
+  TT_TRY(dev_alloc(pl, &L.mid_frag, frag_elems((nb + 63) / 64 * 64, kpad), true, ws));
   size_t pe = 0;
   for (int n = 1; n <= nb; n = n < 256 ? 256 : n + 256) pe = std::max(pe, gemm_f16x2_part_elems(std::min(n, nb), pl->inter, pl->fcsize / 16));
   pe = std::max(pe, gemm_f16x2_part_elems(nb, pl->inter, pl->fcsize / 16));
   pl->part_elems = pe;
-  TT_TRY(dev_alloc(pl, &pl->part, pe, false, ws));
+  TT_TRY(dev_alloc(pl, &L.part, pe, false, ws));
   return TTNET_OK;
-}
-
-void store_lane(ttnet_plan *pl, ttnet_plan::Lane &l) {
-  l.x_rp = pl->x_rp;
-  l.x_cp = pl->x_cp;
-  l.o.resize(pl->blocks.size());
-  l.c3_tmp.resize(pl->blocks.size());
-  l.idx.resize(pl->blocks.size());
-  for (size_t i = 0; i < pl->blocks.size(); ++i) {
-    for (int b = 0; b < 4; ++b) l.o[i][b] = pl->blocks[i].o[b];
-    l.c3_tmp[i] = pl->blocks[i].c3_tmp;
-    l.idx[i] = pl->blocks[i].idx;
-  }
-  l.va_y = pl->va_y;
-  l.last_float = pl->last_float;
-  l.full_fix = pl->full_fix;
-  l.part = pl->part;
-  l.feat = pl->feat;
-  l.mid_frag = pl->mid_frag;
-}
-
-void load_lane(ttnet_plan *pl, const ttnet_plan::Lane &l) {
-  pl->x_rp = l.x_rp;
-  pl->x_cp = l.x_cp;
-  for (size_t i = 0; i < pl->blocks.size(); ++i) {
-    for (int b = 0; b < 4; ++b) pl->blocks[i].o[b] = l.o[i][b];
-    pl->blocks[i].c3_tmp = l.c3_tmp[i];
-    pl->blocks[i].idx = l.idx[i];
-  }
-  pl->va_y = l.va_y;
-  pl->last_float = l.last_float;
-  pl->full_fix = l.full_fix;
-  pl->part = l.part;
-  pl->feat = l.feat;
-  pl->mid_frag = l.mid_frag;
-}
-
-void switch_lane(ttnet_plan *pl, int k) {
-  if (k == pl->cur) return;
-  load_lane(pl, pl->lanes[k]);
-  pl->cur = k;
 }
 
 int allocate(ttnet_plan *pl) {
@@ -564,7 +524,8 @@ int allocate(ttnet_plan *pl) {
   TT_HIP(hipHostGetDevicePointer((void **)&pl->range_dev, pl->range_host, 0));
   const int kpad = (pl->inter + 15) / 16 * 16;
   for (auto &kv : pl->tensors) TT_TRY(dev_alloc(pl, (uint8_t **)&kv.second.dev, kv.second.bytes, true));
-  if (pl->va) {
+  const bool valexnet = pl->path == GatePath::VAlexnet;
+  if (valexnet) {
     TT_TRY(dev_alloc(pl, &pl->va_scale, 64, false));
     TT_TRY(dev_alloc(pl, &pl->va_shift, 64, false));
   } else {
@@ -577,9 +538,9 @@ int allocate(ttnet_plan *pl) {
   }
   for (auto &mh : pl->blocks) {
     for (BlockTT *b : {&mh.c1, &mh.c2, &mh.c3, &mh.cf}) {
-      if (pl->va && b == &mh.cf) continue;            // vAlexnet has no Block_convf
+      if (valexnet && b == &mh.cf) continue;          // vAlexnet has no Block_convf
       const BlockGeom &g = b->g;
-      if (!pl->full) {
+      if (pl->path != GatePath::Full) {
         TT_TRY(dev_alloc(pl, (uint8_t **)&b->table, g.table_bytes(), true, tb));
         TT_TRY(dev_alloc(pl, &b->perm_dev, b->perm.size(), false));
         TT_HIP(hipMemcpy(b->perm_dev, b->perm.data(), b->perm.size(), hipMemcpyHostToDevice));
@@ -591,21 +552,16 @@ int allocate(ttnet_plan *pl) {
       TT_TRY(dev_alloc(pl, &b->near_dev, 1, true));
     }
   }
-  if (pl->fused)
+  if (pl->path == GatePath::Fused)
     for (auto &mh : pl->blocks) {
       TT_TRY(dev_alloc(pl, (uint8_t **)&mh.img_dw, (size_t)mh.C * 16384, false, tb));
       TT_TRY(dev_alloc(pl, (uint8_t **)&mh.img_c3, (size_t)(mh.C / 8) * 65536, false, tb));
     }
-  TT_TRY(dev_alloc(pl, &pl->w1f, frag_elems(pl->va ? 128 : (pl->inter + 127) / 128 * 128, pl->fcsize), false));
+  TT_TRY(dev_alloc(pl, &pl->w1f, frag_elems(valexnet ? 128 : (pl->inter + 127) / 128 * 128, pl->fcsize), false));
   TT_TRY(dev_alloc(pl, &pl->bn_scale, pl->inter, false));
   TT_TRY(dev_alloc(pl, &pl->bn_shift, pl->inter, false));
   TT_TRY(dev_alloc(pl, &pl->w2f, frag_elems((pl->n_classes + 63) / 64 * 64, kpad), true));
-  // lane 0
-  TT_TRY(alloc_workspace(pl));
-  pl->lanes.resize(1);
-  store_lane(pl, pl->lanes[0]);
-  pl->cur = 0;
-  return TTNET_OK;
+  return alloc_workspace(pl, pl->lanes.emplace_back());   // lane 0
 }
 
 int fetch(const Tensor &t, std::vector<float> &host) {
@@ -665,7 +621,7 @@ int build_table(ttnet_plan *pl, BlockTT &b, hipStream_t s) {
   TT_HIP(hipMemcpy(b.t1, t1.data(), t1.size() * 8, hipMemcpyHostToDevice));
   TT_HIP(hipMemcpy(b.s2, s2.data(), s2.size() * 8, hipMemcpyHostToDevice));
   TT_HIP(hipMemcpy(b.t2, t2.data(), t2.size() * 8, hipMemcpyHostToDevice));
-  if (b.user_table || pl->full) return TTNET_OK;
+  if (b.user_table || pl->path == GatePath::Full) return TTNET_OK;
   TT_HIP(hipMemsetAsync(b.near_dev, 0, sizeof(unsigned), s));
   LutBuildArgs a{};
   a.w1 = (const float *)pl->tensors[b.g.name + ".conv1.weight"].dev;
@@ -676,6 +632,17 @@ int build_table(ttnet_plan *pl, BlockTT &b, hipStream_t s) {
   a.table = b.table;
   a.near_ties = b.near_dev;
   return launch_lut_build(a, s);
+}
+
+// the near-tie counts of the tables built at finalize (after its synchronisation)
+int read_near_ties(ttnet_plan *pl) {
+  for (BlockTT *b : all_block_tts(pl)) {
+    if (b->user_table || pl->path == GatePath::Full) continue;
+    unsigned v = 0;
+    TT_HIP(hipMemcpy(&v, b->near_dev, sizeof(v), hipMemcpyDeviceToHost));
+    b->near_ties = v;
+  }
+  return TTNET_OK;
 }
 
 void begin_timing(ttnet_plan *pl, const char *name, hipStream_t s) {
@@ -703,27 +670,85 @@ void end_timing(ttnet_plan *pl, hipStream_t s) {
     if (r__ != TTNET_OK) return r__; \
   } while (0)
 
-GateBlockArgs gate_args(ttnet_plan *pl, size_t i, int n) {
-  MultiHead &mh = pl->blocks[i];
+GateBlockArgs gate_args(const ttnet_plan *pl, const ttnet_plan::Lane &L, size_t i, int n) {
+  const MultiHead &mh = pl->blocks[i];
+  uint16_t *const *o = L.blk[i].o;
   GateBlockArgs a{};
   a.n = n; a.C = mh.C; a.H = mh.H; a.W = mh.W; a.Ho = mh.Ho; a.Wo = mh.Wo; a.off34 = mh.off34;
   a.kh1 = mh.c1.g.kh; a.kw1 = mh.c1.g.kw; a.kh2 = mh.c2.g.kh; a.kw2 = mh.c2.g.kw;
   a.stride = mh.c1.g.stride; a.pad = mh.c1.g.pad;
   a.cf_bits = mh.cf.g.cout_g();
-  a.x_rp = pl->x_rp[i]; a.x_cp = pl->x_cp[i];
+  a.x_rp = L.x_rp[i]; a.x_cp = L.x_cp[i];
   a.t_dw1 = (const uint8_t *)mh.c1.table; a.t_dw2 = (const uint8_t *)mh.c2.table;
   a.t_c3 = (const uint16_t *)mh.c3.table;
-  a.o1 = mh.o[0]; a.o2 = mh.o[1]; a.o3 = mh.o[2]; a.o4 = mh.o[3];
+  a.o1 = o[0]; a.o2 = o[1]; a.o3 = o[2]; a.o4 = o[3];
   return a;
+}
+
+// the branch outputs of block i as uint64 rows (x-small and full variants)
+std::array<uint64_t *, 4> branch_rows(const ttnet_plan::Lane &L, size_t i) {
+  uint16_t *const *o = L.blk[i].o;
+  return {(uint64_t *)o[0], (uint64_t *)o[1], (uint64_t *)o[2], (uint64_t *)o[3]};
 }
 
 static const char *kS1Names[] = {"gate_stage1.f4", "gate_stage1.f5", "gate_stage1.f6", "gate_stage1.f7"};
 static const char *kPfNames[] = {"gate_pf.f4", "gate_pf.f5", "gate_pf.f6", "gate_pf.f7"};
 
+// One block on the two launches of gate.hip: stage 1, then convf (or the last block's pool + flatten)
+int run_two_launch_block(ttnet_plan *pl, const ttnet_plan::Lane &L, size_t i, int n, hipStream_t s) {
+  const MultiHead &mh = pl->blocks[i];
+  const GateBlockArgs a = gate_args(pl, L, i, n);
+  TT_TIMED(pl, kS1Names[std::min<size_t>(i, 3)], s, launch_gate_stage1(a, s));
+  if (!mh.last)
+    TT_TIMED(pl, kPfNames[std::min<size_t>(i, 3)], s, launch_gate_pf(a, (const uint8_t *)mh.cf.table, L.x_cp[i + 1], L.x_rp[i + 1], s));
+  else
+    TT_TIMED(pl, "gate_last", s, launch_gate_last(a, (const float *)mh.cf.table, L.feat, pl->range_dev, s));
+  return TTNET_OK;
+}
+
+// One block in one launch (gate_fused.hip); a last block adds the pool + flatten launch
+int run_fused_block(ttnet_plan *pl, const ttnet_plan::Lane &L, size_t i, int n, hipStream_t s) {
+  static const char *kBlkNames[] = {"gate_block.f4", "gate_block.f5", "gate_block.f6", "gate_block.f7"};
+  const MultiHead &mh = pl->blocks[i];
+  uint32_t *idx = L.blk[i].idx;
+  FusedBlockArgs f{};
+  f.n = n; f.C = mh.C; f.H = mh.H; f.Ho = mh.Ho; f.off34 = mh.off34; f.last = mh.last ? 1 : 0;
+  f.x = L.x_rp[i]; f.img_c3 = mh.img_c3; f.img_dw = mh.img_dw;
+  f.t_cf = mh.last ? nullptr : (const uint8_t *)mh.cf.table;
+  f.y = mh.last ? nullptr : (void *)L.x_rp[i + 1];
+  f.idx = mh.last ? idx : nullptr;
+  TT_TIMED(pl, kBlkNames[std::min<size_t>(i, 3)], s, launch_gate_block(f, s));
+  if (mh.last)
+    TT_TIMED(pl, "gate_last", s, launch_gate_last(gate_args(pl, L, i, n), (const float *)mh.cf.table, L.feat, pl->range_dev, s, idx));
+  return TTNET_OK;
+}
+
+// One block of the x-small variant (gate_xs.hip)
+int run_xs_block(ttnet_plan *pl, const ttnet_plan::Lane &L, size_t i, int n, hipStream_t s) {
+  const MultiHead &mh = pl->blocks[i];
+  const std::array<uint64_t *, 4> o64 = branch_rows(L, i);
+  TT_TIMED(pl, kS1Names[std::min<size_t>(i, 3)], s, launch_xs_branches(gate_args(pl, L, i, n), mh.c3.table, o64.data(), s));
+  if (!mh.last)
+    TT_TIMED(pl, kPfNames[std::min<size_t>(i, 3)], s, launch_xs_pf(n, mh.C, mh.Ho, mh.Wo, mh.cf.g.cout_g(), o64.data(), mh.cf.table, L.x_rp[i + 1], s));
+  else
+    TT_TIMED(pl, "gate_last", s,
+             launch_xs_last(n, mh.C, mh.Ho, mh.Wo, mh.cf.g.cout_g(), o64.data(), (const float *)mh.cf.table, L.feat, pl->range_dev, s));
+  return TTNET_OK;
+}
+
+// The vAlexnet block + Flatten (gate_va.hip), from the stem bits in x_rp[0]
+int run_va_block(ttnet_plan *pl, const ttnet_plan::Lane &L, int n, hipStream_t s) {
+  const MultiHead &mh = pl->blocks[0];
+  TT_TIMED(pl, "va.block", s, launch_va_block(L.x_rp[0], mh.c1.table, mh.c2.table, mh.c3.table, L.va_y, n, s));
+  TT_TIMED(pl, "va.flatten", s, launch_va_feat(L.va_y, L.feat, n, s));
+  return TTNET_OK;
+}
+
 // One block of the full variant: direct float64 evaluation (gate_full.hip)
-int run_full_block(ttnet_plan *pl, size_t i, int n, hipStream_t s) {
-  MultiHead &mh = pl->blocks[i];
-  uint64_t *o64[4] = {(uint64_t *)mh.o[0], (uint64_t *)mh.o[1], (uint64_t *)mh.o[2], (uint64_t *)mh.o[3]};
+int run_full_block(ttnet_plan *pl, const ttnet_plan::Lane &L, size_t i, int n, hipStream_t s) {
+  const MultiHead &mh = pl->blocks[i];
+  const std::array<uint64_t *, 4> o64 = branch_rows(L, i);
+  uint64_t *const c3_tmp = L.blk[i].c3_tmp;
   auto wts = [&](const BlockTT &b, const char *leaf) { return (const float *)pl->tensors[b.g.name + leaf].dev; };
   for (int br = 0; br < 2; ++br) {
     const BlockTT &b = br ? mh.c2 : mh.c1;
@@ -733,14 +758,14 @@ int run_full_block(ttnet_plan *pl, size_t i, int n, hipStream_t s) {
     a.ho = (mh.H + 2 * a.pad - a.kh) / a.stride + 1;
     a.wo = (mh.W + 2 * a.pad - a.kw) / a.stride + 1;
     a.Ho = mh.Ho; a.pad_t = 0; a.pad_l = 0;          // out1 / out2 only ever get bottom / right zero padding
-    a.x_rp = pl->x_rp[i];
+    a.x_rp = L.x_rp[i];
     a.w1 = wts(b, ".conv1.weight"); a.w2 = wts(b, ".conv2.weight");
     a.s1 = b.s1; a.t1 = b.t1; a.s2 = b.s2; a.t2 = b.t2;
     a.out = o64[br];
     a.gel = pl->full_gel;
-    if (pl->full_fix) {                                // (the list area is shared with the 1x1 blocks: launches are ordered)
-      a.fix_count = pl->full_fix;
-      a.fix_list = pl->full_fix + 64;
+    if (L.full_fix) {                                // (the list area is shared with the 1x1 blocks: launches are ordered)
+      a.fix_count = L.full_fix;
+      a.fix_list = L.full_fix + 64;
       a.fix_cap = (uint32_t)std::min<size_t>(pl->full_fix_cap, 0x7FFFFFFFu);
     }
     static const char *const kDw[2][4] = {{"full.conv1.f4", "full.conv1.f5", "full.conv1.f6", "full.conv1.f7"},
@@ -752,18 +777,18 @@ int run_full_block(ttnet_plan *pl, size_t i, int n, hipStream_t s) {
     FullPwArgs a{};
     a.n = n; a.H = mh.H; a.W = mh.W;
     a.groups = b.g.groups; a.cin = b.g.cin_g(); a.mid = b.g.mid_g(); a.cout = b.g.cout_g(); a.Cout = b.g.out_planes;
-    a.Csrc = mh.C; a.interleaved = 0; a.src[0] = pl->x_rp[i];
+    a.Csrc = mh.C; a.interleaved = 0; a.src[0] = L.x_rp[i];
     a.w1 = wts(b, ".conv1.weight"); a.w2 = wts(b, ".conv2.weight");
     a.s1 = b.s1; a.t1 = b.t1; a.s2 = b.s2; a.t2 = b.t2;
-    a.out_rp = mh.c3_tmp; a.out_float = nullptr;
+    a.out_rp = c3_tmp; a.out_float = nullptr;
     a.gel = pl->full_gel ? pl->full_gel + full_gelu_tables_elems() / 2 : nullptr;
-    a.fix_count = pl->full_fix; a.fix_list = pl->full_fix ? pl->full_fix + 64 : nullptr; a.range_flag = pl->range_dev;
+    a.fix_count = L.full_fix; a.fix_list = L.full_fix ? L.full_fix + 64 : nullptr; a.range_flag = pl->range_dev;
     static const char *const kC3[4] = {"full.conv3.f4", "full.conv3.f5", "full.conv3.f6", "full.conv3.f7"};
     TT_TIMED(pl, kC3[std::min<size_t>(i, 3)], s, launch_full_pw(a, s));
     TT_TIMED(pl, "full.maj3", s,
-             launch_rp_majority(mh.c3_tmp, o64[2], n, mh.C, mh.H, mh.W, mh.Ho, mh.off34, mh.off34, s));
+             launch_rp_majority(c3_tmp, o64[2], n, mh.C, mh.H, mh.W, mh.Ho, mh.off34, mh.off34, s));
     TT_TIMED(pl, "full.maj4", s,
-             launch_rp_majority(pl->x_rp[i], o64[3], n, mh.C, mh.H, mh.W, mh.Ho, mh.off34, mh.off34, s));
+             launch_rp_majority(L.x_rp[i], o64[3], n, mh.C, mh.H, mh.W, mh.Ho, mh.off34, mh.off34, s));
   }
   {
     const BlockTT &b = mh.cf;
@@ -775,13 +800,13 @@ int run_full_block(ttnet_plan *pl, size_t i, int n, hipStream_t s) {
     a.w1 = wts(b, ".conv1.weight"); a.w2 = wts(b, ".conv2.weight");
     a.s1 = b.s1; a.t1 = b.t1; a.s2 = b.s2; a.t2 = b.t2;
     a.gel = pl->full_gel ? pl->full_gel + full_gelu_tables_elems() / 2 : nullptr;
-    a.fix_count = pl->full_fix; a.fix_list = pl->full_fix ? pl->full_fix + 64 : nullptr; a.range_flag = pl->range_dev;
+    a.fix_count = L.full_fix; a.fix_list = L.full_fix ? L.full_fix + 64 : nullptr; a.range_flag = pl->range_dev;
     if (mh.last) {
-      a.out_rp = nullptr; a.out_float = pl->last_float;
+      a.out_rp = nullptr; a.out_float = L.last_float;
       TT_TIMED(pl, "full.convf_last", s, launch_full_pw(a, s));
-      TT_TIMED(pl, "full.pool", s, launch_full_pool_split(pl->last_float, pl->feat, n, b.g.out_planes, mh.Ho, mh.Wo, pl->range_dev, s));
+      TT_TIMED(pl, "full.pool", s, launch_full_pool_split(L.last_float, L.feat, n, b.g.out_planes, mh.Ho, mh.Wo, pl->range_dev, s));
     } else {
-      a.out_rp = pl->x_rp[i + 1]; a.out_float = nullptr;
+      a.out_rp = L.x_rp[i + 1]; a.out_float = nullptr;
       static const char *const kCf[4] = {"full.convf.f4", "full.convf.f5", "full.convf.f6", "full.convf.f7"};
       TT_TIMED(pl, kCf[std::min<size_t>(i, 3)], s, launch_full_pw(a, s));
     }
@@ -800,69 +825,32 @@ int prepare_lin2(ttnet_plan *pl, const std::string &key, hipStream_t s) {
                               pl->inter, pl->inter);
 }
 
-// Classifier_scale from the features in pl->feat
-int run_head(ttnet_plan *pl, int n, float *logits, int polynomial, const std::string &head, hipStream_t s) {
+// Classifier_scale from the features in L.feat
+int run_head(ttnet_plan *pl, const ttnet_plan::Lane &L, int n, float *logits, hipStream_t s) {
+  const int polynomial = pl->path == GatePath::VAlexnet ? 0 : 1;
   const int s1 = gemm_f16x2_splits(n, pl->inter, pl->fcsize / 16);
-  TT_TIMED(pl, "head.lin1", s, launch_gemm_f16x2(pl->feat, pl->w1f, pl->part, n, pl->inter, pl->fcsize, s1, s));
+  TT_TIMED(pl, "head.lin1", s, launch_gemm_f16x2(L.feat, pl->w1f, L.part, n, pl->inter, pl->fcsize, s1, s));
   TT_TIMED(pl, polynomial ? "head.bn_poly" : "head.bn", s,
-           launch_head_mid(pl->part, s1, pl->bn_scale, pl->bn_shift, pl->mid_frag, n, pl->inter, polynomial, pl->range_dev, s));
+           launch_head_mid(L.part, s1, pl->bn_scale, pl->bn_shift, L.mid_frag, n, pl->inter, polynomial, pl->range_dev, s));
   TT_TIMED(pl, "head.lin2", s,
-           launch_lin2_f16x2(pl->mid_frag, pl->w2f, (const float *)pl->tensors[head + ".lin2.bias"].dev, pl->lin2_inv, logits, n,
+           launch_lin2_f16x2(L.mid_frag, pl->w2f, (const float *)pl->tensors[pl->head + ".lin2.bias"].dev, pl->lin2_inv, logits, n,
                              pl->n_classes, pl->inter, s));
   return TTNET_OK;
 }
 
-// vAlexnet: block + Flatten + Classifier_scale from the stem bits in x_rp[0]
-int run_va_tail(ttnet_plan *pl, int n, float *logits, hipStream_t s) {
-  MultiHead &mh = pl->blocks[0];
-  TT_TIMED(pl, "va.block", s, launch_va_block(pl->x_rp[0], mh.c1.table, mh.c2.table, mh.c3.table, pl->va_y, n, s));
-  TT_TIMED(pl, "va.flatten", s, launch_va_feat(pl->va_y, pl->feat, n, s));
-  TT_TRY(run_head(pl, n, logits, 0, "features.7", s));
-  pl->last_n = n;
-  return TTNET_OK;
-}
-
-int run_from_blocks(ttnet_plan *pl, int n, float *logits, hipStream_t s) {
+// Blocks + head from the stem's output in L.x_rp[0]
+int run_from_blocks(ttnet_plan *pl, ttnet_plan::Lane &L, int n, float *logits, hipStream_t s) {
   for (size_t i = 0; i < pl->blocks.size(); ++i) {
-    MultiHead &mh = pl->blocks[i];
-    GateBlockArgs a = gate_args(pl, i, n);
-    if (pl->full) {
-      TT_TRY(run_full_block(pl, i, n, s));
-      continue;
-    }
-    if (pl->xs) {
-      uint64_t *const o64[4] = {(uint64_t *)mh.o[0], (uint64_t *)mh.o[1], (uint64_t *)mh.o[2], (uint64_t *)mh.o[3]};
-      TT_TIMED(pl, kS1Names[i], s, launch_xs_branches(a, mh.c3.table, o64, s));
-      if (!mh.last)
-        TT_TIMED(pl, kPfNames[i], s,
-                 launch_xs_pf(n, mh.C, mh.Ho, mh.Wo, mh.cf.g.cout_g(), o64, mh.cf.table, pl->x_rp[i + 1], s));
-      else
-        TT_TIMED(pl, "gate_last", s,
-                 launch_xs_last(n, mh.C, mh.Ho, mh.Wo, mh.cf.g.cout_g(), o64, (const float *)mh.cf.table, pl->feat, pl->range_dev, s));
-      continue;
-    }
-    if (pl->fused) {
-      static const char *kBlkNames[] = {"gate_block.f4", "gate_block.f5", "gate_block.f6", "gate_block.f7"};
-      FusedBlockArgs f{};
-      f.n = n; f.C = mh.C; f.H = mh.H; f.Ho = mh.Ho; f.off34 = mh.off34; f.last = mh.last ? 1 : 0;
-      f.x = pl->x_rp[i]; f.img_c3 = mh.img_c3; f.img_dw = mh.img_dw;
-      f.t_cf = mh.last ? nullptr : (const uint8_t *)mh.cf.table;
-      f.y = mh.last ? nullptr : (void *)pl->x_rp[i + 1];
-      f.idx = mh.last ? mh.idx : nullptr;
-      TT_TIMED(pl, kBlkNames[std::min<size_t>(i, 3)], s, launch_gate_block(f, s));
-      if (mh.last) TT_TIMED(pl, "gate_last", s, launch_gate_last(a, (const float *)mh.cf.table, pl->feat, pl->range_dev, s, mh.idx));
-      continue;
-    }
-    TT_TIMED(pl, kS1Names[i], s, launch_gate_stage1(a, s));
-    if (!mh.last) {
-      TT_TIMED(pl, kPfNames[i], s,
-               launch_gate_pf(a, (const uint8_t *)mh.cf.table, pl->x_cp[i + 1], pl->x_rp[i + 1], s));
-    } else {
-      TT_TIMED(pl, "gate_last", s, launch_gate_last(a, (const float *)mh.cf.table, pl->feat, pl->range_dev, s));
+    switch (pl->path) {
+      case GatePath::TwoLaunch: TT_TRY(run_two_launch_block(pl, L, i, n, s)); break;
+      case GatePath::Fused: TT_TRY(run_fused_block(pl, L, i, n, s)); break;
+      case GatePath::XSmall: TT_TRY(run_xs_block(pl, L, i, n, s)); break;
+      case GatePath::Full: TT_TRY(run_full_block(pl, L, i, n, s)); break;
+      case GatePath::VAlexnet: TT_TRY(run_va_block(pl, L, n, s)); break;
     }
   }
-  TT_TRY(run_head(pl, n, logits, 1, pl->head, s));
-  pl->last_n = n;
+  TT_TRY(run_head(pl, L, n, logits, s));
+  L.last_n = n;
   return TTNET_OK;
 }
 
@@ -993,7 +981,7 @@ int ttnet_plan_finalize(ttnet_plan *pl, void *stream) {
       return TTNET_E_STATE;
     }
   }
-  if (pl->va) {
+  if (pl->path == GatePath::VAlexnet) {
     std::vector<double> sc, sh;
     TT_TRY(fold_bn(pl, "features.2", sc, sh));
     TT_TRY(upload_f32(pl->va_scale, sc));
@@ -1013,12 +1001,7 @@ int ttnet_plan_finalize(ttnet_plan *pl, void *stream) {
                                 s));
     TT_TRY(prepare_lin2(pl, "features.7.lin2.weight", s));
     TT_HIP(hipStreamSynchronize(s));
-    for (BlockTT *b : all_block_tts(pl)) {
-      if (b->user_table) continue;
-      unsigned v = 0;
-      TT_HIP(hipMemcpy(&v, b->near_dev, sizeof(v), hipMemcpyDeviceToHost));
-      b->near_ties = v;
-    }
+    TT_TRY(read_near_ties(pl));
     pl->finalized = true;
     return TTNET_OK;
   }
@@ -1041,7 +1024,7 @@ int ttnet_plan_finalize(ttnet_plan *pl, void *stream) {
   }
   for (auto &mh : pl->blocks) {
     for (BlockTT *b : {&mh.c1, &mh.c2, &mh.c3, &mh.cf}) TT_TRY(build_table(pl, *b, s));
-    if (pl->fused) TT_TRY(launch_fused_images(mh.c1.table, mh.c2.table, mh.c3.table, mh.C, mh.img_dw, mh.img_c3, s));
+    if (pl->path == GatePath::Fused) TT_TRY(launch_fused_images(mh.c1.table, mh.c2.table, mh.c3.table, mh.C, mh.img_dw, mh.img_c3, s));
   }
   {
     std::vector<double> sc, sh;
@@ -1061,36 +1044,31 @@ int ttnet_plan_finalize(ttnet_plan *pl, void *stream) {
     TT_TRY(prepare_lin2(pl, pl->head + ".lin2.weight", s));
   }
   TT_HIP(hipStreamSynchronize(s));
-  for (auto &mh : pl->blocks)
-    for (BlockTT *b : {&mh.c1, &mh.c2, &mh.c3, &mh.cf}) {
-      if (b->user_table || pl->full) continue;
-      unsigned v = 0;
-      TT_HIP(hipMemcpy(&v, b->near_dev, sizeof(v), hipMemcpyDeviceToHost));
-      b->near_ties = v;
-    }
+  TT_TRY(read_near_ties(pl));
   pl->finalized = true;
   return TTNET_OK;
 }
 
 namespace {
 
-int forward_eager(ttnet_plan *pl, const void *x_dev, bool u8, int64_t n, float *logits_dev, hipStream_t s) {
+int forward_eager(ttnet_plan *pl, ttnet_plan::Lane &L, const void *x_dev, bool u8, int64_t n, float *logits_dev, hipStream_t s) {
   pl->timing_used = 0;
-  if (pl->va) {
+  if (pl->path == GatePath::VAlexnet) {
     if (u8) {
       set_error("uint8 input is not implemented for the vAlexnet variant");
       return TTNET_E_UNSUPPORTED;
     }
     TT_TIMED(pl, "va.stem", s,
              launch_va_stem((const float *)x_dev, (const float *)pl->tensors["features.0.weight"].dev,
-                            (const float *)pl->tensors["features.0.bias"].dev, pl->va_scale, pl->va_shift, pl->x_rp[0],
+                            (const float *)pl->tensors["features.0.bias"].dev, pl->va_scale, pl->va_shift, L.x_rp[0],
                             (int)n, s));
-    return run_va_tail(pl, (int)n, logits_dev, s);
+  } else {
+    TT_TIMED(pl, "stem", s,
+             launch_stem(x_dev, u8, pl->norm_tab, u8 ? pl->stem_wt_u8 : pl->stem_wt, u8 ? pl->stem_init_u8 : pl->stem_init, L.x_rp[0],
+                         pl->path == GatePath::TwoLaunch ? L.x_cp[0] : nullptr, (int)n, pl->p, pl->range_dev, s,
+                         (pl->lanes.size() >= 2 && !u8 && pl->path != GatePath::Full) ? 128 : 256));      // (stem.hip: half the CUs for float32 input with batches in flight)
   }
-  TT_TIMED(pl, "stem", s,
-           launch_stem(x_dev, u8, pl->norm_tab, u8 ? pl->stem_wt_u8 : pl->stem_wt, u8 ? pl->stem_init_u8 : pl->stem_init, pl->x_rp[0], (pl->full || pl->fused || pl->xs) ? nullptr : pl->x_cp[0], (int)n,
-                       pl->p, pl->range_dev, s, (pl->lanes.size() >= 2 && !u8 && !pl->full) ? 128 : 256));      // (stem.hip: half the CUs for float32 input with batches in flight)
-  return run_from_blocks(pl, (int)n, logits_dev, s);
+  return run_from_blocks(pl, L, (int)n, logits_dev, s);
 }
 
 // The forward is a fixed chain of ~11 launches whose host cost (~20 us each) equals the device
@@ -1147,11 +1125,11 @@ bool own_params(hipGraphNode_t node, const int *sizes, int nargs, hipKernelNodeP
 
 // *status: what forward_eager returned inside the capture (a caller error -- bad argument, range flag -- is reported to
 // the caller as such and does not turn graph replay off for the plan; only a failure of the capture machinery does)
-bool capture_forward(ttnet_plan *pl, const void *x_dev, bool u8, int64_t n, float *logits_dev, ttnet_plan::GraphEntry &e, int *status) {
+bool capture_forward(ttnet_plan *pl, ttnet_plan::Lane &L, const void *x_dev, bool u8, int64_t n, float *logits_dev, ttnet_plan::GraphEntry &e, int *status) {
   *status = TTNET_OK;
   if (!pl->cap_stream && hipStreamCreateWithFlags(&pl->cap_stream, hipStreamNonBlocking) != hipSuccess) return false;
   if (hipStreamBeginCapture(pl->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return false;
-  const int r = forward_eager(pl, x_dev, u8, n, logits_dev, pl->cap_stream);
+  const int r = forward_eager(pl, L, x_dev, u8, n, logits_dev, pl->cap_stream);
   hipGraph_t g = nullptr;
   const hipError_t ee = hipStreamEndCapture(pl->cap_stream, &g);
   if (r != TTNET_OK || ee != hipSuccess || !g) {
@@ -1185,9 +1163,10 @@ bool capture_forward(ttnet_plan *pl, const void *x_dev, bool u8, int64_t n, floa
   const int first_n = stem_kernel_arg_sizes(&first_sizes);
   static const int first_sizes_va[7] = {8, 8, 8, 8, 8, 8, 4};     // va_stem_kernel(x, w, bias, scale, shift, rp, n)
   static const int last_sizes[8] = {8, 8, 8, 4, 8, 4, 4, 4};      // lin2_f16x2_kernel(A, B, bias, inv, out, M, N, KS)
-  e.first_nargs = pl->va ? 7 : first_n;
+  const bool valexnet = pl->path == GatePath::VAlexnet;
+  e.first_nargs = valexnet ? 7 : first_n;
   if (e.first_nargs > 12) return false;
-  if (!own_params(e.first, pl->va ? first_sizes_va : first_sizes, e.first_nargs, e.first_p, e.first_argv, e.first_args) ||
+  if (!own_params(e.first, valexnet ? first_sizes_va : first_sizes, e.first_nargs, e.first_p, e.first_argv, e.first_args) ||
       !own_params(e.last, last_sizes, kLastKernelArgs, e.last_p, e.last_argv, e.last_args))
     return false;
   // the two slots that will be patched must hold exactly the pointers this capture ran with
@@ -1207,15 +1186,13 @@ int ttnet_plan_set_lanes(ttnet_plan *pl, int lanes) {
     return TTNET_E_INVALID;
   }
   (void)hipSetDevice(pl->device);
-  const int keep = pl->cur;
   if ((int)pl->lanes.size() < lanes && pl->lanes.size() == 1) TT_TRY(invalidate_graphs(pl));      // (the stem's grid depends on lanes >= 2)
   while ((int)pl->lanes.size() < lanes) {
-    // allocate a fresh workspace into the plan's pointers, file it as a new lane, restore
-    pl->lanes[pl->cur].last_n = pl->last_n;
-    TT_TRY(alloc_workspace(pl));
-    pl->lanes.emplace_back();
-    store_lane(pl, pl->lanes.back());
-    load_lane(pl, pl->lanes[keep]);
+    const int r = alloc_workspace(pl, pl->lanes.emplace_back());
+    if (r != TTNET_OK) {
+      pl->lanes.pop_back();                             // (what it did allocate stays owned by the plan)
+      return r;
+    }
   }
   return TTNET_OK;
 }
@@ -1226,7 +1203,7 @@ int forward_impl(ttnet_plan *pl, int lane, const void *x_dev, bool u8, int64_t n
   // The input contract of ttnet.h (16-byte aligned float32, 4-byte aligned uint8: the stem reads it with 16 / 12-byte
   // buffer loads) is checked HERE, in front of the replay, the capture and the plain path alike: a cached graph
   // only has its first argument re-pointed and would otherwise take any pointer.
-  if (!pl->va && ((uintptr_t)x_dev & (u8 ? 3u : 15u)) != 0) {
+  if (pl->path != GatePath::VAlexnet && ((uintptr_t)x_dev & (u8 ? 3u : 15u)) != 0) {
     set_error("forward: the input must be %d-byte aligned", u8 ? 4 : 16);
     return TTNET_E_INVALID;
   }
@@ -1238,31 +1215,27 @@ int forward_impl(ttnet_plan *pl, int lane, const void *x_dev, bool u8, int64_t n
     set_error("forward: lane %d but the plan has %d (ttnet_plan_set_lanes)", lane, (int)pl->lanes.size());
     return TTNET_E_INVALID;
   }
-  if (lane != pl->cur) {
-    pl->lanes[pl->cur].last_n = pl->last_n;
-    switch_lane(pl, lane);
-    pl->last_n = pl->lanes[lane].last_n;
-  }
+  pl->last_lane = lane;
   ttnet_plan::Lane &L = pl->lanes[lane];
   hipStream_t s = (hipStream_t)stream;
-  if (pl->profiling || !pl->graphs_ok) return forward_eager(pl, x_dev, u8, n, logits_dev, s);
+  if (pl->profiling || !pl->graphs_ok) return forward_eager(pl, L, x_dev, u8, n, logits_dev, s);
   const int64_t key = 2 * n + (u8 ? 1 : 0);               // one graph per (batch size, input kind)
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (s && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-    return forward_eager(pl, x_dev, u8, n, logits_dev, s);   // the caller is capturing us into a graph of their own
+    return forward_eager(pl, L, x_dev, u8, n, logits_dev, s);   // the caller is capturing us into a graph of their own
   auto it = L.graphs.find(key);
   if (it == L.graphs.end()) {
-    if (++L.eager_calls[key] <= 2) return forward_eager(pl, x_dev, u8, n, logits_dev, s);   // warm: attributes, lazy module load
+    if (++L.eager_calls[key] <= 2) return forward_eager(pl, L, x_dev, u8, n, logits_dev, s);   // warm: attributes, lazy module load
     ttnet_plan::GraphEntry e;
     int cap_status = TTNET_OK;
-    if (!capture_forward(pl, x_dev, u8, n, logits_dev, e, &cap_status)) {
+    if (!capture_forward(pl, L, x_dev, u8, n, logits_dev, e, &cap_status)) {
       drop_graph(e);
       if (cap_status != TTNET_OK) {          // the forward itself refused the call: the caller's error, graphs stay on
         --L.eager_calls[key];
         return cap_status;
       }
       graphs_off(pl, "capture or instantiation of the forward failed");   // stay on plain launches
-      return forward_eager(pl, x_dev, u8, n, logits_dev, s);
+      return forward_eager(pl, L, x_dev, u8, n, logits_dev, s);
     }
     pl->graph_captures++;
     if (L.graphs.size() >= 8) {                                // bound the cache: drop the smallest batch size
@@ -1295,9 +1268,9 @@ int forward_impl(ttnet_plan *pl, int lane, const void *x_dev, bool u8, int64_t n
     drop_graph(e);
     L.graphs.erase(it);
     graphs_off(pl, "hipGraphExecKernelNodeSetParams / hipGraphLaunch failed");
-    return forward_eager(pl, x_dev, u8, n, logits_dev, s);
+    return forward_eager(pl, L, x_dev, u8, n, logits_dev, s);
   }
-  pl->last_n = n;
+  L.last_n = n;
   pl->timing_used = 0;
   pl->graph_replays++;
   return TTNET_OK;
@@ -1317,7 +1290,7 @@ int ttnet_forward_u8(ttnet_plan *pl, int lane, const uint8_t *x_nhwc_dev, int64_
 }
 
 int ttnet_plan_set_input_norm(ttnet_plan *pl, const float *mean3, const float *std3) {
-  if (!pl || !mean3 || !std3 || pl->va) {
+  if (!pl || !mean3 || !std3 || pl->path == GatePath::VAlexnet) {
     set_error("set_input_norm: null argument (or the vAlexnet variant, which has no uint8 path)");
     return TTNET_E_INVALID;
   }
@@ -1340,11 +1313,11 @@ int ttnet_forward_from_stem_bits(ttnet_plan *pl, const uint64_t *rows_dev, int64
   TT_TRY(check_ready(pl, rows_dev, n, logits_dev));
   hipStream_t s = (hipStream_t)stream;
   pl->timing_used = 0;
+  ttnet_plan::Lane &L = pl->lanes[pl->last_lane];
   const MultiHead &b0 = pl->blocks[0];
-  TT_HIP(hipMemcpyAsync(pl->x_rp[0], rows_dev, (size_t)n * b0.C * b0.H * 8, hipMemcpyDeviceToDevice, s));
-  if (pl->va) return run_va_tail(pl, (int)n, logits_dev, s);
-  if (!pl->full && !pl->xs && !pl->fused) TT_TRY(launch_rp_to_cp(pl->x_rp[0], pl->x_cp[0], (int)n, b0.C, b0.H, b0.W, s));
-  return run_from_blocks(pl, (int)n, logits_dev, s);
+  TT_HIP(hipMemcpyAsync(L.x_rp[0], rows_dev, (size_t)n * b0.C * b0.H * 8, hipMemcpyDeviceToDevice, s));
+  if (pl->path == GatePath::TwoLaunch) TT_TRY(launch_rp_to_cp(L.x_rp[0], L.x_cp[0], (int)n, b0.C, b0.H, b0.W, s));
+  return run_from_blocks(pl, L, (int)n, logits_dev, s);
 }
 
 int ttnet_read_stage(ttnet_plan *pl, const char *stage, int64_t n, void *dst, size_t dst_bytes, int on_device,
@@ -1353,8 +1326,9 @@ int ttnet_read_stage(ttnet_plan *pl, const char *stage, int64_t n, void *dst, si
     set_error("null argument");
     return TTNET_E_INVALID;
   }
-  if (n < 1 || n > pl->last_n) {
-    set_error("read_stage: n=%lld but the last forward ran %lld images", (long long)n, (long long)pl->last_n);
+  const ttnet_plan::Lane &L = pl->lanes[pl->last_lane];
+  if (n < 1 || n > L.last_n) {
+    set_error("read_stage: n=%lld but the last forward ran %lld images", (long long)n, (long long)L.last_n);
     return TTNET_E_STATE;
   }
   hipStream_t s = (hipStream_t)stream;
@@ -1369,81 +1343,62 @@ int ttnet_read_stage(ttnet_plan *pl, const char *stage, int64_t n, void *dst, si
     TT_HIP(hipStreamSynchronize(s));
     return check_range(pl);
   };
-  if (pl->va) {
-    if (st == "features.4") return copy_out(pl->x_rp[0], (size_t)n * 64 * 10 * 8);
-    if (st == "features.5") return copy_out(pl->va_y, (size_t)n * 256 * 11 * 8);
-    if (st == "flatten") {
-      float *tmp = nullptr;
-      const size_t elems = (size_t)n * pl->fcsize;
-      TT_HIP(hipMalloc((void **)&tmp, elems * 4));
-      int r = launch_va_frag_to_flat(pl->feat, tmp, (int)n, s);
-      if (r == TTNET_OK) r = copy_out(tmp, elems * 4);
-      (void)hipFree(tmp);
-      return r;
-    }
+  // a stage kept in another layout: convert(tmp) writes it in the ABI's layout into a temporary of `bytes`
+  auto convert_out = [&](size_t bytes, auto convert) -> int {
+    void *tmp = nullptr;
+    TT_HIP(hipMalloc(&tmp, bytes));
+    int r = convert(tmp);
+    if (r == TTNET_OK) r = copy_out(tmp, bytes);
+    (void)hipFree(tmp);
+    return r;
+  };
+  const GatePath path = pl->path;
+  if (st == "flatten")
+    return convert_out((size_t)n * pl->fcsize * 4, [&](void *tmp) {
+      return path == GatePath::VAlexnet ? launch_va_frag_to_flat(L.feat, (float *)tmp, (int)n, s)
+                                        : launch_frag_to_reference_order(L.feat, (float *)tmp, (int)n, pl->featC / 16, pl->featPP, s);
+    });
+  if (path == GatePath::VAlexnet) {
+    if (st == "features.4") return copy_out(L.x_rp[0], (size_t)n * 64 * 10 * 8);
+    if (st == "features.5") return copy_out(L.va_y, (size_t)n * 256 * 11 * 8);
     set_error("unknown stage %s", stage);
     return TTNET_E_INVALID;
   }
   for (size_t i = 0; i < pl->blocks.size(); ++i) {
-    MultiHead &mh = pl->blocks[i];
+    const MultiHead &mh = pl->blocks[i];
     const std::string in_name = i == 0 ? std::string("features.3") : pl->blocks[i - 1].name;
-    if (st == in_name && pl->fused && i > 0) {          // compact rows -> the uint64 rows of the ABI
+    if (st == in_name) {
       const size_t rows = (size_t)n * mh.C * mh.H;
-      uint64_t *tmp = nullptr;
-      TT_HIP(hipMalloc((void **)&tmp, rows * 8));
-      int r = launch_widen_rows(pl->x_rp[i], tmp, rows, mh.W, s);
-      if (r == TTNET_OK) r = copy_out(tmp, rows * 8);
-      (void)hipFree(tmp);
-      return r;
+      if (path == GatePath::Fused && i > 0)           // compact rows -> the uint64 rows of the ABI
+        return convert_out(rows * 8, [&](void *tmp) { return launch_widen_rows(L.x_rp[i], (uint64_t *)tmp, rows, mh.W, s); });
+      return copy_out(L.x_rp[i], rows * 8);
     }
-    if (st == in_name) return copy_out(pl->x_rp[i], (size_t)n * mh.C * mh.H * 8);
     for (int b = 0; b < 4; ++b) {
-      if (st == mh.name + ".out" + std::to_string(b + 1) && pl->fused) {
-        // the branch tensors never reach HBM on the fused path: a last block's dwords are its output; for
-        // the others the block is run once more on its (still resident) input with the tap buffer attached
-        const size_t words = (size_t)n * mh.C * mh.Ho, dwords = (size_t)pl->desc.max_batch * (mh.C / 8) * mh.Ho * mh.Wo;
-        const uint32_t *src = mh.idx;
-        if (!mh.last) {
-          if (pl->tap_elems < dwords) {
-            uint32_t *t = nullptr;
-            TT_TRY(dev_alloc(pl, &t, dwords, true));
-            pl->tap = t;
-            pl->tap_elems = dwords;
-          }
-          FusedBlockArgs f{};
-          f.n = (int)n; f.C = mh.C; f.H = mh.H; f.Ho = mh.Ho; f.off34 = mh.off34; f.last = 0;
-          f.x = pl->x_rp[i]; f.img_c3 = mh.img_c3; f.img_dw = mh.img_dw; f.t_cf = (const uint8_t *)mh.cf.table;
-          f.y = pl->x_rp[i + 1]; f.idx = pl->tap;
-          TT_TRY(launch_gate_block(f, s));
-          src = pl->tap;
+      if (st != mh.name + ".out" + std::to_string(b + 1)) continue;
+      const size_t words = (size_t)n * mh.C * mh.Ho;
+      if (path == GatePath::XSmall || path == GatePath::Full) return copy_out(L.blk[i].o[b], words * 8);
+      if (path == GatePath::TwoLaunch)
+        return convert_out(words * 8, [&](void *tmp) { return launch_cp_to_rp(L.blk[i].o[b], (uint64_t *)tmp, (int)n, mh.C, mh.Ho, mh.Wo, s); });
+      // Fused: the branch tensors never reach HBM.  A last block's dwords are its output; for the others the
+      // block is run once more on its (still resident) input with the tap buffer attached
+      const uint32_t *src = L.blk[i].idx;
+      if (!mh.last) {
+        const size_t dwords = (size_t)pl->desc.max_batch * (mh.C / 8) * mh.Ho * mh.Wo;
+        if (pl->tap_elems < dwords) {
+          uint32_t *t = nullptr;
+          TT_TRY(dev_alloc(pl, &t, dwords, true));
+          pl->tap = t;
+          pl->tap_elems = dwords;
         }
-        uint64_t *tmp = nullptr;
-        TT_HIP(hipMalloc((void **)&tmp, words * 8));
-        int r = launch_branch_rows(src, tmp, (int)n, mh.C, mh.Ho, b, s);
-        if (r == TTNET_OK) r = copy_out(tmp, words * 8);
-        (void)hipFree(tmp);
-        return r;
+        FusedBlockArgs f{};
+        f.n = (int)n; f.C = mh.C; f.H = mh.H; f.Ho = mh.Ho; f.off34 = mh.off34; f.last = 0;
+        f.x = L.x_rp[i]; f.img_c3 = mh.img_c3; f.img_dw = mh.img_dw; f.t_cf = (const uint8_t *)mh.cf.table;
+        f.y = L.x_rp[i + 1]; f.idx = pl->tap;
+        TT_TRY(launch_gate_block(f, s));
+        src = pl->tap;
       }
-      if (st == mh.name + ".out" + std::to_string(b + 1)) {
-        const size_t words = (size_t)n * mh.C * mh.Ho;
-        if (pl->xs || pl->full) return copy_out(mh.o[b], words * 8);
-        uint64_t *tmp = nullptr;
-        TT_HIP(hipMalloc((void **)&tmp, words * 8));
-        int r = launch_cp_to_rp(mh.o[b], tmp, (int)n, mh.C, mh.Ho, mh.Wo, s);
-        if (r == TTNET_OK) r = copy_out(tmp, words * 8);
-        (void)hipFree(tmp);
-        return r;
-      }
+      return convert_out(words * 8, [&](void *tmp) { return launch_branch_rows(src, (uint64_t *)tmp, (int)n, mh.C, mh.Ho, b, s); });
     }
-  }
-  if (st == "flatten") {
-    float *tmp = nullptr;
-    const size_t elems = (size_t)n * pl->fcsize;
-    TT_HIP(hipMalloc((void **)&tmp, elems * 4));
-    int r = launch_frag_to_reference_order(pl->feat, tmp, (int)n, pl->featC / 16, pl->featPP, s);
-    if (r == TTNET_OK) r = copy_out(tmp, elems * 4);
-    (void)hipFree(tmp);
-    return r;
   }
   set_error("unknown stage %s", stage);
   return TTNET_E_INVALID;
@@ -1459,7 +1414,7 @@ int ttnet_plan_get_table(ttnet_plan *pl, const char *name, void *dst_host, size_
     set_error("no Block_TT named %s", name);
     return TTNET_E_INVALID;
   }
-  if (pl->full) {
+  if (pl->path == GatePath::Full) {
     set_error("the full variant (fan-in 30) has no truth tables: 2^30 entries per output bit");
     return TTNET_E_UNSUPPORTED;
   }
@@ -1507,7 +1462,7 @@ int ttnet_plan_set_table(ttnet_plan *pl, const char *name, const void *src_host,
     set_error("no Block_TT named %s", name);
     return TTNET_E_INVALID;
   }
-  if (pl->full) {
+  if (pl->path == GatePath::Full) {
     set_error("the full variant (fan-in 30) has no truth tables: 2^30 entries per output bit");
     return TTNET_E_UNSUPPORTED;
   }
@@ -1542,7 +1497,7 @@ int ttnet_plan_set_table(ttnet_plan *pl, const char *name, const void *src_host,
   TT_HIP(hipMemcpy(b->table, raw.data(), raw.size(), hipMemcpyHostToDevice));
   b->user_table = true;
   b->near_ties = -1;
-  if (pl->fused)                            // the kernels read images derived from the conv1 / conv2 / conv3 tables
+  if (pl->path == GatePath::Fused)          // the kernels read images derived from the conv1 / conv2 / conv3 tables
     for (auto &mh : pl->blocks)
       if (b == &mh.c1 || b == &mh.c2 || b == &mh.c3) {
         TT_TRY(launch_fused_images(mh.c1.table, mh.c2.table, mh.c3.table, mh.C, mh.img_dw, mh.img_c3, nullptr));
@@ -1584,12 +1539,13 @@ int ttnet_plan_query(ttnet_plan *pl, const char *what, int64_t *out) {
     *pl->range_host = 0u;
   }
   else if (w == "lanes") *out = (int64_t)pl->lanes.size();
-  else if (w == "full_listed_pw" || w == "full_listed_dw") {      // full variant: (pixel, group) pairs / outputs sent to float64 so far (current lane)
+  else if (w == "full_listed_pw" || w == "full_listed_dw") {      // full variant: (pixel, group) pairs / outputs sent to float64 so far (lane used last)
     uint32_t v[2] = {0, 0};
-    if (pl->full_fix) {
+    const uint32_t *fix = pl->lanes[pl->last_lane].full_fix;
+    if (fix) {
       TT_HIP(hipSetDevice(pl->device));
       TT_HIP(hipDeviceSynchronize());
-      TT_HIP(hipMemcpy(v, pl->full_fix + 62, sizeof(v), hipMemcpyDeviceToHost));
+      TT_HIP(hipMemcpy(v, fix + 62, sizeof(v), hipMemcpyDeviceToHost));
     }
     *out = v[w == "full_listed_dw" ? 1 : 0];
   }

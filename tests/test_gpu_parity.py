@@ -367,18 +367,23 @@ def test_graph_replay_matches_plain_launches(small_model, dev):
 
 def test_lanes_in_flight_match_lane0(dev):
     """Three batches in flight on three lanes / streams (shared tables, separate activation
-    workspaces) give the logits of the same batches run one at a time; evaluate() pipelined
-    equals evaluate() serial."""
+    workspaces) give the logits of the same batches run one at a time; read_stage reads the
+    lane used last; each lane adds one workspace; evaluate() pipelined equals evaluate() serial."""
     from scale_imagenet_amd.evaluate import evaluate
     spec, st = spec_and_state("small")
     m = ttnet.TT_vf_19lv3_imgnet_small(args_for("small"))
     m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in st.items()})
     m = m.to(dev).eval().reserve(16)
     xs = [torch.from_numpy(synth.synth_images(16, first=16 * i)).to(dev) for i in range(6)]
+    want, want_rows = [], []
     with torch.no_grad():
-        want = [m(x).clone() for x in xs]
+        for x in xs:
+            want.append(m(x).clone())
+            want_rows.append(m.read_stage("features.3", 16).copy())
+    ws1 = m._any_plan().query("workspace_bytes")
     m.set_lanes(3)
     assert m._any_plan().query("lanes") == 3
+    assert m._any_plan().query("workspace_bytes") == 3 * ws1
     streams = [torch.cuda.Stream(dev) for _ in range(3)]
     got = [None] * len(xs)
     with torch.no_grad():
@@ -389,6 +394,10 @@ def test_lanes_in_flight_match_lane0(dev):
     torch.cuda.synchronize()
     for g, w in zip(got, want):
         assert torch.equal(g, w)
+    assert np.array_equal(m.read_stage("features.3", 16), want_rows[5])      # the last forward: xs[5] on lane 2
+    with torch.no_grad():
+        m(xs[1], lane=1)
+    assert np.array_equal(m.read_stage("features.3", 16), want_rows[1])
     with pytest.raises(Exception):
         m(xs[0], lane=5)
     batches = [(x.cpu(), torch.from_numpy(synth.synth_targets(16, first=16 * i))) for i, x in enumerate(xs)]
