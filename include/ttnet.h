@@ -211,42 +211,78 @@ int ttnet_resize_center_crop_u8_ragged(const uint8_t *src_dev, int64_t src_bytes
  * then the AC Huffman table of its scan as DHT holds them, counts[16] + symbols[256] (272 bytes each) at
  * 384 + 272 * (2c + ac).  comp[c] = {id, h_samp << 4 | v_samp, quant table, dc << 4 | ac table} (informative: the
  * block already holds the selected tables).  block_offset: first of this image's coefficient blocks (MCU columns x MCU
- * rows x blocks per MCU) in the decoder's workspace.  kind 1: data_offset holds uint8 HWC [h][w][3].  Both: the
- * decoded image goes to [out_offset, + h * w * 3) of dst. */
+ * rows x blocks per MCU) in the decoder's workspace.  kind 1: data_offset holds uint8 HWC [h][w][3].  All kinds: the
+ * decoded image goes to [out_offset, + h * w * 3) of dst.
+ *
+ * kind 2 (opt-in: pack_jpeg(..., progressive=True)): a complete Huffman-coded progressive file (SOF2), 8-bit, same
+ * colour spaces, samplings and sizes as kind 0, with or without restart intervals, at most TTNET_JPEG_MAX_SCANS scans.
+ * The host walks every scan and validates the progression as libjpeg's jdphuff.c does (T.81 G.1.1.1).  Refused there,
+ * hence decoded on the host: a progression that leaves any coefficient of any component short of bit 0 (libjpeg would
+ * smooth such blocks), a scan without data, an SOS naming an undefined table, an AC scan before the component's DC scan
+ * or with several components, a refinement whose Ah is not the previous Al, quantisation tables redefined between
+ * scans, more scans than the bound, SOF10, 12-bit, 4 components, DNL.  Layout: the 2048-byte table block at table_offset
+ * holds quant[3][64] at 0 as for kind 0 and, at byte reserved[1] (>= 384, a multiple of 4), reserved[0] & 255 records of
+ * ttnet_jpeg_scan in file order; (reserved[0] >> 16) & 255 Huffman tables of 272 bytes (counts[16] + symbols[256])
+ * follow the block at table_offset + 2048, each distinct table of the file once; (reserved[0] >> 8) & 255 is the number
+ * of rounds of the scans' schedule.  [data_offset, + data_bytes) is the file from the first scan's entropy-coded data to
+ * the end of the last scan's; restart_interval is the first scan's (informative).  block_offset and the block count are
+ * those of a sequential file of the same frame.  With the flag off, and for every other file, nothing changes. */
+#define TTNET_JPEG_MAX_SCANS 32   /* libjpeg-turbo's default script has 10 scans for colour, 6 for greyscale */
 typedef struct ttnet_jpeg_desc {
   int64_t data_offset, data_bytes;
   int64_t table_offset;
   int64_t out_offset;
   int64_t block_offset;
   int32_t h, w;
-  int32_t kind;              /* 0: JPEG decoded on the device, 1: raw pixels copied */
+  int32_t kind;              /* 0: sequential JPEG decoded on the device, 1: raw pixels copied, 2: progressive JPEG */
   int32_t ncomp;             /* 1 or 3 */
   int32_t restart_interval;  /* MCUs per restart segment, 0: none */
   uint8_t comp[3][4];
-  int32_t reserved[2];
+  int32_t reserved[2];       /* kind 2: {scans | rounds << 8 | Huffman tables << 16, scan list offset}; else 0 */
 } ttnet_jpeg_desc;
+
+/* One scan of a kind-2 image, 32 bytes.  [data_offset, + data_bytes) is its entropy-coded data relative to the image's
+ * data_offset (up to the next marker that is not FF00 / RSTn).  comp: frame component indices, increasing; a scan of one
+ * component covers that component's own ceil(w_c / 8) x ceil(h_c / 8) blocks and its restart interval counts blocks, a
+ * scan of several covers the frame's MCUs.  table[q]: index into the image's Huffman pool of the table in force for
+ * scan component q when the SOS was read (the DC table in a DC first pass, table[0] the AC table in an AC scan; unused
+ * in a DC refinement).  slot = 4 * round + wave: scans of one round are decoded side by side, and a scan's round comes
+ * after the round of every earlier scan that codes one of its (component, coefficient) pairs. */
+typedef struct ttnet_jpeg_scan {
+  uint32_t data_offset, data_bytes;
+  uint16_t restart_interval;  /* blocks or MCUs per restart segment in this scan, 0: none */
+  uint8_t ncomp;              /* components in the scan: 1 .. 3 (AC scans: 1) */
+  uint8_t slot;
+  uint8_t comp[4];
+  uint8_t ss, se, ah, al;     /* spectral band Ss .. Se (DC: 0, 0), successive approximation Ah, Al */
+  uint8_t table[4];
+  int32_t reserved[2];
+} ttnet_jpeg_scan;
 
 typedef struct ttnet_jpeg_ctx ttnet_jpeg_ctx;
 
 /* A decoder context on `device`; its workspace is sized by ttnet_jpeg_ctx_reserve (the only calls that allocate). */
 int ttnet_jpeg_ctx_create(int device, ttnet_jpeg_ctx **out);
 /* Sizes the workspace for batches of up to max_images images, max_blocks coefficient blocks in all and max_bytes bytes of
- * source buffer (about 128 bytes per block + 19 bytes per source byte).  Replaces (and frees) the previous workspace:
+ * source buffer (about 128 bytes per block + 19 bytes per source byte; progressive images use the same coefficient blocks
+ * and nothing more).  Replaces (and frees) the previous workspace:
  * call it outside graph capture, with no decode in flight on the context. */
 int ttnet_jpeg_ctx_reserve(ttnet_jpeg_ctx *ctx, int64_t max_images, int64_t max_blocks, int64_t max_bytes);
 /* Decodes n images described by jdesc_dev (device memory) from [src_dev, src_dev + src_bytes) into dst_dev, back to back
  * at each descriptor's out_offset, and writes their ttnet_image_desc records (out_offset, h, w) to dst_desc_dev: the
- * input of ttnet_resize_center_crop_u8_ragged.  n_blocks is the descriptors' total of coefficient blocks.  Three kernel
- * launches on `stream`; nothing is allocated, copied or waited for, nothing is cached per image, so the call can be
+ * input of ttnet_resize_center_crop_u8_ragged.  n_blocks is the descriptors' total of coefficient blocks.  Four kernel
+ * launches on `stream` whatever the batch holds (the progressive kernel leaves at once for images of kind 0 and 1); nothing is allocated, copied or waited for, nothing is cached per image, so the call can be
  * captured into a graph and replayed with new images within the same reservation.  TTNET_E_INVALID when n, n_blocks or
  * src_bytes exceed the reservation.  src_dev and jdesc_dev 16-byte aligned, dst_desc_dev 8-byte aligned.
  *   - corrupt entropy-coded data (truncated, a bad Huffman code, a coefficient index past 63, a missing or misnumbered
- *     RST) makes that image all zero and adds 1 to stats_dev[0]; a descriptor outside the buffers or the reservation
- *     does too, and its output record gets h = w = 0.  The kernels read nothing outside the source buffer and write
+ *     RST; in a progressive scan also data that runs out, a coefficient index past Se, an end-of-band run past the
+ *     scan's last block) makes that image all zero and adds 1 to stats_dev[0]; a descriptor or scan record outside the
+ *     buffers or the reservation does too, and its output record gets h = w = 0.  The kernels read nothing outside the source buffer and write
  *     nothing outside the workspace and each image's own output span, whatever the bitstream holds.
  *   - stats_dev[1] (int32, added to) counts restart segments whose subsequence synchronisation was still changing after
  *     its round bound and that were then walked sequentially (per segment; the settled segments of the same image are
  *     not).  TTNET_JPEG_SEQUENTIAL=1 walks every segment so and counts them all (diagnostic: the result is the same).
+ *     Progressive images are not counted here and ignore the switch.
  *   - the workspace (ttnet_jpeg_ctx_reserve) is baked into a captured graph: it must not be re-reserved while such a
  *     graph may still be replayed. */
 int ttnet_jpeg_decode_ragged(ttnet_jpeg_ctx *ctx, const uint8_t *src_dev, int64_t src_bytes,

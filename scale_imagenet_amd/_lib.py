@@ -36,6 +36,13 @@ class JpegDesc(C.Structure):
                 ("comp", (C.c_uint8 * 4) * 3), ("reserved", C.c_int32 * 2)]
 
 
+class JpegScan(C.Structure):
+    """ttnet_jpeg_scan: one scan of a progressive image (include/ttnet.h), 32 bytes."""
+    _fields_ = [("data_offset", C.c_uint32), ("data_bytes", C.c_uint32), ("restart_interval", C.c_uint16),
+                ("ncomp", C.c_uint8), ("slot", C.c_uint8), ("comp", C.c_uint8 * 4), ("ss", C.c_uint8), ("se", C.c_uint8),
+                ("ah", C.c_uint8), ("al", C.c_uint8), ("table", C.c_uint8 * 4), ("reserved", C.c_int32 * 2)]
+
+
 class TTNetError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"libttnet status {status}: {message}")

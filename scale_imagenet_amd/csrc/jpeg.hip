@@ -1,8 +1,8 @@
-// Baseline / extended sequential Huffman JPEG decoding of a ragged batch on the GPU (ttnet_jpeg_decode_ragged):
+// Baseline / extended sequential and (kind 2) progressive Huffman JPEG decoding of a ragged batch on the GPU (ttnet_jpeg_decode_ragged):
 // PIL.Image.open(f).convert("RGB") of ImageFolder's default loader (main.py:208), byte for byte as Pillow with
 // libjpeg-turbo decodes it (islow IDCT, fancy upsampling, jdcolor.c's SCALEBITS 16 tables).
 //
-// Three kernels, all reading their image's descriptor and tables from the batch buffer (nothing per geometry is
+// Four kernels, all reading their image's descriptor and tables from the batch buffer (nothing per geometry is
 // cached or uploaded; a captured graph replays with new images):
 //   1. jpeg_destuff_kernel   one workgroup per image: drops FF 00 stuffing, splits at RSTn (sequence checked) and
 //                            stops at any other marker, byte-parallel with workgroup prefix sums.  The clean stream is
@@ -17,6 +17,10 @@
 //                            subsequence places the output; a last pass writes int16 coefficients in zig-zag order
 //                            (every position of a block is written once, zero runs included); DC differences are
 //                            resolved by a segmented prefix sum per component, reset at each restart.
+//   2b. jpeg_progressive_kernel  one workgroup per progressive (SOF2, kind 2) image: zeroes the image's coefficients,
+//                            then decodes its scans, up to four side by side (one per wave) in the rounds the host
+//                            scheduled; each scan is walked sequentially with wave-uniform control flow, lane k holding
+//                            coefficient k of the current block.  Sequential images leave at once, and the other way round.
 //   3. jpeg_idct_kernel      workgroups over (image, tile of one MCU row x kTileMcus MCU columns): dequantise + islow
 //                            IDCT into LDS planes (chroma with one context row / column around the tile), fancy
 //                            upsampling, YCbCr -> RGB, dword stores.  Raw-passthrough images are copied here.
@@ -39,6 +43,8 @@ constexpr int kTileMcus = 32;                   // MCU columns per IDCT tile
 constexpr int kIdctGrid = 32;                   // workgroups per image of the IDCT kernel (they stride over its tiles)
 constexpr int kMinSub = 2048, kSubs = 256;     // subsequence bits (at least) and count per large segment
 constexpr int kLut = 9;                         // first-level Huffman lookup bits
+constexpr int kMaxScans = TTNET_JPEG_MAX_SCANS; // scans of a progressive image
+constexpr int kWaves = kThreads / 64;           // scans of a progressive image decoded side by side
 
 enum : int { ST_OK = 0, ST_BAD_DESC = 1, ST_CORRUPT = 2 };
 
@@ -96,8 +102,15 @@ __device__ inline bool desc_ok(const DecodeArgs &a, const ttnet_jpeg_desc &d, in
   if (d.out_offset < 0 || d.out_offset > a.dst_bytes - out) return false;
   if (d.data_offset < 0 || d.data_bytes < 0 || d.data_offset > a.src_bytes - d.data_bytes) return false;
   if (d.kind == 1) return d.data_bytes >= out;
-  if (d.kind != 0) return false;
+  if (d.kind != 0 && d.kind != 2) return false;
   if (d.table_offset < 0 || d.table_offset > a.src_bytes - kTableBytes || (d.table_offset & 1)) return false;
+  if (d.kind == 2) {       // scan list inside the table block, Huffman pool behind it, both inside the source buffer
+    const int ns = d.reserved[0] & 255, nr = (d.reserved[0] >> 8) & 255, nt = (d.reserved[0] >> 16) & 255;
+    if (ns < 1 || ns > kMaxScans || nr < 1 || nr > ns || (d.reserved[0] >> 24)) return false;
+    if (d.reserved[1] < kHuffOff || d.reserved[1] > kTableBytes - ns * (int)sizeof(ttnet_jpeg_scan) || (d.reserved[1] & 3))
+      return false;
+    if ((d.table_offset & 3) || d.table_offset > a.src_bytes - kTableBytes - (int64_t)nt * kHuffBytes) return false;
+  }
   if (d.ncomp == 3) {
     const int hs = d.comp[0][1] >> 4, vs = d.comp[0][1] & 15;
     if (!((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))) return false;
@@ -108,7 +121,7 @@ __device__ inline bool desc_ok(const DecodeArgs &a, const ttnet_jpeg_desc &d, in
   if (d.restart_interval < 0 || d.data_bytes >= (int64_t)1 << 28) return false;  // bit positions (8 * bytes) fit int32
   const Geo g = geometry(d);
   if (d.block_offset < 0 || d.block_offset > a.ws.max_blocks - g.nblocks) return false;
-  if (g.nseg > d.data_bytes / 2 + 1) return false;                                // cannot hold that many RSTs
+  if (d.kind == 0 && g.nseg > d.data_bytes / 2 + 1) return false;                 // cannot hold that many RSTs
   (void)i;
   return true;
 }
@@ -254,6 +267,24 @@ __device__ inline int huff_decode(const Huff &h, uint32_t v) {
   return 0;
 }
 
+// fills `h` from a DHT-style table (counts[16], symbols[256]); h.lut must be zero.  Bounded whatever the counts hold.
+__device__ inline void build_huff(Huff &h, const uint8_t *src) {
+  int code = 0, kk = 0;
+  for (int l = 1; l <= 16; ++l) {
+    const int cnt = src[l - 1];
+    h.valoff[l] = kk - code;
+    h.maxcode[l] = cnt ? code + cnt - 1 : -1;
+    for (int q = 0; q < cnt; ++q, ++code, ++kk) {
+      if (l <= kLut) {
+        const int lo = code << (kLut - l), hi = (code + 1) << (kLut - l);
+        for (int x = lo; x < hi && x < (1 << kLut); ++x) h.lut[x] = (uint16_t)((l << 8) | src[16 + (kk & 255)]);
+      }
+    }
+    code <<= 1;
+  }
+  for (int q = 0; q < 256; ++q) h.vals[q] = src[16 + q];
+}
+
 __device__ inline int extend(int r, int s) { return r < (1 << (s - 1)) ? r - (1 << s) + 1 : r; }
 
 struct DecodeResult {
@@ -352,22 +383,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_entropy_kernel(DecodeArgs a) {
   __syncthreads();
   if (t < 2 * g.ncomp) {
     const int comp = t >> 1, isac = t & 1;
-    Huff &h = s_h[isac * 3 + comp];
-    const uint8_t *src = tb + kHuffOff + (2 * comp + isac) * kHuffBytes;
-    int code = 0, kk = 0;
-    for (int l = 1; l <= 16; ++l) {
-      const int cnt = src[l - 1];
-      h.valoff[l] = kk - code;
-      h.maxcode[l] = cnt ? code + cnt - 1 : -1;
-      for (int q = 0; q < cnt; ++q, ++code, ++kk) {
-        if (l <= kLut) {
-          const int lo = code << (kLut - l), hi = (code + 1) << (kLut - l);
-          for (int x = lo; x < hi && x < (1 << kLut); ++x) h.lut[x] = (uint16_t)((l << 8) | src[16 + (kk & 255)]);
-        }
-      }
-      code <<= 1;
-    }
-    for (int q = 0; q < 256; ++q) h.vals[q] = src[16 + q];
+    build_huff(s_h[isac * 3 + comp], tb + kHuffOff + (2 * comp + isac) * kHuffBytes);
   }
   // subsequence length: at least kMinSub bits, about kSubs subsequences for a large single-segment image.  Bit
   // synchronisation is quick, but the position in the MCU (c) only re-synchronises after some hundreds of symbols.
@@ -552,6 +568,316 @@ __global__ __launch_bounds__(kThreads) void jpeg_entropy_kernel(DecodeArgs a) {
   if (t == 0) {
     *info = make_int4(s_err ? ST_CORRUPT : ST_OK, nseg, clean, nitems);
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// 2b. progressive (SOF2) entropy decoding
+//
+// One workgroup per kind-2 image, its scans spread over the workgroup's waves in rounds that the host scheduled so
+// that a scan runs after every scan it refines (ttnet_jpeg_scan::slot = 4 * round + wave).  A wave walks its scan
+// sequentially with wave-uniform control flow: the bit reader and the Huffman state are the same in every lane, and
+// lane k holds coefficient k (zig-zag) of the current block, so that a block is loaded and stored with one coalesced
+// access and the refinement walk tests "is coefficient k non-zero" in a ballot mask instead of a dependent load.
+
+// Bits of one scan, un-stuffed on the fly.  Stops in front of any marker; bytes come from aligned 8-byte words.
+struct ProgReader {
+  const uint8_t *src;
+  int64_t src_bytes;
+  int64_t base;                 // scan's first byte in src; [base, base + n) is inside [0, src_bytes)
+  int n, pos;
+  uint64_t acc;                 // the next `cnt` bits at the top, zeros below
+  int cnt;
+  bool stop;                    // a marker or the end of the data lies at `pos`
+  bool bad;                     // bits were asked for that the scan does not have, or a code without a symbol
+  int64_t cw_idx;
+  uint64_t cw;
+
+  __device__ inline int byte_at(int p) {
+    const int64_t a = base + p, wi = a >> 3;
+    if (wi != cw_idx) {
+      cw_idx = wi;
+      if ((wi + 1) * 8 <= src_bytes) {
+        cw = *(const uint64_t *)(src + wi * 8);
+      } else {
+        cw = 0;
+        for (int q = 0; q < 8; ++q)
+          if (wi * 8 + q < src_bytes) cw |= (uint64_t)src[wi * 8 + q] << (8 * q);
+      }
+    }
+    return (int)((cw >> ((a & 7) * 8)) & 0xff);
+  }
+  __device__ inline void fill() {
+    while (cnt <= 56 && !stop) {          // every turn advances pos or stops: at most n turns over the scan
+      if (pos >= n) { stop = true; break; }
+      const int b = byte_at(pos);
+      if (b == 0xFF) {
+        if (pos + 1 >= n) { stop = true; break; }
+        const int b2 = byte_at(pos + 1);
+        if (b2 == 0xFF) { ++pos; continue; }            // fill byte
+        if (b2 != 0) { stop = true; break; }            // RSTn or another marker
+        pos += 2;
+      } else {
+        ++pos;
+      }
+      acc |= (uint64_t)b << (56 - cnt);
+      cnt += 8;
+    }
+  }
+  __device__ inline int get(int nb) {                   // 0 <= nb <= 16
+    if (nb == 0) return 0;
+    if (cnt < nb) {
+      fill();
+      if (cnt < nb) { bad = true; return 0; }
+    }
+    const int v = (int)(acc >> (64 - nb));
+    acc <<= nb;
+    cnt -= nb;
+    return v;
+  }
+  __device__ inline int decode(const Huff &h) {
+    if (cnt < 16) fill();
+    const int e = huff_decode(h, (uint32_t)(acc >> 32));
+    const int L = e >> 8;
+    if (!e || L > cnt) { bad = true; return 0; }
+    acc <<= L;
+    cnt -= L;
+    return e & 255;
+  }
+  // the restart marker number `num` must be the next thing in the data (behind less than a byte of padding bits)
+  __device__ inline bool restart(int num) {
+    if (cnt >= 8) return false;
+    acc = 0; cnt = 0; stop = false;
+    if (pos >= n || byte_at(pos) != 0xFF) return false;
+    while (pos < n && byte_at(pos) == 0xFF) ++pos;
+    if (pos >= n || byte_at(pos) != 0xD0 + (num & 7)) return false;
+    ++pos;
+    return true;
+  }
+};
+
+// Block geometry of one scan.  A scan of one component covers that component's own ceil(w_c / 8) x ceil(h_c / 8) blocks
+// in raster order (T.81 A.2.2) and its restart interval counts blocks; a scan of several covers the frame's MCUs.
+struct ScanMap {
+  int single;                   // one component
+  int bw, hi, vi, base;         // single: blocks per row, the component's blocks per MCU (h, v), first block in the MCU
+  int mcux, bpm, ny;
+  int64_t units;                // blocks (single) or MCUs
+  __device__ inline int64_t slot(int64_t u) const {     // single: the block's place in the MCU-ordered buffer
+    const int by = (int)(u / bw), bx = (int)(u - (int64_t)by * bw);
+    return ((int64_t)(by / vi) * mcux + bx / hi) * bpm + base + (by % vi) * hi + (bx % hi);
+  }
+};
+
+__device__ inline ScanMap scan_map(const Geo &g, const ttnet_jpeg_scan &sc) {
+  ScanMap m;
+  m.mcux = g.mcux; m.bpm = g.bpm;
+  m.ny = g.ncomp == 3 ? g.hs * g.vs : 1;
+  m.single = sc.ncomp == 1;
+  const int ci = sc.comp[0];
+  const bool luma = ci == 0;
+  m.hi = luma ? g.hs : 1;
+  m.vi = luma ? g.vs : 1;
+  m.base = luma ? 0 : m.ny + ci - 1;
+  const int cw = luma ? g.w : (g.w + g.hs - 1) / g.hs, ch = luma ? g.h : (g.h + g.vs - 1) / g.vs;
+  m.bw = (cw + 7) / 8;
+  m.units = m.single ? (int64_t)m.bw * ((ch + 7) / 8) : (int64_t)g.mcux * g.mcuy;
+  return m;
+}
+
+// everything a scan record lets the kernel index is inside the image's own buffers
+__device__ inline bool scan_ok(const ttnet_jpeg_desc &d, const ttnet_jpeg_scan &sc, int ntables) {
+  if (sc.ncomp < 1 || sc.ncomp > 3 || sc.ncomp > d.ncomp) return false;
+  for (int q = 0; q < sc.ncomp; ++q) {
+    if (sc.comp[q] >= d.ncomp || (q > 0 && sc.comp[q] <= sc.comp[q - 1])) return false;
+    const bool uses_table = sc.ss > 0 ? q == 0 : sc.ah == 0;
+    if (uses_table && sc.table[q] >= ntables) return false;
+  }
+  if ((int64_t)sc.data_offset + sc.data_bytes > d.data_bytes) return false;
+  if (sc.al > 13 || sc.ah > 13 || sc.ss > sc.se || sc.se > 63) return false;
+  if (sc.ss == 0 ? sc.se != 0 : sc.ncomp != 1) return false;
+  return true;
+}
+
+// DC scans (first pass and refinement): 1 .. 3 components, interleaved over the MCUs when more than one.
+__device__ bool prog_dc_scan(ProgReader &rd, const ttnet_jpeg_scan &sc, const ScanMap &m, const Huff *tab, int16_t *coef,
+                             int64_t nblocks, int lane) {
+  const int ri = sc.restart_interval, al = sc.al;
+  const bool refine = sc.ah != 0;
+  unsigned pred[3] = {0, 0, 0};
+  int rst = 0, pend = 0;
+  int64_t my_slot = 0;          // refinement: lane j keeps the j-th pending block's slot and bit until 64 are flushed
+  int my_bit = 0;
+  auto flush = [&]() {
+    if (lane < pend && my_bit) coef[my_slot * 64] = (int16_t)(coef[my_slot * 64] | (1 << al));
+    pend = 0;
+  };
+  for (int64_t u = 0; u < m.units; ++u) {
+    if (ri > 0 && u > 0 && u % ri == 0) {
+      if (!rd.restart(rst++)) return false;
+      pred[0] = pred[1] = pred[2] = 0;
+    }
+    for (int q = 0; q < sc.ncomp; ++q) {
+      const int ci = sc.comp[q];
+      const int nb = m.single ? 1 : (ci == 0 ? m.ny : 1);
+      const int64_t first = m.single ? m.slot(u) : u * m.bpm + (ci == 0 ? 0 : m.ny + ci - 1);
+      for (int j = 0; j < nb; ++j) {
+        const int64_t s = first + j;
+        if (s < 0 || s >= nblocks) return false;
+        if (refine) {
+          const int bit = rd.get(1);
+          if (lane == pend) { my_slot = s; my_bit = bit; }
+          if (++pend == 64) flush();
+        } else {
+          const int sz = rd.decode(tab[q]);
+          if (sz > 15) return false;
+          const int bits = rd.get(sz);
+          if (rd.bad) return false;
+          pred[q] += (unsigned)(sz ? extend(bits, sz) : 0);
+          if (lane == 0) coef[s * 64] = (int16_t)(pred[q] << al);
+        }
+      }
+    }
+    if (rd.bad) return false;
+  }
+  flush();
+  return true;
+}
+
+// AC scans of one component: first pass of a band (every coefficient of the band still zero) and refinement
+// (T.81 G.1.2.3, jdphuff.c decode_mcu_AC_refine).  c: this lane's coefficient of the current block.
+__device__ bool prog_ac_scan(ProgReader &rd, const ttnet_jpeg_scan &sc, const ScanMap &m, const Huff &tab, int16_t *coef,
+                             int64_t nblocks, int lane) {
+  const int ri = sc.restart_interval, al = sc.al, ss = sc.ss, se = sc.se;
+  const bool refine = sc.ah != 0, inband = lane >= ss && lane <= se;
+  const int p1 = 1 << al, m1 = -(1 << al);
+  int rst = 0;
+  int64_t eobrun = 0;
+  for (int64_t u = 0; u < m.units; ++u) {
+    if (ri > 0 && u > 0 && u % ri == 0) {
+      if (!rd.restart(rst++)) return false;
+      eobrun = 0;
+    }
+    if (!refine && eobrun > 0) {          // a first pass leaves the blocks of an end-of-band run as they are: zero
+      --eobrun;
+      continue;
+    }
+    const int64_t s = m.slot(u);
+    if (s < 0 || s >= nblocks) return false;
+    int16_t *blk = coef + s * 64;
+    int c = (refine && inband) ? blk[lane] : 0;
+    const uint64_t nz = __ballot(c != 0);
+    bool dirty = false;
+    int k = ss;
+    if (eobrun == 0) {
+      for (; k <= se; ++k) {
+        const int sym = rd.decode(tab);
+        int r = sym >> 4;
+        const int sz = sym & 15;
+        if (rd.bad) return false;
+        int val = 0;
+        if (sz) {
+          if (refine) {
+            if (sz != 1) return false;
+            val = rd.get(1) ? p1 : m1;
+          } else {
+            val = extend(rd.get(sz), sz) * (1 << al);
+          }
+        } else if (r != 15) {             // EOBr: this block and (1 << r) + extra - 1 more end here
+          eobrun = ((int64_t)1 << r) + rd.get(r);
+          if (eobrun > m.units - u) return false;
+          break;
+        }
+        if (refine) {
+          // skip r coefficients with a zero history; every non-zero one in the way takes a correction bit
+          do {
+            if ((nz >> k) & 1) {
+              if (rd.get(1)) {
+                if (lane == k && (c & p1) == 0) c += c >= 0 ? p1 : m1;
+                dirty = true;
+              }
+            } else if (--r < 0) {
+              break;
+            }
+            ++k;
+          } while (k <= se);
+        } else {
+          k += r;
+        }
+        if (rd.bad) return false;
+        if (sz) {
+          if (k > se) return false;       // a coefficient index past the band
+          if (lane == k) c = val;
+          dirty = true;
+        }
+      }
+    }
+    if (eobrun > 0) {
+      if (refine) {
+        for (; k <= se; ++k) {
+          if ((nz >> k) & 1) {
+            if (rd.get(1)) {
+              if (lane == k && (c & p1) == 0) c += c >= 0 ? p1 : m1;
+              dirty = true;
+            }
+          }
+        }
+        if (rd.bad) return false;
+      }
+      --eobrun;
+    }
+    if (dirty && inband) blk[lane] = (int16_t)c;
+  }
+  return true;
+}
+
+__global__ __launch_bounds__(kThreads) void jpeg_progressive_kernel(DecodeArgs a) {
+  __shared__ Huff s_h[kWaves][3];
+  __shared__ ttnet_jpeg_scan s_scan[kMaxScans];
+  __shared__ int s_err;
+  const int i = blockIdx.x, t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  const ttnet_jpeg_desc d = a.desc[i];
+  if (d.kind != 2) return;
+  int4 *info = a.ws.info + i;
+  if (!desc_ok(a, d, i)) {
+    if (t == 0) *info = make_int4(ST_BAD_DESC, 0, 0, 0);
+    return;
+  }
+  const Geo g = geometry(d);
+  const int nscans = d.reserved[0] & 255, nrounds = (d.reserved[0] >> 8) & 255, ntables = (d.reserved[0] >> 16) & 255;
+  const uint32_t *sl = (const uint32_t *)(a.src + d.table_offset + d.reserved[1]);
+  for (int e = t; e < nscans * (int)(sizeof(ttnet_jpeg_scan) / 4); e += kThreads) ((uint32_t *)s_scan)[e] = sl[e];
+  if (t == 0) s_err = 0;
+  // every coefficient starts at zero: scans only write what they code
+  int16_t *coef = a.ws.coef + d.block_offset * 64;
+  uint4 *z = (uint4 *)coef;
+  for (int64_t e = t; e < g.nblocks * 8; e += kThreads) z[e] = make_uint4(0, 0, 0, 0);
+  __syncthreads();
+  const uint8_t *pool = a.src + d.table_offset + kTableBytes;
+  for (int round = 0; round < nrounds; ++round) {
+    int mine = -1;
+    for (int j = 0; j < nscans; ++j)
+      if (s_scan[j].slot == round * kWaves + wave) mine = j;
+    const ttnet_jpeg_scan sc = s_scan[mine < 0 ? 0 : mine];
+    const bool run = mine >= 0 && scan_ok(d, sc, ntables);
+    const int ntab = !run ? 0 : (sc.ss > 0 ? 1 : (sc.ah == 0 ? sc.ncomp : 0));
+    for (int e = lane; e < ntab * (1 << kLut); e += 64) s_h[wave][e >> kLut].lut[e & ((1 << kLut) - 1)] = 0;
+    __syncthreads();                                // (every wave has read the last round's s_err)
+    if (mine >= 0 && !run) s_err = 1;
+    if (lane < ntab) build_huff(s_h[wave][lane], pool + (int)sc.table[lane] * kHuffBytes);
+    __syncthreads();
+    if (run && !s_err) {
+      ProgReader rd{};
+      rd.src = a.src; rd.src_bytes = a.src_bytes; rd.base = d.data_offset + sc.data_offset; rd.n = (int)sc.data_bytes;
+      rd.cw_idx = -1;
+      const ScanMap m = scan_map(g, sc);
+      const bool ok = sc.ss == 0 ? prog_dc_scan(rd, sc, m, s_h[wave], coef, g.nblocks, lane)
+                                 : prog_ac_scan(rd, sc, m, s_h[wave][0], coef, g.nblocks, lane);
+      if (!ok) s_err = 1;
+    }
+    __syncthreads();                                // the round's coefficients are visible to the next round's waves
+    if (s_err) break;
+  }
+  if (t == 0) *info = make_int4(s_err ? ST_CORRUPT : ST_OK, 0, 0, 0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -878,6 +1204,7 @@ extern "C" int ttnet_jpeg_decode_ragged(ttnet_jpeg_ctx *c, const uint8_t *src_de
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(jpeg_destuff_kernel, dim3((unsigned)n), dim3(kThreads), 0, s, a);
   hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)n), dim3(kThreads), 0, s, a);
+  hipLaunchKernelGGL(jpeg_progressive_kernel, dim3((unsigned)n), dim3(kThreads), 0, s, a);
   hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)n, kIdctGrid), dim3(kThreads), 0, s, a);
   TT_HIP(hipGetLastError());
   return TTNET_OK;

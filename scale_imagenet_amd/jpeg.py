@@ -9,6 +9,10 @@ extended Huffman-coded sequential 8-bit files with one scan are decoded on the d
 2x1 or 2x2 and chroma 1x1, and greyscale.  Everything else is decoded by Pillow in ``pack_jpeg`` (in the worker) and
 carried through the same batch as raw pixels that the device copies; nothing is dropped.  The device output is byte
 for byte Pillow's (libjpeg's islow IDCT, fancy upsampling, jdcolor.c's tables).
+
+Opt-in: ``pack_jpeg(..., progressive=True)`` / ``collate_jpeg_progressive`` also send complete progressive (SOF2) files
+to the device (``parse_progressive`` walks and validates every scan; kind 2 of the batch), byte-identical as well; with
+the flag off they take the Pillow fallback as before.
 """
 from __future__ import annotations
 
@@ -24,7 +28,7 @@ import torch
 from . import _lib
 from .preprocess import MAX_SIDE, RaggedU8, resize_center_crop_u8_ragged
 
-KIND_JPEG, KIND_RAW = 0, 1
+KIND_JPEG, KIND_RAW, KIND_PROGRESSIVE = 0, 1, 2
 TABLE_BYTES = 2048        # per-image table block: uint16 quant[3][64] (zig-zag) + [3][dc, ac] x (counts[16], symbols[256])
 _HUFF_OFF = 384
 _HUFF_BYTES = 272
@@ -33,6 +37,13 @@ JDESC_DTYPE = np.dtype([("data_offset", "<i8"), ("data_bytes", "<i8"), ("table_o
                         ("block_offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("kind", "<i4"), ("ncomp", "<i4"),
                         ("restart_interval", "<i4"), ("comp", "u1", (3, 4)), ("reserved", "<i4", (2,))])
 assert JDESC_DTYPE.itemsize == 80 == C.sizeof(_lib.JpegDesc)
+# kind 2 (progressive): ttnet_jpeg_scan records (32 bytes) at SCAN_OFF of the table block, a pool of Huffman tables behind it
+MAX_SCANS = 32            # TTNET_JPEG_MAX_SCANS
+SCAN_OFF = _HUFF_OFF
+JSCAN_DTYPE = np.dtype([("data_offset", "<u4"), ("data_bytes", "<u4"), ("restart_interval", "<u2"), ("ncomp", "u1"),
+                        ("slot", "u1"), ("comp", "u1", (4,)), ("ss", "u1"), ("se", "u1"), ("ah", "u1"), ("al", "u1"),
+                        ("table", "u1", (4,)), ("reserved", "<i4", (2,))])
+assert JSCAN_DTYPE.itemsize == 32 == C.sizeof(_lib.JpegScan) and SCAN_OFF + MAX_SCANS * 32 <= TABLE_BYTES
 _JDESC_WORDS = JDESC_DTYPE.itemsize // 8
 
 _SOF_NAMES = {0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)", 0xC5: "differential sequential (SOF5)",
@@ -104,6 +115,40 @@ def _check_huffman(counts: List[int], symbols: List[int], dc: bool) -> Optional[
     return None
 
 
+def _read_dqt(seg, qt) -> Optional[str]:
+    """A DQT segment's tables into ``qt`` (zig-zag order, as stored); an error string if malformed."""
+    j = 0
+    while j < len(seg):
+        pq, tq = seg[j] >> 4, seg[j] & 15
+        size = 64 * (pq + 1)
+        if pq > 1 or tq > 3 or j + 1 + size > len(seg):
+            return "malformed DQT"
+        vals = seg[j + 1:j + 1 + size]
+        qt[tq] = list(vals) if pq == 0 else [(vals[2 * k] << 8) | vals[2 * k + 1] for k in range(64)]
+        j += 1 + size
+    return None
+
+
+def _read_dht(seg, dht) -> Optional[str]:
+    """A DHT segment's tables into ``dht`` ((class, id) -> counts, symbols); an error string if malformed."""
+    j = 0
+    while j < len(seg):
+        if j + 17 > len(seg):
+            return "malformed DHT"
+        tc, th = seg[j] >> 4, seg[j] & 15
+        counts = list(seg[j + 1:j + 17])
+        total = sum(counts)
+        if tc > 1 or th > 3 or j + 17 + total > len(seg):
+            return "malformed DHT"
+        syms = list(seg[j + 17:j + 17 + total])
+        err = _check_huffman(counts, syms, tc == 0)
+        if err:
+            return err
+        dht[(tc, th)] = (counts, syms)
+        j += 17 + total
+    return None
+
+
 def parse_header(buf) -> "JpegHeader | Unsupported":
     """Marker walk up to the first SOS.  Returns a JpegHeader if the device decodes the file, otherwise
     Unsupported(reason).  Never reads outside ``buf``; a truncated or malformed header is Unsupported."""
@@ -147,31 +192,13 @@ def parse_header(buf) -> "JpegHeader | Unsupported":
         elif m == 0xEE and seg[:5] == b"Adobe" and len(seg) >= 12:
             adobe = seg[11]
         elif m == 0xDB:
-            j = 0
-            while j < len(seg):
-                pq, tq = seg[j] >> 4, seg[j] & 15
-                size = 64 * (pq + 1)
-                if pq > 1 or tq > 3 or j + 1 + size > len(seg):
-                    return Unsupported("malformed DQT")
-                vals = seg[j + 1:j + 1 + size]
-                qt[tq] = list(vals) if pq == 0 else [(vals[2 * k] << 8) | vals[2 * k + 1] for k in range(64)]
-                j += 1 + size
+            err = _read_dqt(seg, qt)
+            if err:
+                return Unsupported(err)
         elif m == 0xC4:
-            j = 0
-            while j < len(seg):
-                if j + 17 > len(seg):
-                    return Unsupported("malformed DHT")
-                tc, th = seg[j] >> 4, seg[j] & 15
-                counts = list(seg[j + 1:j + 17])
-                total = sum(counts)
-                if tc > 1 or th > 3 or j + 17 + total > len(seg):
-                    return Unsupported("malformed DHT")
-                syms = list(seg[j + 17:j + 17 + total])
-                err = _check_huffman(counts, syms, tc == 0)
-                if err:
-                    return Unsupported(err)
-                dht[(tc, th)] = (counts, syms)
-                j += 17 + total
+            err = _read_dht(seg, dht)
+            if err:
+                return Unsupported(err)
         elif m == 0xCC:
             return Unsupported("arithmetic coding (DAC)")
         elif m in _SOF_NAMES:
@@ -204,34 +231,51 @@ def parse_header(buf) -> "JpegHeader | Unsupported":
         i = nxt
 
 
+def _classify_frame(h, w, comps) -> Optional[str]:
+    """The frame rules shared by sequential and progressive files: size and component count."""
+    nf = len(comps)
+    if h < 1 or w < 1:
+        return "height given by a DNL marker" if h == 0 else "zero width"
+    if h > MAX_SIDE or w > MAX_SIDE:
+        return f"{w}x{h} is beyond {MAX_SIDE} px"
+    if nf == 4:
+        return "4 components (CMYK / YCCK)"
+    if nf not in (1, 3):
+        return f"{nf} components"
+    return None
+
+
+def _classify_colour(comps, jfif, adobe) -> Optional[str]:
+    """Colour space and sampling, known once every marker in front of the first SOS has been read."""
+    if len(comps) == 3:
+        ids = tuple(c[0] for c in comps)
+        if adobe is not None and adobe != 1:
+            return f"Adobe colour transform {adobe} (not YCbCr)"
+        if adobe is None and not jfif and ids != (1, 2, 3):
+            return f"3 components with ids {ids} and no JFIF / Adobe marker (colour space unknown)"
+        ys = (comps[0][1], comps[0][2])
+        if ys not in ((1, 1), (2, 1), (2, 2)) or any((c[1], c[2]) != (1, 1) for c in comps[1:]):
+            return f"sampling {[(c[1], c[2]) for c in comps]}"
+    elif not (1 <= comps[0][1] <= 4 and 1 <= comps[0][2] <= 4):
+        return "bad sampling factors"
+    return None
+
+
 def _classify(sof, scomps, spectral, qt, dht, ri, scan_offset, jfif, adobe):
     kind, h, w, comps = sof
     nf = len(comps)
-    if h < 1 or w < 1:
-        return Unsupported("height given by a DNL marker" if h == 0 else "zero width")
-    if h > MAX_SIDE or w > MAX_SIDE:
-        return Unsupported(f"{w}x{h} is beyond {MAX_SIDE} px")
-    if nf == 4:
-        return Unsupported("4 components (CMYK / YCCK)")
-    if nf not in (1, 3):
-        return Unsupported(f"{nf} components")
+    err = _classify_frame(h, w, comps)
+    if err:
+        return Unsupported(err)
     if len(scomps) != nf:
         return Unsupported("multi-scan sequential file (a scan without every component)")
     if [c[0] for c in scomps] != [c[0] for c in comps]:
         return Unsupported("scan components in another order than the frame's")
     if spectral != (0, 63, 0):
         return Unsupported("sequential scan with a spectral selection other than 0..63")
-    if nf == 3:
-        ids = tuple(c[0] for c in comps)
-        if adobe is not None and adobe != 1:
-            return Unsupported(f"Adobe colour transform {adobe} (not YCbCr)")
-        if adobe is None and not jfif and ids != (1, 2, 3):
-            return Unsupported(f"3 components with ids {ids} and no JFIF / Adobe marker (colour space unknown)")
-        ys = (comps[0][1], comps[0][2])
-        if ys not in ((1, 1), (2, 1), (2, 2)) or any((c[1], c[2]) != (1, 1) for c in comps[1:]):
-            return Unsupported(f"sampling {[(c[1], c[2]) for c in comps]}")
-    elif not (1 <= comps[0][1] <= 4 and 1 <= comps[0][2] <= 4):
-        return Unsupported("bad sampling factors")
+    err = _classify_colour(comps, jfif, adobe)
+    if err:
+        return Unsupported(err)
     for c in comps:
         if c[3] not in qt:
             return Unsupported(f"quantisation table {c[3]} is not defined")
@@ -242,6 +286,259 @@ def _classify(sof, scomps, spectral, qt, dht, ri, scan_offset, jfif, adobe):
         tables.append((td, ta))
     return JpegHeader(h=h, w=w, sof=kind, comps=comps, scan_tables=tables, qt=qt, dht=dht, restart_interval=ri,
                       scan_offset=scan_offset, jfif=jfif, adobe_transform=adobe)
+
+
+@dataclass
+class ProgressiveScan:
+    """One scan of a progressive file: ``comps`` are frame component indices (increasing), ``tables`` the Huffman
+    table in force for each of them when the SOS was read (DC tables in a DC scan, the AC table in an AC scan, as
+    (counts, symbols); None in a DC refinement, which reads raw bits), [data_start, data_end) the entropy-coded
+    bytes in the file."""
+    comps: List[int]
+    ss: int
+    se: int
+    ah: int
+    al: int
+    restart_interval: int
+    tables: List[Optional[Tuple[List[int], List[int]]]]
+    data_start: int
+    data_end: int
+    slot: int = 0                                # 4 * round + wave of the device schedule (_schedule)
+
+
+@dataclass
+class ProgressiveHeader:
+    """What the device decoder needs of a progressive (SOF2) file: the frame and every scan."""
+    h: int
+    w: int
+    comps: List[Tuple[int, int, int, int]]       # per frame component: (id, h_samp, v_samp, quant table)
+    qt: Dict[int, List[int]]
+    scans: List[ProgressiveScan]
+    rounds: int = 0
+    jfif: bool = False
+    adobe_transform: Optional[int] = None
+
+    ncomp = JpegHeader.ncomp
+    sampling = JpegHeader.sampling
+    mcus = JpegHeader.mcus
+    blocks = JpegHeader.blocks
+
+    @property
+    def restart_interval(self) -> int:
+        """The first scan's (DRI may change between scans; each scan carries its own)."""
+        return self.scans[0].restart_interval
+
+
+def _scan_data_end(b: bytes, i: int) -> int:
+    """End of the entropy-coded data that starts at ``i``: the FF of the next marker other than FF00 / RSTn (fill
+    FFs in front of it belong to the data), or the end of the file."""
+    n = len(b)
+    while True:
+        j = b.find(b"\xff", i)
+        if j < 0 or j + 1 >= n:
+            return n
+        m = b[j + 1]
+        if m == 0x00 or 0xD0 <= m <= 0xD7:
+            i = j + 2
+        elif m == 0xFF:
+            i = j + 1
+        else:
+            return j
+
+
+def _schedule(scans: List[ProgressiveScan]) -> int:
+    """Assigns each scan its slot (4 * round + wave) on the device: a scan runs in a later round than every earlier
+    scan that touches one of its (component, coefficient) pairs (a refinement after the pass it refines; DC and AC
+    bands, and different components, are independent), four scans at most per round, long scans placed first.
+    Returns the round count."""
+    deps = [[i for i in range(j) if set(s.comps) & set(scans[i].comps) and s.ss <= scans[i].se and scans[i].ss <= s.se]
+            for j, s in enumerate(scans)]
+    level = []
+    for j in range(len(scans)):
+        level.append(1 + max((level[i] for i in deps[j]), default=-1))
+    order = sorted(range(len(scans)), key=lambda j: (level[j], scans[j].data_start - scans[j].data_end, j))
+    load: List[int] = []
+    rnd: Dict[int, int] = {}
+    for j in order:
+        r = 1 + max((rnd[i] for i in deps[j]), default=-1)
+        while r < len(load) and load[r] == 4:
+            r += 1
+        if r == len(load):
+            load.append(0)
+        scans[j].slot = 4 * r + load[r]
+        load[r] += 1
+        rnd[j] = r
+    return len(load)
+
+
+def parse_progressive(buf) -> "ProgressiveHeader | Unsupported":
+    """Marker walk over the whole of a progressive (SOF2) file: the frame, then every scan with its spectral band,
+    bit positions, restart interval, the Huffman tables defined at that point and the byte range of its data.
+    Returns a ProgressiveHeader if the device decodes the file under ``pack_jpeg(..., progressive=True)``, otherwise
+    Unsupported(reason); a file that is not SOF2 gets the reason ``parse_header`` gives or "not progressive".  The
+    progression is validated as libjpeg's jdphuff.c does and must be complete (every coefficient of every component
+    refined down to bit 0), because libjpeg smooths blocks of an incomplete one.  Never reads outside ``buf``."""
+    b = bytes(buf)
+    n = len(b)
+    if n < 4 or b[0] != 0xFF or b[1] != 0xD8:
+        return Unsupported("not a JPEG file (no SOI marker)")
+    i = 2
+    qt: Dict[int, List[int]] = {}
+    dht: Dict[Tuple[int, int], Tuple[List[int], List[int]]] = {}
+    frame = None
+    ri = 0
+    jfif = False
+    adobe = None
+    scans: List[ProgressiveScan] = []
+    bits: List[List[int]] = []                   # per component, per coefficient: the bit position reached, -1: none
+    while i < n:
+        if b[i] != 0xFF:
+            return Unsupported(f"garbage between markers at byte {i}")
+        while i < n and b[i] == 0xFF:
+            i += 1
+        if i >= n:
+            break
+        m = b[i]
+        i += 1
+        if m == 0x01 or 0xD0 <= m <= 0xD7:
+            continue
+        if m == 0xD9:
+            break
+        if m == 0xD8 or m == 0x00:
+            return Unsupported(f"unexpected marker 0xFF{m:02X}")
+        if i + 2 > n:
+            return Unsupported("file ends inside a marker length")
+        L = (b[i] << 8) | b[i + 1]
+        if L < 2 or i + L > n:
+            return Unsupported(f"marker 0xFF{m:02X} runs past the end of the file")
+        seg = b[i + 2:i + L]
+        nxt = i + L
+        if m == 0xE0 and seg[:5] == b"JFIF\0":
+            jfif = True
+        elif m == 0xEE and seg[:5] == b"Adobe" and len(seg) >= 12:
+            adobe = seg[11]
+        elif m == 0xDB:
+            if scans:
+                return Unsupported("quantisation tables redefined between scans")
+            err = _read_dqt(seg, qt)
+            if err:
+                return Unsupported(err)
+        elif m == 0xC4:
+            err = _read_dht(seg, dht)
+            if err:
+                return Unsupported(err)
+        elif m == 0xCC:
+            return Unsupported("arithmetic coding (DAC)")
+        elif m == 0xDC:
+            return Unsupported("height given by a DNL marker")
+        elif m == 0xC2:
+            if frame is not None:
+                return Unsupported("more than one SOF")
+            if len(seg) < 6 or len(seg) < 6 + 3 * seg[5]:
+                return Unsupported("malformed SOF")
+            p, h, w, nf = seg[0], (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4], seg[5]
+            if p != 8:
+                return Unsupported(f"{p}-bit samples")
+            comps = [(seg[6 + 3 * k], seg[7 + 3 * k] >> 4, seg[7 + 3 * k] & 15, seg[8 + 3 * k]) for k in range(nf)]
+            err = _classify_frame(h, w, comps)
+            if err:
+                return Unsupported(err)
+            frame = (h, w, comps)
+            bits = [[-1] * 64 for _ in comps]
+        elif m in _SOF_NAMES:
+            return Unsupported(_SOF_NAMES[m])
+        elif m in (0xC0, 0xC1):
+            if frame is not None:
+                return Unsupported("more than one SOF")
+            r = parse_header(b)
+            return r if isinstance(r, Unsupported) else Unsupported("not progressive (sequential: parse_header)")
+        elif m == 0xDD:
+            if len(seg) < 2:
+                return Unsupported("malformed DRI")
+            ri = (seg[0] << 8) | seg[1]
+        elif m == 0xDA:
+            if frame is None:
+                return Unsupported("SOS before SOF")
+            if len(scans) >= MAX_SCANS:
+                return Unsupported(f"more than {MAX_SCANS} scans")
+            if not scans:
+                err = _classify_colour(frame[2], jfif, adobe)
+                if err:
+                    return Unsupported(err)
+            sc = _read_progressive_sos(seg, frame[2], qt, dht, bits, ri)
+            if isinstance(sc, Unsupported):
+                return sc
+            sc.data_start = nxt
+            sc.data_end = nxt = _scan_data_end(b, nxt)
+            if sc.data_end == sc.data_start:
+                return Unsupported(f"scan {len(scans)} has no entropy-coded data")
+            scans.append(sc)
+        i = nxt
+    if frame is None:
+        return Unsupported("no SOF before the end of the file")
+    if not scans:
+        return Unsupported("no scan before the end of the file")
+    for c, cb in enumerate(bits):
+        for k, v in enumerate(cb):
+            if v != 0:
+                return Unsupported(f"incomplete progression (component {c}, coefficient {k} "
+                                   f"{'never coded' if v < 0 else f'stops at bit {v}'}): libjpeg would smooth it")
+    hd = ProgressiveHeader(h=frame[0], w=frame[1], comps=frame[2], qt=qt, scans=scans, jfif=jfif, adobe_transform=adobe)
+    hd.rounds = _schedule(scans)
+    return hd
+
+
+def _read_progressive_sos(seg, comps, qt, dht, bits, ri) -> "ProgressiveScan | Unsupported":
+    """One SOS header of a progressive file, checked against T.81 G.1.1.1 the way jdphuff.c does (and stricter: what
+    libjpeg only warns about is refused); updates ``bits``."""
+    if len(seg) < 1 or len(seg) < 1 + 2 * seg[0] + 3:
+        return Unsupported("malformed SOS")
+    ns = seg[0]
+    if ns < 1 or ns > len(comps):
+        return Unsupported(f"scan with {ns} components")
+    ids = [c[0] for c in comps]
+    idx, sel = [], []
+    for k in range(ns):
+        cid = seg[1 + 2 * k]
+        if cid not in ids:
+            return Unsupported(f"scan names component {cid}, which the frame does not have")
+        idx.append(ids.index(cid))
+        sel.append((seg[2 + 2 * k] >> 4, seg[2 + 2 * k] & 15))
+    if any(a >= c for a, c in zip(idx, idx[1:])):
+        return Unsupported("scan components in another order than the frame's")
+    ss, se, ah, al = seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns] >> 4, seg[3 + 2 * ns] & 15
+    if ss > se or se > 63 or al > 13 or ah > 13:
+        return Unsupported(f"bad progression parameters Ss {ss} Se {se} Ah {ah} Al {al}")
+    if ss == 0 and se != 0:
+        return Unsupported(f"scan mixes DC and AC coefficients (Ss 0, Se {se})")
+    if ss > 0 and ns != 1:
+        return Unsupported("AC scan with more than one component")
+    if ah != 0 and al != ah - 1:
+        return Unsupported(f"refinement scan with Al {al} other than Ah - 1 ({ah - 1})")
+    for c in idx:
+        if comps[c][3] not in qt:
+            return Unsupported(f"quantisation table {comps[c][3]} is not defined")
+        if ss > 0 and bits[c][0] < 0:
+            return Unsupported(f"AC scan of component {c} before its DC scan")
+        for k in range(ss, se + 1):
+            have = bits[c][k]
+            if have == 0:
+                return Unsupported(f"component {c}, coefficient {k} is coded again after its last bit")
+            if ah != (0 if have < 0 else have):
+                return Unsupported(f"out-of-order refinement (component {c}, coefficient {k}: Ah {ah} after "
+                                   f"{'no scan' if have < 0 else f'Al {have}'})")
+            bits[c][k] = al
+    tables: List[Optional[Tuple[List[int], List[int]]]] = []
+    for (td, ta) in sel:
+        if ss == 0 and ah != 0:
+            tables.append(None)
+            continue
+        key = (0, td) if ss == 0 else (1, ta)
+        if key not in dht:
+            return Unsupported(f"Huffman table {'DC' if ss == 0 else 'AC'} {key[1]} is not defined")
+        tables.append(dht[key])
+    return ProgressiveScan(comps=idx, ss=ss, se=se, ah=ah, al=al, restart_interval=ri, tables=tables, data_start=0,
+                           data_end=0)
 
 
 def table_block(hd: JpegHeader) -> np.ndarray:
@@ -312,9 +609,37 @@ def _align16(x: int) -> int:
     return (x + 15) & ~15
 
 
-def pack_jpeg(items: Sequence, names: Optional[Sequence[str]] = None) -> RaggedJpeg:
+def progressive_block(hd: ProgressiveHeader) -> Tuple[np.ndarray, np.ndarray]:
+    """(table block, Huffman pool) the device reads for one progressive image (layout: include/ttnet.h,
+    ttnet_jpeg_scan): quant tables, the scan list with data offsets relative to the first scan's data, and each distinct
+    Huffman table once."""
+    blk = np.zeros(TABLE_BYTES, dtype=np.uint8)
+    q = blk[:_HUFF_OFF].view("<u2").reshape(3, 64)
+    for k, c in enumerate(hd.comps):
+        q[k] = hd.qt[c[3]]
+    sl = blk[SCAN_OFF:SCAN_OFF + 32 * len(hd.scans)].view(JSCAN_DTYPE)
+    pool: Dict[Tuple[Tuple[int, ...], Tuple[int, ...]], int] = {}
+    base = hd.scans[0].data_start
+    for e, sc in zip(sl, hd.scans):
+        e["data_offset"], e["data_bytes"] = sc.data_start - base, sc.data_end - sc.data_start
+        e["restart_interval"], e["ncomp"], e["slot"] = sc.restart_interval, len(sc.comps), sc.slot
+        e["comp"][:len(sc.comps)] = sc.comps
+        e["ss"], e["se"], e["ah"], e["al"] = sc.ss, sc.se, sc.ah, sc.al
+        for k, t in enumerate(sc.tables):
+            if t is not None:
+                e["table"][k] = pool.setdefault((tuple(t[0]), tuple(t[1])), len(pool))
+    tabs = np.zeros(max(len(pool), 1) * _HUFF_BYTES, dtype=np.uint8)
+    for (counts, syms), k in pool.items():
+        tabs[k * _HUFF_BYTES:k * _HUFF_BYTES + 16] = counts
+        tabs[k * _HUFF_BYTES + 16:k * _HUFF_BYTES + 16 + len(syms)] = syms
+    return blk, tabs[:len(pool) * _HUFF_BYTES]
+
+
+def pack_jpeg(items: Sequence, names: Optional[Sequence[str]] = None, progressive: bool = False) -> RaggedJpeg:
     """Compressed files (bytes-like) and already-decoded images (uint8 HWC [h, w, 3] arrays) -> one host RaggedJpeg,
     in order.  A file the device does not decode is decoded here with Pillow and packed raw; ``reasons[i]`` says why.
+    With ``progressive=True`` a complete progressive (SOF2) file that ``parse_progressive`` accepts is packed for the
+    device's progressive decoder (kind 2) instead of taking that fallback.
     Raises RuntimeError naming the item if it can be neither decoded on the device nor by Pillow."""
     n = len(items)
     if n < 1 or n > 65535:
@@ -336,7 +661,13 @@ def pack_jpeg(items: Sequence, names: Optional[Sequence[str]] = None) -> RaggedJ
         if not isinstance(it, (bytes, bytearray, memoryview)):
             raise RuntimeError(f"pack_jpeg: {names[i]} is a {type(it).__name__}, not file bytes or a uint8 array")
         hd = parse_header(it)
-        if isinstance(hd, Unsupported):
+        if progressive and isinstance(hd, Unsupported) and hd.reason == _SOF_NAMES[0xC2]:
+            hd = parse_progressive(it)
+        if isinstance(hd, ProgressiveHeader):
+            lo, hi = hd.scans[0].data_start, hd.scans[-1].data_end
+            plan.append((KIND_PROGRESSIVE, hd, memoryview(bytes(it))[lo:hi]))
+            reasons.append(None)
+        elif isinstance(hd, Unsupported):
             a = _pillow_decode(it, names[i], hd.reason)
             if not (1 <= a.shape[0] <= MAX_SIDE and 1 <= a.shape[1] <= MAX_SIDE):
                 raise RuntimeError(f"pack_jpeg: {names[i]} is {a.shape[1]}x{a.shape[0]}; sides must lie in [1, {MAX_SIDE}]")
@@ -349,7 +680,7 @@ def pack_jpeg(items: Sequence, names: Optional[Sequence[str]] = None) -> RaggedJ
     size = 0
     out = 0
     blocks = 0
-    for i, (kind, obj, scan) in enumerate(plan):
+    for i, (kind, obj, scan, *_) in enumerate(plan):
         d = desc[i]
         d["kind"] = kind
         if kind == KIND_RAW:
@@ -359,27 +690,37 @@ def pack_jpeg(items: Sequence, names: Optional[Sequence[str]] = None) -> RaggedJ
             d["ncomp"] = 3
         else:
             h, w = obj.h, obj.w
+            extra = 0
+            if kind == KIND_PROGRESSIVE:
+                tabs = progressive_block(obj)
+                extra = len(tabs[1])                                   # (a multiple of 16)
+                d["reserved"] = (len(obj.scans) | (obj.rounds << 8) | ((extra // _HUFF_BYTES) << 16), SCAN_OFF)
+                plan[i] = (kind, obj, scan, tabs)
             d["table_offset"] = size
-            d["data_offset"], d["data_bytes"] = size + TABLE_BYTES, len(scan)
-            size = _align16(size + TABLE_BYTES + len(scan))
+            d["data_offset"], d["data_bytes"] = size + TABLE_BYTES + extra, len(scan)
+            size = _align16(size + TABLE_BYTES + extra + len(scan))
             d["block_offset"] = blocks
             blocks += obj.blocks()
             d["ncomp"] = obj.ncomp
             d["restart_interval"] = obj.restart_interval
             for k, c in enumerate(obj.comps):
-                d["comp"][k] = (c[0], (c[1] << 4) | c[2], c[3], (obj.scan_tables[k][0] << 4) | obj.scan_tables[k][1])
+                sel = 0 if kind == KIND_PROGRESSIVE else (obj.scan_tables[k][0] << 4) | obj.scan_tables[k][1]
+                d["comp"][k] = (c[0], (c[1] << 4) | c[2], c[3], sel)
         d["h"], d["w"] = h, w
         d["out_offset"] = out
         out += h * w * 3
     data = torch.zeros(max(size, 16), dtype=torch.uint8)
     flat = data.numpy()
-    for (kind, obj, scan), d in zip(plan, desc):
+    for (kind, obj, scan, *tabs), d in zip(plan, desc):
         o = int(d["data_offset"])
         if kind == KIND_RAW:
             flat[o:o + obj.size] = obj.reshape(-1)
         else:
             t = int(d["table_offset"])
-            flat[t:t + TABLE_BYTES] = table_block(obj)
+            if kind == KIND_PROGRESSIVE:
+                flat[t:t + TABLE_BYTES], flat[t + TABLE_BYTES:o] = tabs[0]
+            else:
+                flat[t:t + TABLE_BYTES] = table_block(obj)
             flat[o:o + len(scan)] = np.frombuffer(scan, dtype=np.uint8)
     return RaggedJpeg(data, torch.from_numpy(desc.view(np.int64).reshape(n, _JDESC_WORDS)), blocks, out,
                       int(desc["h"].max()), int(desc["w"].max()), reasons)
@@ -390,6 +731,13 @@ def collate_jpeg(batch):
     ``(RaggedJpeg, targets)``, the targets collated as the default collate does."""
     files, targets = zip(*batch)
     return pack_jpeg(files), torch.utils.data.default_collate(list(targets))
+
+
+def collate_jpeg_progressive(batch):
+    """``collate_jpeg`` with the device's progressive decoder switched on: complete progressive files are shipped
+    compressed (kind 2) instead of being decoded by Pillow in the worker."""
+    files, targets = zip(*batch)
+    return pack_jpeg(files, progressive=True), torch.utils.data.default_collate(list(targets))
 
 
 IMG_EXTENSIONS = (".jpg", ".jpeg", ".png", ".ppm", ".bmp", ".pgm", ".tif", ".tiff", ".webp")

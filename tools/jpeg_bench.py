@@ -3,6 +3,7 @@ Batches of 256 are built from the committed fixtures (tests/golden/jpeg: the 500
 quality-90 files and the other device-decoded ones, repeated).
 
     python tools/jpeg_bench.py [--batch 256] [--windows 5] [--iters 20] [--workers 16] [--loader-batches 64]
+    python tools/jpeg_bench.py --progressive     (the progressive legs only; needs Pillow to re-encode the batch)
 
 Legs (medians over timed windows after warm-up):
   1. host cost per image on one thread: pack_jpeg (header walk + packing) against Pillow decode + pack_u8;
@@ -12,6 +13,10 @@ Legs (medians over timed windows after warm-up):
      H2D -> ragged resize -> forward_u8 (host packing excluded from both);
   4. end to end: the same DataLoader (spawned workers, pin_memory, two batches in flight) over the files' bytes, whose
      collate_fn is either collate_jpeg or Pillow decode + collate_u8 (host packing included in both).
+--progressive: the same batch composition re-encoded progressively by Pillow (same tables and sampling, libjpeg's
+default scan script), timed the same way: decode only next to the sequential batch of the same run, and the loader end
+to end with collate_jpeg_progressive (device decode) against collate_jpeg (which decodes every such file with Pillow
+in the worker).
 Legs 1 and 4 need Pillow; without it they are skipped and say so.  Per-kernel device times: run under
 `rocprofv3 --kernel-trace --stats`.
 """
@@ -92,9 +97,12 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--workers", type=int, default=16)
     ap.add_argument("--loader-batches", type=int, default=64)
+    ap.add_argument("--progressive", action="store_true", help="the progressive legs only")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     files = fixture_files()
+    if a.progressive:
+        return progressive_legs(a, dev, files)
     data = batch_of(files, a.batch)
     nbytes = sum(len(b) for b in data)
     try:
@@ -178,6 +186,72 @@ def main():
         print(f"end to end, DataLoader({a.workers} spawned workers, pin_memory) -> {name} -> ... -> forward_u8 "
               f"(2 in flight): {n / t:,.0f} images/s over {a.loader_batches} batches")
         del loader
+    J.check_jpeg(dev)
+
+
+def to_progressive(b):
+    from PIL import Image
+    out = io.BytesIO()
+    Image.open(io.BytesIO(b)).save(out, "JPEG", quality="keep", subsampling="keep", progressive=True, optimize=True)
+    return out.getvalue()
+
+
+def loader_rate(a, dev, model, streams, files, collate, fwd):
+    loader = torch.utils.data.DataLoader(
+        Files(files, a.batch * a.loader_batches), batch_size=a.batch, num_workers=a.workers, collate_fn=collate,
+        pin_memory=True, multiprocessing_context="spawn", persistent_workers=True, prefetch_factor=2)
+    times = []
+    for rep in range(3):                          # the first pass starts the workers: not counted
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for i, (b, _) in enumerate(loader):
+            with torch.cuda.stream(streams[i & 1]), torch.no_grad():
+                fwd(model, b.to(dev, non_blocking=True), lane=i & 1)
+        torch.cuda.synchronize(dev)
+        if rep:
+            times.append(time.perf_counter() - t0)
+    del loader
+    return a.batch * a.loader_batches / statistics.median(times), a.batch * a.loader_batches / max(times)
+
+
+def progressive_legs(a, dev, files):
+    prog = [to_progressive(b) for b in files]
+    seq_b, prog_b = batch_of(files, a.batch), batch_of(prog, a.batch)
+    t_pack = statistics.median(_t(lambda: J.pack_jpeg(prog_b, progressive=True)) for _ in range(5))
+    t_fall = statistics.median(_t(lambda: J.pack_jpeg(prog_b)) for _ in range(3))
+    rs, rp = J.pack_jpeg(seq_b).to(dev), J.pack_jpeg(prog_b, progressive=True).to(dev)
+    assert set(rp.descriptors()["kind"].tolist()) == {J.KIND_PROGRESSIVE}
+    chk = J.pack_jpeg(prog_b[:16])                # Pillow's pixels, copied through (the buffer's 16-byte padding aside)
+    ref = J.decode_ragged(chk.to(dev)).data[:chk.out_bytes].cpu()
+    got = J.decode_ragged(J.pack_jpeg(prog_b[:16], progressive=True).to(dev)).data[:chk.out_bytes].cpu()
+    assert torch.equal(got, ref), "the device's progressive decode differs from Pillow's"
+    print(f"progressive batch {a.batch}: {sum(len(b) for b in prog_b) / 2**20:.2f} MiB of files "
+          f"({sum(len(b) for b in seq_b) / 2**20:.2f} MiB sequential), {rp.data.numel() / 2**20:.2f} MiB packed")
+    print(f"host, one thread: pack_jpeg(progressive=True) {t_pack / a.batch * 1e6:.0f} us per image; "
+          f"pack_jpeg (Pillow fallback) {t_fall / a.batch * 1e6:.0f} us per image")
+    for _ in range(20):                           # clocks up before the first timed window
+        J.decode_ragged(rs)
+    res = {}
+    for name, rj in (("sequential", rs), ("progressive", rp), ("sequential", rs), ("progressive", rp)):
+        res.setdefault(name, []).append(median_windows(lambda: J.decode_ragged(rj), a.iters, a.windows, dev))
+    for name, v in res.items():
+        print(f"decode only, {name}: {min(v) * 1e3:.3f} / {max(v) * 1e3:.3f} ms per batch (two alternating runs of "
+              f"{a.windows} windows x {a.iters} decodes, medians), {a.batch / statistics.mean(v):,.0f} images/s")
+    if a.loader_batches < 1:                      # (--loader-batches 0: the decode legs alone, e.g. under rocprofv3)
+        return J.check_jpeg(dev)
+    from _util import args_for, spec_and_state
+    _, st = spec_and_state("small")
+    model = ttnet.TT_vf_19lv3_imgnet_small(args_for("small"))
+    model.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in st.items()}, strict=True)
+    model = model.to(dev).eval().reserve(a.batch)
+    model.set_lanes(2)
+    streams = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]
+    for name, collate in (("collate_jpeg_progressive (device decode)", J.collate_jpeg_progressive),
+                          ("collate_jpeg (Pillow fallback in the worker)", J.collate_jpeg)):
+        med, low = loader_rate(a, dev, model, streams, prog, collate, J.jpeg_eval_forward)
+        print(f"end to end, progressive files, DataLoader({a.workers} spawned workers, pin_memory) -> {name} -> ... -> "
+              f"forward_u8 (2 in flight): {med:,.0f} images/s over {a.loader_batches} batches (slower of two passes "
+              f"{low:,.0f})")
     J.check_jpeg(dev)
 
 
