@@ -290,6 +290,39 @@ int ttnet_jpeg_decode_ragged(ttnet_jpeg_ctx *ctx, const uint8_t *src_dev, int64_
                              int64_t dst_bytes, ttnet_image_desc *dst_desc_dev, int32_t *stats_dev, void *stream);
 void ttnet_jpeg_ctx_destroy(ttnet_jpeg_ctx *ctx);
 
+/* Evaluation metrics on the device: replaces `loss = criterion(outputs, targets)`, `accuracy(outputs, targets, (1, 5))`
+ * and the three AverageMeter.update calls of test() (main.py:262-268; utils/bar_show.py:110-148) with one call that keeps
+ * nothing but this accumulator.  The call ADDS to it, so one accumulator per lane (zeroed by the caller, 8-byte aligned,
+ * device memory) collects a whole evaluation and is read back once: loss = loss_sum / images, Acc@k = 100 * hitsk / images. */
+typedef struct ttnet_eval_acc {
+  double loss_sum;      /* sum of the per-image losses (float64) */
+  int64_t images;       /* rows with a valid target */
+  int64_t hits1, hits5;
+  int64_t bad_targets;  /* rows whose target was outside [0, n_classes) */
+  int64_t reserved[3];
+} ttnet_eval_acc;       /* 64 bytes */
+
+/* logits_dev float32 [n][n_classes] contiguous (any 4-byte aligned address), targets_dev int64 [n]; n in [1, 65535],
+ * n_classes in [2, 65536].  Per row, with v = the row, t = its target:
+ *   loss = logsumexp(v) - v[t], evaluated in float64 from the float32 logits: log(sum_j exp(v_j - max v)) + max v - v_t,
+ *          the sum taken in a fixed lane / tree order.
+ *   rank = #{j : v_j > v_t} + #{j < t : v_j == v_t}; the image is a top-k hit iff rank < k.  This is the reference's
+ *          topk-based accuracy whenever the target's logit is not tied across the k-th place; torch.topk leaves the order
+ *          of ties unspecified, so ties are DEFINED here to go to the lower class index.
+ *   A NaN anywhere in the row: loss = NaN (and so the accumulator's loss_sum), no hit; rank is recorded as INT32_MAX.
+ *   t outside [0, n_classes): no hit, nothing added to loss_sum or images, bad_targets + 1; rank is recorded as -1, loss
+ *          as 0.  The row is never indexed with such a target.
+ * per_image_dev, when not NULL, receives n records {double loss; int32 rank; int32 zero} (16 bytes each, 8-byte aligned)
+ * and is the buffer the reduction reads.  The reduction is deterministic: the records are summed in a fixed order (a
+ * fixed stride over the images, then a fixed tree) by one workgroup and added to the accumulator by one thread; no
+ * floating-point atomics, so the same batches in the same order give the same bits run to run.
+ * Two launches on `stream`; no plan, no host synchronisation, capturable in a graph.  With per_image_dev there is no
+ * allocation either; with NULL the library keeps one 1 MiB scratch per accumulator address, allocated by the first call
+ * that names that accumulator (which must therefore not be a capturing one: TTNET_E_STATE) and kept for the life of the
+ * process, at most 64 of them.  Calls that add to one accumulator must be ordered by their stream. */
+int ttnet_eval_metrics(const float *logits_dev, const int64_t *targets_dev, int64_t n, int64_t n_classes,
+                       ttnet_eval_acc *acc_dev, void *per_image_dev, void *stream);
+
 /* Same, starting from the binarised stem output (features[3], netbin.py:193) given as
  * row-packed bits uint64 [n][p][56]; used by the parity tests to separate the integer
  * gate path (bit exact) from the float stem (exact except at near ties). */

@@ -43,6 +43,12 @@ class JpegScan(C.Structure):
                 ("ah", C.c_uint8), ("al", C.c_uint8), ("table", C.c_uint8 * 4), ("reserved", C.c_int32 * 2)]
 
 
+class EvalAcc(C.Structure):
+    """ttnet_eval_acc: the device-resident accumulator of ttnet_eval_metrics (include/ttnet.h), 64 bytes."""
+    _fields_ = [("loss_sum", C.c_double), ("images", C.c_int64), ("hits1", C.c_int64), ("hits5", C.c_int64),
+                ("bad_targets", C.c_int64), ("reserved", C.c_int64 * 3)]
+
+
 class TTNetError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"libttnet status {status}: {message}")
@@ -67,6 +73,7 @@ SYMBOLS: List[Tuple[str, object, list]] = [
     ("ttnet_jpeg_ctx_reserve", C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64]),
     ("ttnet_jpeg_decode_ragged", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, _P]),
     ("ttnet_jpeg_ctx_destroy", None, [_P]),
+    ("ttnet_eval_metrics", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P]),
     ("ttnet_forward_from_stem_bits", C.c_int, [_P, _P, C.c_int64, _P, _P]),
     ("ttnet_read_stage", C.c_int, [_P, C.c_char_p, C.c_int64, _P, C.c_size_t, C.c_int, _P]),
     ("ttnet_plan_get_table", C.c_int, [_P, C.c_char_p, _P, C.c_size_t]),

@@ -6,6 +6,9 @@ state_dict (no parameter broadcast, unlike DataParallel.replicate / the DDP cons
 main.py:181-192); the only exchange is the gather of logits that
 ``torch.nn.DataParallel.gather`` performs on GPU 0 in the reference (main.py:192), here one
 all-gather of ``[B/world, 1000]`` fp32.
+
+Evaluating a dataset needs less still: every rank evaluates its ``ShardedSampler`` slice and one
+``all_reduce_metrics`` sums four numbers (loss sum, images, top-1 hits, top-5 hits).
 """
 from __future__ import annotations
 
@@ -74,3 +77,35 @@ def all_gather_logits(local: torch.Tensor, n_total: int, group=None) -> torch.Te
         return out
     rows = [out[r * width: r * width + shard_bounds(n_total, r, world)[1]] for r in range(world)]
     return torch.cat(rows)
+
+
+class ShardedSampler(torch.utils.data.Sampler):
+    """``rank``'s contiguous ``shard_bounds`` slice of a dataset of ``n`` samples, in order: the shards partition
+    ``range(n)`` -- no padding, no duplicates, so the summed metrics are those of the dataset.  (The reference's DDP
+    path gives every rank the full validation set, main.py:214; ``DistributedSampler`` pads with repeats.)"""
+
+    def __init__(self, n: int, rank: int, world: int):
+        self.first, self.count = shard_bounds(int(n), rank, world)
+
+    def __iter__(self):
+        return iter(range(self.first, self.first + self.count))
+
+    def __len__(self) -> int:
+        return self.count
+
+
+def all_reduce_metrics(part, group=None):
+    """Sum the evaluation of every rank's shard: one ``all_reduce(SUM)`` of ``[loss_sum, images, hits1, hits5]``
+    (float64 / int64 carried in one float64 tensor: the counts are far below 2^53, so their sum is exact).  ``part``
+    is this rank's ``EvalResult`` (or ``EvalParts``); every rank returns the same ``EvalResult``.  Host tensors under
+    gloo, device tensors under nccl.  A single process returns its input."""
+    from .evaluate import EvalParts, EvalResult
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return part
+    p = part.to_parts() if isinstance(part, EvalResult) else part
+    v = torch.tensor([p.loss_sum, float(p.images), float(p.hits1), float(p.hits5)], dtype=torch.float64)
+    if dist.get_backend(group) != "gloo":
+        v = v.to(torch.device("cuda", torch.cuda.current_device()))
+    dist.all_reduce(v, op=dist.ReduceOp.SUM, group=group)
+    loss_sum, images, hits1, hits5 = v.cpu().tolist()
+    return EvalParts(loss_sum, int(round(images)), int(round(hits1)), int(round(hits5))).result()

@@ -2,16 +2,34 @@
 
 Reproduces the reference's metric definitions -- cross-entropy loss, top-1 / top-5 running
 means weighted by batch size (utils/bar_show.py:110-148), the final ``Acc..`` line
-(main.py:284) -- around ``model(inputs)``.  The JPEG pipeline, TensorBoard and the terminal
-progress bar of the reference are out of scope.
+(main.py:284) -- around the forward.  The whole input pipeline is in scope: a batch may be a
+float tensor (``model(x)``), the decoder's uint8 crops (``model.forward_u8``), decoded images of
+mixed sizes (``RaggedU8`` -> ``preprocess.imgnet_eval_forward``) or compressed files
+(``RaggedJpeg`` -> ``jpeg.jpeg_eval_forward``); ``forward=`` overrides the choice.  TensorBoard
+and the terminal progress bar of the reference stay out of scope.
+
+Two ways to the metrics:
+
+``metrics="torch"`` (default)  ``F.cross_entropy`` + ``topk`` per batch, three scalars read back
+    per batch, float32 batch means accumulated on the host as the reference does.
+``metrics="device"``  ``DeviceMetrics``: one ``ttnet_eval_metrics`` call per batch on the lane's
+    stream adds the batch to a 64-byte accumulator on the device; nothing is read back until
+    the end (or a ``log_every`` line).  ``loss`` is then ``loss_sum / images`` with every
+    per-image loss and the sum in float64, so it differs from the ``"torch"`` path in the last
+    digits (float32 batch means there); ``top1`` / ``top5`` are ``100 * hits / images`` from
+    exact integer counts and equal the ``"torch"`` path's whenever no target's logit is tied
+    across the k-th place (ties go to the lower class index here, include/ttnet.h).
 """
 from __future__ import annotations
 
+import ctypes as C
 from dataclasses import dataclass
-from typing import Iterable, Tuple
+from typing import Callable, Iterable, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
+
+from . import _lib
 
 
 class RunningMean:
@@ -41,11 +59,95 @@ def topk_percent(logits: torch.Tensor, targets: torch.Tensor, ks=(1, 5)):
 
 
 @dataclass
+class EvalParts:
+    """The sums an evaluation is made of: what crosses ranks (``dist.all_reduce_metrics``)."""
+    loss_sum: float
+    images: int
+    hits1: int
+    hits5: int
+
+    def result(self) -> "EvalResult":
+        n = self.images
+        res = EvalResult(self.loss_sum / n if n else 0.0, 100.0 * self.hits1 / n if n else 0.0,
+                         100.0 * self.hits5 / n if n else 0.0, n)
+        res.parts = self
+        return res
+
+
+@dataclass
 class EvalResult:
     loss: float
     top1: float
     top5: float
     images: int
+    parts = None        # (not a field) the exact sums behind the four numbers, when the device metrics produced them
+
+    def to_parts(self) -> EvalParts:
+        """The sums behind this result: exact when ``parts`` is set, otherwise recovered from the means (the hit
+        counts exactly, ``loss_sum`` to the last digit of ``loss * images``)."""
+        if self.parts is not None:
+            return self.parts
+        return EvalParts(self.loss * self.images, self.images, int(round(self.top1 * self.images / 100.0)),
+                         int(round(self.top5 * self.images / 100.0)))
+
+
+class DeviceMetrics:
+    """Loss / top-1 / top-5 accumulated on the device by ``ttnet_eval_metrics`` (csrc/metrics.hip): one 64-byte
+    accumulator per lane, added to by ``update`` on the current stream, read back once by ``result``."""
+
+    def __init__(self, device, lanes: int = 1):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"DeviceMetrics needs a HIP device, got {device}: the device metrics have no CPU path "
+                               "(use metrics=\"torch\")")
+        if lanes < 1:
+            raise ValueError("lanes must be positive")
+        self.device, self.lanes = device, int(lanes)
+        self.acc = torch.zeros((self.lanes, 8), dtype=torch.int64, device=device)      # ttnet_eval_acc [lanes]
+        assert self.acc.element_size() * 8 == C.sizeof(_lib.EvalAcc)
+
+    def update(self, logits: torch.Tensor, targets: torch.Tensor, lane: int = 0, per_image: bool = False):
+        """Add a batch (float32 ``[n, n_classes]`` logits, int64 ``[n]`` targets, both on the device) to ``lane``'s
+        accumulator: asynchronous on the current stream, capturable.  ``per_image=True`` returns the per-image
+        ``(loss float64 [n], rank int32 [n])`` (rank -1: target out of range; INT32_MAX: a NaN in the row)."""
+        if not (0 <= lane < self.lanes):
+            raise RuntimeError(f"lane {lane} outside [0, {self.lanes})")
+        if (not logits.is_cuda) or logits.dtype != torch.float32 or logits.dim() != 2:
+            raise RuntimeError(f"expected float32 HIP logits [n, n_classes], got {logits.dtype} {tuple(logits.shape)} on "
+                               f"{logits.device}")
+        n, n_classes = logits.shape
+        if targets.device != logits.device or targets.dtype != torch.int64 or tuple(targets.shape) != (n,):
+            raise RuntimeError(f"expected int64 targets [{n}] on {logits.device}, got {targets.dtype} "
+                               f"{tuple(targets.shape)} on {targets.device}")
+        logits, targets = logits.contiguous(), targets.contiguous()
+        rec = torch.empty((n, 2), dtype=torch.int64, device=logits.device)               # {double loss; int32 rank, 0}
+        with torch.cuda.device(logits.device):
+            stream = torch.cuda.current_stream(logits.device).cuda_stream
+            _lib.check(_lib.load().ttnet_eval_metrics(
+                C.c_void_p(logits.data_ptr()), C.c_void_p(targets.data_ptr()), n, n_classes,
+                C.c_void_p(self.acc[lane].data_ptr()), C.c_void_p(rec.data_ptr()), C.c_void_p(stream)))
+        if per_image:
+            return rec[:, 0].view(torch.float64), rec.view(torch.int32)[:, 2]
+        return None
+
+    def parts(self, check: bool = True) -> EvalParts:
+        """Synchronise the device once and sum the lanes in lane order."""
+        torch.cuda.synchronize(self.device)
+        host = self.acc.cpu()
+        loss = host[:, 0].view(torch.float64).tolist()
+        ints = host[:, 1:5].tolist()
+        bad = sum(r[3] for r in ints)
+        if check and bad:
+            raise RuntimeError(f"evaluate: {bad} target(s) were outside [0, n_classes): they count as no hit and are "
+                               "left out of the loss, so the metrics are not those of the dataset")
+        loss_sum = 0.0
+        for v in loss:
+            loss_sum += v
+        return EvalParts(loss_sum, sum(r[0] for r in ints), sum(r[1] for r in ints), sum(r[2] for r in ints))
+
+    def result(self) -> EvalResult:
+        """``EvalResult`` of everything added so far; raises, naming the count, if any target was out of range."""
+        return self.parts().result()
 
 
 class _Pending:
@@ -55,16 +157,37 @@ class _Pending:
         self.loss, self.hits1, self.hits5, self.n, self.event = loss, hits1, hits5, n, event
 
 
+def _batch_len(inputs) -> int:
+    return inputs.size(0) if isinstance(inputs, torch.Tensor) else len(inputs)
+
+
 @torch.no_grad()
 def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]],
-             device: torch.device, log_every: int = 0, inflight: int = 1) -> EvalResult:
+             device: torch.device, log_every: int = 0, inflight: int = 1, *,
+             forward: Optional[Callable] = None, metrics: str = "torch") -> EvalResult:
     """main.py:242-284: ``model.eval()``, no_grad, per batch loss / top-1 / top-5.
 
     ``inflight`` > 1 keeps that many batches in flight on separate HIP streams and model lanes
     (``model.set_lanes``): the loss / top-k of a batch stay on the device until its lane comes
     round again, instead of the reference's ``.item()`` after every batch, so the ramp and tail
     of one batch's kernels overlap the next batch.  The metrics are the same numbers in the same
-    order of accumulation."""
+    order of accumulation.
+
+    A batch is ``(inputs, targets)``; ``inputs`` is moved with ``.to(device, non_blocking=True)`` on the lane's
+    stream and its type selects the forward: float tensor -> ``model(x)``; uint8 ``[n,224,224,3]`` ->
+    ``model.forward_u8``; ``RaggedU8`` -> ``preprocess.imgnet_eval_forward``; ``RaggedJpeg`` ->
+    ``jpeg.jpeg_eval_forward``.  ``forward(model, inputs, lane)`` replaces that choice.  After the loop the sticky
+    error counts of the pipeline are checked (``check_range``, and ``check_ragged`` / ``check_jpeg`` when such
+    batches were seen): a corrupt file or an overflow raises instead of returning metrics.
+
+    ``metrics="device"`` reduces loss and hits on the device (``DeviceMetrics``): nothing is read back per batch, a
+    lane is reused after its event, and ``log_every`` reads the accumulators -- one synchronisation -- only on the
+    batches it logs.  See the module docstring for how its numbers relate to the default ``"torch"`` path."""
+    if metrics not in ("torch", "device"):
+        raise ValueError(f"metrics must be \"torch\" or \"device\", got {metrics!r}")
+    if metrics == "device" and device.type != "cuda":
+        raise RuntimeError(f"evaluate(metrics=\"device\") needs a HIP device, got {device}: the device metrics have no "
+                           "CPU path (use metrics=\"torch\")")
     model.eval()
     loss_m, top1_m, top5_m = RunningMean("Loss"), RunningMean("Acc@1"), RunningMean("Acc@5")
     use_lanes = inflight > 1 and device.type == "cuda" and hasattr(model, "set_lanes")
@@ -72,6 +195,7 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
         model.set_lanes(inflight)
         streams = [torch.cuda.Stream(device) for _ in range(inflight)]
     pending = []
+    seen = set()                                           # "ragged", "jpeg": which sticky counts to check at the end
 
     def retire(p: _Pending, i: int):
         if p.event is not None:
@@ -82,40 +206,101 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
         if log_every and i % log_every == 0:
             print("Loss: %.3f | Acc1: %.3f%% Acc5: %.3f%% " % (loss_m.avg, top1_m.avg, top5_m.avg), flush=True)
 
-    def metrics(outputs, targets):
+    def torch_metrics(outputs, targets):
         loss = F.cross_entropy(outputs, targets)
         order = outputs.topk(5, dim=1).indices
         hits = order.eq(targets.reshape(-1, 1))
         return loss, hits[:, :1].any(dim=1).float().mean(), hits[:, :5].any(dim=1).float().mean()
 
-    done = 0
-    for i, (inputs, targets) in enumerate(batches):
-        if use_lanes:
-            lane = i % inflight
-            if len(pending) == inflight:              # this lane's previous batch: read its metrics now
-                retire(pending.pop(0), done)
-                done += 1
-            with torch.cuda.stream(streams[lane]):
+    def run(inputs, lane: Optional[int]):
+        """The forward the batch type asks for; ``lane`` None: the model is called as ``model(x)``."""
+        if forward is not None:
+            return forward(model, inputs, lane or 0)
+        if isinstance(inputs, torch.Tensor):
+            if inputs.dtype == torch.uint8:
+                return model.forward_u8(inputs, lane=lane or 0)
+            return model(inputs) if lane is None else model(inputs, lane=lane)
+        from . import jpeg, preprocess                    # (not needed by the float path)
+        if isinstance(inputs, jpeg.RaggedJpeg):
+            seen.update(("jpeg", "ragged"))
+            return jpeg.jpeg_eval_forward(model, inputs, lane=lane or 0)
+        if isinstance(inputs, preprocess.RaggedU8):
+            seen.add("ragged")
+            return preprocess.imgnet_eval_forward(model, inputs, lane=lane or 0)
+        raise RuntimeError(f"evaluate: no forward for a batch of type {type(inputs).__name__}; pass forward=")
+
+    if metrics == "device":
+        res = _evaluate_device(batches, device, log_every, inflight if use_lanes else 1,
+                               streams if use_lanes else None, run)
+    else:
+        done = 0
+        for i, (inputs, targets) in enumerate(batches):
+            if use_lanes:
+                lane = i % inflight
+                if len(pending) == inflight:              # this lane's previous batch: read its metrics now
+                    retire(pending.pop(0), done)
+                    done += 1
+                with torch.cuda.stream(streams[lane]):
+                    inputs = inputs.to(device, non_blocking=True)
+                    targets = targets.to(device, non_blocking=True)
+                    outputs = run(inputs, lane)
+                    loss, h1, h5 = torch_metrics(outputs, targets)
+                    ev = torch.cuda.Event()
+                    ev.record(streams[lane])
+                pending.append(_Pending(loss, h1, h5, _batch_len(inputs), ev))
+            else:
                 inputs = inputs.to(device, non_blocking=True)
                 targets = targets.to(device, non_blocking=True)
-                outputs = model(inputs, lane=lane)
-                loss, h1, h5 = metrics(outputs, targets)
-                ev = torch.cuda.Event()
-                ev.record(streams[lane])
-            pending.append(_Pending(loss, h1, h5, inputs.size(0), ev))
-        else:
-            inputs = inputs.to(device, non_blocking=True)
-            targets = targets.to(device, non_blocking=True)
-            outputs = model(inputs)
-            loss, h1, h5 = metrics(outputs, targets)
-            retire(_Pending(loss, h1, h5, inputs.size(0), None), i)
-    for p in pending:
-        retire(p, done)
-        done += 1
+                outputs = run(inputs, None)
+                loss, h1, h5 = torch_metrics(outputs, targets)
+                retire(_Pending(loss, h1, h5, _batch_len(inputs), None), i)
+        for p in pending:
+            retire(p, done)
+            done += 1
+        res = None
     # the range flag of the split operands is reported on the next call of a plan: without this, an overflow in the
     # last (or only) batch would end in silently invalid metrics
     inner = getattr(model, "module", model)              # (nn.DataParallel wrapper, main.py:192)
     if hasattr(inner, "check_range"):
         inner.check_range()
+    if "jpeg" in seen:                                    # likewise: a corrupt file decodes as zeros and is only counted
+        from . import jpeg
+        jpeg.check_jpeg(device)
+    if "ragged" in seen:
+        from . import preprocess
+        preprocess.check_ragged(device)
+    if res is not None:
+        res = res.result()                                # (one synchronisation; raises on a target out of range)
+        print("Acc..", res.top1, res.top5)
+        return res
     print("Acc..", top1_m.avg, top5_m.avg)
     return EvalResult(loss_m.avg, top1_m.avg, top5_m.avg, loss_m.count)
+
+
+def _evaluate_device(batches, device, log_every, lanes, streams, run) -> DeviceMetrics:
+    """The loop of ``evaluate(metrics="device")``: forward + ``ttnet_eval_metrics`` per batch on the lane's stream,
+    nothing read back; returns the accumulators."""
+    dm = DeviceMetrics(device, lanes)
+    if streams is not None:
+        for s in streams:                                 # the accumulators were zeroed on the current stream
+            s.wait_stream(torch.cuda.current_stream(device))
+    events = [None] * lanes
+    for i, (inputs, targets) in enumerate(batches):
+        lane = i % lanes
+        if events[lane] is not None:                      # this lane's previous batch still owns its workspace
+            events[lane].synchronize()
+        if streams is not None:
+            with torch.cuda.stream(streams[lane]):
+                inputs = inputs.to(device, non_blocking=True)
+                targets = targets.to(device, non_blocking=True)
+                dm.update(run(inputs, lane), targets, lane)
+                events[lane] = torch.cuda.Event()
+                events[lane].record(streams[lane])
+        else:
+            inputs = inputs.to(device, non_blocking=True)
+            targets = targets.to(device, non_blocking=True)
+            dm.update(run(inputs, None), targets, 0)
+        if log_every and i % log_every == 0:
+            p = dm.parts(check=False).result()
+            print("Loss: %.3f | Acc1: %.3f%% Acc5: %.3f%% " % (p.loss, p.top1, p.top5), flush=True)
+    return dm

@@ -1,0 +1,199 @@
+"""``python -m scale_imagenet_amd.main``: evaluate an ImageNet-style folder, the counterpart of ``python3 main.py``.
+
+The reference's driver (main.py) builds TT_vf_19lv3_imgnet_small, loads ``./ckpt/last.pth``, runs ``test()`` over
+``<data_dir>/val`` and prints ``Acc.. <top-1> <top-5>`` (main.py:196-284).  This command does the same through the
+project's own path: the files' bytes go to the device (``FileBytesFolder`` + ``collate_jpeg``), are decoded, resized,
+cropped and classified there (``evaluate(..., metrics="device")``), and only four numbers per rank come back.  The
+flags carry the reference's names and defaults; its training flags are accepted and ignored, as the reference's own
+evaluation-only ``main_worker`` ignores them.  Nothing is parsed, created or written at import time.
+"""
+from __future__ import annotations
+
+import argparse
+import contextlib
+import os
+import subprocess
+import sys
+from typing import List, Optional, Sequence
+
+VARIANT_CLASSES = {"small": "TT_vf_19lv3_imgnet_small", "xsmall": "TT_vf_19lv3_imgnet_xsmall", "full": "TT_vf_19lv3_imgnet"}
+# the reference's flags that only its (absent) training loop, its log directories or its own launcher read
+_IGNORED = [("--root_dir", str, "./"), ("--log_name", str, "resnet_imagenet_4w4f"), ("--pretrain_dir", str, "resnet_4w4f"),
+            ("--lr", float, 0.1), ("--wd", float, 1e-4), ("--train_batch_size", int, 256), ("--max_epochs", int, 90),
+            ("--Wbits", int, 32), ("--Abit_inter", int, 2), ("--world-size", int, 1), ("--rank", int, 0),
+            ("--dist-url", str, "tcp://127.0.0.1:2345"), ("--dist-backend", str, "nccl"), ("--seed", int, None)]
+_IGNORED_SWITCHES = ["--pretrain", "--multiprocessing-distributed"]
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(
+        prog="python -m scale_imagenet_amd.main",
+        description="Evaluate <data_dir>/val (one directory per class) with a TTNet ImageNet classifier on the HIP path "
+                    "and print the reference's final line, `Acc.. <top-1> <top-5>`.",
+        epilog="The reference's trained checkpoint is published on a file-sharing site and cannot be fetched by this "
+               "command; put it at --ckpt yourself, or try the command with --synthetic-ckpt (deterministic synthetic "
+               "weights: the accuracy is then that of chance).")
+    ref = p.add_argument_group("flags of the reference's main.py (same names and defaults)")
+    ref.add_argument("--data_dir", type=str, default="./../datasets/ILSVRC/Data/CLS-LOC/",
+                     help="dataset root; <data_dir>/val is evaluated")
+    ref.add_argument("--eval_batch_size", type=int, default=100)
+    ref.add_argument("--num_workers", type=int, default=6)
+    ref.add_argument("--nfilter", type=int, default=8)
+    ref.add_argument("--tfilter", type=int, default=8)
+    ref.add_argument("--layers", type=int, default=1)
+    ref.add_argument("--groups", type=str, default="1,None,4,None")
+    ref.add_argument("--gpu", type=int, default=None, help="GPU id to use (single process; default 0)")
+    ref.add_argument("--log_interval", type=int, default=40, help="print running metrics every N batches (0: never)")
+    own = p.add_argument_group("flags of this command")
+    own.add_argument("--variant", choices=sorted(VARIANT_CLASSES), default="small",
+                     help="model family (the reference hard-codes small)")
+    own.add_argument("--ckpt", type=str, default=None,
+                     help="checkpoint with a 'model_state_dict' entry, bare or 'module.'-prefixed keys "
+                          "(default ./ckpt/last.pth, the path the reference hard-codes)")
+    own.add_argument("--synthetic-ckpt", action="store_true",
+                     help="use synth.synth_state_dict's deterministic weights instead of a trained checkpoint; when --ckpt "
+                          "names a file that does not exist yet, the synthetic checkpoint is written there first")
+    own.add_argument("--input", choices=["jpeg", "jpeg-progressive", "pillow"], default="jpeg",
+                     help="jpeg: files decoded on the device (progressive ones by Pillow in the workers); "
+                          "jpeg-progressive: progressive files on the device too; pillow: everything decoded by Pillow "
+                          "in the workers (slow; for cross-checking a folder)")
+    own.add_argument("--inflight", type=int, default=2, help="batches in flight on separate streams / lanes")
+    own.add_argument("--gpus", type=int, default=1, help="evaluate on N GPUs: starts one rank per GPU itself")
+    ign = p.add_argument_group("accepted and ignored (training, logging and launcher flags of the reference)")
+    for name, typ, default in _IGNORED:
+        ign.add_argument(name, type=typ, default=default, help=argparse.SUPPRESS)
+    for name in _IGNORED_SWITCHES:
+        ign.add_argument(name, action="store_true", default=False, help=argparse.SUPPRESS)
+    return p
+
+
+def parse_groups(text: str) -> List[Optional[int]]:
+    return [None if g.strip() == "None" else int(g) for g in text.split(",")]
+
+
+def _note_ignored(args, argv: Sequence[str]):
+    given = sorted({a.split("=")[0] for a in argv if a.startswith("--")} &
+                   ({n for n, _, _ in _IGNORED} | set(_IGNORED_SWITCHES)))
+    if given:
+        print(f"note: {', '.join(given)} only matter to training or to the reference's own launcher; ignored", file=sys.stderr)
+
+
+def _probe_devices() -> int:
+    """Number of HIP devices, counted by a child process: the parent of the ranks must not initialise the GPU itself."""
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count() if torch.cuda.is_available() else 0)"],
+                       capture_output=True, text=True, timeout=300)
+    if r.returncode != 0:
+        raise SystemExit(f"could not count the HIP devices:\n{r.stderr[-2000:]}")
+    return int(r.stdout.strip().splitlines()[-1])
+
+
+def _check_paths(args):
+    val = os.path.join(args.data_dir, "val")
+    if not os.path.isdir(val):
+        raise SystemExit(f"--data_dir: {val} is not a directory (expected <data_dir>/val/<class>/<image files>)")
+    if not args.synthetic_ckpt and not os.path.isfile(args.ckpt or "./ckpt/last.pth"):
+        raise SystemExit(f"--ckpt: {args.ckpt or './ckpt/last.pth'} does not exist.  The reference's checkpoint has to be "
+                         "downloaded by hand; --synthetic-ckpt runs the command on synthetic weights instead")
+
+
+def _state_dict(args, spec, rank: int):
+    import torch
+    if args.synthetic_ckpt:
+        from . import synth
+        state = {k: torch.from_numpy(v.copy()) for k, v in synth.synth_state_dict(spec).items()}
+        if args.ckpt and rank == 0 and not os.path.exists(args.ckpt):
+            tmp = f"{args.ckpt}.tmp{os.getpid()}"
+            torch.save({"model_state_dict": state}, tmp)
+            os.replace(tmp, args.ckpt)
+        return state
+    ckpt = torch.load(args.ckpt or "./ckpt/last.pth", map_location="cpu")     # main.py:220-222
+    return ckpt["model_state_dict"]
+
+
+class _PillowFolder:
+    """``FileBytesFolder``'s samples decoded in the worker as the reference's loader does
+    (``Image.open(path).convert("RGB")``): uint8 HWC images for ``collate_u8``."""
+
+    def __init__(self, folder):
+        self.samples = folder.samples
+
+    def __len__(self) -> int:
+        return len(self.samples)
+
+    def __getitem__(self, i):
+        import numpy as np
+        from PIL import Image
+        path, target = self.samples[i]
+        with Image.open(path) as im:
+            return np.asarray(im.convert("RGB")), target
+
+
+def run(args) -> int:
+    """One rank (or the only process): evaluate this rank's shard, sum over the ranks, rank 0 prints the line."""
+    import torch
+
+    from . import jpeg, preprocess, ttnet
+    from .dist import ShardedSampler, all_reduce_metrics, init_from_env
+    from .evaluate import evaluate
+
+    rank, world, local_rank = init_from_env("nccl")
+    if world != args.gpus and world > 1:
+        args.gpus = world                                 # started by torch.distributed.run: its world size holds
+    if not torch.cuda.is_available():
+        raise SystemExit("scale_imagenet_amd.main needs a HIP device (the product has no CPU path)")
+    index = (args.gpu or 0) if world == 1 else local_rank % torch.cuda.device_count()
+    device = torch.device("cuda", index)
+    torch.cuda.set_device(device)
+    _check_paths(args)
+
+    model = getattr(ttnet, VARIANT_CLASSES[args.variant])(argparse.Namespace(
+        nfilter=args.nfilter, tfilter=args.tfilter, layers=args.layers, groups=parse_groups(args.groups)))
+    model.load_state_dict(_state_dict(args, model.spec, rank), strict=True)
+    model = model.to(device).eval().reserve(max(1, args.eval_batch_size))
+
+    folder = jpeg.FileBytesFolder(os.path.join(args.data_dir, "val"))
+    dataset, collate = {"jpeg": (folder, jpeg.collate_jpeg),
+                        "jpeg-progressive": (folder, jpeg.collate_jpeg_progressive),
+                        "pillow": (_PillowFolder(folder), preprocess.collate_u8)}[args.input]
+    # the workers are fresh interpreters: this process has initialised the GPU and is not forked (launch.py)
+    loader = torch.utils.data.DataLoader(dataset, batch_size=args.eval_batch_size, sampler=ShardedSampler(len(dataset), rank, world),
+                                         num_workers=args.num_workers, collate_fn=collate, pin_memory=True,
+                                         multiprocessing_context="spawn" if args.num_workers > 0 else None)
+    # a rank's own lines (running metrics, its shard's Acc..) go to stderr when there are several: stdout carries the result
+    with contextlib.redirect_stdout(sys.stderr) if world > 1 else contextlib.nullcontext():
+        part = evaluate(model, loader, device, log_every=args.log_interval, inflight=max(1, args.inflight), metrics="device")
+    res = all_reduce_metrics(part)
+    if world > 1:
+        import torch.distributed as dist
+        if rank == 0:
+            print("Acc..", res.top1, res.top5, flush=True)             # main.py:284
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    argv = list(sys.argv[1:] if argv is None else argv)
+    args = build_parser().parse_args(argv)
+    from .launch import spawn_ranks, under_launcher
+    if args.gpus < 1:
+        raise SystemExit("--gpus must be positive")
+    if args.gpus > 1 and not under_launcher():
+        # this process has not touched the GPU and does not: the ranks are fresh interpreters (launch.py)
+        have = _probe_devices()
+        if have < 1:
+            raise SystemExit(f"--gpus {args.gpus}: no HIP device on this machine (the product has no CPU path); no rank was started")
+        if have < args.gpus and os.environ.get("TTNET_DIST_BACKEND") != "gloo":
+            raise SystemExit(f"--gpus {args.gpus}: only {have} HIP device(s) here (TTNET_DIST_BACKEND=gloo rehearses several "
+                             "ranks on one device)")
+        _check_paths(args)
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))       # the ranks import the same package
+        path = os.pathsep.join(p for p in (root, os.environ.get("PYTHONPATH")) if p)
+        return spawn_ranks(["-m", "scale_imagenet_amd.main", *argv], args.gpus, extra_env={"PYTHONPATH": path})
+    if os.environ.get("RANK", "0") == "0":
+        _note_ignored(args, argv)
+    return run(args)
+
+
+if __name__ == "__main__":
+    sys.exit(main())
