@@ -22,6 +22,7 @@ Two ways to the metrics:
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from dataclasses import dataclass
 from typing import Callable, Iterable, Optional, Tuple
@@ -150,15 +151,53 @@ class DeviceMetrics:
         return self.parts().result()
 
 
-class _Pending:
-    """Device-side metrics of one batch, read back only when its lane is needed again."""
+class _TorchMetrics:
+    """``metrics="torch"``: ``F.cross_entropy`` + ``topk`` per batch on the batch's stream; the three scalars are read
+    back when the batch retires and accumulated as float32 batch means, as the reference does."""
+    logs = "retired"
 
-    def __init__(self, loss, hits1, hits5, n, event):
-        self.loss, self.hits1, self.hits5, self.n, self.event = loss, hits1, hits5, n, event
+    def __init__(self):
+        self.loss, self.top1, self.top5 = RunningMean("Loss"), RunningMean("Acc@1"), RunningMean("Acc@5")
+
+    def add(self, outputs, targets, lane):
+        loss = F.cross_entropy(outputs, targets)
+        order = outputs.topk(5, dim=1).indices
+        hits = order.eq(targets.reshape(-1, 1))
+        return loss, hits[:, :1].any(dim=1).float().mean(), hits[:, :5].any(dim=1).float().mean()
+
+    def retire(self, batch, n):
+        loss, hits1, hits5 = batch
+        self.loss.update(loss.item(), n)
+        self.top1.update(100.0 * hits1.item(), n)
+        self.top5.update(100.0 * hits5.item(), n)
+
+    def running(self):
+        return self.loss.avg, self.top1.avg, self.top5.avg
+
+    def result(self) -> EvalResult:
+        return EvalResult(self.loss.avg, self.top1.avg, self.top5.avg, self.loss.count)
 
 
-def _batch_len(inputs) -> int:
-    return inputs.size(0) if isinstance(inputs, torch.Tensor) else len(inputs)
+class _OnDeviceMetrics:
+    """``metrics="device"``: ``DeviceMetrics.update`` per batch on the batch's stream; nothing is read back when a batch
+    retires, a log line reads the accumulators (one synchronisation, no range check), ``result`` reads them once."""
+    logs = "issued"
+
+    def __init__(self, device, lanes, streams):
+        self.dm = DeviceMetrics(device, lanes)
+        self.add = self.dm.update                         # add(outputs, targets, lane): nothing to keep for retire
+        for s in streams:                                 # the accumulators were zeroed on the current stream
+            s.wait_stream(torch.cuda.current_stream(device))
+
+    def retire(self, batch, n):
+        pass
+
+    def running(self):
+        p = self.dm.parts(check=False).result()
+        return p.loss, p.top1, p.top5
+
+    def result(self) -> EvalResult:
+        return self.dm.result()                           # (one synchronisation; raises on a target out of range)
 
 
 @torch.no_grad()
@@ -189,28 +228,13 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
         raise RuntimeError(f"evaluate(metrics=\"device\") needs a HIP device, got {device}: the device metrics have no "
                            "CPU path (use metrics=\"torch\")")
     model.eval()
-    loss_m, top1_m, top5_m = RunningMean("Loss"), RunningMean("Acc@1"), RunningMean("Acc@5")
     use_lanes = inflight > 1 and device.type == "cuda" and hasattr(model, "set_lanes")
+    lanes = inflight if use_lanes else 1
     if use_lanes:
         model.set_lanes(inflight)
-        streams = [torch.cuda.Stream(device) for _ in range(inflight)]
-    pending = []
+    streams = [torch.cuda.Stream(device) for _ in range(lanes)] if use_lanes else []
+    acc = _OnDeviceMetrics(device, lanes, streams) if metrics == "device" else _TorchMetrics()
     seen = set()                                           # "ragged", "jpeg": which sticky counts to check at the end
-
-    def retire(p: _Pending, i: int):
-        if p.event is not None:
-            p.event.synchronize()
-        loss_m.update(p.loss.item(), p.n)
-        top1_m.update(100.0 * p.hits1.item(), p.n)
-        top5_m.update(100.0 * p.hits5.item(), p.n)
-        if log_every and i % log_every == 0:
-            print("Loss: %.3f | Acc1: %.3f%% Acc5: %.3f%% " % (loss_m.avg, top1_m.avg, top5_m.avg), flush=True)
-
-    def torch_metrics(outputs, targets):
-        loss = F.cross_entropy(outputs, targets)
-        order = outputs.topk(5, dim=1).indices
-        hits = order.eq(targets.reshape(-1, 1))
-        return loss, hits[:, :1].any(dim=1).float().mean(), hits[:, :5].any(dim=1).float().mean()
 
     def run(inputs, lane: Optional[int]):
         """The forward the batch type asks for; ``lane`` None: the model is called as ``model(x)``."""
@@ -229,35 +253,38 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
             return preprocess.imgnet_eval_forward(model, inputs, lane=lane or 0)
         raise RuntimeError(f"evaluate: no forward for a batch of type {type(inputs).__name__}; pass forward=")
 
-    if metrics == "device":
-        res = _evaluate_device(batches, device, log_every, inflight if use_lanes else 1,
-                               streams if use_lanes else None, run)
-    else:
-        done = 0
-        for i, (inputs, targets) in enumerate(batches):
+    def log(index: int, when: str):
+        if acc.logs == when and index % log_every == 0:
+            print("Loss: %.3f | Acc1: %.3f%% Acc5: %.3f%% " % acc.running(), flush=True)
+
+    pending = []                                           # batches in flight, oldest first: (index, event, metrics, images)
+
+    def retire():
+        index, event, batch, n = pending.pop(0)
+        if event is not None:
+            event.synchronize()
+        acc.retire(batch, n)
+        if log_every:
+            log(index, "retired")
+
+    for i, (inputs, targets) in enumerate(batches):
+        lane = i % lanes
+        if len(pending) == lanes:                          # this lane's previous batch still owns its workspace
+            retire()
+        with torch.cuda.stream(streams[lane]) if use_lanes else contextlib.nullcontext():
+            inputs = inputs.to(device, non_blocking=True)
+            targets = targets.to(device, non_blocking=True)
+            batch = acc.add(run(inputs, lane if use_lanes else None), targets, lane)
+            event = torch.cuda.Event() if use_lanes else None
             if use_lanes:
-                lane = i % inflight
-                if len(pending) == inflight:              # this lane's previous batch: read its metrics now
-                    retire(pending.pop(0), done)
-                    done += 1
-                with torch.cuda.stream(streams[lane]):
-                    inputs = inputs.to(device, non_blocking=True)
-                    targets = targets.to(device, non_blocking=True)
-                    outputs = run(inputs, lane)
-                    loss, h1, h5 = torch_metrics(outputs, targets)
-                    ev = torch.cuda.Event()
-                    ev.record(streams[lane])
-                pending.append(_Pending(loss, h1, h5, _batch_len(inputs), ev))
-            else:
-                inputs = inputs.to(device, non_blocking=True)
-                targets = targets.to(device, non_blocking=True)
-                outputs = run(inputs, None)
-                loss, h1, h5 = torch_metrics(outputs, targets)
-                retire(_Pending(loss, h1, h5, _batch_len(inputs), None), i)
-        for p in pending:
-            retire(p, done)
-            done += 1
-        res = None
+                event.record(streams[lane])
+        pending.append((i, event, batch, inputs.size(0) if isinstance(inputs, torch.Tensor) else len(inputs)))
+        if not use_lanes:                                  # nothing in flight: read the batch now, as the reference does
+            retire()
+        if log_every:
+            log(i, "issued")
+    while pending:
+        retire()
     # the range flag of the split operands is reported on the next call of a plan: without this, an overflow in the
     # last (or only) batch would end in silently invalid metrics
     inner = getattr(model, "module", model)              # (nn.DataParallel wrapper, main.py:192)
@@ -269,38 +296,6 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
     if "ragged" in seen:
         from . import preprocess
         preprocess.check_ragged(device)
-    if res is not None:
-        res = res.result()                                # (one synchronisation; raises on a target out of range)
-        print("Acc..", res.top1, res.top5)
-        return res
-    print("Acc..", top1_m.avg, top5_m.avg)
-    return EvalResult(loss_m.avg, top1_m.avg, top5_m.avg, loss_m.count)
-
-
-def _evaluate_device(batches, device, log_every, lanes, streams, run) -> DeviceMetrics:
-    """The loop of ``evaluate(metrics="device")``: forward + ``ttnet_eval_metrics`` per batch on the lane's stream,
-    nothing read back; returns the accumulators."""
-    dm = DeviceMetrics(device, lanes)
-    if streams is not None:
-        for s in streams:                                 # the accumulators were zeroed on the current stream
-            s.wait_stream(torch.cuda.current_stream(device))
-    events = [None] * lanes
-    for i, (inputs, targets) in enumerate(batches):
-        lane = i % lanes
-        if events[lane] is not None:                      # this lane's previous batch still owns its workspace
-            events[lane].synchronize()
-        if streams is not None:
-            with torch.cuda.stream(streams[lane]):
-                inputs = inputs.to(device, non_blocking=True)
-                targets = targets.to(device, non_blocking=True)
-                dm.update(run(inputs, lane), targets, lane)
-                events[lane] = torch.cuda.Event()
-                events[lane].record(streams[lane])
-        else:
-            inputs = inputs.to(device, non_blocking=True)
-            targets = targets.to(device, non_blocking=True)
-            dm.update(run(inputs, None), targets, 0)
-        if log_every and i % log_every == 0:
-            p = dm.parts(check=False).result()
-            print("Loss: %.3f | Acc1: %.3f%% Acc5: %.3f%% " % (p.loss, p.top1, p.top5), flush=True)
-    return dm
+    res = acc.result()
+    print("Acc..", res.top1, res.top5)
+    return res

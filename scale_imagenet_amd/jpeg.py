@@ -20,13 +20,13 @@ import ctypes as C
 import io
 import os
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
-from .preprocess import MAX_SIDE, RaggedU8, resize_center_crop_u8_ragged
+from .preprocess import MAX_SIDE, RaggedU8, _StickyCount, resize_center_crop_u8_ragged
 
 KIND_JPEG, KIND_RAW, KIND_PROGRESSIVE = 0, 1, 2
 TABLE_BYTES = 2048        # per-image table block: uint16 quant[3][64] (zig-zag) + [3][dc, ac] x (counts[16], symbols[256])
@@ -59,18 +59,14 @@ class Unsupported:
     reason: str
 
 
-@dataclass
-class JpegHeader:
-    """What the device decoder needs, from the markers before the first SOS."""
+@dataclass(kw_only=True)
+class JpegFrame:
+    """The frame of a file, as both decoders need it: the SOF's size and components, the quantisation tables and the
+    colour-space markers."""
     h: int
     w: int
-    sof: int                                     # 0 or 1
     comps: List[Tuple[int, int, int, int]]       # per frame component: (id, h_samp, v_samp, quant table)
-    scan_tables: List[Tuple[int, int]]           # per component, in frame order: (dc table, ac table)
     qt: Dict[int, List[int]]                     # quant tables, zig-zag order, as in DQT
-    dht: Dict[Tuple[int, int], Tuple[List[int], List[int]]] = field(default_factory=dict)  # (class, id) -> counts, symbols
-    restart_interval: int = 0
-    scan_offset: int = 0                         # first byte of the entropy-coded data
     jfif: bool = False
     adobe_transform: Optional[int] = None
 
@@ -93,10 +89,50 @@ class JpegHeader:
         mx, my, b = self.mcus()
         return mx * my * b
 
+
+@dataclass(kw_only=True)
+class JpegHeader(JpegFrame):
+    """What the device decoder needs, from the markers before the first SOS."""
+    sof: int                                     # 0 or 1
+    scan_tables: List[Tuple[int, int]]           # per component, in frame order: (dc table, ac table)
+    dht: Dict[Tuple[int, int], Tuple[List[int], List[int]]] = field(default_factory=dict)  # (class, id) -> counts, symbols
+    restart_interval: int = 0
+    scan_offset: int = 0                         # first byte of the entropy-coded data
+
     def segments(self) -> int:
         mx, my, _ = self.mcus()
         ri = self.restart_interval
         return 1 if ri == 0 else (mx * my + ri - 1) // ri
+
+
+@dataclass
+class ProgressiveScan:
+    """One scan of a progressive file: ``comps`` are frame component indices (increasing), ``tables`` the Huffman
+    table in force for each of them when the SOS was read (DC tables in a DC scan, the AC table in an AC scan, as
+    (counts, symbols); None in a DC refinement, which reads raw bits), [data_start, data_end) the entropy-coded
+    bytes in the file."""
+    comps: List[int]
+    ss: int
+    se: int
+    ah: int
+    al: int
+    restart_interval: int
+    tables: List[Optional[Tuple[List[int], List[int]]]]
+    data_start: int
+    data_end: int
+    slot: int = 0                                # 4 * round + wave of the device schedule (_schedule)
+
+
+@dataclass(kw_only=True)
+class ProgressiveHeader(JpegFrame):
+    """What the device decoder needs of a progressive (SOF2) file: the frame and every scan."""
+    scans: List[ProgressiveScan]
+    rounds: int = 0
+
+    @property
+    def restart_interval(self) -> int:
+        """The first scan's (DRI may change between scans; each scan carries its own)."""
+        return self.scans[0].restart_interval
 
 
 def _check_huffman(counts: List[int], symbols: List[int], dc: bool) -> Optional[str]:
@@ -149,86 +185,151 @@ def _read_dht(seg, dht) -> Optional[str]:
     return None
 
 
+def _read_sos(seg):
+    """An SOS payload as ([(component id, dc table, ac table)], Ss, Se, Ah, Al); None if malformed."""
+    if len(seg) < 1 or len(seg) < 1 + 2 * seg[0] + 3:
+        return None
+    ns = seg[0]
+    sel = [(seg[1 + 2 * k], seg[2 + 2 * k] >> 4, seg[2 + 2 * k] & 15) for k in range(ns)]
+    return sel, seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns] >> 4, seg[3 + 2 * ns] & 15
+
+
+class _Walk:
+    """The marker walk behind ``parse_header`` and ``parse_progressive``: SOI, fill FFs, stand-alone markers, segment
+    lengths, and the segments that mean the same to both -- JFIF, Adobe, DQT, DHT, DAC, DRI and the SOF payload, kept
+    in ``jfif``, ``adobe``, ``qt``, ``dht``, ``ri`` and ``sof``.  Iterating yields ``(marker, payload)`` for what a client
+    decides about -- the frame just read (SOF0 / SOF1 / SOF2), SOS (a frame has been read by then), DNL -- with ``i``
+    behind the segment, and may be resumed after a ``break``.  It ends with ``error`` set at a malformed or refused
+    file, with ``eoi`` set at EOI, with neither at the end of the buffer, and never reads outside the buffer.
+
+    ``progressive`` names the client and may be switched off during the walk: ``parse_progressive`` takes SOF2 for a
+    frame where ``parse_header`` refuses it by name, and each words a cut-off length and a misplaced SOI its own way."""
+
+    def __init__(self, buf, progressive: bool):
+        self.b = bytes(buf)
+        self.progressive = progressive
+        self.i = 2                               # behind the segment last yielded
+        self.qt: Dict[int, List[int]] = {}
+        self.dht: Dict[Tuple[int, int], Tuple[List[int], List[int]]] = {}
+        self.sof = None                          # (marker, h, w, components)
+        self.ri, self.jfif, self.adobe = 0, False, None
+        self.scans = 0                           # scans passed by skip_scan_data
+        self.eoi, self.error = False, None
+        self._events = self._run()
+
+    def __iter__(self):
+        return self._events
+
+    def _run(self):
+        b, n, i = self.b, len(self.b), 2
+        if n < 4 or b[0] != 0xFF or b[1] != 0xD8:
+            self.error = "not a JPEG file (no SOI marker)"
+            return
+        while i < n:
+            if b[i] != 0xFF:
+                self.error = f"garbage between markers at byte {i}"
+                return
+            while i < n and b[i] == 0xFF:
+                i += 1
+            if i >= n:
+                return
+            m = b[i]
+            i += 1
+            if m == 0x01 or 0xD0 <= m <= 0xD7:
+                continue
+            if m == 0xD9:
+                self.eoi = True
+                return
+            if m == 0xD8 or m == 0x00:
+                self.error = f"unexpected marker 0xFF{m:02X}" + ("" if self.progressive else " in the header")
+                return
+            if i + 2 > n:
+                self.error = f"{'file' if self.progressive else 'header'} ends inside a marker length"
+                return
+            length = (b[i] << 8) | b[i + 1]
+            if length < 2 or i + length > n:
+                self.error = f"marker 0xFF{m:02X} runs past the end of the file"
+                return
+            seg = b[i + 2:i + length]
+            i += length
+            self.error = self._segment(m, seg)
+            if self.error is not None:
+                return
+            if m in (0xC0, 0xC1, 0xC2, 0xDA, 0xDC):
+                self.i = i
+                yield m, seg
+                i = self.i                       # (skip_scan_data may have moved it)
+
+    def _segment(self, m: int, seg: bytes) -> Optional[str]:
+        """Digests one marker segment; the reason if the file ends here."""
+        if m == 0xE0 and seg[:5] == b"JFIF\0":
+            self.jfif = True
+        elif m == 0xEE and seg[:5] == b"Adobe" and len(seg) >= 12:
+            self.adobe = seg[11]
+        elif m == 0xDB:
+            return "quantisation tables redefined between scans" if self.scans else _read_dqt(seg, self.qt)
+        elif m == 0xC4:
+            return _read_dht(seg, self.dht)
+        elif m == 0xCC:
+            return "arithmetic coding (DAC)"
+        elif m == 0xDD:
+            if len(seg) < 2:
+                return "malformed DRI"
+            self.ri = (seg[0] << 8) | seg[1]
+        elif m in _SOF_NAMES and not (m == 0xC2 and self.progressive):
+            return _SOF_NAMES[m]
+        elif m in (0xC0, 0xC1, 0xC2):
+            if self.sof is not None:
+                return "more than one SOF"
+            if len(seg) < 6 or len(seg) < 6 + 3 * seg[5]:
+                return "malformed SOF"
+            p, h, w, nf = seg[0], (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4], seg[5]
+            if p != 8:
+                return f"{p}-bit samples"
+            self.sof = (m, h, w, [(seg[6 + 3 * k], seg[7 + 3 * k] >> 4, seg[7 + 3 * k] & 15, seg[8 + 3 * k])
+                                  for k in range(nf)])
+        elif m == 0xDA and self.sof is None:
+            return "SOS before SOF"
+        return None
+
+    def skip_scan_data(self) -> Tuple[int, int]:
+        """After an SOS: moves behind the entropy-coded data that starts at ``i`` and returns its [start, end).  It
+        ends at the FF of the next marker other than FF00 / RSTn (fill FFs in front of it belong to the data), or at
+        the end of the file."""
+        b, n, start = self.b, len(self.b), self.i
+        i = start
+        while True:
+            j = b.find(b"\xff", i)
+            if j < 0 or j + 1 >= n:
+                j = n
+                break
+            m = b[j + 1]
+            if m == 0x00 or 0xD0 <= m <= 0xD7:
+                i = j + 2
+            elif m == 0xFF:
+                i = j + 1
+            else:
+                break
+        self.i = j
+        self.scans += 1
+        return start, j
+
+
 def parse_header(buf) -> "JpegHeader | Unsupported":
     """Marker walk up to the first SOS.  Returns a JpegHeader if the device decodes the file, otherwise
     Unsupported(reason).  Never reads outside ``buf``; a truncated or malformed header is Unsupported."""
-    b = bytes(buf)
-    n = len(b)
-    if n < 4 or b[0] != 0xFF or b[1] != 0xD8:
-        return Unsupported("not a JPEG file (no SOI marker)")
-    i = 2
-    qt: Dict[int, List[int]] = {}
-    dht: Dict[Tuple[int, int], Tuple[List[int], List[int]]] = {}
-    sof = None
-    ri = 0
-    jfif = False
-    adobe = None
-    while True:
-        if i >= n:
-            return Unsupported("header ends before the first SOS")
-        if b[i] != 0xFF:
-            return Unsupported(f"garbage between markers at byte {i}")
-        while i < n and b[i] == 0xFF:
-            i += 1
-        if i >= n:
-            return Unsupported("header ends before the first SOS")
-        m = b[i]
-        i += 1
-        if m == 0x01 or 0xD0 <= m <= 0xD7:
-            continue
-        if m == 0xD9:
-            return Unsupported("EOI before any scan")
-        if m == 0xD8 or m == 0x00:
-            return Unsupported(f"unexpected marker 0xFF{m:02X} in the header")
-        if i + 2 > n:
-            return Unsupported("header ends inside a marker length")
-        L = (b[i] << 8) | b[i + 1]
-        if L < 2 or i + L > n:
-            return Unsupported(f"marker 0xFF{m:02X} runs past the end of the file")
-        seg = b[i + 2:i + L]
-        nxt = i + L
-        if m == 0xE0 and seg[:5] == b"JFIF\0":
-            jfif = True
-        elif m == 0xEE and seg[:5] == b"Adobe" and len(seg) >= 12:
-            adobe = seg[11]
-        elif m == 0xDB:
-            err = _read_dqt(seg, qt)
-            if err:
-                return Unsupported(err)
-        elif m == 0xC4:
-            err = _read_dht(seg, dht)
-            if err:
-                return Unsupported(err)
-        elif m == 0xCC:
-            return Unsupported("arithmetic coding (DAC)")
-        elif m in _SOF_NAMES:
-            return Unsupported(_SOF_NAMES[m])
-        elif m in (0xC0, 0xC1):
-            if sof is not None:
-                return Unsupported("more than one SOF")
-            if len(seg) < 6:
-                return Unsupported("malformed SOF")
-            p, h, w, nf = seg[0], (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4], seg[5]
-            if len(seg) < 6 + 3 * nf:
-                return Unsupported("malformed SOF")
-            if p != 8:
-                return Unsupported(f"{p}-bit samples")
-            comps = [(seg[6 + 3 * k], seg[7 + 3 * k] >> 4, seg[7 + 3 * k] & 15, seg[8 + 3 * k]) for k in range(nf)]
-            sof = (m - 0xC0, h, w, comps)
-        elif m == 0xDD:
-            if len(seg) < 2:
-                return Unsupported("malformed DRI")
-            ri = (seg[0] << 8) | seg[1]
-        elif m == 0xDA:
-            if sof is None:
-                return Unsupported("SOS before SOF")
-            if len(seg) < 1 or len(seg) < 1 + 2 * seg[0] + 3:
-                return Unsupported("malformed SOS")
-            ns = seg[0]
-            scomps = [(seg[1 + 2 * k], seg[2 + 2 * k] >> 4, seg[2 + 2 * k] & 15) for k in range(ns)]
-            ss, se, ahal = seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns]
-            return _classify(sof, scomps, (ss, se, ahal), qt, dht, ri, nxt, jfif, adobe)
-        i = nxt
+    return _sequential(_Walk(buf, progressive=False))
+
+
+def _sequential(walk: _Walk) -> "JpegHeader | Unsupported":
+    """Reads on to the first SOS and classifies a sequential frame (a DNL in front of it is passed over)."""
+    walk.progressive = False
+    for m, seg in walk:
+        if m == 0xDA:
+            return _classify(walk, seg)
+    if walk.error is not None:
+        return Unsupported(walk.error)
+    return Unsupported("EOI before any scan" if walk.eoi else "header ends before the first SOS")
 
 
 def _classify_frame(h, w, comps) -> Optional[str]:
@@ -261,89 +362,35 @@ def _classify_colour(comps, jfif, adobe) -> Optional[str]:
     return None
 
 
-def _classify(sof, scomps, spectral, qt, dht, ri, scan_offset, jfif, adobe):
-    kind, h, w, comps = sof
-    nf = len(comps)
+def _classify(walk: _Walk, seg) -> "JpegHeader | Unsupported":
+    """The first SOS of a sequential file: a JpegHeader if this one scan is all the device has to decode."""
+    sos = _read_sos(seg)
+    if sos is None:
+        return Unsupported("malformed SOS")
+    scomps, ss, se, ah, al = sos
+    m, h, w, comps = walk.sof
     err = _classify_frame(h, w, comps)
     if err:
         return Unsupported(err)
-    if len(scomps) != nf:
+    if len(scomps) != len(comps):
         return Unsupported("multi-scan sequential file (a scan without every component)")
     if [c[0] for c in scomps] != [c[0] for c in comps]:
         return Unsupported("scan components in another order than the frame's")
-    if spectral != (0, 63, 0):
+    if (ss, se, ah, al) != (0, 63, 0, 0):
         return Unsupported("sequential scan with a spectral selection other than 0..63")
-    err = _classify_colour(comps, jfif, adobe)
+    err = _classify_colour(comps, walk.jfif, walk.adobe)
     if err:
         return Unsupported(err)
     for c in comps:
-        if c[3] not in qt:
+        if c[3] not in walk.qt:
             return Unsupported(f"quantisation table {c[3]} is not defined")
     tables = []
     for (_, td, ta) in scomps:
-        if (0, td) not in dht or (1, ta) not in dht:
+        if (0, td) not in walk.dht or (1, ta) not in walk.dht:
             return Unsupported(f"Huffman table DC {td} / AC {ta} is not defined")
         tables.append((td, ta))
-    return JpegHeader(h=h, w=w, sof=kind, comps=comps, scan_tables=tables, qt=qt, dht=dht, restart_interval=ri,
-                      scan_offset=scan_offset, jfif=jfif, adobe_transform=adobe)
-
-
-@dataclass
-class ProgressiveScan:
-    """One scan of a progressive file: ``comps`` are frame component indices (increasing), ``tables`` the Huffman
-    table in force for each of them when the SOS was read (DC tables in a DC scan, the AC table in an AC scan, as
-    (counts, symbols); None in a DC refinement, which reads raw bits), [data_start, data_end) the entropy-coded
-    bytes in the file."""
-    comps: List[int]
-    ss: int
-    se: int
-    ah: int
-    al: int
-    restart_interval: int
-    tables: List[Optional[Tuple[List[int], List[int]]]]
-    data_start: int
-    data_end: int
-    slot: int = 0                                # 4 * round + wave of the device schedule (_schedule)
-
-
-@dataclass
-class ProgressiveHeader:
-    """What the device decoder needs of a progressive (SOF2) file: the frame and every scan."""
-    h: int
-    w: int
-    comps: List[Tuple[int, int, int, int]]       # per frame component: (id, h_samp, v_samp, quant table)
-    qt: Dict[int, List[int]]
-    scans: List[ProgressiveScan]
-    rounds: int = 0
-    jfif: bool = False
-    adobe_transform: Optional[int] = None
-
-    ncomp = JpegHeader.ncomp
-    sampling = JpegHeader.sampling
-    mcus = JpegHeader.mcus
-    blocks = JpegHeader.blocks
-
-    @property
-    def restart_interval(self) -> int:
-        """The first scan's (DRI may change between scans; each scan carries its own)."""
-        return self.scans[0].restart_interval
-
-
-def _scan_data_end(b: bytes, i: int) -> int:
-    """End of the entropy-coded data that starts at ``i``: the FF of the next marker other than FF00 / RSTn (fill
-    FFs in front of it belong to the data), or the end of the file."""
-    n = len(b)
-    while True:
-        j = b.find(b"\xff", i)
-        if j < 0 or j + 1 >= n:
-            return n
-        m = b[j + 1]
-        if m == 0x00 or 0xD0 <= m <= 0xD7:
-            i = j + 2
-        elif m == 0xFF:
-            i = j + 1
-        else:
-            return j
+    return JpegHeader(h=h, w=w, sof=m - 0xC0, comps=comps, scan_tables=tables, qt=walk.qt, dht=walk.dht,
+                      restart_interval=walk.ri, scan_offset=walk.i, jfif=walk.jfif, adobe_transform=walk.adobe)
 
 
 def _schedule(scans: List[ProgressiveScan]) -> int:
@@ -378,103 +425,38 @@ def parse_progressive(buf) -> "ProgressiveHeader | Unsupported":
     Unsupported(reason); a file that is not SOF2 gets the reason ``parse_header`` gives or "not progressive".  The
     progression is validated as libjpeg's jdphuff.c does and must be complete (every coefficient of every component
     refined down to bit 0), because libjpeg smooths blocks of an incomplete one.  Never reads outside ``buf``."""
-    b = bytes(buf)
-    n = len(b)
-    if n < 4 or b[0] != 0xFF or b[1] != 0xD8:
-        return Unsupported("not a JPEG file (no SOI marker)")
-    i = 2
-    qt: Dict[int, List[int]] = {}
-    dht: Dict[Tuple[int, int], Tuple[List[int], List[int]]] = {}
-    frame = None
-    ri = 0
-    jfif = False
-    adobe = None
+    walk = _Walk(buf, progressive=True)
     scans: List[ProgressiveScan] = []
     bits: List[List[int]] = []                   # per component, per coefficient: the bit position reached, -1: none
-    while i < n:
-        if b[i] != 0xFF:
-            return Unsupported(f"garbage between markers at byte {i}")
-        while i < n and b[i] == 0xFF:
-            i += 1
-        if i >= n:
-            break
-        m = b[i]
-        i += 1
-        if m == 0x01 or 0xD0 <= m <= 0xD7:
-            continue
-        if m == 0xD9:
-            break
-        if m == 0xD8 or m == 0x00:
-            return Unsupported(f"unexpected marker 0xFF{m:02X}")
-        if i + 2 > n:
-            return Unsupported("file ends inside a marker length")
-        L = (b[i] << 8) | b[i + 1]
-        if L < 2 or i + L > n:
-            return Unsupported(f"marker 0xFF{m:02X} runs past the end of the file")
-        seg = b[i + 2:i + L]
-        nxt = i + L
-        if m == 0xE0 and seg[:5] == b"JFIF\0":
-            jfif = True
-        elif m == 0xEE and seg[:5] == b"Adobe" and len(seg) >= 12:
-            adobe = seg[11]
-        elif m == 0xDB:
-            if scans:
-                return Unsupported("quantisation tables redefined between scans")
-            err = _read_dqt(seg, qt)
-            if err:
-                return Unsupported(err)
-        elif m == 0xC4:
-            err = _read_dht(seg, dht)
-            if err:
-                return Unsupported(err)
-        elif m == 0xCC:
-            return Unsupported("arithmetic coding (DAC)")
-        elif m == 0xDC:
+    for m, seg in walk:
+        if m == 0xDC:
             return Unsupported("height given by a DNL marker")
-        elif m == 0xC2:
-            if frame is not None:
-                return Unsupported("more than one SOF")
-            if len(seg) < 6 or len(seg) < 6 + 3 * seg[5]:
-                return Unsupported("malformed SOF")
-            p, h, w, nf = seg[0], (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4], seg[5]
-            if p != 8:
-                return Unsupported(f"{p}-bit samples")
-            comps = [(seg[6 + 3 * k], seg[7 + 3 * k] >> 4, seg[7 + 3 * k] & 15, seg[8 + 3 * k]) for k in range(nf)]
+        if m in (0xC0, 0xC1):                    # a sequential frame: the reason is the sequential walk's
+            r = _sequential(walk)
+            return r if isinstance(r, Unsupported) else Unsupported("not progressive (sequential: parse_header)")
+        _, h, w, comps = walk.sof
+        if m == 0xC2:
             err = _classify_frame(h, w, comps)
             if err:
                 return Unsupported(err)
-            frame = (h, w, comps)
             bits = [[-1] * 64 for _ in comps]
-        elif m in _SOF_NAMES:
-            return Unsupported(_SOF_NAMES[m])
-        elif m in (0xC0, 0xC1):
-            if frame is not None:
-                return Unsupported("more than one SOF")
-            r = parse_header(b)
-            return r if isinstance(r, Unsupported) else Unsupported("not progressive (sequential: parse_header)")
-        elif m == 0xDD:
-            if len(seg) < 2:
-                return Unsupported("malformed DRI")
-            ri = (seg[0] << 8) | seg[1]
-        elif m == 0xDA:
-            if frame is None:
-                return Unsupported("SOS before SOF")
-            if len(scans) >= MAX_SCANS:
-                return Unsupported(f"more than {MAX_SCANS} scans")
-            if not scans:
-                err = _classify_colour(frame[2], jfif, adobe)
-                if err:
-                    return Unsupported(err)
-            sc = _read_progressive_sos(seg, frame[2], qt, dht, bits, ri)
-            if isinstance(sc, Unsupported):
-                return sc
-            sc.data_start = nxt
-            sc.data_end = nxt = _scan_data_end(b, nxt)
-            if sc.data_end == sc.data_start:
-                return Unsupported(f"scan {len(scans)} has no entropy-coded data")
-            scans.append(sc)
-        i = nxt
-    if frame is None:
+            continue
+        if len(scans) >= MAX_SCANS:
+            return Unsupported(f"more than {MAX_SCANS} scans")
+        if not scans:
+            err = _classify_colour(comps, walk.jfif, walk.adobe)
+            if err:
+                return Unsupported(err)
+        sc = _read_progressive_sos(seg, comps, walk.qt, walk.dht, bits, walk.ri)
+        if isinstance(sc, Unsupported):
+            return sc
+        sc.data_start, sc.data_end = walk.skip_scan_data()
+        if sc.data_end == sc.data_start:
+            return Unsupported(f"scan {len(scans)} has no entropy-coded data")
+        scans.append(sc)
+    if walk.error is not None:
+        return Unsupported(walk.error)
+    if walk.sof is None:
         return Unsupported("no SOF before the end of the file")
     if not scans:
         return Unsupported("no scan before the end of the file")
@@ -483,7 +465,8 @@ def parse_progressive(buf) -> "ProgressiveHeader | Unsupported":
             if v != 0:
                 return Unsupported(f"incomplete progression (component {c}, coefficient {k} "
                                    f"{'never coded' if v < 0 else f'stops at bit {v}'}): libjpeg would smooth it")
-    hd = ProgressiveHeader(h=frame[0], w=frame[1], comps=frame[2], qt=qt, scans=scans, jfif=jfif, adobe_transform=adobe)
+    _, h, w, comps = walk.sof
+    hd = ProgressiveHeader(h=h, w=w, comps=comps, qt=walk.qt, scans=scans, jfif=walk.jfif, adobe_transform=walk.adobe)
     hd.rounds = _schedule(scans)
     return hd
 
@@ -491,22 +474,21 @@ def parse_progressive(buf) -> "ProgressiveHeader | Unsupported":
 def _read_progressive_sos(seg, comps, qt, dht, bits, ri) -> "ProgressiveScan | Unsupported":
     """One SOS header of a progressive file, checked against T.81 G.1.1.1 the way jdphuff.c does (and stricter: what
     libjpeg only warns about is refused); updates ``bits``."""
-    if len(seg) < 1 or len(seg) < 1 + 2 * seg[0] + 3:
+    sos = _read_sos(seg)
+    if sos is None:
         return Unsupported("malformed SOS")
-    ns = seg[0]
+    sel, ss, se, ah, al = sos
+    ns = len(sel)
     if ns < 1 or ns > len(comps):
         return Unsupported(f"scan with {ns} components")
     ids = [c[0] for c in comps]
-    idx, sel = [], []
-    for k in range(ns):
-        cid = seg[1 + 2 * k]
+    idx = []
+    for cid, _, _ in sel:
         if cid not in ids:
             return Unsupported(f"scan names component {cid}, which the frame does not have")
         idx.append(ids.index(cid))
-        sel.append((seg[2 + 2 * k] >> 4, seg[2 + 2 * k] & 15))
     if any(a >= c for a, c in zip(idx, idx[1:])):
         return Unsupported("scan components in another order than the frame's")
-    ss, se, ah, al = seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns] >> 4, seg[3 + 2 * ns] & 15
     if ss > se or se > 63 or al > 13 or ah > 13:
         return Unsupported(f"bad progression parameters Ss {ss} Se {se} Ah {ah} Al {al}")
     if ss == 0 and se != 0:
@@ -529,7 +511,7 @@ def _read_progressive_sos(seg, comps, qt, dht, bits, ri) -> "ProgressiveScan | U
                                    f"{'no scan' if have < 0 else f'Al {have}'})")
             bits[c][k] = al
     tables: List[Optional[Tuple[List[int], List[int]]]] = []
-    for (td, ta) in sel:
+    for (_, td, ta) in sel:
         if ss == 0 and ah != 0:
             tables.append(None)
             continue
@@ -539,21 +521,6 @@ def _read_progressive_sos(seg, comps, qt, dht, bits, ri) -> "ProgressiveScan | U
         tables.append(dht[key])
     return ProgressiveScan(comps=idx, ss=ss, se=se, ah=ah, al=al, restart_interval=ri, tables=tables, data_start=0,
                            data_end=0)
-
-
-def table_block(hd: JpegHeader) -> np.ndarray:
-    """The TABLE_BYTES table block the device reads for one image (layout: include/ttnet.h, ttnet_jpeg_desc)."""
-    blk = np.zeros(TABLE_BYTES, dtype=np.uint8)
-    q = blk[:_HUFF_OFF].view("<u2").reshape(3, 64)
-    for k, c in enumerate(hd.comps):
-        q[k] = hd.qt[c[3]]
-    for k, (td, ta) in enumerate(hd.scan_tables):
-        for t, key in enumerate(((0, td), (1, ta))):
-            counts, syms = hd.dht[key]
-            o = _HUFF_OFF + (2 * k + t) * _HUFF_BYTES
-            blk[o:o + 16] = counts
-            blk[o + 16:o + 16 + len(syms)] = syms
-    return blk
 
 
 def _pillow_decode(item, name: str, reason: str) -> np.ndarray:
@@ -609,30 +576,82 @@ def _align16(x: int) -> int:
     return (x + 15) & ~15
 
 
+def _write_quant(blk: np.ndarray, hd: JpegFrame):
+    """The head of a table block: uint16 quant[3][64], zig-zag order, one row per frame component."""
+    q = blk[:_HUFF_OFF].view("<u2").reshape(3, 64)
+    for k, c in enumerate(hd.comps):
+        q[k] = hd.qt[c[3]]
+
+
+def _write_huffman(buf: np.ndarray, offset: int, table):
+    """One Huffman record of _HUFF_BYTES at ``offset``: counts[16], symbols[256]."""
+    counts, syms = table
+    buf[offset:offset + 16 + len(syms)] = np.frombuffer(bytes(counts) + bytes(syms), dtype=np.uint8)
+
+
+def table_block(hd: JpegHeader) -> np.ndarray:
+    """The TABLE_BYTES table block the device reads for one image (layout: include/ttnet.h, ttnet_jpeg_desc)."""
+    blk = np.zeros(TABLE_BYTES, dtype=np.uint8)
+    _write_quant(blk, hd)
+    for k, (td, ta) in enumerate(hd.scan_tables):
+        _write_huffman(blk, _HUFF_OFF + 2 * k * _HUFF_BYTES, hd.dht[(0, td)])
+        _write_huffman(blk, _HUFF_OFF + (2 * k + 1) * _HUFF_BYTES, hd.dht[(1, ta)])
+    return blk
+
+
 def progressive_block(hd: ProgressiveHeader) -> Tuple[np.ndarray, np.ndarray]:
     """(table block, Huffman pool) the device reads for one progressive image (layout: include/ttnet.h,
     ttnet_jpeg_scan): quant tables, the scan list with data offsets relative to the first scan's data, and each distinct
     Huffman table once."""
     blk = np.zeros(TABLE_BYTES, dtype=np.uint8)
-    q = blk[:_HUFF_OFF].view("<u2").reshape(3, 64)
-    for k, c in enumerate(hd.comps):
-        q[k] = hd.qt[c[3]]
-    sl = blk[SCAN_OFF:SCAN_OFF + 32 * len(hd.scans)].view(JSCAN_DTYPE)
+    _write_quant(blk, hd)
     pool: Dict[Tuple[Tuple[int, ...], Tuple[int, ...]], int] = {}
     base = hd.scans[0].data_start
-    for e, sc in zip(sl, hd.scans):
-        e["data_offset"], e["data_bytes"] = sc.data_start - base, sc.data_end - sc.data_start
-        e["restart_interval"], e["ncomp"], e["slot"] = sc.restart_interval, len(sc.comps), sc.slot
-        e["comp"][:len(sc.comps)] = sc.comps
-        e["ss"], e["se"], e["ah"], e["al"] = sc.ss, sc.se, sc.ah, sc.al
+    rows = []                                    # the JSCAN_DTYPE records, field by field
+    for sc in hd.scans:
+        table = [0, 0, 0, 0]
         for k, t in enumerate(sc.tables):
             if t is not None:
-                e["table"][k] = pool.setdefault((tuple(t[0]), tuple(t[1])), len(pool))
-    tabs = np.zeros(max(len(pool), 1) * _HUFF_BYTES, dtype=np.uint8)
-    for (counts, syms), k in pool.items():
-        tabs[k * _HUFF_BYTES:k * _HUFF_BYTES + 16] = counts
-        tabs[k * _HUFF_BYTES + 16:k * _HUFF_BYTES + 16 + len(syms)] = syms
-    return blk, tabs[:len(pool) * _HUFF_BYTES]
+                table[k] = pool.setdefault((tuple(t[0]), tuple(t[1])), len(pool))
+        rows.append((sc.data_start - base, sc.data_end - sc.data_start, sc.restart_interval, len(sc.comps), sc.slot,
+                     tuple(sc.comps) + (0,) * (4 - len(sc.comps)), sc.ss, sc.se, sc.ah, sc.al, tuple(table), (0, 0)))
+    blk[SCAN_OFF:SCAN_OFF + 32 * len(rows)] = np.array(rows, dtype=JSCAN_DTYPE).view(np.uint8)
+    tabs = np.zeros(len(pool) * _HUFF_BYTES, dtype=np.uint8)
+    for table, k in pool.items():
+        _write_huffman(tabs, k * _HUFF_BYTES, table)
+    return blk, tabs
+
+
+class _Item(NamedTuple):
+    """One item of a batch, ready to be laid out: ``pieces`` are the uint8 arrays that go into ``data`` back to back
+    (a coded image: its table block, a progressive one's Huffman pool, the entropy-coded bytes; a raw image: its
+    pixels), the rest is what its descriptor says."""
+    kind: int
+    h: int
+    w: int
+    pieces: Tuple[np.ndarray, ...]
+    reason: Optional[str]
+    blocks: int = 0
+    ncomp: int = 3
+    restart_interval: int = 0
+    comp: Tuple = ((0, 0, 0, 0),) * 3            # per frame component: id, sampling, quant table, dc << 4 | ac table
+    reserved: Tuple[int, int] = (0, 0)
+
+
+def _coded_item(hd: JpegFrame, file: np.ndarray) -> _Item:
+    if isinstance(hd, ProgressiveHeader):
+        kind, tables = KIND_PROGRESSIVE, progressive_block(hd)
+        payload = file[hd.scans[0].data_start:hd.scans[-1].data_end]
+        sel = [0] * hd.ncomp
+        reserved = (len(hd.scans) | (hd.rounds << 8) | ((len(tables[1]) // _HUFF_BYTES) << 16), SCAN_OFF)
+    else:
+        kind, tables = KIND_JPEG, (table_block(hd),)
+        payload = file[hd.scan_offset:]
+        sel = [(td << 4) | ta for td, ta in hd.scan_tables]
+        reserved = (0, 0)
+    comp = [(c[0], (c[1] << 4) | c[2], c[3], s) for c, s in zip(hd.comps, sel)] + [(0, 0, 0, 0)] * (3 - hd.ncomp)
+    return _Item(kind, hd.h, hd.w, (*tables, payload), None, hd.blocks(), hd.ncomp, hd.restart_interval, tuple(comp),
+                 reserved)
 
 
 def pack_jpeg(items: Sequence, names: Optional[Sequence[str]] = None, progressive: bool = False) -> RaggedJpeg:
@@ -645,99 +664,67 @@ def pack_jpeg(items: Sequence, names: Optional[Sequence[str]] = None, progressiv
     if n < 1 or n > 65535:
         raise RuntimeError(f"pack_jpeg: expected 1 to 65535 items, got {n}")
     names = list(names) if names is not None else [f"item {i}" for i in range(n)]
-    plan = []                      # (kind, header or array, payload bytes)
-    reasons: List[Optional[str]] = []
+    plan: List[_Item] = []
     for i, it in enumerate(items):
         if isinstance(it, torch.Tensor):
             it = it.numpy()
+        reason = "already decoded"
         if isinstance(it, np.ndarray):
             if it.dtype != np.uint8 or it.ndim != 3 or it.shape[2] != 3 or not (
                     1 <= it.shape[0] <= MAX_SIDE and 1 <= it.shape[1] <= MAX_SIDE):
                 raise RuntimeError(f"pack_jpeg: {names[i]} must be file bytes or uint8 HWC [h, w, 3] with sides in "
                                    f"[1, {MAX_SIDE}], got {it.dtype} {tuple(it.shape)}")
-            plan.append((KIND_RAW, np.ascontiguousarray(it), None))
-            reasons.append("already decoded")
-            continue
-        if not isinstance(it, (bytes, bytearray, memoryview)):
+        elif not isinstance(it, (bytes, bytearray, memoryview)):
             raise RuntimeError(f"pack_jpeg: {names[i]} is a {type(it).__name__}, not file bytes or a uint8 array")
-        hd = parse_header(it)
-        if progressive and isinstance(hd, Unsupported) and hd.reason == _SOF_NAMES[0xC2]:
-            hd = parse_progressive(it)
-        if isinstance(hd, ProgressiveHeader):
-            lo, hi = hd.scans[0].data_start, hd.scans[-1].data_end
-            plan.append((KIND_PROGRESSIVE, hd, memoryview(bytes(it))[lo:hi]))
-            reasons.append(None)
-        elif isinstance(hd, Unsupported):
-            a = _pillow_decode(it, names[i], hd.reason)
-            if not (1 <= a.shape[0] <= MAX_SIDE and 1 <= a.shape[1] <= MAX_SIDE):
-                raise RuntimeError(f"pack_jpeg: {names[i]} is {a.shape[1]}x{a.shape[0]}; sides must lie in [1, {MAX_SIDE}]")
-            plan.append((KIND_RAW, np.ascontiguousarray(a), None))
-            reasons.append(hd.reason)
         else:
-            plan.append((KIND_JPEG, hd, memoryview(bytes(it))[hd.scan_offset:]))
-            reasons.append(None)
+            hd = parse_header(it)
+            if progressive and isinstance(hd, Unsupported) and hd.reason == _SOF_NAMES[0xC2]:
+                hd = parse_progressive(it)
+            if not isinstance(hd, Unsupported):
+                plan.append(_coded_item(hd, np.frombuffer(bytes(it), dtype=np.uint8)))
+                continue
+            reason = hd.reason
+            it = _pillow_decode(it, names[i], reason)
+            if not (1 <= it.shape[0] <= MAX_SIDE and 1 <= it.shape[1] <= MAX_SIDE):
+                raise RuntimeError(f"pack_jpeg: {names[i]} is {it.shape[1]}x{it.shape[0]}; sides must lie in [1, {MAX_SIDE}]")
+        plan.append(_Item(KIND_RAW, it.shape[0], it.shape[1], (np.ascontiguousarray(it).reshape(-1),), reason))
+    # layout: every item 16-byte aligned; a coded item's tables in front of its data
+    size = out = blocks = 0
+    rows = []                      # per item: where its pieces start, then the five offsets of its descriptor
+    for it in plan:
+        coded = it.kind != KIND_RAW
+        head = sum(len(p) for p in it.pieces[:-1])
+        rows.append((size, size + head, len(it.pieces[-1]), size if coded else 0, out, blocks if coded else 0))
+        size = _align16(size + head + len(it.pieces[-1]))
+        out += it.h * it.w * 3
+        blocks += it.blocks
+    starts, *offsets = zip(*rows)
     desc = np.zeros(n, dtype=JDESC_DTYPE)
-    size = 0
-    out = 0
-    blocks = 0
-    for i, (kind, obj, scan, *_) in enumerate(plan):
-        d = desc[i]
-        d["kind"] = kind
-        if kind == KIND_RAW:
-            h, w = obj.shape[:2]
-            d["data_offset"], d["data_bytes"] = size, obj.size
-            size = _align16(size + obj.size)
-            d["ncomp"] = 3
-        else:
-            h, w = obj.h, obj.w
-            extra = 0
-            if kind == KIND_PROGRESSIVE:
-                tabs = progressive_block(obj)
-                extra = len(tabs[1])                                   # (a multiple of 16)
-                d["reserved"] = (len(obj.scans) | (obj.rounds << 8) | ((extra // _HUFF_BYTES) << 16), SCAN_OFF)
-                plan[i] = (kind, obj, scan, tabs)
-            d["table_offset"] = size
-            d["data_offset"], d["data_bytes"] = size + TABLE_BYTES + extra, len(scan)
-            size = _align16(size + TABLE_BYTES + extra + len(scan))
-            d["block_offset"] = blocks
-            blocks += obj.blocks()
-            d["ncomp"] = obj.ncomp
-            d["restart_interval"] = obj.restart_interval
-            for k, c in enumerate(obj.comps):
-                sel = 0 if kind == KIND_PROGRESSIVE else (obj.scan_tables[k][0] << 4) | obj.scan_tables[k][1]
-                d["comp"][k] = (c[0], (c[1] << 4) | c[2], c[3], sel)
-        d["h"], d["w"] = h, w
-        d["out_offset"] = out
-        out += h * w * 3
+    for name, column in zip(("data_offset", "data_bytes", "table_offset", "out_offset", "block_offset"), offsets):
+        desc[name] = column
+    for name in ("h", "w", "kind", "ncomp", "restart_interval", "comp", "reserved"):
+        desc[name] = [getattr(it, name) for it in plan]
     data = torch.zeros(max(size, 16), dtype=torch.uint8)
     flat = data.numpy()
-    for (kind, obj, scan, *tabs), d in zip(plan, desc):
-        o = int(d["data_offset"])
-        if kind == KIND_RAW:
-            flat[o:o + obj.size] = obj.reshape(-1)
-        else:
-            t = int(d["table_offset"])
-            if kind == KIND_PROGRESSIVE:
-                flat[t:t + TABLE_BYTES], flat[t + TABLE_BYTES:o] = tabs[0]
-            else:
-                flat[t:t + TABLE_BYTES] = table_block(obj)
-            flat[o:o + len(scan)] = np.frombuffer(scan, dtype=np.uint8)
+    for it, o in zip(plan, starts):
+        for p in it.pieces:
+            flat[o:o + len(p)] = p
+            o += len(p)
     return RaggedJpeg(data, torch.from_numpy(desc.view(np.int64).reshape(n, _JDESC_WORDS)), blocks, out,
-                      int(desc["h"].max()), int(desc["w"].max()), reasons)
+                      int(desc["h"].max()), int(desc["w"].max()), [it.reason for it in plan])
 
 
-def collate_jpeg(batch):
+def collate_jpeg(batch, progressive: bool = False):
     """``DataLoader`` ``collate_fn`` for ``(file_bytes, target)`` samples (``FileBytesFolder``): returns
     ``(RaggedJpeg, targets)``, the targets collated as the default collate does."""
     files, targets = zip(*batch)
-    return pack_jpeg(files), torch.utils.data.default_collate(list(targets))
+    return pack_jpeg(files, progressive=progressive), torch.utils.data.default_collate(list(targets))
 
 
 def collate_jpeg_progressive(batch):
     """``collate_jpeg`` with the device's progressive decoder switched on: complete progressive files are shipped
     compressed (kind 2) instead of being decoded by Pillow in the worker."""
-    files, targets = zip(*batch)
-    return pack_jpeg(files, progressive=True), torch.utils.data.default_collate(list(targets))
+    return collate_jpeg(batch, progressive=True)
 
 
 IMG_EXTENSIONS = (".jpg", ".jpeg", ".png", ".ppm", ".bmp", ".pgm", ".tif", ".tiff", ".webp")
@@ -773,6 +760,12 @@ class FileBytesFolder(torch.utils.data.Dataset):
 # ----------------------------------------------------------------------------------------------------------------------
 # device side
 
+def _raise_corrupt(count: int):
+    raise RuntimeError(f"decode_ragged: {count} image(s) of an earlier batch had corrupt entropy-coded data (truncated, "
+                       "a bad Huffman code, a coefficient index past 63 or a missing restart marker): they were "
+                       "decoded as all-zero images")
+
+
 class _Ctx:
     def __init__(self, device: torch.device):
         self.device = device
@@ -780,9 +773,9 @@ class _Ctx:
         _lib.check(_lib.load().ttnet_jpeg_ctx_create(device.index, C.byref(h)))
         self.h = h
         self.res = (0, 0, 0)
-        # int32 [2]: corrupt images, segments decoded sequentially (added to by the device); host mirror
-        self.stats = torch.zeros(2, dtype=torch.int32, device=device)
-        self.host = torch.zeros(2, dtype=torch.int32).pin_memory()
+        # int32 [2]: corrupt images, segments decoded sequentially (added to by the device)
+        self.count = _StickyCount(device, 2, _raise_corrupt)
+        self.stats = self.count.dev
         self.captured = False      # a graph captured a decode on this workspace: it must never be replaced
 
     def reserve(self, images: int, blocks: int, nbytes: int):
@@ -832,18 +825,9 @@ def jpeg_counters(device=None, clear: bool = True) -> Tuple[int, int]:
     bad = seq = 0
     for (dev, _), c in _ctx.items():
         if dev == device:
-            v = c.stats.cpu().tolist()
+            v = c.count.read(clear)
             bad, seq = bad + v[0], seq + v[1]
-            if clear:
-                c.stats.zero_()
-                c.host.zero_()
     return int(bad), int(seq)
-
-
-def _raise_corrupt(count: int):
-    raise RuntimeError(f"decode_ragged: {count} image(s) of an earlier batch had corrupt entropy-coded data (truncated, "
-                       "a bad Huffman code, a coefficient index past 63 or a missing restart marker): they were "
-                       "decoded as all-zero images")
 
 
 def check_jpeg(device=None):
@@ -870,11 +854,7 @@ def decode_ragged(rj: RaggedJpeg, lane: int = 0) -> RaggedU8:
     ctx = _context(dev, lane)
     capturing = torch.cuda.is_current_stream_capturing()
     ctx.captured = ctx.captured or capturing
-    if not capturing and int(ctx.host[0]):
-        count = int(ctx.host[0])
-        ctx.stats[0].zero_()
-        ctx.host[0] = 0
-        _raise_corrupt(count)
+    ctx.count.raise_pending(capturing)
     n = len(rj)
     ctx.reserve(n, rj.n_blocks, rj.data.numel())
     data = rj.data if rj.data.data_ptr() % 16 == 0 else rj.data.clone()
@@ -887,8 +867,7 @@ def decode_ragged(rj: RaggedJpeg, lane: int = 0) -> RaggedU8:
             ctx.h, C.c_void_p(data.data_ptr()), data.numel(), C.c_void_p(desc.data_ptr()), n, rj.n_blocks,
             C.c_void_p(out.data_ptr()), out.numel(), C.c_void_p(odesc.data_ptr()), C.c_void_p(ctx.stats.data_ptr()),
             C.c_void_p(stream)))
-        if not capturing:
-            ctx.host.copy_(ctx.stats, non_blocking=True)
+        ctx.count.mirror(capturing)
     return RaggedU8(out, odesc, rj.max_h, rj.max_w)
 
 

@@ -14,7 +14,7 @@ launch (ttnet_resize_center_crop_u8_ragged), in input order.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Sequence
+from typing import Dict, List, Sequence
 
 import numpy as np
 import torch
@@ -98,19 +98,44 @@ def collate_u8(batch):
     return pack_u8(images), torch.utils.data.default_collate(list(targets))
 
 
-# per device: a running count of bad descriptors (device int32) and its host mirror, copied after each call
-_bad: Dict[torch.device, tuple] = {}
+class _StickyCount:
+    """A count the device adds to and the host learns of late: ``dev`` (int32 [n] on the device, handed to the
+    kernels) and ``host``, its pinned mirror.  The call that may add to it frames itself with ``raise_pending`` and
+    ``mirror``, neither of which synchronises: a count that an earlier call left shows in the mirror and is raised
+    then.  ``read`` synchronises and is exact.  Nothing is raised or copied while a graph is being captured."""
 
+    def __init__(self, device: torch.device, n: int, raiser):
+        self.dev = torch.zeros(n, dtype=torch.int32, device=device)
+        self.host = torch.zeros(n, dtype=torch.int32).pin_memory()
+        self.raiser = raiser                       # raiser(count) raises the error that names element 0
 
-def _bad_counter(device: torch.device):
-    if device not in _bad:
-        _bad[device] = (torch.zeros(1, dtype=torch.int32, device=device), torch.zeros(1, dtype=torch.int32).pin_memory())
-    return _bad[device]
+    def raise_pending(self, capturing: bool):
+        if not capturing and int(self.host[0]):
+            count = int(self.host[0])
+            self.dev[0].zero_()
+            self.host[0] = 0
+            self.raiser(count)
+
+    def mirror(self, capturing: bool):
+        if not capturing:
+            self.host.copy_(self.dev, non_blocking=True)
+
+    def read(self, clear: bool = True) -> List[int]:
+        torch.cuda.synchronize(self.dev.device)
+        counts = self.dev.cpu().tolist()
+        if clear and any(counts):
+            self.dev.zero_()
+            self.host.zero_()
+        return counts
 
 
 def _raise_bad(count: int):
     raise RuntimeError(f"resize_center_crop_u8_ragged: {count} image descriptor(s) of an earlier batch were out of "
                        "bounds (h, w beyond max_h / max_w or bytes past the buffer): their crops are zero")
+
+
+# per device: the running count of bad descriptors
+_bad: Dict[torch.device, _StickyCount] = {}
 
 
 def check_ragged(device=None):
@@ -119,12 +144,8 @@ def check_ragged(device=None):
     last batch of a loop."""
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     if device in _bad:
-        dev_count, host = _bad[device]
-        torch.cuda.synchronize(device)
-        count = int(dev_count.item())
+        count = _bad[device].read()[0]
         if count:
-            dev_count.zero_()
-            host.zero_()
             _raise_bad(count)
 
 
@@ -137,13 +158,11 @@ def resize_center_crop_u8_ragged(r: RaggedU8, resize: int = 256, crop: int = 224
     if not r.data.is_cuda:
         raise RuntimeError(f"the ragged batch is on {r.device}: move it with .to(device, non_blocking=True)")
     dev = r.data.device
-    dev_count, host = _bad_counter(dev)
+    if dev not in _bad:
+        _bad[dev] = _StickyCount(dev, 1, _raise_bad)
+    bad = _bad[dev]
     capturing = torch.cuda.is_current_stream_capturing()
-    if not capturing and int(host[0]):
-        count = int(host[0])
-        dev_count.zero_()
-        host.zero_()
-        _raise_bad(count)
+    bad.raise_pending(capturing)
     data = r.data if r.data.data_ptr() % 16 == 0 else r.data.clone()
     desc = r.desc.contiguous()
     n = len(r)
@@ -152,9 +171,8 @@ def resize_center_crop_u8_ragged(r: RaggedU8, resize: int = 256, crop: int = 224
         stream = torch.cuda.current_stream(dev).cuda_stream
         _lib.check(_lib.load().ttnet_resize_center_crop_u8_ragged(
             C.c_void_p(data.data_ptr()), data.numel(), C.c_void_p(desc.data_ptr()), n, r.max_h, r.max_w, int(resize),
-            int(crop), C.c_void_p(out.data_ptr()), C.c_void_p(dev_count.data_ptr()), C.c_void_p(stream)))
-        if not capturing:
-            host.copy_(dev_count, non_blocking=True)
+            int(crop), C.c_void_p(out.data_ptr()), C.c_void_p(bad.dev.data_ptr()), C.c_void_p(stream)))
+        bad.mirror(capturing)
     return out
 
 

@@ -70,3 +70,52 @@ def resize_test_images(n: int, h: int, w: int, seed: int) -> np.ndarray:
 def golden_resize():
     with np.load(os.path.join(GOLD, "ref_resize.npz")) as z:
         return {k: z[k] for k in z.files}
+
+
+def _jpeg_set(progressive: bool) -> str:
+    return "jpeg_progressive" if progressive else "jpeg"
+
+
+@lru_cache(maxsize=None)
+def jpeg_fixture(progressive: bool = False):
+    """The entries of ref_jpeg.json / ref_jpeg_progressive.json (what Pillow decodes of tests/golden/jpeg*/)."""
+    with open(os.path.join(GOLD, f"ref_{_jpeg_set(progressive)}.json")) as f:
+        return json.load(f)["images"]
+
+
+def jpeg_bytes(name: str, progressive: bool = False) -> bytes:
+    with open(os.path.join(GOLD, _jpeg_set(progressive), name + ".jpg"), "rb") as f:
+        return f.read()
+
+
+@lru_cache(maxsize=None)
+def jpeg_arrays(progressive: bool = False):
+    """Pillow's pixels of the fixtures that are small enough to be committed."""
+    with np.load(os.path.join(GOLD, f"ref_{_jpeg_set(progressive)}_arrays.npz")) as z:
+        return {k: z[k] for k in z.files}
+
+
+def ragged_images(r):
+    """The images of a RaggedU8 as host arrays [h, w, 3]."""
+    data = r.data.cpu().numpy()
+    out = []
+    for d in r.descriptors():
+        o, h, w = int(d["offset"]), int(d["h"]), int(d["w"])
+        out.append(data[o:o + h * w * 3].reshape(h, w, 3))
+    return out
+
+
+def jpeg_diff(name: str, got: np.ndarray, progressive: bool = False) -> str:
+    """For an assertion message: where a decoded image differs from Pillow's."""
+    arr = jpeg_arrays(progressive).get(name)
+    if arr is None:
+        return f"{name}: sha differs ({int((got != 0).sum())} non-zero bytes)"
+    d = np.argwhere(got != arr)
+    return (f"{name}: {len(d)} bytes differ, first (y, x, c) {d[:8].tolist()}, "
+            f"max |diff| {int(np.abs(got.astype(int) - arr.astype(int)).max())}")
+
+
+def decode_images(items, device, progressive: bool = False):
+    """pack_jpeg -> device -> decode_ragged -> host images."""
+    from scale_imagenet_amd import jpeg as J
+    return ragged_images(J.decode_ragged(J.pack_jpeg(items, progressive=progressive).to(device)))

@@ -2,34 +2,18 @@
 decodes (tests/golden/ref_jpeg.json, ref_jpeg_arrays.npz, from tools/gen_jpeg_fixture.py); batches, corrupt data,
 graph replay, lanes, the reservation, and the eval forward from file bytes."""
 import ctypes as C
-import json
-import os
 
 import numpy as np
 import pytest
 import torch
 
-from _util import GOLD, args_for, sha, spec_and_state
+from _util import (args_for, decode_images, jpeg_arrays as _arrays, jpeg_bytes as _bytes, jpeg_diff as _diff,
+                   jpeg_fixture as _fixture, ragged_images as _images, sha, spec_and_state)
 from scale_imagenet_amd import _lib, jpeg as J, preprocess, ttnet
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda", 0)
-
-
-def _fixture():
-    with open(os.path.join(GOLD, "ref_jpeg.json")) as f:
-        return json.load(f)["images"]
-
-
-def _bytes(name):
-    with open(os.path.join(GOLD, "jpeg", name + ".jpg"), "rb") as f:
-        return f.read()
-
-
-def _arrays():
-    with np.load(os.path.join(GOLD, "ref_jpeg_arrays.npz")) as z:
-        return {k: z[k] for k in z.files}
 
 
 DEVICE_FIX = [e for e in _fixture() if e["device"]]
@@ -43,36 +27,13 @@ def _items(entries):
     return [(_bytes(e["name"]) if e["device"] else arr[e["name"]]) for e in entries]
 
 
-def _images(r: preprocess.RaggedU8):
-    data = r.data.cpu().numpy()
-    out = []
-    for d in r.descriptors():
-        o, h, w = int(d["offset"]), int(d["h"]), int(d["w"])
-        out.append(data[o:o + h * w * 3].reshape(h, w, 3))
-    return out
-
-
-def _diff(name, got, want_sha):
-    arr = _arrays().get(name)
-    if arr is None:
-        return f"{name}: sha differs"
-    d = np.argwhere(got != arr)
-    return (f"{name}: {len(d)} bytes differ, first (y, x, c) {d[:5].tolist()}, "
-            f"max |diff| {int(np.abs(got.astype(int) - arr.astype(int)).max())}")
-
-
-def _decode(items):
-    out = _images(J.decode_ragged(J.pack_jpeg(items).to(DEV)))
-    return out
-
-
 @pytest.mark.parametrize("e", DEVICE_FIX, ids=lambda e: e["name"])
 def test_every_device_fixture_is_pillow_byte_identical(e):
     rj = J.pack_jpeg([_bytes(e["name"])])
     assert rj.descriptors()[0]["kind"] == J.KIND_JPEG
     got = _images(J.decode_ragged(rj.to(DEV)))[0]
     assert got.shape == (e["h"], e["w"], 3)
-    assert sha(got) == e["sha256"], _diff(e["name"], got, e["sha256"])
+    assert sha(got) == e["sha256"], _diff(e["name"], got)
     assert J.jpeg_counters(DEV)[0] == 0
 
 
@@ -84,7 +45,7 @@ def test_ragged_batch_shuffled_with_fallback_entries_and_repeats():
     a = _images(J.decode_ragged(rj))
     b = _images(J.decode_ragged(rj))
     for e, x, y in zip(entries, a, b):
-        assert sha(x) == e["sha256"], _diff(e["name"], x, e["sha256"])
+        assert sha(x) == e["sha256"], _diff(e["name"], x)
         assert np.array_equal(x, y)
     J.check_jpeg(DEV)
 
@@ -248,7 +209,7 @@ def test_marker_at_the_end_of_a_destuff_chunk():
     e = next(e for e in DEVICE_FIX if e["name"] == "s444_q90_64x48")
     base = _bytes(e["name"])
     items = [_fill_before_eoi(base, last) for last in (6143, 6144, 7167)] + [base]
-    for x in _decode(items * 8):
+    for x in decode_images(items * 8, DEV):
         assert sha(x) == e["sha256"]
     J.check_jpeg(DEV)
 

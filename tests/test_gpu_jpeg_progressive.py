@@ -3,14 +3,14 @@ ttnet_jpeg_decode_ragged) against what Pillow decodes (tests/golden/ref_jpeg_pro
 tools/gen_jpeg_progressive_fixture.py): every fixture byte for byte, mixed batches, the same logits as the Pillow
 fallback, containment of corrupt scans, graph replay, lanes and the reservation.  Reads only tests/golden."""
 import ctypes as C
-import json
-import os
+from functools import partial
 
 import numpy as np
 import pytest
 import torch
 
-from _util import GOLD, args_for, sha, spec_and_state
+from _util import (args_for, jpeg_arrays, jpeg_bytes as _sbytes, jpeg_diff, jpeg_fixture, ragged_images as _images, sha,
+                   spec_and_state)
 from scale_imagenet_amd import _lib, jpeg as J, preprocess, ttnet
 
 pytestmark = pytest.mark.gpu
@@ -18,50 +18,9 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
 
 
-def _load(name):
-    with open(os.path.join(GOLD, name)) as f:
-        return json.load(f)["images"]
-
-
-PROG = _load("ref_jpeg_progressive.json")
-SEQ = [e for e in _load("ref_jpeg.json") if e["device"]]
-
-
-def _pbytes(name):
-    with open(os.path.join(GOLD, "jpeg_progressive", name + ".jpg"), "rb") as f:
-        return f.read()
-
-
-def _sbytes(name):
-    with open(os.path.join(GOLD, "jpeg", name + ".jpg"), "rb") as f:
-        return f.read()
-
-
-def _arrays():
-    with np.load(os.path.join(GOLD, "ref_jpeg_progressive_arrays.npz")) as z:
-        return {k: z[k] for k in z.files}
-
-
-def _images(r: preprocess.RaggedU8):
-    data = r.data.cpu().numpy()
-    out = []
-    for d in r.descriptors():
-        o, h, w = int(d["offset"]), int(d["h"]), int(d["w"])
-        out.append(data[o:o + h * w * 3].reshape(h, w, 3))
-    return out
-
-
-def _diff(name, got):
-    arr = _arrays().get(name)
-    if arr is None:
-        return f"{name}: sha differs ({int((got != 0).sum())} non-zero bytes)"
-    d = np.argwhere(got != arr)
-    return (f"{name}: {len(d)} bytes differ, first (y, x, c) {d[:8].tolist()}, "
-            f"max |diff| {int(np.abs(got.astype(int) - arr.astype(int)).max())}")
-
-
-def _decode(items, **kw):
-    return _images(J.decode_ragged(J.pack_jpeg(items, progressive=True).to(DEV), **kw))
+PROG = jpeg_fixture(progressive=True)
+SEQ = [e for e in jpeg_fixture() if e["device"]]
+_pbytes, _arrays, _diff = (partial(f, progressive=True) for f in (_sbytes, jpeg_arrays, jpeg_diff))
 
 
 @pytest.mark.parametrize("e", PROG, ids=lambda e: e["name"])

@@ -1,13 +1,12 @@
 """CPU: the JPEG header walk (scale_imagenet_amd/jpeg.py parse_header) against the committed fixtures and Pillow, the
 classification of what the device does not decode, malformed headers, and pack_jpeg's layout."""
 import io
-import json
 import os
 
 import numpy as np
 import pytest
 
-from _util import GOLD
+from _util import GOLD, jpeg_bytes as _bytes, jpeg_fixture as _fixture
 from scale_imagenet_amd import jpeg as J
 
 
@@ -22,16 +21,6 @@ def _natural(zz):
     for k, v in enumerate(zz):
         out[ZIGZAG[k]] = v
     return out
-
-
-def _fixture():
-    with open(os.path.join(GOLD, "ref_jpeg.json")) as f:
-        return json.load(f)["images"]
-
-
-def _bytes(name):
-    with open(os.path.join(GOLD, "jpeg", name + ".jpg"), "rb") as f:
-        return f.read()
 
 
 @pytest.mark.parametrize("e", _fixture(), ids=lambda e: e["name"])

@@ -1,29 +1,15 @@
 """CPU: the walk over every scan of a progressive file (scale_imagenet_amd/jpeg.py parse_progressive) against the
 committed fixtures, the unchanged defaults, pack_jpeg's kind-2 layout, the refusals and malformed input."""
 import io
-import json
-import os
+from functools import partial
 
 import numpy as np
 import pytest
 
-from _util import GOLD
+from _util import jpeg_bytes as _seq_bytes, jpeg_fixture
 from scale_imagenet_amd import jpeg as J
 
-
-def _fixture():
-    with open(os.path.join(GOLD, "ref_jpeg_progressive.json")) as f:
-        return json.load(f)["images"]
-
-
-def _bytes(name):
-    with open(os.path.join(GOLD, "jpeg_progressive", name + ".jpg"), "rb") as f:
-        return f.read()
-
-
-def _seq_bytes(name):
-    with open(os.path.join(GOLD, "jpeg", name + ".jpg"), "rb") as f:
-        return f.read()
+_bytes = partial(_seq_bytes, progressive=True)
 
 
 # libjpeg's default progressive script (jcparam.c jpeg_simple_progression), as (components, Ss, Se, Ah, Al)
@@ -33,7 +19,7 @@ GREY_SCRIPT = [([0], 0, 0, 0, 1), ([0], 1, 5, 0, 2), ([0], 6, 63, 0, 2), ([0], 1
                ([0], 1, 63, 1, 0)]
 
 
-@pytest.mark.parametrize("e", _fixture(), ids=lambda e: e["name"])
+@pytest.mark.parametrize("e", jpeg_fixture(progressive=True), ids=lambda e: e["name"])
 def test_parser_reproduces_fixture_scan_list(e):
     data = _bytes(e["name"])
     hd = J.parse_progressive(data)
