@@ -323,6 +323,39 @@ typedef struct ttnet_eval_acc {
 int ttnet_eval_metrics(const float *logits_dev, const int64_t *targets_dev, int64_t n, int64_t n_classes,
                        ttnet_eval_acc *acc_dev, void *per_image_dev, void *stream);
 
+/* Per-image predictions: the k best classes of every row, best first.  logits_dev as for ttnet_eval_metrics (float32
+ * [n][n_classes] contiguous, any 4-byte aligned address; n in [1, 65535], n_classes in [2, 65536]); k in
+ * [1, min(n_classes, TTNET_TOPK_MAX)].  topk_dev (8-byte aligned) receives n * k records of 16 bytes,
+ * {int32 class; float32 logit; double logprob}, row after row.  Per row, with v = the row:
+ *   order    larger logit first; equal logits go to the lower class index -- the tie rule of ttnet_eval_metrics, so slot
+ *            r of a row holds the class whose rank there is r.  -inf logits are ordinary values (they come last, lower
+ *            index first); -0 and +0 are equal.
+ *   logprob  = -(log(sum_j exp(v_j - max v)) + max v - v_class) in float64, the sum taken in the same lane / tree order
+ *            as ttnet_eval_metrics takes it (one piece of code): bit for bit the negative of the loss that call records
+ *            for a row whose target is that class.
+ *   A NaN anywhere in the row: every slot gets class -1, logit NaN, logprob NaN (rank INT32_MAX there).
+ * Deterministic: the same input gives the same bytes, run to run.  One launch on `stream`; no plan, no host
+ * synchronisation, no allocation, capturable in a graph.  TTNET_E_INVALID (nothing launched) for a NULL pointer, n,
+ * n_classes or k outside their ranges, k > n_classes, or a misaligned buffer. */
+#define TTNET_TOPK_MAX 32
+int ttnet_topk_rows(const float *logits_dev, int64_t n, int64_t n_classes, int64_t k, void *topk_dev, void *stream);
+
+/* Per-class counters from a batch that ttnet_eval_metrics and ttnet_topk_rows have seen: targets_dev int64 [n],
+ * per_image_dev the n per-image records of ttnet_eval_metrics, topk_dev the n * k records of ttnet_topk_rows (only slot
+ * 0, the top-1 class, is read).  ADDS into counts_dev, int64 [n_classes][4] = {images, hits1, hits5, predicted}, and,
+ * when confusion_dev is not NULL, into int64 [n_classes][n_classes] indexed [target][top-1 class]; both zeroed by the
+ * caller, 8-byte aligned.  Per row, following the accumulator of ttnet_eval_metrics:
+ *   target outside [0, n_classes) (rank -1): the row is left out of everything.
+ *   otherwise images[target] + 1, hits1[target] + 1 if rank == 0, hits5[target] + 1 if rank < 5; predicted[class] + 1 and
+ *   confusion[target][class] + 1 for the row's top-1 class.  A row with a NaN (rank INT32_MAX, class -1) is an image
+ *   without a hit, as it is there, and predicts nothing: it adds to images[target] only.
+ * So the column sums of counts over the classes are the accumulator's images, hits1, hits5, and predicted sums to the
+ * rows without a NaN.  Integer atomic adds only: the result does not depend on the order of the rows, of the calls, or
+ * of the streams that add to the same counters.  One launch on `stream`; no synchronisation, no allocation,
+ * capturable.  Argument ranges as for ttnet_topk_rows; TTNET_E_INVALID otherwise (nothing launched). */
+int ttnet_class_counts(const int64_t *targets_dev, const void *per_image_dev, const void *topk_dev, int64_t n, int64_t k,
+                       int64_t n_classes, int64_t *counts_dev, int64_t *confusion_dev, void *stream);
+
 /* Same, starting from the binarised stem output (features[3], netbin.py:193) given as
  * row-packed bits uint64 [n][p][56]; used by the parity tests to separate the integer
  * gate path (bit exact) from the float stem (exact except at near ties). */

@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libttnet.so")
 
 TTNET_F32, TTNET_I64, TTNET_U8, TTNET_U16, TTNET_U64 = 0, 1, 2, 3, 4
+TOPK_MAX = 32                                              # TTNET_TOPK_MAX
 VARIANTS = {"small": 0, "xsmall": 1, "full": 2, "valexnet": 3}
 
 
@@ -74,6 +75,8 @@ SYMBOLS: List[Tuple[str, object, list]] = [
     ("ttnet_jpeg_decode_ragged", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, _P]),
     ("ttnet_jpeg_ctx_destroy", None, [_P]),
     ("ttnet_eval_metrics", C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P]),
+    ("ttnet_topk_rows", C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
+    ("ttnet_class_counts", C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
     ("ttnet_forward_from_stem_bits", C.c_int, [_P, _P, C.c_int64, _P, _P]),
     ("ttnet_read_stage", C.c_int, [_P, C.c_char_p, C.c_int64, _P, C.c_size_t, C.c_int, _P]),
     ("ttnet_plan_get_table", C.c_int, [_P, C.c_char_p, _P, C.c_size_t]),

@@ -8,6 +8,10 @@
 //   eval_reduce_kernel  one workgroup: the records summed in a fixed order (thread t takes images t, t + 1024, ..
 //                       in order; then a fixed butterfly over the lanes and the 16 waves in order) and ADDED to the
 //                       accumulator by one thread.  No floating-point atomics: same batches, same bits.
+//
+// ttnet_topk_rows and ttnet_class_counts (one launch each) answer "what did it say about each image" and "which classes
+// fail" from the same rows: topk_rows_kernel shares the row walk and the float64 exp-sum of eval_rows_kernel, so a
+// record's logprob is bit for bit the negative of the loss eval_rows_kernel reports for that class as the target.
 #include <math.h>
 
 #include <mutex>
@@ -23,6 +27,12 @@ struct PerImage {
   int32_t pad;
 };
 static_assert(sizeof(PerImage) == 16, "per-image record is 16 bytes (ttnet.h)");
+struct TopkRecord {
+  int32_t cls;
+  float logit;
+  double logprob;
+};
+static_assert(sizeof(TopkRecord) == 16, "top-k record is 16 bytes (ttnet.h)");
 static_assert(sizeof(ttnet_eval_acc) == 64, "accumulator is 64 bytes (ttnet.h)");
 
 constexpr int kRowsPerBlock = 4;          // waves of eval_rows_kernel's workgroup
@@ -65,9 +75,65 @@ __device__ inline double wave_sum_f64(double v) {
   return v;
 }
 
-// One wave per row.  The row starts at any 4-byte address (n_classes = 1001, 10, ..): up to 3 head elements bring it
-// to 16 bytes, nv float4 follow, up to 3 tail elements end it; lanes 0..5 take the head / tail elements one each.
-// CACHED: nv <= 64 * kCachedVecs, the float4 stay in registers between the two passes; otherwise they are read twice.
+// A wave's view of one row.  The row starts at any 4-byte address (n_classes = 1001, 10, ..): up to 3 head elements bring
+// it to 16 bytes, nv float4 follow, up to 3 tail elements end it; lanes 0..5 take the head / tail elements one each.
+struct Row {
+  const float *p;
+  const float4 *pv;
+  int head, nv;
+  bool has_edge;                                         // this lane holds one of the <= 6 head / tail elements:
+  int ej;                                                //   its index
+  float ev;                                              //   and its value
+};
+__device__ inline Row row_view(const float *p, int C, int lane) {
+  Row w;
+  w.p = p;
+  w.head = min(C, (int)(((16 - ((uintptr_t)p & 15)) & 15) >> 2));
+  w.nv = (C - w.head) >> 2;
+  const int tail0 = w.head + 4 * w.nv;
+  const int nedge = w.head + (C - tail0);                // <= 6
+  w.pv = reinterpret_cast<const float4 *>(p + w.head);
+  w.has_edge = lane < nedge;
+  w.ej = lane < w.head ? lane : tail0 + (lane - w.head);
+  w.ev = w.has_edge ? p[w.ej] : 0.0f;
+  return w;
+}
+// f(value, class index) for every element of the row this lane owns, always in the same order: its edge element, then
+// its float4 in index order.  CACHED: nv <= 64 * kCachedVecs, the float4 are read by the LOAD pass and stay in the
+// registers r for every later pass; otherwise every pass reads them again.
+template <bool CACHED, bool LOAD, typename F>
+__device__ inline void row_visit(const Row &w, int lane, float4 (&r)[kCachedVecs], F &&f) {
+  if (w.has_edge) f(w.ev, w.ej);
+  if constexpr (CACHED) {
+#pragma unroll
+    for (int k = 0; k < kCachedVecs; ++k) {
+      const int vi = lane + 64 * k;
+      if (vi < w.nv) {
+        if constexpr (LOAD) r[k] = w.pv[vi];
+        const int j = w.head + 4 * vi;
+        f(r[k].x, j), f(r[k].y, j + 1), f(r[k].z, j + 2), f(r[k].w, j + 3);
+      }
+    }
+  } else {
+    for (int vi = lane; vi < w.nv; vi += 64) {
+      const float4 q = w.pv[vi];
+      const int j = w.head + 4 * vi;
+      f(q.x, j), f(q.y, j + 1), f(q.z, j + 2), f(q.w, j + 3);
+    }
+  }
+}
+// float64 sum of exp(v - max) over the row: per lane in element order, then the butterfly.  The one place the order of
+// that sum is written down: the loss of ttnet_eval_metrics and the logprob of ttnet_topk_rows both come from it.
+template <bool CACHED>
+__device__ inline double row_exp_sum(const Row &w, int lane, float4 (&r)[kCachedVecs], double md) {
+  double s = 0.0;
+  row_visit<CACHED, false>(w, lane, r, [&](float v, int) { s += exp((double)v - md); });
+  return wave_sum_f64(s);
+}
+// -log softmax of the row at an element of value v, given the row's max and exp-sum (float64)
+__device__ inline double row_loss(double s, double md, float v) { return log(s) + md - (double)v; }
+
+// One wave per row.
 template <bool CACHED>
 __global__ __launch_bounds__(64 * kRowsPerBlock) void eval_rows_kernel(const float *__restrict__ logits,
                                                                        const int64_t *__restrict__ targets, int n, int C,
@@ -80,71 +146,23 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void eval_rows_kernel(const flo
   const bool bad = t64 < 0 || t64 >= C;                  // never indexes the row
   const int t = bad ? 0 : (int)t64;
   const float vt = p[t];
-  const int head = min(C, (int)(((16 - ((uintptr_t)p & 15)) & 15) >> 2));
-  const int nv = (C - head) >> 2;
-  const int tail0 = head + 4 * nv;
-  const int nedge = head + (C - tail0);                  // <= 6
-  const float4 *pv = reinterpret_cast<const float4 *>(p + head);
-
-  const bool has_edge = lane < nedge;
-  const int ej = lane < head ? lane : tail0 + (lane - head);
-  const float ev = has_edge ? p[ej] : 0.0f;
+  const Row w = row_view(p, C, lane);
 
   float m = -INFINITY;
   uint32_t cnt = 0;                                      // elements ranked before the target: larger, or equal at a lower index
   bool nan = false;
-  auto pass1 = [&](float v, int j) {
+  float4 r[kCachedVecs];
+  row_visit<CACHED, true>(w, lane, r, [&](float v, int j) {
     m = fmaxf(m, v);
     nan |= v != v;
     cnt += (v > vt || (v == vt && j < t)) ? 1u : 0u;
-  };
-  if (has_edge) pass1(ev, ej);
-  float4 r[kCachedVecs];
-  if constexpr (CACHED) {
-#pragma unroll
-    for (int k = 0; k < kCachedVecs; ++k) {
-      const int vi = lane + 64 * k;
-      if (vi < nv) {
-        r[k] = pv[vi];
-        const int j = head + 4 * vi;
-        pass1(r[k].x, j), pass1(r[k].y, j + 1), pass1(r[k].z, j + 2), pass1(r[k].w, j + 3);
-      }
-    }
-  } else {
-    for (int vi = lane; vi < nv; vi += 64) {
-      const float4 q = pv[vi];
-      const int j = head + 4 * vi;
-      pass1(q.x, j), pass1(q.y, j + 1), pass1(q.z, j + 2), pass1(q.w, j + 3);
-    }
-  }
+  });
   m = wave_max(m);
   cnt = wave_sum_u32(cnt);
   const bool any_nan = __ballot(nan) != 0;
 
-  // float64 sum of exp(v - max): per lane in element order, then the butterfly
   const double md = (double)m;
-  double s = 0.0;
-  if (has_edge) s += exp((double)ev - md);
-  if constexpr (CACHED) {
-#pragma unroll
-    for (int k = 0; k < kCachedVecs; ++k) {
-      if (lane + 64 * k < nv) {
-        s += exp((double)r[k].x - md);
-        s += exp((double)r[k].y - md);
-        s += exp((double)r[k].z - md);
-        s += exp((double)r[k].w - md);
-      }
-    }
-  } else {
-    for (int vi = lane; vi < nv; vi += 64) {
-      const float4 q = pv[vi];
-      s += exp((double)q.x - md);
-      s += exp((double)q.y - md);
-      s += exp((double)q.z - md);
-      s += exp((double)q.w - md);
-    }
-  }
-  s = wave_sum_f64(s);
+  const double s = row_exp_sum<CACHED>(w, lane, r, md);
   if (lane == 0) {
     PerImage o;
     o.pad = 0;
@@ -155,11 +173,91 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void eval_rows_kernel(const flo
       o.loss = __builtin_nan("");
       o.rank = INT32_MAX;
     } else {
-      o.loss = log(s) + md - (double)vt;
+      o.loss = row_loss(s, md, vt);
       o.rank = (int32_t)cnt;
     }
     out[row] = o;
   }
+}
+
+// ttnet_topk_rows: one wave per row, k rounds of "the largest element that comes after the one taken last" over the
+// row the wave holds in registers (or reads again, past 1027 classes).  The order is total -- larger value first, equal
+// values by lower index -- so "after (pv, pj)" needs no marking of taken elements: v < pv, or v == pv and j > pj.  Each
+// round is a per-lane scan of its <= 17 elements and one (value, index) butterfly; lane r keeps the winner of round r
+// and lanes 0 .. k-1 store the 16-byte records side by side.
+__device__ inline bool ranks_before(float v, int j, float bv, int bj) { return v > bv || (v == bv && j < bj); }
+
+template <bool CACHED>
+__global__ __launch_bounds__(64 * kRowsPerBlock) void topk_rows_kernel(const float *__restrict__ logits, int n, int C, int K,
+                                                                       TopkRecord *__restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
+  if (row >= n) return;                                  // (the whole wave)
+  const Row w = row_view(logits + (size_t)row * C, C, lane);
+
+  float m = -INFINITY;
+  bool nan = false;
+  float4 r[kCachedVecs];
+  row_visit<CACHED, true>(w, lane, r, [&](float v, int) {
+    m = fmaxf(m, v);
+    nan |= v != v;
+  });
+  m = wave_max(m);
+  const bool any_nan = __ballot(nan) != 0;
+  const double md = (double)m;
+  const double s = row_exp_sum<CACHED>(w, lane, r, md);
+
+  float pv = INFINITY, mine_v = 0.0f;                    // the element taken last; this lane's record
+  int pj = -1, mine_j = -1;
+  for (int round = 0; round < K; ++round) {              // (K <= n_classes: every round finds an element)
+    float bv = -INFINITY;
+    int bj = INT32_MAX;                                  // no element yet: any real one, -inf included, ranks before it
+    row_visit<CACHED, false>(w, lane, r, [&](float v, int j) {
+      const bool after = v < pv || (v == pv && j > pj);
+      if (after && ranks_before(v, j, bv, bj)) bv = v, bj = j;
+    });
+    static_for<0, 6>([&](auto i) {
+      constexpr int S = 1 << decltype(i)::value;
+      const float ov = __builtin_bit_cast(float, lane_xor<S>(__builtin_bit_cast(uint32_t, bv)));
+      const int oj = (int)lane_xor<S>((uint32_t)bj);
+      if (ranks_before(ov, oj, bv, bj)) bv = ov, bj = oj;
+    });
+    pv = bv, pj = bj;
+    if (lane == round) mine_v = bv, mine_j = bj;
+  }
+  if (lane < K) {
+    TopkRecord o;
+    if (any_nan) {
+      o.cls = -1;
+      o.logit = __builtin_nanf("");
+      o.logprob = __builtin_nan("");
+    } else {
+      o.cls = mine_j;
+      o.logit = mine_v;
+      o.logprob = -row_loss(s, md, mine_v);
+    }
+    out[(size_t)row * K + lane] = o;
+  }
+}
+
+// ttnet_class_counts: one thread per image, integer atomics only.
+__global__ __launch_bounds__(256) void class_counts_kernel(const int64_t *__restrict__ targets, const PerImage *__restrict__ pi,
+                                                           const TopkRecord *__restrict__ topk, int n, int K, int C,
+                                                           unsigned long long *__restrict__ counts,
+                                                           unsigned long long *__restrict__ confusion) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t t = targets[i];
+  if (t < 0 || t >= C) return;                           // a bad target: the accumulator leaves the row out, so do we
+  const int32_t rank = pi[i].rank;
+  if (rank < 0) return;                                  // (the record says the same)
+  atomicAdd(&counts[4 * t + 0], 1ull);
+  if (rank == 0) atomicAdd(&counts[4 * t + 1], 1ull);
+  if (rank < 5) atomicAdd(&counts[4 * t + 2], 1ull);
+  const int32_t c = topk[(size_t)i * K].cls;
+  if (c < 0 || c >= C) return;                           // a NaN row predicts nothing (class -1)
+  atomicAdd(&counts[4 * (size_t)c + 3], 1ull);
+  if (confusion) atomicAdd(&confusion[(size_t)t * C + c], 1ull);
 }
 
 __global__ __launch_bounds__(kReduceThreads) void eval_reduce_kernel(const PerImage *__restrict__ pi, int n,
@@ -263,6 +361,48 @@ extern "C" int ttnet_eval_metrics(const float *logits_dev, const int64_t *target
   else
     hipLaunchKernelGGL(eval_rows_kernel<false>, grid, block, 0, s, logits_dev, targets_dev, (int)n, C, (PerImage *)pi);
   hipLaunchKernelGGL(eval_reduce_kernel, dim3(1), dim3(kReduceThreads), 0, s, (const PerImage *)pi, (int)n, acc_dev);
+  TT_HIP(hipGetLastError());
+  return TTNET_OK;
+}
+
+extern "C" int ttnet_topk_rows(const float *logits_dev, int64_t n, int64_t n_classes, int64_t k, void *topk_dev, void *stream) {
+  if (!logits_dev || !topk_dev || n < 1 || n > 65535 || n_classes < 2 || n_classes > 65536 || k < 1 || k > TTNET_TOPK_MAX ||
+      k > n_classes) {
+    set_error("topk_rows: bad argument (n %lld in [1, 65535], n_classes %lld in [2, 65536], k %lld in [1, min(n_classes, %d)], "
+              "no NULL)", (long long)n, (long long)n_classes, (long long)k, TTNET_TOPK_MAX);
+    return TTNET_E_INVALID;
+  }
+  if (((uintptr_t)logits_dev & 3) || ((uintptr_t)topk_dev & 7)) {
+    set_error("topk_rows: the logits must be 4-byte aligned, the records 8-byte aligned");
+    return TTNET_E_INVALID;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int C = (int)n_classes;
+  const dim3 grid((unsigned)((n + kRowsPerBlock - 1) / kRowsPerBlock)), block(64 * kRowsPerBlock);
+  if ((C >> 2) <= 64 * kCachedVecs)
+    hipLaunchKernelGGL(topk_rows_kernel<true>, grid, block, 0, s, logits_dev, (int)n, C, (int)k, (TopkRecord *)topk_dev);
+  else
+    hipLaunchKernelGGL(topk_rows_kernel<false>, grid, block, 0, s, logits_dev, (int)n, C, (int)k, (TopkRecord *)topk_dev);
+  TT_HIP(hipGetLastError());
+  return TTNET_OK;
+}
+
+extern "C" int ttnet_class_counts(const int64_t *targets_dev, const void *per_image_dev, const void *topk_dev, int64_t n,
+                                  int64_t k, int64_t n_classes, int64_t *counts_dev, int64_t *confusion_dev, void *stream) {
+  if (!targets_dev || !per_image_dev || !topk_dev || !counts_dev || n < 1 || n > 65535 || n_classes < 2 || n_classes > 65536 ||
+      k < 1 || k > TTNET_TOPK_MAX || k > n_classes) {
+    set_error("class_counts: bad argument (n %lld in [1, 65535], n_classes %lld in [2, 65536], k %lld in [1, min(n_classes, %d)], "
+              "no NULL but confusion_dev)", (long long)n, (long long)n_classes, (long long)k, TTNET_TOPK_MAX);
+    return TTNET_E_INVALID;
+  }
+  if (((uintptr_t)targets_dev & 7) || ((uintptr_t)per_image_dev & 7) || ((uintptr_t)topk_dev & 7) || ((uintptr_t)counts_dev & 7) ||
+      ((uintptr_t)confusion_dev & 7)) {
+    set_error("class_counts: every buffer must be 8-byte aligned");
+    return TTNET_E_INVALID;
+  }
+  hipLaunchKernelGGL(class_counts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, targets_dev,
+                     (const PerImage *)per_image_dev, (const TopkRecord *)topk_dev, (int)n, (int)k, (int)n_classes,
+                     (unsigned long long *)counts_dev, (unsigned long long *)confusion_dev);
   TT_HIP(hipGetLastError());
   return TTNET_OK;
 }

@@ -8,7 +8,8 @@ main.py:181-192); the only exchange is the gather of logits that
 all-gather of ``[B/world, 1000]`` fp32.
 
 Evaluating a dataset needs less still: every rank evaluates its ``ShardedSampler`` slice and one
-``all_reduce_metrics`` sums four numbers (loss sum, images, top-1 hits, top-5 hits).
+``all_reduce_metrics`` sums four numbers (loss sum, images, top-1 hits, top-5 hits).  Per-image predictions are
+joined in rank order (``all_gather_predictions``), per-class counters summed (``all_reduce_counts``).
 """
 from __future__ import annotations
 
@@ -109,3 +110,44 @@ def all_reduce_metrics(part, group=None):
     dist.all_reduce(v, op=dist.ReduceOp.SUM, group=group)
     loss_sum, images, hits1, hits5 = v.cpu().tolist()
     return EvalParts(loss_sum, int(round(images)), int(round(hits1)), int(round(hits5))).result()
+
+
+def _wire(t: torch.Tensor, group=None) -> torch.Tensor:
+    """Where a collective wants its tensor: the host under gloo, this rank's device under nccl."""
+    return t if dist.get_backend(group) == "gloo" else t.to(torch.device("cuda", torch.cuda.current_device()))
+
+
+def all_gather_predictions(pred, group=None):
+    """Every rank's ``Predictions`` joined in rank order, which is dataset order for ``ShardedSampler`` shards
+    (contiguous, earlier ranks first).  The shards may differ in length: two collectives, one of the lengths and one
+    of the 16-byte records padded to the longest.  Every rank returns the whole; a single process returns its input."""
+    from .evaluate import Predictions
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return pred
+    world = dist.get_world_size(group)
+    counts = _wire(torch.zeros(world, dtype=torch.int64), group)
+    dist.all_gather_into_tensor(counts, _wire(torch.tensor([len(pred)], dtype=torch.int64), group), group=group)
+    counts = counts.cpu().tolist()
+    width = max(max(counts), 1)
+    local = torch.zeros((width, pred.k, 2), dtype=torch.int64)
+    local[:len(pred)] = torch.from_numpy(pred.to_records())
+    out = _wire(torch.empty((world * width, pred.k, 2), dtype=torch.int64), group)
+    dist.all_gather_into_tensor(out, _wire(local, group), group=group)
+    out = out.cpu().numpy()
+    return Predictions.join([Predictions.from_records(out[r * width: r * width + counts[r]]) for r in range(world)])
+
+
+def all_reduce_counts(counts, confusion=None, group=None):
+    """Sum the per-class counters (and the confusion matrix, when there is one) of every rank: one
+    ``all_reduce(SUM)`` of one int64 tensor.  numpy in, numpy out; a single process returns its input."""
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return counts, confusion
+    import numpy as np
+    flat = [torch.from_numpy(np.ascontiguousarray(counts)).reshape(-1)]
+    if confusion is not None:
+        flat.append(torch.from_numpy(np.ascontiguousarray(confusion)).reshape(-1))
+    v = _wire(torch.cat(flat), group)
+    dist.all_reduce(v, op=dist.ReduceOp.SUM, group=group)
+    v = v.cpu().numpy()
+    n = counts.size
+    return v[:n].reshape(counts.shape).copy(), None if confusion is None else v[n:].reshape(confusion.shape).copy()

@@ -19,14 +19,21 @@ Two ways to the metrics:
     digits (float32 batch means there); ``top1`` / ``top5`` are ``100 * hits / images`` from
     exact integer counts and equal the ``"torch"`` path's whenever no target's logit is tied
     across the k-th place (ties go to the lower class index here, include/ttnet.h).
+
+Beyond the four numbers, the same loop answers *what did it say about each image* and *which classes fail*:
+``topk=k`` adds ``Predictions`` (the k best classes of every image, their logits and float64 log-probabilities, in
+dataset order) from one ``ttnet_topk_rows`` call per batch, whose ``n * k * 16`` bytes are the only thing copied back;
+``per_class`` / ``confusion`` add per-class counters and a confusion matrix that ``ttnet_class_counts`` keeps on the
+device until the end.  A batch ``(inputs, None)`` has no labels: forward and top-k only.
 """
 from __future__ import annotations
 
 import contextlib
 import ctypes as C
 from dataclasses import dataclass
-from typing import Callable, Iterable, Optional, Tuple
+from typing import Callable, Iterable, List, Optional, Tuple
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -82,6 +89,9 @@ class EvalResult:
     top5: float
     images: int
     parts = None        # (not a field) the exact sums behind the four numbers, when the device metrics produced them
+    predictions = None  # (not a field) ``Predictions`` in dataset order, with ``topk=k``
+    per_class = None    # (not a field) int64 [n_classes, 4] {images, hits1, hits5, predicted}, with ``per_class=True``
+    confusion = None    # (not a field) int64 [n_classes, n_classes] indexed [target][top-1 class], with ``confusion=True``
 
     def to_parts(self) -> EvalParts:
         """The sums behind this result: exact when ``parts`` is set, otherwise recovered from the means (the hit
@@ -92,11 +102,89 @@ class EvalResult:
                          int(round(self.top5 * self.images / 100.0)))
 
 
+@dataclass
+class Predictions:
+    """The k best classes of N images, best first (the rules of ``ttnet_topk_rows``, include/ttnet.h): larger logit
+    first, equal logits by lower class index; a row with a NaN holds class -1, logit NaN, logprob NaN in every slot."""
+    classes: np.ndarray     # int32 [N, k]
+    logit: np.ndarray       # float32 [N, k]
+    logprob: np.ndarray     # float64 [N, k]: log softmax of the row at that class
+
+    def __len__(self) -> int:
+        return self.classes.shape[0]
+
+    @property
+    def k(self) -> int:
+        return self.classes.shape[1]
+
+    @staticmethod
+    def from_records(rec: np.ndarray) -> "Predictions":
+        """From ``[N, k]`` records of 16 bytes ``{int32 class; float32 logit; double logprob}`` given as int64 [N, k, 2]."""
+        rec = np.ascontiguousarray(rec, dtype=np.int64)
+        n, k = rec.shape[:2]
+        w = rec.view(np.int32).reshape(n, k, 4)
+        return Predictions(w[:, :, 0].copy(), w[:, :, 1].copy().view(np.float32), rec[:, :, 1].copy().view(np.float64))
+
+    def to_records(self) -> np.ndarray:
+        """The inverse of ``from_records``: what crosses the ranks (``dist.all_gather_predictions``)."""
+        rec = np.empty((len(self), self.k, 2), dtype=np.int64)
+        w = rec.view(np.int32).reshape(len(self), self.k, 4)
+        w[:, :, 0] = self.classes
+        w[:, :, 1] = np.ascontiguousarray(self.logit, dtype=np.float32).view(np.int32)
+        rec[:, :, 1] = np.ascontiguousarray(self.logprob, dtype=np.float64).view(np.int64)
+        return rec
+
+    @staticmethod
+    def join(parts: "List[Predictions]") -> "Predictions":
+        """Shards in dataset order -> one ``Predictions`` (``ShardedSampler`` shards are contiguous: rank order)."""
+        return Predictions(np.concatenate([p.classes for p in parts]), np.concatenate([p.logit for p in parts]),
+                           np.concatenate([p.logprob for p in parts]))
+
+
+def _check_k(k: int, n_classes: int):
+    if not (1 <= k <= min(n_classes, _lib.TOPK_MAX)):
+        raise ValueError(f"topk must be in [1, min(n_classes, {_lib.TOPK_MAX})], got {k} for {n_classes} classes")
+
+
+def topk_rows(logits: torch.Tensor, k: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``ttnet_topk_rows`` on the current stream: float32 HIP logits ``[n, n_classes]`` -> the records, int64
+    ``[n, k, 2]`` on the device (``Predictions.from_records`` unpacks them on the host).  Asynchronous, capturable."""
+    if (not logits.is_cuda) or logits.dtype != torch.float32 or logits.dim() != 2:
+        raise RuntimeError(f"expected float32 HIP logits [n, n_classes], got {logits.dtype} {tuple(logits.shape)} on "
+                           f"{logits.device}: ttnet_topk_rows has no CPU path")
+    n, n_classes = logits.shape
+    _check_k(k, n_classes)
+    logits = logits.contiguous()
+    if out is None:
+        out = torch.empty((n, k, 2), dtype=torch.int64, device=logits.device)
+    elif out.device != logits.device or out.dtype != torch.int64 or tuple(out.shape) != (n, k, 2) or not out.is_contiguous():
+        raise RuntimeError(f"expected contiguous int64 records [{n}, {k}, 2] on {logits.device}")
+    with torch.cuda.device(logits.device):
+        stream = torch.cuda.current_stream(logits.device).cuda_stream
+        _lib.check(_lib.load().ttnet_topk_rows(C.c_void_p(logits.data_ptr()), n, n_classes, k, C.c_void_p(out.data_ptr()),
+                                               C.c_void_p(stream)))
+    return out
+
+
+def topk_rows_host(logits: torch.Tensor, k: int) -> Predictions:
+    """The same rules for logits on the CPU (a stub model in a test; the product has no CPU path): a stable descending
+    sort puts equal logits in index order, the log-probabilities are float64."""
+    n, n_classes = logits.shape
+    _check_k(k, n_classes)
+    x = logits.detach().to(torch.float32)
+    order = torch.sort(x, dim=1, descending=True, stable=True).indices[:, :k]
+    logprob = torch.log_softmax(x.double(), dim=1).gather(1, order)
+    classes, logit = order.to(torch.int32), x.gather(1, order)
+    nan = torch.isnan(x).any(dim=1)
+    classes[nan], logit[nan], logprob[nan] = -1, float("nan"), float("nan")
+    return Predictions(classes.numpy(), logit.numpy(), logprob.numpy())
+
+
 class DeviceMetrics:
     """Loss / top-1 / top-5 accumulated on the device by ``ttnet_eval_metrics`` (csrc/metrics.hip): one 64-byte
     accumulator per lane, added to by ``update`` on the current stream, read back once by ``result``."""
 
-    def __init__(self, device, lanes: int = 1):
+    def __init__(self, device, lanes: int = 1, confusion: bool = False):
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError(f"DeviceMetrics needs a HIP device, got {device}: the device metrics have no CPU path "
@@ -106,11 +194,28 @@ class DeviceMetrics:
         self.device, self.lanes = device, int(lanes)
         self.acc = torch.zeros((self.lanes, 8), dtype=torch.int64, device=device)      # ttnet_eval_acc [lanes]
         assert self.acc.element_size() * 8 == C.sizeof(_lib.EvalAcc)
+        self.want_confusion = bool(confusion)
+        self.counts = self.confusion = None               # shared by the lanes (integer atomics): made by the first
+                                                          # per_class update, which knows n_classes
 
-    def update(self, logits: torch.Tensor, targets: torch.Tensor, lane: int = 0, per_image: bool = False):
+    def _counters(self, n_classes: int):
+        if self.counts is None:
+            self.counts = torch.zeros((n_classes, 4), dtype=torch.int64, device=self.device)
+            if self.want_confusion:
+                self.confusion = torch.zeros((n_classes, n_classes), dtype=torch.int64, device=self.device)
+            torch.cuda.current_stream(self.device).synchronize()     # once: zeroed before any other lane's stream adds
+        elif self.counts.shape[0] != n_classes:
+            raise RuntimeError(f"per-class counters were made for {self.counts.shape[0]} classes, got {n_classes}")
+
+    def update(self, logits: torch.Tensor, targets: torch.Tensor, lane: int = 0, per_image: bool = False, *,
+               topk: Optional[torch.Tensor] = None, per_class: bool = False):
         """Add a batch (float32 ``[n, n_classes]`` logits, int64 ``[n]`` targets, both on the device) to ``lane``'s
         accumulator: asynchronous on the current stream, capturable.  ``per_image=True`` returns the per-image
-        ``(loss float64 [n], rank int32 [n])`` (rank -1: target out of range; INT32_MAX: a NaN in the row)."""
+        ``(loss float64 [n], rank int32 [n])`` (rank -1: target out of range; INT32_MAX: a NaN in the row).
+
+        ``per_class=True`` also adds the batch to ``counts`` (and ``confusion``, when the object was made with it) by
+        one ``ttnet_class_counts`` call; it needs the batch's ``topk_rows`` records, passed as ``topk`` (computed here
+        with k = 1 when absent).  The return value is what it is without these arguments."""
         if not (0 <= lane < self.lanes):
             raise RuntimeError(f"lane {lane} outside [0, {self.lanes})")
         if (not logits.is_cuda) or logits.dtype != torch.float32 or logits.dim() != 2:
@@ -127,9 +232,28 @@ class DeviceMetrics:
             _lib.check(_lib.load().ttnet_eval_metrics(
                 C.c_void_p(logits.data_ptr()), C.c_void_p(targets.data_ptr()), n, n_classes,
                 C.c_void_p(self.acc[lane].data_ptr()), C.c_void_p(rec.data_ptr()), C.c_void_p(stream)))
+            if per_class:
+                if topk is None:
+                    topk = topk_rows(logits, 1)
+                elif topk.device != logits.device or topk.dtype != torch.int64 or topk.dim() != 3 or topk.shape[0] != n \
+                        or topk.shape[2] != 2 or not topk.is_contiguous():
+                    raise RuntimeError(f"expected the contiguous int64 [{n}, k, 2] records of topk_rows on {logits.device}")
+                self._counters(n_classes)
+                _lib.check(_lib.load().ttnet_class_counts(
+                    C.c_void_p(targets.data_ptr()), C.c_void_p(rec.data_ptr()), C.c_void_p(topk.data_ptr()), n,
+                    topk.shape[1], n_classes, C.c_void_p(self.counts.data_ptr()),
+                    C.c_void_p(self.confusion.data_ptr()) if self.confusion is not None else None, C.c_void_p(stream)))
         if per_image:
             return rec[:, 0].view(torch.float64), rec.view(torch.int32)[:, 2]
         return None
+
+    def class_counts(self) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
+        """Synchronise once and read the counters back: ``(counts int64 [n_classes, 4], confusion or None)``;
+        ``(None, None)`` when no ``per_class`` update was made."""
+        if self.counts is None:
+            return None, None
+        torch.cuda.synchronize(self.device)
+        return self.counts.cpu().numpy(), self.confusion.cpu().numpy() if self.confusion is not None else None
 
     def parts(self, check: bool = True) -> EvalParts:
         """Synchronise the device once and sum the lanes in lane order."""
@@ -165,6 +289,9 @@ class _TorchMetrics:
         hits = order.eq(targets.reshape(-1, 1))
         return loss, hits[:, :1].any(dim=1).float().mean(), hits[:, :5].any(dim=1).float().mean()
 
+    def add_with_topk(self, outputs, targets, lane, topk):
+        return self.add(outputs, targets, lane)           # (the records are of no use to the torch metrics)
+
     def retire(self, batch, n):
         loss, hits1, hits5 = batch
         self.loss.update(loss.item(), n)
@@ -183,11 +310,17 @@ class _OnDeviceMetrics:
     retires, a log line reads the accumulators (one synchronisation, no range check), ``result`` reads them once."""
     logs = "issued"
 
-    def __init__(self, device, lanes, streams):
-        self.dm = DeviceMetrics(device, lanes)
-        self.add = self.dm.update                         # add(outputs, targets, lane): nothing to keep for retire
+    def __init__(self, device, lanes, streams, per_class=False, confusion=False):
+        self.dm = DeviceMetrics(device, lanes, confusion=confusion)
+        self.per_class = per_class
+        # add(outputs, targets, lane): nothing to keep for retire
+        self.add = self.add_with_topk if per_class else self.dm.update
         for s in streams:                                 # the accumulators were zeroed on the current stream
             s.wait_stream(torch.cuda.current_stream(device))
+
+    def add_with_topk(self, outputs, targets, lane, topk=None):
+        """``add`` for a batch whose ``topk_rows`` records exist already: the per-class counters read their first slot."""
+        return self.dm.update(outputs, targets, lane, topk=topk, per_class=self.per_class)
 
     def retire(self, batch, n):
         pass
@@ -197,13 +330,47 @@ class _OnDeviceMetrics:
         return p.loss, p.top1, p.top5
 
     def result(self) -> EvalResult:
-        return self.dm.result()                           # (one synchronisation; raises on a target out of range)
+        res = self.dm.result()                            # (one synchronisation; raises on a target out of range)
+        res.per_class, res.confusion = self.dm.class_counts()
+        return res
+
+
+class _TopK:
+    """``topk=k``: one ``ttnet_topk_rows`` call per batch on the batch's stream, its ``n * k * 16`` bytes copied to the
+    lane's pinned buffer on that stream and collected when the batch retires (by then the lane's event has passed).
+    Logits on the CPU (a stub model) go through ``topk_rows_host``."""
+
+    def __init__(self, k: int, lanes: int):
+        self.k = k
+        self.pinned = [None] * lanes
+        self.parts: List[Predictions] = []
+
+    def add(self, outputs, lane: int, asynchronous: bool):
+        """Returns ``(what retire() needs, the records on the device or None)``."""
+        if not outputs.is_cuda:
+            return topk_rows_host(outputs, self.k), None
+        rec = topk_rows(outputs, self.k)
+        n = rec.shape[0]
+        if self.pinned[lane] is None or self.pinned[lane].shape[0] < n:
+            self.pinned[lane] = torch.empty((n, self.k, 2), dtype=torch.int64, pin_memory=True)
+        host = self.pinned[lane][:n]
+        host.copy_(rec, non_blocking=asynchronous)
+        return host, rec
+
+    def retire(self, kept):
+        self.parts.append(kept if isinstance(kept, Predictions) else Predictions.from_records(kept.numpy()))
+
+    def result(self) -> Predictions:
+        if not self.parts:
+            return Predictions(np.empty((0, self.k), np.int32), np.empty((0, self.k), np.float32), np.empty((0, self.k), np.float64))
+        return Predictions.join(self.parts)
 
 
 @torch.no_grad()
 def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]],
              device: torch.device, log_every: int = 0, inflight: int = 1, *,
-             forward: Optional[Callable] = None, metrics: str = "torch") -> EvalResult:
+             forward: Optional[Callable] = None, metrics: str = "torch", topk: int = 0, per_class: bool = False,
+             confusion: bool = False) -> EvalResult:
     """main.py:242-284: ``model.eval()``, no_grad, per batch loss / top-1 / top-5.
 
     ``inflight`` > 1 keeps that many batches in flight on separate HIP streams and model lanes
@@ -221,7 +388,19 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
 
     ``metrics="device"`` reduces loss and hits on the device (``DeviceMetrics``): nothing is read back per batch, a
     lane is reused after its event, and ``log_every`` reads the accumulators -- one synchronisation -- only on the
-    batches it logs.  See the module docstring for how its numbers relate to the default ``"torch"`` path."""
+    batches it logs.  See the module docstring for how its numbers relate to the default ``"torch"`` path.
+
+    ``topk=k`` (1 .. 32): the result's ``predictions`` are the k best classes of every image, in dataset order
+    whatever ``inflight`` is.  ``per_class`` / ``confusion`` (device metrics only): its ``per_class`` / ``confusion``
+    are the counters of ``ttnet_class_counts``, read back once at the end.  With the defaults nothing changes.  A batch
+    ``(inputs, None)`` is unlabelled: forward and top-k only; the result then has ``loss = top1 = top5 = None`` and no
+    ``Acc..`` line is printed.  Labelled and unlabelled batches do not mix."""
+    if topk < 0 or topk > _lib.TOPK_MAX:
+        raise ValueError(f"topk must be in [0, {_lib.TOPK_MAX}], got {topk}")
+    per_class = per_class or confusion
+    if per_class and (metrics != "device" or device.type != "cuda"):
+        raise RuntimeError(f"evaluate(per_class / confusion) needs metrics=\"device\" on a HIP device, got metrics={metrics!r} on "
+                           f"{device}: the per-class counters are kept by the device metrics, which have no CPU path")
     if metrics not in ("torch", "device"):
         raise ValueError(f"metrics must be \"torch\" or \"device\", got {metrics!r}")
     if metrics == "device" and device.type != "cuda":
@@ -233,7 +412,9 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
     if use_lanes:
         model.set_lanes(inflight)
     streams = [torch.cuda.Stream(device) for _ in range(lanes)] if use_lanes else []
-    acc = _OnDeviceMetrics(device, lanes, streams) if metrics == "device" else _TorchMetrics()
+    acc = _OnDeviceMetrics(device, lanes, streams, per_class, confusion) if metrics == "device" else _TorchMetrics()
+    top = _TopK(topk, lanes) if topk else None
+    labelled = None                                        # True / False once the first batch has been seen
     seen = set()                                           # "ragged", "jpeg": which sticky counts to check at the end
 
     def run(inputs, lane: Optional[int]):
@@ -260,11 +441,14 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
     pending = []                                           # batches in flight, oldest first: (index, event, metrics, images)
 
     def retire():
-        index, event, batch, n = pending.pop(0)
+        index, event, batch, n, kept = pending.pop(0)
         if event is not None:
             event.synchronize()
-        acc.retire(batch, n)
-        if log_every:
+        if labelled:
+            acc.retire(batch, n)
+        if top is not None:
+            top.retire(kept)
+        if log_every and labelled:
             log(index, "retired")
 
     for i, (inputs, targets) in enumerate(batches):
@@ -272,16 +456,32 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
         if len(pending) == lanes:                          # this lane's previous batch still owns its workspace
             retire()
         with torch.cuda.stream(streams[lane]) if use_lanes else contextlib.nullcontext():
+            if labelled is None:
+                labelled = targets is not None
+                if not labelled and top is None:
+                    raise ValueError("evaluate: batches without targets need topk > 0 (there is nothing else to compute)")
+                if not labelled and per_class:
+                    raise ValueError("evaluate: per_class / confusion need targets")
+            elif labelled != (targets is not None):
+                raise ValueError(f"evaluate: batch {i} mixes labelled and unlabelled batches")
             inputs = inputs.to(device, non_blocking=True)
-            targets = targets.to(device, non_blocking=True)
-            batch = acc.add(run(inputs, lane if use_lanes else None), targets, lane)
+            if labelled:
+                targets = targets.to(device, non_blocking=True)
+            outputs = run(inputs, lane if use_lanes else None)
+            batch = kept = None
+            if top is None:
+                batch = acc.add(outputs, targets, lane)
+            else:
+                kept, rec = top.add(outputs, lane, use_lanes)
+                if labelled:
+                    batch = acc.add_with_topk(outputs, targets, lane, rec)
             event = torch.cuda.Event() if use_lanes else None
             if use_lanes:
                 event.record(streams[lane])
-        pending.append((i, event, batch, inputs.size(0) if isinstance(inputs, torch.Tensor) else len(inputs)))
+        pending.append((i, event, batch, inputs.size(0) if isinstance(inputs, torch.Tensor) else len(inputs), kept))
         if not use_lanes:                                  # nothing in flight: read the batch now, as the reference does
             retire()
-        if log_every:
+        if log_every and labelled:
             log(i, "issued")
     while pending:
         retire()
@@ -296,6 +496,12 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
     if "ragged" in seen:
         from . import preprocess
         preprocess.check_ragged(device)
-    res = acc.result()
-    print("Acc..", res.top1, res.top5)
+    if labelled is False:                                  # no labels: the predictions are the result
+        res = EvalResult(None, None, None, sum(len(p) for p in top.parts))
+    else:
+        res = acc.result()
+    if top is not None:
+        res.predictions = top.result()
+    if labelled is not False:
+        print("Acc..", res.top1, res.top5)
     return res

@@ -757,6 +757,35 @@ class FileBytesFolder(torch.utils.data.Dataset):
             return f.read(), target
 
 
+class FileBytesList(torch.utils.data.Dataset):
+    """The unlabelled sibling of ``FileBytesFolder``: every image file under a directory (sorted, walked recursively --
+    no class directories needed) or an explicit list of paths, kept in the order given.  Returns
+    ``(file bytes, index)``, so ``collate_jpeg`` works on it unchanged and a batch knows which files it holds."""
+
+    def __init__(self, root_or_paths):
+        if isinstance(root_or_paths, (str, os.PathLike)):
+            root = os.fspath(root_or_paths)
+            if not os.path.isdir(root):
+                raise FileNotFoundError(f"FileBytesList: {root} is not a directory")
+            self.paths = []
+            for base, dirs, files in os.walk(root, followlinks=True):
+                dirs.sort()                               # (os.walk descends in this order)
+                self.paths += [os.path.join(base, f) for f in files if f.lower().endswith(IMG_EXTENSIONS)]
+            self.paths.sort()
+            if not self.paths:
+                raise FileNotFoundError(f"FileBytesList: no image files under {root}")
+        else:
+            self.paths = [os.fspath(p) for p in root_or_paths]
+        self.samples = [(p, i) for i, p in enumerate(self.paths)]
+
+    def __len__(self) -> int:
+        return len(self.paths)
+
+    def __getitem__(self, i):
+        with open(self.paths[i], "rb") as f:
+            return f.read(), i
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # device side
 

@@ -25,17 +25,10 @@ _IGNORED = [("--root_dir", str, "./"), ("--log_name", str, "resnet_imagenet_4w4f
 _IGNORED_SWITCHES = ["--pretrain", "--multiprocessing-distributed"]
 
 
-def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(
-        prog="python -m scale_imagenet_amd.main",
-        description="Evaluate <data_dir>/val (one directory per class) with a TTNet ImageNet classifier on the HIP path "
-                    "and print the reference's final line, `Acc.. <top-1> <top-5>`.",
-        epilog="The reference's trained checkpoint is published on a file-sharing site and cannot be fetched by this "
-               "command; put it at --ckpt yourself, or try the command with --synthetic-ckpt (deterministic synthetic "
-               "weights: the accuracy is then that of chance).")
+def add_model_flags(p: argparse.ArgumentParser, data_help: str):
+    """The flags that carry the reference's names and defaults: data, loader, model geometry, device, logging."""
     ref = p.add_argument_group("flags of the reference's main.py (same names and defaults)")
-    ref.add_argument("--data_dir", type=str, default="./../datasets/ILSVRC/Data/CLS-LOC/",
-                     help="dataset root; <data_dir>/val is evaluated")
+    ref.add_argument("--data_dir", type=str, default="./../datasets/ILSVRC/Data/CLS-LOC/", help=data_help)
     ref.add_argument("--eval_batch_size", type=int, default=100)
     ref.add_argument("--num_workers", type=int, default=6)
     ref.add_argument("--nfilter", type=int, default=8)
@@ -44,6 +37,10 @@ def build_parser() -> argparse.ArgumentParser:
     ref.add_argument("--groups", type=str, default="1,None,4,None")
     ref.add_argument("--gpu", type=int, default=None, help="GPU id to use (single process; default 0)")
     ref.add_argument("--log_interval", type=int, default=40, help="print running metrics every N batches (0: never)")
+
+
+def add_own_flags(p: argparse.ArgumentParser):
+    """Model family, checkpoint, input path, lanes and ranks: shared by ``main`` and ``predict``."""
     own = p.add_argument_group("flags of this command")
     own.add_argument("--variant", choices=sorted(VARIANT_CLASSES), default="small",
                      help="model family (the reference hard-codes small)")
@@ -59,6 +56,34 @@ def build_parser() -> argparse.ArgumentParser:
                           "in the workers (slow; for cross-checking a folder)")
     own.add_argument("--inflight", type=int, default=2, help="batches in flight on separate streams / lanes")
     own.add_argument("--gpus", type=int, default=1, help="evaluate on N GPUs: starts one rank per GPU itself")
+    return own
+
+
+def add_topk_flags(group, default: int):
+    group.add_argument("--topk", type=int, default=default, metavar="K",
+                       help=f"the K best classes per image, 1 .. 32 (default {default}" + (": none)" if not default else ")"))
+    group.add_argument("--classes", type=str, default=None, metavar="FILE",
+                       help="class names, one per line in index order: written instead of the indices")
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(
+        prog="python -m scale_imagenet_amd.main",
+        description="Evaluate <data_dir>/val (one directory per class) with a TTNet ImageNet classifier on the HIP path "
+                    "and print the reference's final line, `Acc.. <top-1> <top-5>`.",
+        epilog="The reference's trained checkpoint is published on a file-sharing site and cannot be fetched by this "
+               "command; put it at --ckpt yourself, or try the command with --synthetic-ckpt (deterministic synthetic "
+               "weights: the accuracy is then that of chance).")
+    add_model_flags(p, "dataset root; <data_dir>/val is evaluated")
+    add_own_flags(p)
+    out = p.add_argument_group("per-image and per-class results (files written by rank 0; stdout is unchanged)")
+    add_topk_flags(out, 0)
+    out.add_argument("--predictions", type=str, default=None, metavar="FILE",
+                     help="CSV path,target,class_1,logprob_1,.. of every image in dataset order (--topk, default 5 here)")
+    out.add_argument("--per_class", type=str, default=None, metavar="FILE",
+                     help="CSV class,images,hits1,hits5,predicted,acc1,acc5")
+    out.add_argument("--confusion", type=str, default=None, metavar="FILE",
+                     help=".npy, int64 [n_classes][n_classes] indexed [target][top-1 class]")
     ign = p.add_argument_group("accepted and ignored (training, logging and launcher flags of the reference)")
     for name, typ, default in _IGNORED:
         ign.add_argument(name, type=typ, default=default, help=argparse.SUPPRESS)
@@ -91,6 +116,10 @@ def _check_paths(args):
     val = os.path.join(args.data_dir, "val")
     if not os.path.isdir(val):
         raise SystemExit(f"--data_dir: {val} is not a directory (expected <data_dir>/val/<class>/<image files>)")
+    _check_ckpt(args)
+
+
+def _check_ckpt(args):
     if not args.synthetic_ckpt and not os.path.isfile(args.ckpt or "./ckpt/last.pth"):
         raise SystemExit(f"--ckpt: {args.ckpt or './ckpt/last.pth'} does not exist.  The reference's checkpoint has to be "
                          "downloaded by hand; --synthetic-ckpt runs the command on synthetic weights instead")
@@ -128,53 +157,104 @@ class _PillowFolder:
             return np.asarray(im.convert("RGB")), target
 
 
-def run(args) -> int:
-    """One rank (or the only process): evaluate this rank's shard, sum over the ranks, rank 0 prints the line."""
+def start_rank(args, prog: str = "scale_imagenet_amd.main"):
+    """Join the job, pick this rank's device: ``(rank, world, device)``."""
     import torch
 
-    from . import jpeg, preprocess, ttnet
-    from .dist import ShardedSampler, all_reduce_metrics, init_from_env
-    from .evaluate import evaluate
-
+    from .dist import init_from_env
     rank, world, local_rank = init_from_env("nccl")
     if world != args.gpus and world > 1:
         args.gpus = world                                 # started by torch.distributed.run: its world size holds
     if not torch.cuda.is_available():
-        raise SystemExit("scale_imagenet_amd.main needs a HIP device (the product has no CPU path)")
+        raise SystemExit(f"{prog} needs a HIP device (the product has no CPU path)")
     index = (args.gpu or 0) if world == 1 else local_rank % torch.cuda.device_count()
     device = torch.device("cuda", index)
     torch.cuda.set_device(device)
-    _check_paths(args)
+    return rank, world, device
 
+
+def load_model(args, device, rank: int):
+    from . import ttnet
     model = getattr(ttnet, VARIANT_CLASSES[args.variant])(argparse.Namespace(
         nfilter=args.nfilter, tfilter=args.tfilter, layers=args.layers, groups=parse_groups(args.groups)))
     model.load_state_dict(_state_dict(args, model.spec, rank), strict=True)
-    model = model.to(device).eval().reserve(max(1, args.eval_batch_size))
+    return model.to(device).eval().reserve(max(1, args.eval_batch_size))
 
-    folder = jpeg.FileBytesFolder(os.path.join(args.data_dir, "val"))
+
+def shard_loader(args, folder, rank: int, world: int):
+    """This rank's ``ShardedSampler`` slice of ``folder`` (``FileBytesFolder`` / ``FileBytesList``) behind --input's collate."""
+    import torch
+
+    from . import jpeg, preprocess
+    from .dist import ShardedSampler
     dataset, collate = {"jpeg": (folder, jpeg.collate_jpeg),
                         "jpeg-progressive": (folder, jpeg.collate_jpeg_progressive),
                         "pillow": (_PillowFolder(folder), preprocess.collate_u8)}[args.input]
     # the workers are fresh interpreters: this process has initialised the GPU and is not forked (launch.py)
-    loader = torch.utils.data.DataLoader(dataset, batch_size=args.eval_batch_size, sampler=ShardedSampler(len(dataset), rank, world),
-                                         num_workers=args.num_workers, collate_fn=collate, pin_memory=True,
-                                         multiprocessing_context="spawn" if args.num_workers > 0 else None)
-    # a rank's own lines (running metrics, its shard's Acc..) go to stderr when there are several: stdout carries the result
-    with contextlib.redirect_stdout(sys.stderr) if world > 1 else contextlib.nullcontext():
-        part = evaluate(model, loader, device, log_every=args.log_interval, inflight=max(1, args.inflight), metrics="device")
-    res = all_reduce_metrics(part)
+    return torch.utils.data.DataLoader(dataset, batch_size=args.eval_batch_size, sampler=ShardedSampler(len(dataset), rank, world),
+                                       num_workers=args.num_workers, collate_fn=collate, pin_memory=True,
+                                       multiprocessing_context="spawn" if args.num_workers > 0 else None)
+
+
+def check_topk(args, needed: bool):
+    if args.topk == 0 and needed:
+        args.topk = 5
+    if not (0 <= args.topk <= 32):
+        raise SystemExit("--topk must be in [1, 32]")
+
+
+def end_ranks(world: int):
     if world > 1:
         import torch.distributed as dist
-        if rank == 0:
-            print("Acc..", res.top1, res.top5, flush=True)             # main.py:284
         dist.barrier()
         dist.destroy_process_group()
+
+
+def run(args) -> int:
+    """One rank (or the only process): evaluate this rank's shard, sum over the ranks, rank 0 prints the line."""
+    from . import jpeg, report
+    from .dist import all_gather_predictions, all_reduce_counts, all_reduce_metrics
+    from .evaluate import evaluate
+
+    rank, world, device = start_rank(args)
+    _check_paths(args)
+    model = load_model(args, device, rank)
+    folder = jpeg.FileBytesFolder(os.path.join(args.data_dir, "val"))
+    loader = shard_loader(args, folder, rank, world)
+    extra = {}
+    if args.topk or args.predictions or args.per_class or args.confusion:      # (otherwise the call is what it was)
+        extra = dict(topk=args.topk, per_class=bool(args.per_class or args.confusion), confusion=bool(args.confusion))
+    # a rank's own lines (running metrics, its shard's Acc..) go to stderr when there are several: stdout carries the result
+    with contextlib.redirect_stdout(sys.stderr) if world > 1 else contextlib.nullcontext():
+        part = evaluate(model, loader, device, log_every=args.log_interval, inflight=max(1, args.inflight), metrics="device",
+                        **extra)
+    res = all_reduce_metrics(part)
+    if world > 1 and rank == 0:
+        print("Acc..", res.top1, res.top5, flush=True)                 # main.py:284
+    if extra:
+        names = report.read_class_names(args.classes) if args.classes else None
+        pred = all_gather_predictions(part.predictions) if args.predictions else None
+        counts, confusion = all_reduce_counts(part.per_class, part.confusion) if extra["per_class"] else (None, None)
+        if rank == 0:
+            if args.predictions:
+                report.write_predictions_csv(args.predictions, [p for p, _ in folder.samples], folder.targets, pred, names)
+            if args.per_class:
+                report.write_per_class_csv(args.per_class, counts, names)
+            if args.confusion:
+                report.write_confusion(args.confusion, confusion)
+    end_ranks(world)
     return 0
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     args = build_parser().parse_args(argv)
+    check_topk(args, needed=bool(args.predictions))
+    return launch(args, argv, "scale_imagenet_amd.main", _check_paths, run)
+
+
+def launch(args, argv, module: str, check_paths, run_rank) -> int:
+    """Run ``run_rank(args)`` here, or -- for --gpus N from a plain command line -- start N fresh ranks of ``module``."""
     from .launch import spawn_ranks, under_launcher
     if args.gpus < 1:
         raise SystemExit("--gpus must be positive")
@@ -186,13 +266,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         if have < args.gpus and os.environ.get("TTNET_DIST_BACKEND") != "gloo":
             raise SystemExit(f"--gpus {args.gpus}: only {have} HIP device(s) here (TTNET_DIST_BACKEND=gloo rehearses several "
                              "ranks on one device)")
-        _check_paths(args)
+        check_paths(args)
         root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))       # the ranks import the same package
         path = os.pathsep.join(p for p in (root, os.environ.get("PYTHONPATH")) if p)
-        return spawn_ranks(["-m", "scale_imagenet_amd.main", *argv], args.gpus, extra_env={"PYTHONPATH": path})
+        return spawn_ranks(["-m", module, *argv], args.gpus, extra_env={"PYTHONPATH": path})
     if os.environ.get("RANK", "0") == "0":
         _note_ignored(args, argv)
-    return run(args)
+    return run_rank(args)
 
 
 if __name__ == "__main__":

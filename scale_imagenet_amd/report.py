@@ -1,0 +1,104 @@
+"""The files the commands write: per-image predictions (CSV), per-class counters (CSV), the confusion matrix (.npy).
+
+Formats (fixed: tests and users' scripts read them):
+  predictions  ``path,target,class_1,logprob_1,...,class_K,logprob_K``; ``target`` is empty for an unlabelled image;
+               floats are written with ``repr()`` and so read back to the same bits; with class names ``target`` and
+               ``class_i`` are names, otherwise indices (a row with a NaN has class -1, whatever the names).
+  per class    ``class,images,hits1,hits5,predicted,acc1,acc5`` from the int64 ``[n_classes, 4]`` counters of
+               ``ttnet_class_counts``; ``acc`` in percent, empty for a class without images.
+  confusion    ``numpy.save`` of the int64 ``[n_classes, n_classes]`` matrix, indexed ``[target][top-1 class]``.
+Every file is written to a temporary name beside its own and then renamed, so a reader never sees half of one.
+"""
+from __future__ import annotations
+
+import contextlib
+import csv
+import os
+import sys
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+
+def read_class_names(path: str) -> List[str]:
+    """One name per line (the line's text without its line end; empty lines at the end of the file are dropped)."""
+    with open(path, encoding="utf-8") as f:
+        names = [line.rstrip("\r\n") for line in f]
+    while names and not names[-1]:
+        names.pop()
+    return names
+
+
+@contextlib.contextmanager
+def _replacing(path: Optional[str], mode: str = "w"):
+    """A file that becomes ``path`` when the block ends well; ``path`` None: standard output."""
+    if path is None:
+        yield sys.stdout.buffer if "b" in mode else sys.stdout
+        sys.stdout.flush()
+        return
+    tmp = f"{path}.tmp{os.getpid()}"
+    kw = {} if "b" in mode else {"newline": "", "encoding": "utf-8"}
+    try:
+        with open(tmp, mode, **kw) as f:
+            yield f
+        os.replace(tmp, path)
+    except BaseException:
+        with contextlib.suppress(OSError):
+            os.remove(tmp)
+        raise
+
+
+def _name(index: int, names: Optional[Sequence[str]]) -> str:
+    if names is None or index < 0:
+        return str(int(index))
+    if index >= len(names):
+        raise ValueError(f"class {index} has no name: the class list has {len(names)} lines")
+    return names[index]
+
+
+def write_predictions_csv(path: Optional[str], paths: Sequence[str], targets: Optional[Sequence[int]], pred,
+                          names: Optional[Sequence[str]] = None):
+    """``pred``: ``evaluate.Predictions`` of ``len(paths)`` images in the order of ``paths``; ``targets`` None: unlabelled."""
+    if len(pred) != len(paths) or (targets is not None and len(targets) != len(paths)):
+        raise ValueError(f"{len(paths)} paths, {len(pred)} predictions, {None if targets is None else len(targets)} targets")
+    k = pred.k
+    with _replacing(path) as f:
+        w = csv.writer(f, lineterminator="\n")
+        w.writerow(["path", "target"] + [c for i in range(1, k + 1) for c in (f"class_{i}", f"logprob_{i}")])
+        for n, p in enumerate(paths):
+            row = [p, "" if targets is None else _name(int(targets[n]), names)]
+            for i in range(k):
+                row += [_name(int(pred.classes[n, i]), names), repr(float(pred.logprob[n, i]))]
+            w.writerow(row)
+
+
+def read_predictions_csv(path: str) -> Tuple[List[str], List[str], List[List[str]], np.ndarray]:
+    """``(paths, targets, classes, logprob)``: targets and classes as written (names or indices, "" for no target),
+    ``logprob`` float64 ``[N, K]`` with the bits that were written."""
+    with open(path, newline="", encoding="utf-8") as f:
+        rows = list(csv.reader(f))
+    head, rows = rows[0], rows[1:]
+    k = (len(head) - 2) // 2
+    if head != ["path", "target"] + [c for i in range(1, k + 1) for c in (f"class_{i}", f"logprob_{i}")]:
+        raise ValueError(f"{path}: not a predictions file (header {head})")
+    logprob = np.array([[float(r[3 + 2 * i]) for i in range(k)] for r in rows], dtype=np.float64).reshape(len(rows), k)
+    return [r[0] for r in rows], [r[1] for r in rows], [[r[2 + 2 * i] for i in range(k)] for r in rows], logprob
+
+
+def per_class_rows(counts: np.ndarray, names: Optional[Sequence[str]] = None) -> List[list]:
+    """The rows of the per-class file, header first."""
+    rows = [["class", "images", "hits1", "hits5", "predicted", "acc1", "acc5"]]
+    for c, (images, hits1, hits5, predicted) in enumerate(np.asarray(counts, dtype=np.int64).tolist()):
+        acc = [repr(100.0 * h / images) if images else "" for h in (hits1, hits5)]
+        rows.append([_name(c, names), images, hits1, hits5, predicted] + acc)
+    return rows
+
+
+def write_per_class_csv(path: Optional[str], counts: np.ndarray, names: Optional[Sequence[str]] = None):
+    with _replacing(path) as f:
+        csv.writer(f, lineterminator="\n").writerows(per_class_rows(counts, names))
+
+
+def write_confusion(path: str, confusion: np.ndarray):
+    with _replacing(path, "wb") as f:
+        np.save(f, np.ascontiguousarray(confusion, dtype=np.int64))
