@@ -380,9 +380,36 @@ int ttnet_read_stage(ttnet_plan *plan, const char *stage, int64_t n, void *dst, 
 int ttnet_plan_get_table(ttnet_plan *plan, const char *name, void *dst_host, size_t dst_bytes);
 int ttnet_plan_set_table(ttnet_plan *plan, const char *name, const void *src_host, size_t src_bytes);
 
+/* Truth-table usage counts: which entries of the tables a forward actually read.  For Block_TT `name` with G groups
+ * and n input bits, usage is int64 [G][2^n] in the canonical order of ttnet_plan_get_table (index = pattern read MSB
+ * first over (c_in_group, kh, kw), convolution zero padding = bit 0): usage[g][i] = number of (image, output position)
+ * pairs at which the input window of group g had index i.  Output positions are all Ho x Wo positions of the block's own
+ * convolution, those a later floor-cropped majority pool discards included; Block_convf reads the interleaved,
+ * branch-padded concat (channel 4c + branch, the zero pads are bit 0).  So usage[g].sum() == images * Ho * Wo for every g.
+ *   enable  allocates and zeroes one int64 counter per table entry of the plan (543 MB for TT-small p = 64 --layers 1) and
+ *           the per-lane scratch of the add (ttnet_plan_set_lanes grows it with the lanes); enabled = 0 frees both.
+ *           Synchronises the device: call it outside graph capture.  "usage_bytes" (ttnet_plan_query) is what it holds.
+ *   reset   zeroes the counters, asynchronously on `stream`.
+ *   add     adds the lookups of the forward last issued on `lane` (all of its images), whichever entry point issued it
+ *           (ttnet_forward, _lane, _u8, _from_stem_bits) and whether it ran as plain launches or as a replayed graph: it
+ *           reads the stage buffers the lane still holds.  Asynchronous on `stream`; the caller orders it after that
+ *           lane's forward and before the lane is reused.  Its own launches only (the forward kernels do not change); no
+ *           allocation, no host synchronisation.  On the block-fused path the branch tensors never reach memory, so every
+ *           non-last block is run once more with a tap buffer, as ttnet_read_stage does.  64-bit integer atomics: the
+ *           counts do not depend on batch order, lane, stream or rank.
+ *   get     synchronises the device and copies the counters of one block to the host (dst_bytes = G * 2^n * 8).
+ * Errors: add / reset / get before enable TTNET_E_STATE; an unknown block name or a wrong dst_bytes TTNET_E_INVALID.
+ * Served: TTNET_SMALL (every built p and --layers, fused and two-launch gate paths) and TTNET_XSMALL.  Refused by enable
+ * with TTNET_E_UNSUPPORTED: TTNET_FULL (fan-in 30: no tables, the reason ttnet_plan_get_table gives) and TTNET_VALEXNET
+ * (not built: its block has no Block_convf and its own stage layout). */
+int ttnet_plan_table_usage_enable(ttnet_plan *plan, int enabled);
+int ttnet_plan_table_usage_reset(ttnet_plan *plan, void *stream);
+int ttnet_table_usage_add(ttnet_plan *plan, int lane, void *stream);
+int ttnet_plan_get_table_usage(ttnet_plan *plan, const char *name, int64_t *dst_host, size_t dst_bytes);
+
 /* Integer facts about the plan: "fcsize", "n_classes", "n_state_tensors", "max_batch",
  * "near_ties:<block_tt name>" (entries with |pre-activation| < 1e-5 found while building
- * that table), "table_bytes", "workspace_bytes", "graph_replays" (forwards replayed from a
+ * that table), "table_bytes", "usage_bytes", "workspace_bytes", "graph_replays" (forwards replayed from a
  * captured hipGraph so far), "graphs_enabled" (0: ttnet_last_error() then says why), "graph_captures",
  * "graph_drops", "graphs_cached", "lanes", "range_overflow" (synchronises; 1 if a forward since the last
  * query left the fp16 x 2 range, and clears the flag). */

@@ -58,6 +58,7 @@ struct BlockTT {
   unsigned *near_dev = nullptr;
   int64_t near_ties = -1;
   bool user_table = false;
+  int64_t *usage = nullptr;      // [groups][2^n] lookups per entry, canonical order (ttnet_plan_table_usage_enable)
 };
 
 struct MultiHead {
@@ -132,6 +133,10 @@ struct ttnet_plan {
   float lin2_inv = 1.f;             // 1 / (weight prescale x activation prescale)
   size_t part_elems = 0;
   size_t table_bytes = 0, workspace_bytes = 0;
+  // truth-table usage counts (usage.hip): the counters live in the BlockTTs, the scratch in the lanes
+  bool usage_on = false;
+  size_t usage_bytes = 0;
+  int usage_scheme_dw = kUsageMerged, usage_scheme_pw = kUsageMerged;   // per table shape: depthwise / grouped 1x1 (DESIGN: table usage)
 
   bool profiling = false;
   // captured forward per batch size (hipGraph): one launch instead of ~11 on the host side
@@ -165,6 +170,10 @@ struct ttnet_plan {
     float *part = nullptr;          // lin1's partial sums
     uint16_t *feat = nullptr;       // features as two fp16 planes in lin1 fragment order
     uint16_t *mid_frag = nullptr;   // lin2's A operand (head_mid_kernel), rows padded to 64
+    // table usage: the block input widened to uint64 rows (fused path), the four branch tensors as uint64 rows
+    // (fused and two-launch paths) and the branch dwords of a re-run non-last block (fused path)
+    uint64_t *u_rows = nullptr, *u_br[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t *u_tap = nullptr;
     std::map<int64_t, GraphEntry> graphs;
     std::map<int64_t, int> eager_calls;
     int64_t last_n = 0;             // images of the last forward on this lane
@@ -219,6 +228,13 @@ int dev_alloc(ttnet_plan *pl, T **out, size_t count, bool zero, size_t *account 
   if (account) *account += bytes;
   *out = (T *)ptr;
   return TTNET_OK;
+}
+
+void dev_free(ttnet_plan *pl, void *ptr) {
+  if (!ptr) return;
+  auto it = std::find(pl->owned.begin(), pl->owned.end(), ptr);
+  if (it != pl->owned.end()) pl->owned.erase(it);
+  (void)hipFree(ptr);
 }
 
 void add_tensor(ttnet_plan *pl, const std::string &key, std::vector<int64_t> shape, int dtype, bool required) {
@@ -899,6 +915,40 @@ inline uint32_t canonical_index(const BlockTT &b, uint32_t idx) {
   return ci;
 }
 
+// Per-lane scratch of ttnet_table_usage_add, sized for max_batch (a lane that has its scratch keeps it)
+int alloc_usage_scratch(ttnet_plan *pl, ttnet_plan::Lane &L) {
+  if (L.u_br[0] || pl->path == GatePath::XSmall) return TTNET_OK;      // (x-small keeps everything as uint64 rows already)
+  const size_t nb = (size_t)pl->desc.max_batch;
+  size_t rows = 0, br = 0, tap = 0;
+  for (size_t i = 0; i < pl->blocks.size(); ++i) {
+    const MultiHead &mh = pl->blocks[i];
+    if (i > 0) rows = std::max(rows, nb * mh.C * mh.H);
+    br = std::max(br, nb * mh.C * mh.Ho);
+    if (!mh.last) tap = std::max(tap, nb * (mh.C / 8) * mh.Ho * mh.Wo);
+  }
+  size_t *acc = &pl->usage_bytes;
+  for (int k = 0; k < 4; ++k) TT_TRY(dev_alloc(pl, &L.u_br[k], br, true, acc));
+  if (pl->path == GatePath::Fused) {
+    TT_TRY(dev_alloc(pl, &L.u_rows, rows, true, acc));
+    TT_TRY(dev_alloc(pl, &L.u_tap, tap, true, acc));
+  }
+  return TTNET_OK;
+}
+
+void free_usage(ttnet_plan *pl) {
+  for (BlockTT *b : all_block_tts(pl)) {
+    dev_free(pl, b->usage);
+    b->usage = nullptr;
+  }
+  for (auto &l : pl->lanes) {
+    for (auto &p : l.u_br) { dev_free(pl, p); p = nullptr; }
+    dev_free(pl, l.u_rows); l.u_rows = nullptr;
+    dev_free(pl, l.u_tap); l.u_tap = nullptr;
+  }
+  pl->usage_bytes = 0;
+  pl->usage_on = false;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1194,6 +1244,150 @@ int ttnet_plan_set_lanes(ttnet_plan *pl, int lanes) {
       return r;
     }
   }
+  if (pl->usage_on)
+    for (auto &l : pl->lanes) TT_TRY(alloc_usage_scratch(pl, l));     // (lanes that have theirs keep it)
+  return TTNET_OK;
+}
+
+int ttnet_plan_table_usage_enable(ttnet_plan *pl, int enabled) {
+  if (!pl) {
+    set_error("null plan");
+    return TTNET_E_INVALID;
+  }
+  if (pl->path == GatePath::Full) {
+    set_error("the full variant (fan-in 30) has no truth tables: 2^30 entries per output bit");
+    return TTNET_E_UNSUPPORTED;
+  }
+  if (pl->path == GatePath::VAlexnet) {
+    set_error("table usage is not built for the vAlexnet variant");
+    return TTNET_E_UNSUPPORTED;
+  }
+  TT_HIP(hipSetDevice(pl->device));
+  if ((enabled != 0) == pl->usage_on) return TTNET_OK;
+  TT_HIP(hipDeviceSynchronize());
+  if (!enabled) {
+    free_usage(pl);
+    return TTNET_OK;
+  }
+  if (const char *e = getenv("TTNET_USAGE_SCHEME"))      // measurements: "plain" / "merged" for every table shape
+    pl->usage_scheme_dw = pl->usage_scheme_pw = std::string(e) == "plain" ? kUsagePlain : kUsageMerged;
+  int r = TTNET_OK;
+  for (BlockTT *b : all_block_tts(pl)) {
+    if (r == TTNET_OK) r = dev_alloc(pl, &b->usage, (size_t)b->g.groups << b->g.nbits(), true, &pl->usage_bytes);
+  }
+  for (auto &l : pl->lanes)
+    if (r == TTNET_OK) r = alloc_usage_scratch(pl, l);
+  if (r != TTNET_OK) {
+    free_usage(pl);
+    return r;
+  }
+  pl->usage_on = true;
+  return TTNET_OK;
+}
+
+int ttnet_plan_table_usage_reset(ttnet_plan *pl, void *stream) {
+  if (!pl) {
+    set_error("null plan");
+    return TTNET_E_INVALID;
+  }
+  if (!pl->usage_on) {
+    set_error("table_usage_reset before ttnet_plan_table_usage_enable");
+    return TTNET_E_STATE;
+  }
+  for (BlockTT *b : all_block_tts(pl))
+    TT_HIP(hipMemsetAsync(b->usage, 0, ((size_t)b->g.groups << b->g.nbits()) * sizeof(int64_t), (hipStream_t)stream));
+  return TTNET_OK;
+}
+
+int ttnet_table_usage_add(ttnet_plan *pl, int lane, void *stream) {
+  if (!pl) {
+    set_error("null plan");
+    return TTNET_E_INVALID;
+  }
+  if (!pl->usage_on) {
+    set_error("table_usage_add before ttnet_plan_table_usage_enable");
+    return TTNET_E_STATE;
+  }
+  if (lane < 0 || lane >= (int)pl->lanes.size()) {
+    set_error("table_usage_add: lane %d but the plan has %d (ttnet_plan_set_lanes)", lane, (int)pl->lanes.size());
+    return TTNET_E_INVALID;
+  }
+  const ttnet_plan::Lane &L = pl->lanes[lane];
+  if (L.last_n < 1) {
+    set_error("table_usage_add: no forward has run on lane %d", lane);
+    return TTNET_E_STATE;
+  }
+  const int n = (int)L.last_n;
+  hipStream_t s = (hipStream_t)stream;
+  for (size_t i = 0; i < pl->blocks.size(); ++i) {
+    const MultiHead &mh = pl->blocks[i];
+    // the block's input as uint64 rows
+    const uint64_t *xin = L.x_rp[i];
+    if (pl->path == GatePath::Fused && i > 0) {
+      TT_TIMED(pl, "usage.prep", s, launch_widen_rows(L.x_rp[i], L.u_rows, (size_t)n * mh.C * mh.H, mh.W, s));
+      xin = L.u_rows;
+    }
+    for (const BlockTT *b : {&mh.c1, &mh.c2}) {
+      const BlockGeom &g = b->g;
+      const int ho = (mh.H + 2 * g.pad - g.kh) / g.stride + 1, wo = (mh.W + 2 * g.pad - g.kw) / g.stride + 1;
+      TT_TIMED(pl, "usage.dw", s,
+               launch_usage_dw(xin, n, mh.C, mh.H, mh.W, ho, wo, g.kh, g.kw, g.stride, g.pad, b->usage, pl->usage_scheme_dw, s));
+    }
+    TT_TIMED(pl, "usage.conv3", s,
+             launch_usage_pw(&xin, 1, n, mh.C, mh.c3.g.groups, mh.c3.g.cin_g(), mh.H, mh.W, mh.c3.usage, pl->usage_scheme_pw, s));
+    // the four branch tensors after their padding, as uint64 rows [n][C][Ho]
+    std::array<uint64_t *, 4> br = branch_rows(L, i);
+    if (pl->path == GatePath::TwoLaunch) {
+      for (int k = 0; k < 4; ++k) {
+        TT_TIMED(pl, "usage.prep", s, launch_cp_to_rp(L.blk[i].o[k], L.u_br[k], n, mh.C, mh.Ho, mh.Wo, s));
+        br[k] = L.u_br[k];
+      }
+    } else if (pl->path == GatePath::Fused) {
+      // the branch tensors never reach HBM: a last block's dwords are its output, any other block is run once more
+      // on its (still resident) input with the lane's tap buffer attached -- it rewrites the next block's input
+      // with the same bits
+      const uint32_t *src = L.blk[i].idx;
+      if (!mh.last) {
+        FusedBlockArgs f{};
+        f.n = n; f.C = mh.C; f.H = mh.H; f.Ho = mh.Ho; f.off34 = mh.off34; f.last = 0;
+        f.x = L.x_rp[i]; f.img_c3 = mh.img_c3; f.img_dw = mh.img_dw; f.t_cf = (const uint8_t *)mh.cf.table;
+        f.y = L.x_rp[i + 1]; f.idx = L.u_tap;
+        TT_TIMED(pl, "usage.tap", s, launch_gate_block(f, s));
+        src = L.u_tap;
+      }
+      for (int k = 0; k < 4; ++k) {
+        TT_TIMED(pl, "usage.prep", s, launch_branch_rows(src, L.u_br[k], n, mh.C, mh.Ho, k, s));
+        br[k] = L.u_br[k];
+      }
+    }
+    TT_TIMED(pl, "usage.convf", s,
+             launch_usage_pw(br.data(), 4, n, mh.C, mh.cf.g.groups, mh.cf.g.cin_g(), mh.Ho, mh.Wo, mh.cf.usage, pl->usage_scheme_pw, s));
+  }
+  return TTNET_OK;
+}
+
+int ttnet_plan_get_table_usage(ttnet_plan *pl, const char *name, int64_t *dst_host, size_t dst_bytes) {
+  if (!pl || !name || !dst_host) {
+    set_error("null argument");
+    return TTNET_E_INVALID;
+  }
+  if (!pl->usage_on) {
+    set_error("get_table_usage before ttnet_plan_table_usage_enable");
+    return TTNET_E_STATE;
+  }
+  BlockTT *b = find_block(pl, name);
+  if (!b) {
+    set_error("no Block_TT named %s", name);
+    return TTNET_E_INVALID;
+  }
+  const size_t need = ((size_t)b->g.groups << b->g.nbits()) * sizeof(int64_t);
+  if (dst_bytes != need) {
+    set_error("get_table_usage(%s): destination is %zu bytes, the counters are %zu", name, dst_bytes, need);
+    return TTNET_E_INVALID;
+  }
+  TT_HIP(hipSetDevice(pl->device));
+  TT_HIP(hipDeviceSynchronize());
+  TT_HIP(hipMemcpy(dst_host, b->usage, need, hipMemcpyDeviceToHost));
   return TTNET_OK;
 }
 
@@ -1518,6 +1712,7 @@ int ttnet_plan_query(ttnet_plan *pl, const char *what, int64_t *out) {
   else if (w == "max_batch") *out = pl->desc.max_batch;
   else if (w == "table_bytes") *out = (int64_t)pl->table_bytes;
   else if (w == "workspace_bytes") *out = (int64_t)pl->workspace_bytes;
+  else if (w == "usage_bytes") *out = (int64_t)pl->usage_bytes;
   else if (w == "p") *out = pl->p;
   else if (w == "graph_replays") *out = pl->graph_replays;
   else if (w == "graphs_enabled") {

@@ -344,4 +344,14 @@ int launch_lin2_f16x2(const void *mid_frag, const void *w2f, const float *bias, 
 // W1p[o][(g*PP+pp)*16+k] = W1[o][(16g+k)*PP+pp]
 int launch_permute_lin1(const float *w1, float *w1p, int O, int G, int PP, hipStream_t s);
 
+// usage.hip: truth-table usage counts, int64 counters [groups][2^n] in the canonical index order, from row-packed
+// uint64 planes.  scheme: one atomic per lookup, or equal counters merged within a wave first (same counts).
+constexpr int kUsagePlain = 0, kUsageMerged = 1;
+// depthwise block on x_rp [n][C][H] (W <= 64 - 2 * pad): every Ho x Wo output position of its own convolution
+int launch_usage_dw(const uint64_t *x_rp, int n, int C, int H, int W, int Ho, int Wo, int kh, int kw, int stride, int pad,
+                    int64_t *counters, int scheme, hipStream_t s);
+// grouped 1x1 block on the H x W positions of nsrc (1, or 4 = the interleaved branch concat) tensors [n][Csrc][H]
+int launch_usage_pw(const uint64_t *const *src, int nsrc, int n, int Csrc, int groups, int cin_g, int H, int W, int64_t *counters,
+                    int scheme, hipStream_t s);
+
 }  // namespace ttnet

@@ -9,7 +9,8 @@ all-gather of ``[B/world, 1000]`` fp32.
 
 Evaluating a dataset needs less still: every rank evaluates its ``ShardedSampler`` slice and one
 ``all_reduce_metrics`` sums four numbers (loss sum, images, top-1 hits, top-5 hits).  Per-image predictions are
-joined in rank order (``all_gather_predictions``), per-class counters summed (``all_reduce_counts``).
+joined in rank order (``all_gather_predictions``), per-class counters summed (``all_reduce_counts``), truth-table
+usage counters summed (``all_reduce_table_usage``).
 """
 from __future__ import annotations
 
@@ -151,3 +152,20 @@ def all_reduce_counts(counts, confusion=None, group=None):
     v = v.cpu().numpy()
     n = counts.size
     return v[:n].reshape(counts.shape).copy(), None if confusion is None else v[n:].reshape(confusion.shape).copy()
+
+
+def all_reduce_table_usage(usage, group=None):
+    """Sum the truth-table usage counters of every rank (``EvalResult.table_usage``: ``{Block_TT name: int64 [groups,
+    2^n]}``): one ``all_reduce(SUM)`` per block, in name order, so that no more than one block's counters (268 MB for
+    the largest of TT-small p = 64) is on the wire at a time.  Integer sums: the result does not depend on how the
+    images were sharded.  numpy in, numpy out; every rank must hold the same blocks; a single process returns its input."""
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return usage
+    import numpy as np
+    out = {}
+    for name in sorted(usage):
+        a = np.ascontiguousarray(usage[name], dtype=np.int64)
+        v = _wire(torch.from_numpy(a.copy()).reshape(-1), group)
+        dist.all_reduce(v, op=dist.ReduceOp.SUM, group=group)
+        out[name] = v.cpu().numpy().reshape(a.shape)
+    return {name: out[name] for name in usage}

@@ -92,6 +92,7 @@ class EvalResult:
     predictions = None  # (not a field) ``Predictions`` in dataset order, with ``topk=k``
     per_class = None    # (not a field) int64 [n_classes, 4] {images, hits1, hits5, predicted}, with ``per_class=True``
     confusion = None    # (not a field) int64 [n_classes, n_classes] indexed [target][top-1 class], with ``confusion=True``
+    table_usage = None  # (not a field) {Block_TT name: int64 [groups, 2^n]} lookups per table entry, with ``table_usage=True``
 
     def to_parts(self) -> EvalParts:
         """The sums behind this result: exact when ``parts`` is set, otherwise recovered from the means (the hit
@@ -370,7 +371,7 @@ class _TopK:
 def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]],
              device: torch.device, log_every: int = 0, inflight: int = 1, *,
              forward: Optional[Callable] = None, metrics: str = "torch", topk: int = 0, per_class: bool = False,
-             confusion: bool = False) -> EvalResult:
+             confusion: bool = False, table_usage: bool = False) -> EvalResult:
     """main.py:242-284: ``model.eval()``, no_grad, per batch loss / top-1 / top-5.
 
     ``inflight`` > 1 keeps that many batches in flight on separate HIP streams and model lanes
@@ -394,7 +395,13 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
     whatever ``inflight`` is.  ``per_class`` / ``confusion`` (device metrics only): its ``per_class`` / ``confusion``
     are the counters of ``ttnet_class_counts``, read back once at the end.  With the defaults nothing changes.  A batch
     ``(inputs, None)`` is unlabelled: forward and top-k only; the result then has ``loss = top1 = top5 = None`` and no
-    ``Acc..`` line is printed.  Labelled and unlabelled batches do not mix."""
+    ``Acc..`` line is printed.  Labelled and unlabelled batches do not mix.
+
+    ``table_usage=True``: the result's ``table_usage`` says how often the evaluation read every entry of every truth
+    table (``{Block_TT name: int64 [groups, 2^n]}``, canonical order; include/ttnet.h).  The counters are enabled and
+    zeroed first and ``model.add_table_usage(lane)`` follows every forward on the batch's stream, whatever the input
+    type and ``inflight``; nothing is read back before the end.  Size the plan first (``model.reserve``): a plan that has
+    to grow for a larger batch would start its counters again, which raises here."""
     if topk < 0 or topk > _lib.TOPK_MAX:
         raise ValueError(f"topk must be in [0, {_lib.TOPK_MAX}], got {topk}")
     per_class = per_class or confusion
@@ -407,6 +414,10 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
         raise RuntimeError(f"evaluate(metrics=\"device\") needs a HIP device, got {device}: the device metrics have no "
                            "CPU path (use metrics=\"torch\")")
     model.eval()
+    inner = getattr(model, "module", model)              # (nn.DataParallel wrapper, main.py:192)
+    if table_usage and not all(hasattr(inner, a) for a in ("count_table_usage", "add_table_usage", "table_usage")):
+        raise RuntimeError(f"evaluate(table_usage=True): {type(inner).__name__} keeps no truth-table usage counters (it needs "
+                           "count_table_usage / add_table_usage / table_usage, as the TTNet models have)")
     use_lanes = inflight > 1 and device.type == "cuda" and hasattr(model, "set_lanes")
     lanes = inflight if use_lanes else 1
     if use_lanes:
@@ -414,6 +425,14 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
     streams = [torch.cuda.Stream(device) for _ in range(lanes)] if use_lanes else []
     acc = _OnDeviceMetrics(device, lanes, streams, per_class, confusion) if metrics == "device" else _TorchMetrics()
     top = _TopK(topk, lanes) if topk else None
+    usage_plan = None
+    if table_usage:
+        inner.count_table_usage(True)
+        if getattr(inner, "_plans", None):               # (a plan made later starts from zeroed counters)
+            inner.reset_table_usage()
+            usage_plan = inner._any_plan()
+        for s in streams:                                 # zeroed on the current stream before any lane's stream adds
+            s.wait_stream(torch.cuda.current_stream(device))
     labelled = None                                        # True / False once the first batch has been seen
     seen = set()                                           # "ragged", "jpeg": which sticky counts to check at the end
 
@@ -468,6 +487,13 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
             if labelled:
                 targets = targets.to(device, non_blocking=True)
             outputs = run(inputs, lane if use_lanes else None)
+            if table_usage:
+                inner.add_table_usage(lane)
+                if usage_plan is None:
+                    usage_plan = inner._any_plan()
+                elif usage_plan is not inner._any_plan():
+                    raise RuntimeError("evaluate(table_usage=True): the plan was rebuilt for a larger batch and its counters "
+                                       "started again; call model.reserve(<largest batch>) first")
             batch = kept = None
             if top is None:
                 batch = acc.add(outputs, targets, lane)
@@ -487,7 +513,6 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
         retire()
     # the range flag of the split operands is reported on the next call of a plan: without this, an overflow in the
     # last (or only) batch would end in silently invalid metrics
-    inner = getattr(model, "module", model)              # (nn.DataParallel wrapper, main.py:192)
     if hasattr(inner, "check_range"):
         inner.check_range()
     if "jpeg" in seen:                                    # likewise: a corrupt file decodes as zeros and is only counted
@@ -502,6 +527,8 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
         res = acc.result()
     if top is not None:
         res.predictions = top.result()
+    if table_usage:
+        res.table_usage = inner.table_usage()             # (synchronises the device)
     if labelled is not False:
         print("Acc..", res.top1, res.top5)
     return res

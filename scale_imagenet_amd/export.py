@@ -15,6 +15,13 @@ Expressions are produced for n <= ``max_expr_bits`` inputs (the reference: n in 
 for the 16-input tables of TT-small only the CSV is practical.  Unlike the reference's exporter,
 grouped blocks (several input channels per group) work too: the table of group g is used for
 its filters.  Host-side Python (pandas + sympy), not a hot path.
+
+Don't-care terms: with ``usage`` (the lookup counts of ``model.table_usage()`` / ``evaluate(..., table_usage=True)``,
+int64 [2^n] per group, canonical order) a pattern that no image produced (count 0) is a don't-care of the
+minimisation: it goes to ``SOPform`` / ``POSform`` as ``dontcares``, so the expressions agree with the table on every
+pattern seen and are free elsewhere, which makes them smaller.  The CSV gains a ``count`` column, and a filter that is
+constant on the patterns seen is written as that constant.  ``dnf_literals`` / ``cnf_literals`` of the returned record
+are the literal counts of the two forms, to report the saving.  With ``usage=None`` every file is what it was.
 """
 from __future__ import annotations
 
@@ -32,12 +39,15 @@ def pattern_frame(n: int):
     return pd.DataFrame(bits).reset_index()
 
 
-def minimal_forms(minterms: List[int], n: int):
-    """(DNF, CNF) of the function that is 1 exactly on ``minterms`` (TT_FHE_SMALL.py:405-427)."""
+def minimal_forms(minterms: List[int], n: int, dontcares: Optional[List[int]] = None):
+    """(DNF, CNF) of the function that is 1 exactly on ``minterms`` (TT_FHE_SMALL.py:405-427); on ``dontcares`` either
+    form may take either value."""
     from sympy import symbols
     from sympy.logic import POSform, SOPform
     xs = symbols(", ".join(f"x_{i}" for i in range(n)))
     xs = list(xs) if n > 1 else [xs]
+    if dontcares:
+        return SOPform(xs, minterms=minterms, dontcares=dontcares), POSform(xs, minterms=minterms, dontcares=dontcares)
     return SOPform(xs, minterms=minterms), POSform(xs, minterms=minterms)
 
 
@@ -58,14 +68,26 @@ def cnf_with_output(dnf, cnf) -> str:
 
 
 def export_filter(column: np.ndarray, n: int, filter_index: int, out_dir: str, block: int, sub_block: int,
-                  max_expr_bits: int = 9) -> Dict[str, Optional[str]]:
-    """Files for one filter.  ``column``: its 2^n table entries (0/1), canonical order."""
+                  max_expr_bits: int = 9, usage: Optional[np.ndarray] = None) -> Dict[str, Optional[str]]:
+    """Files for one filter.  ``column``: its 2^n table entries (0/1), canonical order.  ``usage``: the lookup counts of
+    the filter's group, int64 [2^n] (module docstring)."""
     import pandas as pd
     os.makedirs(out_dir, exist_ok=True)
     col = np.asarray(column).astype(np.float32)
     uniq = np.unique(col)
     prefix = os.path.join(out_dir, "")
-    out: Dict[str, Optional[str]] = {"dnf": None, "cnf": None, "cnf_with_y": None, "csv": None}
+    out: Dict[str, Optional[str]] = {"dnf": None, "cnf": None, "cnf_with_y": None, "csv": None, "dnf_literals": 0,
+                                     "cnf_literals": 0}
+    counts = dontcares = None
+    if usage is not None:
+        counts = np.asarray(usage, dtype=np.int64).reshape(-1)
+        if counts.shape != col.shape:
+            raise ValueError(f"usage has {counts.size} counts, the filter has {col.size} entries")
+        seen = counts > 0
+        dontcares = np.flatnonzero(~seen).tolist()
+        on_seen = np.unique(col[seen]) if seen.any() else uniq[:1]       # (never looked up: any constant will do)
+        if len(on_seen) == 1:
+            uniq = on_seen
     if len(uniq) == 1:                                   # constant filter: the value only (:351-361)
         with open(f"{prefix}table_outputblock_{block}_filter_{filter_index}_coefdefault_{uniq[0]}.txt", "w") as f:
             f.write(str(uniq[0]))
@@ -74,13 +96,17 @@ def export_filter(column: np.ndarray, n: int, filter_index: int, out_dir: str, b
     for value in uniq[1:]:
         answer = col == value
         frame = pd.concat([pattern_frame(n), pd.DataFrame(answer, columns=[f"Filter_{filter_index}_Value_{int(value)}"])], axis=1)
+        if counts is not None:
+            frame["count"] = counts
         csv = f"{prefix}Truth_Table_block{block}_filter_{filter_index}_coefdefault_{value}_sousblock_{sub_block}.csv"
         frame.to_csv(csv)
         out["csv"] = csv
         if n <= max_expr_bits:
-            dnf, cnf = minimal_forms(frame["index"].values[answer].tolist(), n)
+            minterms = frame["index"].values[answer if counts is None else answer & (counts > 0)].tolist()
+            dnf, cnf = minimal_forms(minterms, n, dontcares)
             y = cnf_with_output(dnf, cnf)
-            out.update(dnf=str(dnf), cnf=str(cnf), cnf_with_y=y)
+            out.update(dnf=str(dnf), cnf=str(cnf), cnf_with_y=y, dnf_literals=literal_count(str(dnf)),
+                       cnf_literals=literal_count(str(cnf)))
             with open(f"{prefix}table_outputblock_{block}_filter_{filter_index}_coefdefault_{value}.txt", "w") as f:
                 f.write(y)
             with open(f"{prefix}CNF_expression_block{block}_filter_{filter_index}_coefdefault_{value}_sousblock_{sub_block}.txt", "w") as f:
@@ -91,15 +117,18 @@ def export_filter(column: np.ndarray, n: int, filter_index: int, out_dir: str, b
 
 
 def export_block(table: np.ndarray, out_dir: str, block: int, sub_block: int, filters: Optional[Iterable[int]] = None,
-                 max_expr_bits: int = 9) -> Dict[int, Dict[str, Optional[str]]]:
+                 max_expr_bits: int = 9, usage: Optional[np.ndarray] = None) -> Dict[int, Dict[str, Optional[str]]]:
     """``table``: [groups][2^n][cout_g] bits as returned by ``model.get_table(name)`` (or by the
     oracle's ``build_lut``).  Filter f = output channel f of the block = (group f // cout_g,
-    output f % cout_g)."""
+    output f % cout_g).  ``usage``: int64 [groups][2^n] lookup counts of the block (module docstring)."""
     g, size, cout_g = table.shape
     n = int(size).bit_length() - 1
     assert 2 ** n == size
     todo = range(g * cout_g) if filters is None else filters
-    return {f: export_filter(table[f // cout_g, :, f % cout_g], n, f, out_dir, block, sub_block, max_expr_bits) for f in todo}
+    if usage is not None and tuple(np.shape(usage)) != (g, size):
+        raise ValueError(f"usage has shape {tuple(np.shape(usage))}, the table has {g} groups of {size} entries")
+    return {f: export_filter(table[f // cout_g, :, f % cout_g], n, f, out_dir, block, sub_block, max_expr_bits,
+                             None if usage is None else usage[f // cout_g]) for f in todo}
 
 
 def literal_count(expr_text: Optional[str]) -> int:

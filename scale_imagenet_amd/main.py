@@ -84,6 +84,11 @@ def build_parser() -> argparse.ArgumentParser:
                      help="CSV class,images,hits1,hits5,predicted,acc1,acc5")
     out.add_argument("--confusion", type=str, default=None, metavar="FILE",
                      help=".npy, int64 [n_classes][n_classes] indexed [target][top-1 class]")
+    out.add_argument("--table_usage", type=str, default=None, metavar="FILE",
+                     help=".npz, one int64 [groups][2^n] array per Block_TT: how often the evaluation read every truth-table "
+                          "entry (counted on the device; 8 bytes of device memory per table entry)")
+    out.add_argument("--table_coverage", type=str, default=None, metavar="FILE",
+                     help="CSV block,groups,inputs,entries,seen,share_seen,constant_groups,top1pct_share (with --table_usage)")
     ign = p.add_argument_group("accepted and ignored (training, logging and launcher flags of the reference)")
     for name, typ, default in _IGNORED:
         ign.add_argument(name, type=typ, default=default, help=argparse.SUPPRESS)
@@ -213,7 +218,7 @@ def end_ranks(world: int):
 def run(args) -> int:
     """One rank (or the only process): evaluate this rank's shard, sum over the ranks, rank 0 prints the line."""
     from . import jpeg, report
-    from .dist import all_gather_predictions, all_reduce_counts, all_reduce_metrics
+    from .dist import all_gather_predictions, all_reduce_counts, all_reduce_metrics, all_reduce_table_usage
     from .evaluate import evaluate
 
     rank, world, device = start_rank(args)
@@ -224,6 +229,8 @@ def run(args) -> int:
     extra = {}
     if args.topk or args.predictions or args.per_class or args.confusion:      # (otherwise the call is what it was)
         extra = dict(topk=args.topk, per_class=bool(args.per_class or args.confusion), confusion=bool(args.confusion))
+    if args.table_usage:
+        extra["table_usage"] = True
     # a rank's own lines (running metrics, its shard's Acc..) go to stderr when there are several: stdout carries the result
     with contextlib.redirect_stdout(sys.stderr) if world > 1 else contextlib.nullcontext():
         part = evaluate(model, loader, device, log_every=args.log_interval, inflight=max(1, args.inflight), metrics="device",
@@ -231,7 +238,13 @@ def run(args) -> int:
     res = all_reduce_metrics(part)
     if world > 1 and rank == 0:
         print("Acc..", res.top1, res.top5, flush=True)                 # main.py:284
-    if extra:
+    if args.table_usage:
+        usage = all_reduce_table_usage(part.table_usage)
+        if rank == 0:
+            report.save_table_usage(args.table_usage, usage)
+            if args.table_coverage:
+                report.write_coverage_csv(args.table_coverage, usage, {name: model.get_table(name) for name in usage})
+    if extra.get("topk") is not None:
         names = report.read_class_names(args.classes) if args.classes else None
         pred = all_gather_predictions(part.predictions) if args.predictions else None
         counts, confusion = all_reduce_counts(part.per_class, part.confusion) if extra["per_class"] else (None, None)
@@ -250,6 +263,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     args = build_parser().parse_args(argv)
     check_topk(args, needed=bool(args.predictions))
+    if args.table_coverage and not args.table_usage:
+        raise SystemExit("--table_coverage needs --table_usage")
     return launch(args, argv, "scale_imagenet_amd.main", _check_paths, run)
 
 

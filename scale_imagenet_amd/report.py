@@ -7,6 +7,9 @@ Formats (fixed: tests and users' scripts read them):
   per class    ``class,images,hits1,hits5,predicted,acc1,acc5`` from the int64 ``[n_classes, 4]`` counters of
                ``ttnet_class_counts``; ``acc`` in percent, empty for a class without images.
   confusion    ``numpy.save`` of the int64 ``[n_classes, n_classes]`` matrix, indexed ``[target][top-1 class]``.
+  table usage  ``numpy.savez_compressed``: one int64 ``[groups, 2^n]`` array per ``Block_TT`` name (``EvalResult.table_usage``).
+  coverage     ``block,groups,inputs,entries,seen,share_seen,constant_groups,top1pct_share`` per ``Block_TT``
+               (``coverage_rows``).
 Every file is written to a temporary name beside its own and then renamed, so a reader never sees half of one.
 """
 from __future__ import annotations
@@ -102,3 +105,48 @@ def write_per_class_csv(path: Optional[str], counts: np.ndarray, names: Optional
 def write_confusion(path: str, confusion: np.ndarray):
     with _replacing(path, "wb") as f:
         np.save(f, np.ascontiguousarray(confusion, dtype=np.int64))
+
+
+def save_table_usage(path: str, usage) -> None:
+    """``{Block_TT name: int64 [groups, 2^n]}`` -> a compressed ``.npz`` with one array per block name."""
+    with _replacing(path, "wb") as f:
+        np.savez_compressed(f, **{k: np.ascontiguousarray(v, dtype=np.int64) for k, v in usage.items()})
+
+
+def load_table_usage(path: str):
+    with np.load(path) as z:
+        return {k: z[k] for k in z.files}
+
+
+def coverage_rows(usage, tables=None) -> List[list]:
+    """The rows of the coverage file, header first; one row per ``Block_TT`` of ``usage``:
+      entries          table entries of the block (groups x 2^n)
+      seen             entries looked up at least once
+      share_seen       seen / entries
+      constant_groups  groups whose output never varies on the entries seen (a group without a lookup counts); needs
+                       ``tables`` (``{name: model.get_table(name)}``, [groups, 2^n, cout_g]), empty without
+      top1pct_share    share of all lookups that fall on the 1 % most used entries of their group (at least one entry per
+                       group), summed over the groups: 1.0 for a block whose every group reads a single entry"""
+    rows = [["block", "groups", "inputs", "entries", "seen", "share_seen", "constant_groups", "top1pct_share"]]
+    for name, u in usage.items():
+        u = np.asarray(u, dtype=np.int64)
+        groups, size = u.shape
+        seen = u > 0
+        k = max(1, size // 100)
+        top = np.sort(u, axis=1)[:, size - k:].sum()
+        total = int(u.sum())
+        constant = ""
+        if tables is not None and name in tables:
+            t = np.asarray(tables[name])
+            constant = 0
+            for g in range(groups):
+                used = t[g][seen[g]]
+                constant += int(len(used) == 0 or bool((used == used[0]).all()))
+        rows.append([name, groups, int(size).bit_length() - 1, groups * size, int(seen.sum()),
+                     repr(float(seen.sum()) / (groups * size)), constant, repr(float(top) / total) if total else ""])
+    return rows
+
+
+def write_coverage_csv(path: Optional[str], usage, tables=None):
+    with _replacing(path) as f:
+        csv.writer(f, lineterminator="\n").writerows(coverage_rows(usage, tables))

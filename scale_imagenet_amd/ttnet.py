@@ -278,6 +278,8 @@ class _TTNetBase(nn.Module):
                 if self.__dict__.get("_lanes", 1) > 1:
                     plan.set_lanes(self._lanes)
                 self._apply_input_norm(plan)
+                if self.__dict__.get("_count_usage"):
+                    _lib.check(plan.lib.ttnet_plan_table_usage_enable(plan.handle, 1))
                 self._plans[idx] = plan
             sig = self._state_signature()
             if plan.signature != sig:
@@ -346,11 +348,12 @@ class _TTNetBase(nn.Module):
         return out
 
     def export_truth_tables(self, block_name: str, out_dir: str, block: int = 0, sub_block: int = 0, filters=None,
-                            max_expr_bits: int = 9):
+                            max_expr_bits: int = 9, usage=None):
         """Write the reference's truth-table files (CSV, DNF / CNF, SAT form) for one
-        ``Block_TT`` from the table the plan built on the GPU.  See ``scale_imagenet_amd.export``."""
+        ``Block_TT`` from the table the plan built on the GPU.  ``usage``: that block's lookup counts
+        (``table_usage()[block_name]``), whose zero entries become don't-care terms.  See ``scale_imagenet_amd.export``."""
         from . import export
-        return export.export_block(self.get_table(block_name), out_dir, block, sub_block, filters, max_expr_bits)
+        return export.export_block(self.get_table(block_name), out_dir, block, sub_block, filters, max_expr_bits, usage)
 
     def set_input_norm(self, mean, std):
         """Normalisation constants of ``forward_u8`` (default: the ImageNet ones)."""
@@ -430,6 +433,39 @@ class _TTNetBase(nn.Module):
         plan = self._any_plan()
         t = np.ascontiguousarray(table)
         _lib.check(plan.lib.ttnet_plan_set_table(plan.handle, name.encode(), t.ctypes.data_as(C.c_void_p), t.nbytes))
+
+    # -- truth-table usage counts (include/ttnet.h: ttnet_plan_table_usage_enable ..) -------------
+    def count_table_usage(self, enabled: bool = True):
+        """Allocate (``True``) or free (``False``) the usage counters: one int64 per table entry, zeroed.  Holds for the
+        plans that exist and for those made later.  The counters belong to a plan: ``reserve`` the largest batch first,
+        a plan that has to grow starts again from zero."""
+        self.__dict__["_count_usage"] = bool(enabled)
+        for plan in self._plans.values():
+            _lib.check(plan.lib.ttnet_plan_table_usage_enable(plan.handle, int(bool(enabled))))
+        return self
+
+    def add_table_usage(self, lane: int = 0):
+        """Add the lookups of the forward last issued on ``lane`` to the counters: asynchronous on the current stream,
+        which must be the one that forward was issued on (or be ordered after it)."""
+        plan = self._any_plan()
+        dev = torch.device("cuda", plan.device_index)
+        _lib.check(plan.lib.ttnet_table_usage_add(plan.handle, int(lane), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+    def reset_table_usage(self):
+        plan = self._any_plan()
+        dev = torch.device("cuda", plan.device_index)
+        _lib.check(plan.lib.ttnet_plan_table_usage_reset(plan.handle, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+    def table_usage(self) -> Dict[str, np.ndarray]:
+        """``{Block_TT name: int64 [groups, 2^n]}``: lookups per table entry since the last reset, in the canonical
+        order of ``get_table``.  Synchronises the device."""
+        plan = self._any_plan()
+        out = {}
+        for b in self.spec.block_tts():
+            a = np.empty((b.groups, 1 << b.fan_in_bits), dtype=np.int64)
+            _lib.check(plan.lib.ttnet_plan_get_table_usage(plan.handle, b.name.encode(), a.ctypes.data_as(C.c_void_p), a.nbytes))
+            out[b.name] = a
+        return out
 
     def near_ties(self) -> Dict[str, int]:
         plan = self._any_plan()
