@@ -412,7 +412,10 @@ int ttnet_plan_get_table_usage(ttnet_plan *plan, const char *name, int64_t *dst_
  * that table), "table_bytes", "usage_bytes", "workspace_bytes", "graph_replays" (forwards replayed from a
  * captured hipGraph so far), "graphs_enabled" (0: ttnet_last_error() then says why), "graph_captures",
  * "graph_drops", "graphs_cached", "lanes", "range_overflow" (synchronises; 1 if a forward since the last
- * query left the fp16 x 2 range, and clears the flag). */
+ * query left the fp16 x 2 range, and clears the flag), "gate_path" (which kernels evaluate the blocks, fixed at
+ * finalize: 0 the two launches per block of TT-small, also kept by TTNET_GATE_UNFUSED=1; 1 one fused launch per
+ * block; 2 x-small; 3 full; 4 vAlexnet), "gate_grid:<block index>" (paths 0 and 1: workgroups of that block's
+ * first launch at the batch size of the forward last issued on the lane used last). */
 int ttnet_plan_query(ttnet_plan *plan, const char *what, int64_t *out);
 
 /* Device time of the kernels of the last forward, measured with HIP events on the stream

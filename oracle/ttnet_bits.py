@@ -208,10 +208,11 @@ def valexnet_from_stem_bits(bits: np.ndarray, sd: Dict[str, np.ndarray], spec, l
     return y, z @ sd["features.7.lin2.weight"].astype(np.float64).T + sd["features.7.lin2.bias"].astype(np.float64)
 
 
-def forward_from_stem_bits(bits: np.ndarray, sd: Dict[str, np.ndarray], spec: VariantSpec, luts,
-                           taps: Optional[Dict[str, np.ndarray]] = None, near=None) -> np.ndarray:
-    """Gate path + float tail from the binarised stem output. Returns float64 logits.
-    ``luts`` may be None (every block evaluated directly in float64)."""
+def features_from_stem_bits(bits: np.ndarray, sd: Dict[str, np.ndarray], spec: VariantSpec, luts,
+                            taps: Optional[Dict[str, np.ndarray]] = None, near=None) -> np.ndarray:
+    """Gate path, AvgPool2d(2) and Flatten from the binarised stem output: float64 features [N, fcsize], i.e.
+    ``forward_from_stem_bits`` without the head (whose float64 weights cost more per call than the gate path of a
+    small chunk: a caller that walks a large batch in chunks runs ``head64`` once over all features)."""
     x = bits
     for blk in spec.blocks:
         x = multihead_block_bits(x, luts, blk, spec.variant, taps, sd, near)
@@ -223,6 +224,14 @@ def forward_from_stem_bits(bits: np.ndarray, sd: Dict[str, np.ndarray], spec: Va
     feat = x.reshape(n_, -1)
     if taps is not None:
         taps["flatten"] = feat
+    return feat
+
+
+def forward_from_stem_bits(bits: np.ndarray, sd: Dict[str, np.ndarray], spec: VariantSpec, luts,
+                           taps: Optional[Dict[str, np.ndarray]] = None, near=None) -> np.ndarray:
+    """Gate path + float tail from the binarised stem output. Returns float64 logits.
+    ``luts`` may be None (every block evaluated directly in float64)."""
+    feat = features_from_stem_bits(bits, sd, spec, luts, taps, near)
     return head64(feat, sd, f"features.{4 + len(spec.blocks) + 2}")
 
 

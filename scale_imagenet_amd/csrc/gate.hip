@@ -616,6 +616,7 @@ __global__ void rp_to_cp_kernel(const uint64_t *rp, uint16_t *cp, int n, int C, 
 
 // batch slices per table set so that `units` table sets spread over at most `target` workgroups
 int slices_for(int n, int units, int target) { return std::max(1, std::min(n, target / std::max(1, units))); }
+constexpr int kDwTarget = 208, kPwTarget = 48;       // stage 1: workgroups of the depthwise / conv3 units (launch_stage1_t)
 
 template <typename K>
 int allow_big_lds(K kernel, size_t bytes) {
@@ -628,7 +629,7 @@ int launch_stage1_t(const GateBlockArgs &a, hipStream_t s) {
   // staging: the whole launch is one round of the chip, 208 depthwise + 48 conv3 workgroups
   // (measured best split at B = 256; a second round of conv3 blocks cost 3-5 us per launch).
   const int n_dw = (a.C / 16) * 2, n_pw = a.C / 16;
-  const int sl_dw = slices_for(a.n, n_dw, 208), sl_pw = slices_for(a.n, n_pw, 48);
+  const int sl_dw = slices_for(a.n, n_dw, kDwTarget), sl_pw = slices_for(a.n, n_pw, kPwTarget);
   const int dw_blocks = n_dw * sl_dw, pw_blocks = n_pw * sl_pw;
   auto k = gate_stage1_kernel<4, 4, STRIDE, 2, H, HO>;
   TT_TRY(allow_big_lds(k, kTableLds));
@@ -649,6 +650,11 @@ int launch_pf_t(const GateBlockArgs &a, const uint8_t *t_cf, uint16_t *out_cp, u
 }
 
 }  // namespace
+
+int gate_stage1_grid(int C, int n) {
+  const int n_dw = (C / 16) * 2, n_pw = C / 16;
+  return n_dw * slices_for(n, n_dw, kDwTarget) + n_pw * slices_for(n, n_pw, kPwTarget);
+}
 
 int launch_gate_stage1(const GateBlockArgs &a, hipStream_t s) {
   if (a.C % 16 || a.H != a.W || a.Ho != a.Wo || a.kh1 != 4 || a.kw1 != 4 || a.kh2 != 4 || a.kw2 != 4 ||

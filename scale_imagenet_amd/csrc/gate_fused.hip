@@ -519,8 +519,7 @@ int launch_block_t(const FusedBlockArgs &f, hipStream_t s) {
   constexpr int PIX = HO * HO;
   const int strands = f.C / 8;
   int R = fused_round<HO>();
-  int slices = std::max(1, std::min(f.n, 256 / strands));
-  if (strands == 8 && slices > 1 && (slices & 1)) slices -= 1;       // (the pair placement wants an even count)
+  const int slices = fused_block_slices(f.C, f.n);
   R = std::max(1, std::min(R, (f.n + slices - 1) / slices));
   const size_t lds = (size_t)2 * kFBuf + (size_t)R * PIX * 4;
   TT_TRY(ensure_dynamic_lds((const void *)k, kMaxLds));
@@ -535,6 +534,14 @@ int launch_block_t(const FusedBlockArgs &f, hipStream_t s) {
 }  // namespace
 
 int row_bytes(int W) { return W > 32 ? 8 : (W > 16 ? 4 : 2); }
+
+// batch slices per strand: the grid of a block is (C / 8) * slices workgroups (launch_block_t; "gate_grid:<i>" of ttnet_plan_query)
+int fused_block_slices(int C, int n) {
+  const int strands = C / 8;
+  int slices = std::max(1, std::min(n, 256 / strands));
+  if (strands == 8 && slices > 1 && (slices & 1)) slices -= 1;       // (the pair placement wants an even count)
+  return slices;
+}
 
 bool fused_block_supported(int C, int H, int Ho, int stride, int pad, int kh, int kw) {
   if (stride != 2 || pad != 2 || kh != 4 || kw != 4 || C % 16) return false;

@@ -1734,6 +1734,20 @@ int ttnet_plan_query(ttnet_plan *pl, const char *what, int64_t *out) {
     *pl->range_host = 0u;
   }
   else if (w == "lanes") *out = (int64_t)pl->lanes.size();
+  else if (w == "gate_path") *out = (int64_t)pl->path;       // GatePath, in the order include/ttnet.h documents
+  else if (w.rfind("gate_grid:", 0) == 0) {                   // workgroups of block i's first launch at the last forward's batch size
+    char *end = nullptr;
+    const long i = strtol(w.c_str() + 10, &end, 10);
+    const int n = (int)pl->lanes[pl->last_lane].last_n;
+    if (end == w.c_str() + 10 || *end || i < 0 || (size_t)i >= pl->blocks.size() || n <= 0 ||
+        (pl->path != GatePath::Fused && pl->path != GatePath::TwoLaunch)) {
+      set_error("%s: needs a block index below %zu, a forward on the lane used last, and the two-launch or fused path", what,
+                pl->blocks.size());
+      return TTNET_E_INVALID;
+    }
+    const int C = pl->blocks[(size_t)i].C;
+    *out = pl->path == GatePath::Fused ? (int64_t)(C / 8) * fused_block_slices(C, n) : (int64_t)gate_stage1_grid(C, n);
+  }
   else if (w == "full_listed_pw" || w == "full_listed_dw") {      // full variant: (pixel, group) pairs / outputs sent to float64 so far (lane used last)
     uint32_t v[2] = {0, 0};
     const uint32_t *fix = pl->lanes[pl->last_lane].full_fix;

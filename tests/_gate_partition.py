@@ -1,0 +1,303 @@
+"""The batch partition of the gate kernels, restated in plain Python (test infrastructure).
+
+Which image a workgroup handles, in how many rounds and with which table buffer is decided by a few integer
+formulas in scale_imagenet_amd/csrc/gate_fused.hip and gate.hip.  They are restated here so that the batch sizes
+of tests/test_gpu_gate_batches.py are DERIVED from the launch arithmetic (first two-round batch, a last round of
+one image, unequal slices, ...) and tests/test_gate_batch_sizes_cpu.py can assert, without a GPU, that the chosen
+sizes reach every one of those cases.
+
+Drift.  A restatement can fall behind the kernels if their constants change.  Part of it is guarded on the GPU
+side: the sweep asserts that ``ttnet_plan_query("gate_grid:<block>")`` equals ``fused_grid`` / ``stage1_grid`` below
+for every batch size it runs.  On the fused path that query calls fused_block_slices(), the function launch_block_t
+itself calls, so ``fused_slices`` is pinned to the launcher.  On the two-launch path it calls gate_stage1_grid(),
+which sits beside launch_stage1_t in gate.hip and shares its slices_for() and its kDwTarget / kPwTarget, but is a
+second statement of the sum inside the library, not the value the launcher passes to the launch: the guard pins the
+two constants and slices_for(), not the launcher's own line.  NOT guarded at all, and so free to drift unnoticed:
+``PF_TARGET`` (a literal 256 in launch_pf_t), the round length R of ``fused_round`` (inside the kernel; only the
+static_assert ``RMAX * RG * 16 <= kFT`` of gate_block_kernel bounds it), the placement branches of ``fused_owner``
+and the tasks per image of the flat grids (``xs_kernels``, ``VA_KERNELS``).  If one of those changes in the
+kernels, the bit comparison still holds for every size that is run, but a size may stop reaching the case it was
+derived for; whoever changes them updates this file, and tests/test_gate_batch_sizes_cpu.py then says whether the
+sizes still reach every case.
+"""
+from __future__ import annotations
+
+from math import gcd
+from typing import List, NamedTuple, Tuple
+
+# gate_fused.hip: kFT, kFBuf, kFMaxScratch
+FT = 1024
+FBUF = 65536
+MAX_SCRATCH = 160 * 1024 - 2 * FBUF
+# gate.hip: launch_stage1_t (kDwTarget, kPwTarget) and launch_pf_t
+DW_TARGET, PW_TARGET, PF_TARGET = 208, 48, 256
+
+
+class Block(NamedTuple):
+    """One 4-branch block as the launchers see it."""
+    C: int          # input planes
+    H: int          # input size
+    HO: int         # branch output size after padding
+    stride: int
+    last: bool
+
+
+def blocks_of(spec) -> List[Block]:
+    return [Block(b.in_planes, b.in_hw[0], b.out_hw[0], b.stride, b.last) for b in spec.blocks]
+
+
+def fusable(blocks: List[Block]) -> bool:
+    """plan.hip: the fused path needs fused_block_supported() of every block (gate_fused.hip)."""
+    return all(b.stride == 2 and b.C % 16 == 0 and (b.H, b.HO) in ((56, 29), (29, 15), (15, 8), (8, 5)) for b in blocks)
+
+
+# ---- gate_fused.hip ---------------------------------------------------------------------------------------------
+
+def fused_round(HO: int) -> int:
+    """fused_round<HO>(): images per round of a workgroup (8, 16, 32, 32 for HO = 29, 15, 8, 5)."""
+    RG = (HO + 3) // 4
+    a, b = FT // (16 * RG), MAX_SCRATCH // (HO * HO * 4)
+    return min(a, b, 32)
+
+
+def fused_slices(n: int, C: int) -> int:
+    """fused_block_slices(): batch slices per strand; even when there are 8 strands (the pair placement)."""
+    strands = C // 8
+    slices = max(1, min(n, 256 // strands))
+    if strands == 8 and slices > 1 and slices & 1:
+        slices -= 1
+    return slices
+
+
+def fused_R(n: int, C: int, HO: int) -> int:
+    """launch_block_t: R = min(fused_round<HO>(), ceil(n / slices))."""
+    slices = fused_slices(n, C)
+    return max(1, min(fused_round(HO), (n + slices - 1) // slices))
+
+
+def fused_grid(n: int, C: int) -> int:
+    return (C // 8) * fused_slices(n, C)
+
+
+def placement_branch(n: int, C: int) -> str:
+    """gate_block_kernel, "which strand, which images": the branch that maps blockIdx.x to (strand, slice)."""
+    P = C // 8 // 2
+    if P >= 8 and P % 8 == 0:
+        return "pairs8"
+    if P == 4 and fused_slices(n, C) % 2 == 0:
+        return "quad"
+    return "plain"
+
+
+def fused_owner(b: int, n: int, C: int) -> Tuple[int, int]:
+    """(strand, slice) of workgroup b, as gate_block_kernel computes st and sl."""
+    strands, slices = C // 8, fused_slices(n, C)
+    P = strands // 2
+    x, k = b & 7, b >> 3
+    if P >= 8 and P % 8 == 0:
+        m = P // 8
+        pair, kk = x + 8 * (k % m), k // m
+        return 2 * pair + (kk & 1), kk >> 1
+    if P == 4 and slices % 2 == 0:
+        return 2 * (x >> 1) + (k & 1), (x & 1) * (slices // 2) + (k >> 1)
+    return b % strands, b // strands
+
+
+def slice_bounds(sl: int, n: int, slices: int) -> Tuple[int, int]:
+    """n0, n1 of a batch slice (gate_block_kernel; the same formula in gate_stage1_kernel and gate_pf_kernel)."""
+    return sl * n // slices, (sl + 1) * n // slices
+
+
+def fused_rounds(n: int, C: int, HO: int) -> List[Tuple[int, List[int]]]:
+    """Per batch slice (every strand walks the same ones): (n0, [images of round 0, round 1, ...]); the round loop
+    ``for (i0 = 0; i0 < total; i0 += R)`` with rn = min(R, total - i0).  A slice without images has no rounds."""
+    slices, R = fused_slices(n, C), fused_R(n, C, HO)
+    out = []
+    for sl in range(slices):
+        n0, n1 = slice_bounds(sl, n, slices)
+        out.append((n0, [min(R, n1 - n0 - i0) for i0 in range(0, n1 - n0, R)]))
+    return out
+
+
+def fused_locate(image: int, n: int, C: int, HO: int) -> str:
+    """For an assertion message: where image ``image`` of a batch of n sits in the fused kernel's walk."""
+    R = fused_R(n, C, HO)
+    for sl, (n0, rounds) in enumerate(fused_rounds(n, C, HO)):
+        if n0 <= image < n0 + sum(rounds):
+            i = image - n0
+            return f"slice {sl} (images {n0}..{n0 + sum(rounds) - 1}), round {i // R} of {len(rounds)}, position {i % R} of {rounds[i // R]}"
+    return "no slice"
+
+
+# ---- gate.hip ---------------------------------------------------------------------------------------------------
+
+def slices_for(n: int, units: int, target: int) -> int:
+    """slices_for(): batch slices per table set so that ``units`` sets spread over at most ``target`` workgroups."""
+    return max(1, min(n, target // max(1, units)))
+
+
+def stage1_slices(n: int, C: int) -> Tuple[int, int]:
+    """launch_stage1_t: slices of the depthwise units (2 per 16 channels) and of the conv3 units (1 per 16)."""
+    return slices_for(n, (C // 16) * 2, DW_TARGET), slices_for(n, C // 16, PW_TARGET)
+
+
+def stage1_grid(n: int, C: int) -> int:
+    sl_dw, sl_pw = stage1_slices(n, C)
+    return (C // 16) * 2 * sl_dw + (C // 16) * sl_pw
+
+
+def pf_slices(n: int, C: int) -> int:
+    """launch_pf_t: grid (C / 8, slices)."""
+    return slices_for(n, C // 8, PF_TARGET)
+
+
+def slice_sizes(n: int, slices: int) -> List[int]:
+    return [slice_bounds(sl, n, slices)[1] - slice_bounds(sl, n, slices)[0] for sl in range(slices)]
+
+
+# ---- batch sizes, derived ---------------------------------------------------------------------------------------
+
+ALWAYS = (1, 3, 63, 64, 65, 255, 256, 257)     # lin1's 256-row tiles, mid_frag's 64-row tiles, an odd n below every slice count
+
+
+def fused_sizes(blocks: List[Block]) -> List[int]:
+    """Batch sizes for a geometry on the fused path.  Per block, with S its largest slice count and R its round:
+    S * R (the largest single-round batch), S * R + 1 (the first two-round batch: one slice gets R + 1 images, a last
+    round of one, slices unequal), 2 * S * R + 1 (three rounds, the buffer flip at both parities, again a last round
+    of one); 31 where a block has 8 strands (odd n, slice count forced down to 30); and the largest of these plus 13
+    (many slices with three rounds at once).  The last entry is N_max."""
+    sizes = set(ALWAYS)
+    for b in blocks:
+        S, R = fused_slices(1 << 20, b.C), fused_round(b.HO)
+        sizes |= {S * R, S * R + 1, 2 * S * R + 1}
+        if b.C // 8 == 8:
+            sizes.add(31)
+    sizes.add(max(sizes) + 13)
+    return sorted(sizes)
+
+
+def two_launch_sizes(blocks: List[Block], fused_too: bool = False) -> List[int]:
+    """Batch sizes for the two-launch kernels: no round loop, so what varies is the slice count against n.  Per
+    block and per kernel (depthwise, conv3, convf) with S its largest slice count: S and S + 1 (n == slices, and the
+    first unequal partition); 2, 3 and 255..257 lie below and far above every S > 2.  ``fused_too``: the geometry also
+    runs fused (the switch comparison), so the fused sizes are included."""
+    sizes = set(ALWAYS) | {2}
+    for b in blocks:
+        for S in stage1_slices(1 << 20, b.C) + ((pf_slices(1 << 20, b.C),) if not b.last else ()):
+            sizes |= {S, S + 1}
+    if fused_too:
+        sizes |= set(fused_sizes(blocks))
+    return sorted(sizes)
+
+
+# ---- gate_xs.hip, gate_va.hip: flat grids, one thread per task, ceil(n * tasks per image / threads) workgroups -------
+
+class FlatKernel(NamedTuple):
+    name: str
+    per_image: int      # tasks (threads) per image
+    threads: int        # workgroup size
+
+
+def xs_kernels(blocks: List[Block]) -> List[FlatKernel]:
+    """launch_xs_branches: n * (C / 4) * Ho tasks; launch_xs_pf: n * C * Ho; launch_xs_last: n * C * (Ho / 2) * (Wo / 2);
+    128 threads each."""
+    out = []
+    for i, b in enumerate(blocks):
+        out.append(FlatKernel(f"xs_branches[{i}]", (b.C // 4) * b.HO, 128))
+        out.append(FlatKernel("xs_last", b.C * (b.HO // 2) ** 2, 128) if b.last else FlatKernel(f"xs_pf[{i}]", b.C * b.HO, 128))
+    return out
+
+
+# launch_va_block: va_dw n * 64 * 11 and va_c3 n * 88 tasks on 128 threads; launch_va_feat: n * 256 * 121 / 16 on 256
+VA_KERNELS = [FlatKernel("va_dw", 64 * 11, 128), FlatKernel("va_c3", 88, 128), FlatKernel("va_feat", 256 * 121 // 16, 256)]
+
+
+def flat_period(k: FlatKernel) -> int:
+    """The smallest n whose tasks fill whole workgroups; every other multiple of it does too, no other n does."""
+    return k.threads // gcd(k.per_image, k.threads)
+
+
+def flat_last_workgroup(k: FlatKernel, n: int) -> Tuple[int, int]:
+    """(workgroups, active threads of the last one) of kernel k at batch n."""
+    t = n * k.per_image
+    return -(-t // k.threads), (t - 1) % k.threads + 1
+
+
+def flat_sizes(kernels: List[FlatKernel]) -> List[int]:
+    """Batch sizes for flat grids.  Per kernel with period g (flat_period): g and g + 1 (the last workgroup full, and
+    the first partial one after that), and, since g divides the workgroup size, threads - 1, threads and
+    threads + 1 (the same pair far from the start, and the partial workgroup one image short of full)."""
+    sizes = set(ALWAYS) | {2}
+    for k in kernels:
+        g = flat_period(k)
+        sizes |= {g, g + 1, k.threads - 1, k.threads, k.threads + 1}
+    return sorted(sizes)
+
+
+def run_order(sizes: List[int]) -> List[int]:
+    """Smallest, largest, then the rest from both ends towards the middle, then the largest again: up, down and up, so
+    that every size but the first runs on a workspace that a larger batch has written.  (The order shows a WRONG write
+    that depends on earlier contents; a MISSING write is shown by the scrub forward the sweep runs before each size.)"""
+    s = sorted(sizes)
+    if len(s) < 3:
+        return s
+    rest, out = s[1:-1], [s[0], s[-1]]
+    while rest:
+        out.append(rest.pop(0))
+        if rest:
+            out.append(rest.pop())
+    return out + [s[-1]]
+
+
+def edge_images(blocks: List[Block], sizes: List[int]) -> List[int]:
+    """Image indices that fall first / last in a slice and first / last in a round of the fused walk, for the second
+    slice and the last slice with images, at the two- and three-round sizes of every block (the constant images of
+    the sweep are placed there)."""
+    n_max, out = max(sizes), {0, max(sizes) - 1}
+    for b in blocks:
+        S, R = fused_slices(1 << 20, b.C), fused_round(b.HO)
+        for n in (S * R + 1, 2 * S * R + 1, n_max):
+            if n > n_max:
+                continue
+            rounds = [r for r in fused_rounds(n, b.C, b.HO) if r[1]]
+            for n0, rn in (rounds[min(1, len(rounds) - 1)], rounds[-1], max(rounds, key=lambda r: len(r[1]))):
+                i0 = n0
+                for k in rn:
+                    out |= {i0, i0 + k - 1}
+                    i0 += k
+    return sorted(out)
+
+
+def slice_edge_images(blocks: List[Block], sizes: List[int]) -> List[int]:
+    """The same for the two-launch kernels: first and last image of the second and of the last batch slice of every
+    kernel (depthwise, conv3, convf) of every block, at n = S + 1 (the first unequal partition) and at the largest n."""
+    n_max, out = max(sizes), {0, max(sizes) - 1}
+    for b in blocks:
+        for S in stage1_slices(1 << 20, b.C) + ((pf_slices(1 << 20, b.C),) if not b.last else ()):
+            for n in (S + 1, n_max):
+                if n > n_max:
+                    continue
+                sl_n = slices_for(n, 1, S)
+                for sl in {min(1, sl_n - 1), sl_n - 1}:
+                    n0, n1 = slice_bounds(sl, n, sl_n)
+                    out |= {n0, n1 - 1}
+    return sorted(out)
+
+
+def flat_edge_images(kernels: List[FlatKernel], sizes: List[int]) -> List[int]:
+    """For flat grids: the last image before and the first after a workgroup boundary that falls between two images
+    (multiples of flat_period), the first such boundary and the last one below the largest n, per kernel."""
+    n_max, out = max(sizes), {0, max(sizes) - 1}
+    for k in kernels:
+        g = flat_period(k)
+        for m in (g, (n_max - 1) // g * g):
+            if 0 < m < n_max:
+                out |= {m - 1, m}
+    return sorted(out)
+
+
+# ---- the geometries of the sweep: (nfilter, tfilter, --layers) ---------------------------------------------------
+FUSED_ONLY = [(2, 8, 1), (6, 8, 1), (12, 8, 1), (16, 8, 1)]             # TT-small p = 16, 48, 96, 128
+BOTH_PATHS = [(8, 8, 0), (8, 8, 1), (8, 8, 2), (4, 8, 1)]               # p = 64 --layers 0, 1, 2 and p = 32: fused AND two-launch by switch
+TWO_LAUNCH_BY_GEOMETRY = [(8, 8, 3), (8, 8, 4)]                         # stride-1 blocks: never fused
+XSMALL = [(8, 8, 0), (8, 8, 1), (8, 8, 2), (4, 8, 1)]

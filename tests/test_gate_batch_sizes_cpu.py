@@ -1,0 +1,177 @@
+"""The batch sizes of tests/test_gpu_gate_batches.py reach what they are meant to reach (no GPU needed).
+
+The GPU sweep compares bits; whether a given batch size makes a workgroup walk a second round, flip its table buffer at
+both parities or end on a round of one image follows from integer arithmetic alone (tests/_gate_partition.py, a
+restatement of the launchers).  This file asserts it for every geometry and every block of the sweep, so that the sweep
+cannot quietly cover nothing.
+"""
+import numpy as np
+import pytest
+
+import _gate_partition as GP
+from scale_imagenet_amd.spec import make_spec
+
+SWEEP = {k: getattr(GP, k) for k in ("FUSED_ONLY", "BOTH_PATHS", "TWO_LAUNCH_BY_GEOMETRY", "XSMALL")}
+FUSED_GEOMETRIES = [(g, False) for g in SWEEP["FUSED_ONLY"]] + [(g, True) for g in SWEEP["BOTH_PATHS"]]
+
+
+def _blocks(g):
+    return GP.blocks_of(make_spec("small", *g))
+
+
+def _sizes(g, both):
+    blocks = _blocks(g)
+    return GP.two_launch_sizes(blocks, fused_too=True) if both else GP.fused_sizes(blocks)
+
+
+def test_the_issue_geometries_are_all_there():
+    p_layers = lambda gs: sorted((a * b, l) for a, b, l in gs)
+    assert p_layers(SWEEP["FUSED_ONLY"] + SWEEP["BOTH_PATHS"]) == sorted([(64, 0), (64, 1), (64, 2), (16, 1), (32, 1), (48, 1), (96, 1), (128, 1)])
+    assert p_layers(SWEEP["BOTH_PATHS"]) == [(32, 1), (64, 0), (64, 1), (64, 2)]
+    assert p_layers(SWEEP["TWO_LAUNCH_BY_GEOMETRY"]) == [(64, 3), (64, 4)]
+    assert p_layers(SWEEP["XSMALL"]) == [(32, 1), (64, 0), (64, 1), (64, 2)]
+    for g, _ in FUSED_GEOMETRIES:
+        assert GP.fusable(_blocks(g)), g
+    for g in SWEEP["TWO_LAUNCH_BY_GEOMETRY"]:
+        assert not GP.fusable(_blocks(g)), g
+
+
+def test_restated_constants():
+    assert [GP.fused_round(h) for h in (29, 15, 8, 5)] == [8, 16, 32, 32]
+    assert GP.fused_slices(600, 64) == 32 and GP.fused_slices(31, 64) == 30 and GP.fused_slices(1, 64) == 1
+    assert GP.fused_slices(600, 16) == 128 and GP.fused_slices(600, 512) == 4
+    # 600 images at p = 64: 19 per workgroup of the first block, rounds of 8, the last one partial
+    # (test_large_batch_rounds_equal_small_batches)
+    assert GP.fused_rounds(600, 64, 29)[1][1] == [8, 8, 3]
+    assert GP.stage1_slices(600, 64) == (26, 12) and GP.pf_slices(600, 64) == 32
+
+
+@pytest.mark.parametrize("g,both", FUSED_GEOMETRIES)
+def test_fused_sizes_reach_every_case_of_every_block(g, both):
+    sizes = _sizes(g, both)
+    assert {1, 63, 64, 65, 255, 256, 257} <= set(sizes)
+    assert sizes == sorted(set(sizes))
+    for bi, b in enumerate(_blocks(g)):
+        tag = f"p={g[0] * g[1]} --layers {g[2]} block {bi} (C={b.C}, HO={b.HO})"
+        walks = {n: [r for _, r in GP.fused_rounds(n, b.C, b.HO)] for n in sizes}
+        depth = {len(r) for w in walks.values() for r in w}
+        assert {1, 2} <= depth and max(depth) >= 3, f"{tag}: round counts {sorted(depth)}"
+        # a last round of exactly one image after a full round; and the same after two (both parities of the flip)
+        R = GP.fused_round(b.HO)
+        assert any(r == [R, 1] for w in walks.values() for r in w), tag
+        assert any(r == [R, R, 1] for w in walks.values() for r in w), tag
+        # the largest single-round batch: every workgroup holds exactly R images
+        assert any(all(r == [R] for r in w) for w in walks.values()), tag
+        # unequal slices; an odd n below the slice count (one image per workgroup)
+        assert any(len({sum(r) for r in w}) > 1 for w in walks.values()), tag
+        top = GP.fused_slices(1 << 20, b.C)
+        assert any(n % 2 and 1 < n < top for n in sizes), tag
+        if b.C // 8 == 8:                                 # the even-forcing rule: an odd n that loses a slice
+            assert any(n % 2 and GP.fused_slices(n, b.C) == n - 1 for n in sizes), tag
+        # every image belongs to exactly one slice, every (strand, slice) to exactly one workgroup
+        for n in sizes:
+            assert sum(sum(r) for r in walks[n]) == n
+            grid = GP.fused_grid(n, b.C)
+            owners = {GP.fused_owner(w, n, b.C) for w in range(grid)}
+            assert owners == {(st, sl) for st in range(b.C // 8) for sl in range(GP.fused_slices(n, b.C))}, (tag, n)
+
+
+def test_every_placement_branch_and_both_strand_parities_are_reached():
+    seen, strands = set(), set()
+    for g, both in FUSED_GEOMETRIES:
+        for b in _blocks(g):
+            strands.add(b.C // 8)
+            for n in _sizes(g, both):
+                seen.add((GP.placement_branch(n, b.C), len(max((r for _, r in GP.fused_rounds(n, b.C, b.HO)), key=len)) > 1))
+    # each branch, with and without a second round
+    assert seen == {(br, multi) for br in ("pairs8", "quad", "plain") for multi in (False, True)}
+    assert any((s // 2) % 2 for s in strands) and any((s // 2) % 2 == 0 for s in strands)      # odd and even pair counts
+    assert 8 in strands                                   # the even-forcing rule applies somewhere
+
+
+@pytest.mark.parametrize("g,both", [(g, False) for g in SWEEP["TWO_LAUNCH_BY_GEOMETRY"]] + [(g, True) for g in SWEEP["BOTH_PATHS"]])
+def test_two_launch_sizes_reach_every_slice_case(g, both):
+    blocks = _blocks(g)
+    sizes = GP.two_launch_sizes(blocks, fused_too=both)
+    assert {1, 63, 64, 65, 255, 256, 257} <= set(sizes)
+    for bi, b in enumerate(blocks):
+        kernels = dict(zip(("depthwise", "conv3"), ((lambda n, C=b.C: GP.stage1_slices(n, C)[0]), (lambda n, C=b.C: GP.stage1_slices(n, C)[1]))))
+        if not b.last:
+            kernels["convf"] = lambda n, C=b.C: GP.pf_slices(n, C)
+        for name, fn in kernels.items():
+            tag = f"p={g[0] * g[1]} --layers {g[2]} block {bi} {name}"
+            top = fn(1 << 20)
+            if top == 1:                                  # (one slice at every n: nothing to partition)
+                continue
+            assert any(n < top for n in sizes if n > 1) or top <= 2, tag     # one image per workgroup, fewer workgroups than the target
+            assert top in sizes and top + 1 in sizes, tag                   # n == slices, and the first unequal partition
+            assert any(len(set(GP.slice_sizes(n, fn(n)))) > 1 for n in sizes), tag
+            assert any(min(GP.slice_sizes(n, fn(n))) >= 2 for n in sizes), tag
+            for n in sizes:
+                assert sum(GP.slice_sizes(n, fn(n))) == n
+
+
+def test_run_order_goes_up_down_and_up():
+    for g, both in FUSED_GEOMETRIES:
+        sizes = _sizes(g, both)
+        order = GP.run_order(sizes)
+        assert set(order) == set(sizes) and order[0] == min(sizes) and order[1] == order[-1] == max(sizes)
+        steps = np.sign(np.diff(order))
+        assert (steps > 0).any() and (steps < 0).any() and steps[0] > 0 and steps[1] < 0 and steps[-1] > 0
+    flat = GP.flat_sizes(GP.VA_KERNELS)
+    assert GP.run_order(flat)[1] == max(flat)
+
+
+def _flat_geometries():
+    out = [(f"xsmall p={g[0] * g[1]} --layers {g[2]}", GP.xs_kernels(GP.blocks_of(make_spec("xsmall", *g)))) for g in SWEEP["XSMALL"]]
+    return out + [("valexnet", GP.VA_KERNELS)]
+
+
+@pytest.mark.parametrize("tag,kernels", _flat_geometries(), ids=[t for t, _ in _flat_geometries()])
+def test_flat_sizes_reach_full_and_partial_last_workgroups(tag, kernels):
+    sizes = GP.flat_sizes(kernels)
+    assert {1, 63, 64, 65, 255, 256, 257} <= set(sizes)
+    assert any(GP.flat_period(k) > 1 for k in kernels), tag
+    edges = GP.flat_edge_images(kernels, sizes)
+    for k in kernels:
+        last = {n: GP.flat_last_workgroup(k, n) for n in sizes}
+        g = GP.flat_period(k)
+        assert k.threads % g == 0, (tag, k)
+        if g == 1:                                        # (a whole number of workgroups per image: no n leaves a partial one)
+            assert all(act == k.threads for _, act in last.values())
+            continue
+        # several workgroups with the last one full; and with the last one partial, right after a full one
+        assert any(wg > 1 and act == k.threads for wg, act in last.values()), (tag, k)
+        assert any(wg > 1 and act < k.threads and last.get(n - 1, (0, 0))[1] == k.threads for n, (wg, act) in last.items()), (tag, k)
+        assert {g - 1, g} <= set(edges), (tag, k)
+
+
+@pytest.mark.parametrize("g,both", [(g, False) for g in SWEEP["TWO_LAUNCH_BY_GEOMETRY"]] + [(g, True) for g in SWEEP["BOTH_PATHS"]])
+def test_constant_images_sit_on_two_launch_slice_edges(g, both):
+    blocks = _blocks(g)
+    sizes = GP.two_launch_sizes(blocks, fused_too=both)
+    edges = set(GP.slice_edge_images(blocks, sizes))
+    assert 0 in edges and max(sizes) - 1 in edges and len(edges) < max(sizes) // 4
+    for b in blocks:
+        for S in GP.stage1_slices(1 << 20, b.C) + (() if b.last else (GP.pf_slices(1 << 20, b.C),)):
+            if S < 2:
+                continue
+            # n = S + 1: the one slice of two images, and the last slice
+            sz = GP.slice_sizes(S + 1, S)
+            two = sz.index(2)
+            n0 = sum(sz[:two])
+            assert sorted(sz) == [1] * (S - 1) + [2] and S in edges and ({n0, n0 + 1} <= edges or two not in (1, S - 1))
+
+
+@pytest.mark.parametrize("g,both", FUSED_GEOMETRIES)
+def test_constant_images_sit_on_slice_and_round_edges(g, both):
+    blocks, sizes = _blocks(g), _sizes(g, both)
+    edges = GP.edge_images(blocks, sizes)
+    assert 0 in edges and max(sizes) - 1 in edges and len(edges) < max(sizes) // 4
+    for b in blocks:
+        S, R = GP.fused_slices(1 << 20, b.C), GP.fused_round(b.HO)
+        n = 2 * S * R + 1
+        n0, rounds = max(GP.fused_rounds(n, b.C, b.HO), key=lambda r: len(r[1]))
+        assert rounds == [R, R, 1]
+        # first and last image of each of the three rounds of that workgroup
+        assert {n0, n0 + R - 1, n0 + R, n0 + 2 * R - 1, n0 + 2 * R} <= set(edges)

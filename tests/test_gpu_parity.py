@@ -14,14 +14,14 @@ import torch
 
 import json
 
-from _util import GOLD, args_for, golden_json, golden_npz, sha, spec_and_state
+from _util import GOLD, LOGIT_TOL, args_for, golden_json, golden_npz, scaled_tol, sha, spec_and_state
 from oracle import ttnet_bits as OB
 from oracle import ttnet_float as OF
 from scale_imagenet_amd import _lib, synth, ttnet
 
 pytestmark = pytest.mark.gpu
 
-LOGIT_TOL = 1e-5          # the north star's bound; the only absolute logit tolerance in this file
+# LOGIT_TOL (tests/_util.py) is the north star's bound and the only absolute logit tolerance in this file.
 # The reference's own float32 head is not exact: tests/golden/ref_spread.json (written by
 # oracle/gen_golden.py from the imported reference) records, per variant, how far its committed
 # logits sit from the float64 evaluation of the same head on its own features (ref_vs_exact:
@@ -76,13 +76,6 @@ def model(variant, dev):
 @pytest.fixture(scope="module")
 def small_model(dev):
     return _model("small", dev)
-
-
-def scaled_tol(ref):
-    """1e-5 is stated for logits of the reference's scale (|logit| <= ~3 on the golden images).  Inputs
-    far from the calibration set (random stem bits, uncalibrated heads) give logits k times larger,
-    where float32 itself no longer resolves 1e-5 (an ulp at 64 is 7.6e-6): the bound scales with k."""
-    return LOGIT_TOL * max(1.0, float(np.abs(ref).max()) / 4.0)
 
 
 @pytest.fixture(scope="module")
