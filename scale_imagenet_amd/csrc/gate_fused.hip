@@ -71,7 +71,7 @@ struct FusedArgs {
   int n, C, slices, off34, R;
   const void *x;              // rows [n][C][H]
   const uint8_t *img_c3;      // [C/8][65536]: Block_conv3 of the strand's group, own 8 output bits
-  const uint8_t *img_dw;      // [C/8][2][2048][4][2] dwords: conv1 / conv2 bit tables of 4 channels, interleaved
+  const uint8_t *img_dw;      // [C/8][2][4096][4] dwords: conv1 / conv2 bits of 16 indices of a channel (dw_image_kernel)
   const uint8_t *t_cf;        // [C/4][65536] bytes (binarised Block_convf); unused by a last block
   void *y;                    // rows [n][2C][HO] (binarised blocks)
   uint32_t *idx;              // [n][C/8][HO*HO] branch dwords: the output of a last block; optional tap otherwise
@@ -94,6 +94,14 @@ __device__ inline void phase_sync() {
   __syncthreads();
 }
 
+// Table reads by LDS byte address.  The two table buffers are the first 128 KiB of the kernel's only (dynamic)
+// LDS array, so a buffer's address has its low 16 bits clear (checked once at kernel entry) and a 16-bit index
+// joins it by OR inside the instruction that masks or moves the index: no separate address add per read.
+typedef const __attribute__((address_space(3))) uint8_t *lds_bytes_t;
+__device__ inline uint32_t lds_addr(const void *p) { return (uint32_t)(uintptr_t)(lds_bytes_t)p; }
+__device__ inline uint32_t lds_read_u8(uint32_t addr) { return *(lds_bytes_t)(uintptr_t)addr; }
+__device__ inline uint32_t lds_read_u32(uint32_t addr) { return *(const __attribute__((address_space(3))) uint32_t *)(uintptr_t)addr; }
+
 __device__ inline uint32_t spread_nibbles(uint32_t x) {      // nibbles 0..3 of x -> low nibbles of bytes 0..3
   uint32_t y = (x | (x << 8)) & 0x00FF00FFu;
   return (y | (y << 4)) & 0x0F0F0F0Fu;
@@ -106,45 +114,51 @@ __device__ inline uint32_t spread_nibbles(uint32_t x) {      // nibbles 0..3 of 
 //     t0 = bfi(0x0F0F0F0F, R0, R1 << 4)   bytes j = [R1.nib(2j) : R0.nib(2j)]
 //     t1 = bfi(0x0F0F0F0F, R0 >> 4, R1)   bytes j = [R1.nib(2j+1) : R0.nib(2j+1)]
 // (likewise u0, u1 from R2, R3) and one byte permute joins a t byte and a u byte into a complete
-// 16-bit index, two per dword: 12 instructions for 8 indices.  A lookup is one 8-byte LDS read (the
-// conv1 and conv2 dwords of the channel sit side by side), a bit-field extract whose offset is the low
-// 5 bits of the index register as it stands, and a shift-or into the output row.
+// 16-bit index, two per dword: 12 instructions for 8 indices.  A lookup is one 4-byte LDS read: the
+// dword of (index >> 4, channel) holds the conv1 bit of index i at position i & 31 and its conv2 bit
+// 16 positions further round the word (dw_image_kernel), so ONE rotate by the index register, less the
+// output column, puts both bits where the packed accumulator wants them (conv1 in the low half, conv2
+// in the high half, column c at bit c & 15), and one and-or merges them.  The column is taken off both
+// indices of a pair by one packed 16-bit subtract (the rotate reads the low 5 bits only).
+typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
+
 template <int WO, int OX0, int OX1>
-__device__ inline void dw_lookup_pair(uint32_t pair, const uint8_t *tab, uint32_t c8, uint32_t &acc1, uint32_t &acc2) {
+__device__ inline void dw_lookup_pair(uint32_t pair, uint32_t base, uint32_t &acc) {
+  constexpr uint32_t P0 = OX0 & 15, P1 = OX1 & 15;
+  const uint32_t adj = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, pair) - __builtin_bit_cast(u16x2, P0 | (P1 << 16)));
   if constexpr (OX0 < WO) {
-    const uint2 w = *(const uint2 *)(tab + ((pair & 0xFFE0u) | c8));
-    acc1 |= __builtin_amdgcn_ubfe(w.x, pair, 1) << OX0;
-    acc2 |= __builtin_amdgcn_ubfe(w.y, pair, 1) << OX0;
+    const uint32_t w = lds_read_u32((pair & 0xFFF0u) | base);
+    acc |= __builtin_amdgcn_alignbit(w, w, adj) & (0x00010001u << P0);
   }
   if constexpr (OX1 < WO) {
-    const uint32_t hi = pair >> 16;
-    const uint2 w = *(const uint2 *)(tab + ((hi & 0xFFE0u) | c8));
-    acc1 |= __builtin_amdgcn_ubfe(w.x, hi, 1) << OX1;
-    acc2 |= __builtin_amdgcn_ubfe(w.y, hi, 1) << OX1;
+    const uint32_t w = lds_read_u32(((pair >> 16) & 0xFFF0u) | base);
+    acc |= __builtin_amdgcn_alignbit(w, w, adj >> 16) & (0x00010001u << P1);
   }
 }
 
-// eight nibble positions of four rows; nibble k is output column OXB + OXS * k
+// eight nibble positions of four rows; nibble k is output column OXB + OXS * k (all in one 16-column half)
 template <int WO, int OXB, int OXS>
-__device__ inline void dw_eight(uint32_t R0, uint32_t R1, uint32_t R2, uint32_t R3, const uint8_t *tab, uint32_t c8,
-                                uint32_t &acc1, uint32_t &acc2) {
+__device__ inline void dw_eight(uint32_t R0, uint32_t R1, uint32_t R2, uint32_t R3, uint32_t base, uint32_t &acc) {
   if constexpr (OXB >= WO) return;
+  static_assert((OXB >> 4) == ((OXB + 7 * OXS) >> 4), "one accumulator per 16 columns");
   constexpr uint32_t M = 0x0F0F0F0Fu;
   const uint32_t t0 = (R0 & M) | ((R1 << 4) & ~M), u0 = (R2 & M) | ((R3 << 4) & ~M);
-  dw_lookup_pair<WO, OXB, OXB + 2 * OXS>(__builtin_amdgcn_perm(u0, t0, 0x05010400u), tab, c8, acc1, acc2);
-  dw_lookup_pair<WO, OXB + 4 * OXS, OXB + 6 * OXS>(__builtin_amdgcn_perm(u0, t0, 0x07030602u), tab, c8, acc1, acc2);
+  dw_lookup_pair<WO, OXB, OXB + 2 * OXS>(__builtin_amdgcn_perm(u0, t0, 0x05010400u), base, acc);
+  dw_lookup_pair<WO, OXB + 4 * OXS, OXB + 6 * OXS>(__builtin_amdgcn_perm(u0, t0, 0x07030602u), base, acc);
   if constexpr (OXB + OXS < WO) {
     const uint32_t t1 = ((R0 >> 4) & M) | (R1 & ~M), u1 = ((R2 >> 4) & M) | (R3 & ~M);
-    dw_lookup_pair<WO, OXB + OXS, OXB + 3 * OXS>(__builtin_amdgcn_perm(u1, t1, 0x05010400u), tab, c8, acc1, acc2);
-    dw_lookup_pair<WO, OXB + 5 * OXS, OXB + 7 * OXS>(__builtin_amdgcn_perm(u1, t1, 0x07030602u), tab, c8, acc1, acc2);
+    dw_lookup_pair<WO, OXB + OXS, OXB + 3 * OXS>(__builtin_amdgcn_perm(u1, t1, 0x05010400u), base, acc);
+    dw_lookup_pair<WO, OXB + 5 * OXS, OXB + 7 * OXS>(__builtin_amdgcn_perm(u1, t1, 0x07030602u), base, acc);
   }
 }
 
-// one output row (all WO columns) of conv1 and conv2 for one channel, from its four window rows
+// one output row (all WO columns) of conv1 and conv2 for one channel, from its four window rows: accl = columns
+// 0..15, acch = columns 16..31 (W > 32 only), conv1 in the low and conv2 in the high 16 bits of each.
+// base = LDS address of the table | 4 * (channel & 3)
 template <int W, int WO>
-__device__ inline void dw_row_both(const row_t<W> (&r)[4], const uint8_t *tab, uint32_t c8, uint32_t &acc1, uint32_t &acc2) {
-  acc1 = 0;
-  acc2 = 0;
+__device__ inline void dw_row_both(const row_t<W> (&r)[4], uint32_t base, uint32_t &accl, uint32_t &acch) {
+  accl = 0;
+  acch = 0;
   if constexpr (W > 32) {
     uint32_t plo[4], phi[4], qlo[4], qhi[4];
 #pragma unroll
@@ -154,10 +168,10 @@ __device__ inline void dw_row_both(const row_t<W> (&r)[4], const uint8_t *tab, u
       plo[k] = qlo[k] << 2;
       phi[k] = __builtin_amdgcn_alignbit(qhi[k], qlo[k], 30);
     }
-    dw_eight<WO, 0, 2>(plo[0], plo[1], plo[2], plo[3], tab, c8, acc1, acc2);      // even columns 0..14
-    dw_eight<WO, 16, 2>(phi[0], phi[1], phi[2], phi[3], tab, c8, acc1, acc2);     // even columns 16..30
-    dw_eight<WO, 1, 2>(qlo[0], qlo[1], qlo[2], qlo[3], tab, c8, acc1, acc2);      // odd columns 1..15
-    dw_eight<WO, 17, 2>(qhi[0], qhi[1], qhi[2], qhi[3], tab, c8, acc1, acc2);     // odd columns 17..31
+    dw_eight<WO, 0, 2>(plo[0], plo[1], plo[2], plo[3], base, accl);      // even columns 0..14
+    dw_eight<WO, 16, 2>(phi[0], phi[1], phi[2], phi[3], base, acch);     // even columns 16..30
+    dw_eight<WO, 1, 2>(qlo[0], qlo[1], qlo[2], qlo[3], base, accl);      // odd columns 1..15
+    dw_eight<WO, 17, 2>(qhi[0], qhi[1], qhi[2], qhi[3], base, acch);     // odd columns 17..31
   } else {
     uint32_t p[4], q[4];
 #pragma unroll
@@ -165,8 +179,8 @@ __device__ inline void dw_row_both(const row_t<W> (&r)[4], const uint8_t *tab, u
       q[k] = (uint32_t)r[k];
       p[k] = q[k] << 2;
     }
-    dw_eight<WO, 0, 2>(p[0], p[1], p[2], p[3], tab, c8, acc1, acc2);
-    dw_eight<WO, 1, 2>(q[0], q[1], q[2], q[3], tab, c8, acc1, acc2);
+    dw_eight<WO, 0, 2>(p[0], p[1], p[2], p[3], base, accl);
+    dw_eight<WO, 1, 2>(q[0], q[1], q[2], q[3], base, accl);
     static_assert(WO <= 16, "a 32-bit input row gives at most 16 output columns");
   }
 }
@@ -188,6 +202,7 @@ __global__ __launch_bounds__(kFT) void gate_block_kernel(FusedArgs a) {
   using TOut = row_t<WO>;
   uint8_t *const buf0 = lds, *const buf1 = lds + kFBuf;
   uint32_t *const S = (uint32_t *)(lds + 2 * kFBuf);   // [R][PIX] branch dwords
+  if (lds_addr(lds) & (kFBuf - 1)) __builtin_trap();   // (never: a kernel without static LDS has its dynamic array at 0)
 
   // ---- which strand, which images (placement: see the file header) ----------------------------
   const int strands = a.C / 8, P = strands / 2;
@@ -273,6 +288,7 @@ __global__ __launch_bounds__(kFT) void gate_block_kernel(FusedArgs a) {
       *(uint16_t *)((uint8_t *)(S + im * PIX + pix) + 2) = 0;
     }
     const int g = tid >> 4, j = tid & 15;
+    const uint32_t tb = lds_addr(tab);
     // Four transposes at a time (their LDS round trips overlap): the two rows x two 32-pixel chunks of a
     // task at W = 56, the two rows of two tasks otherwise.  Unit u of a batch = one (task, chunk).
     constexpr int CHUNKS = W > 32 ? 2 : 1, TPB = 2 / CHUNKS;          // tasks per batch
@@ -293,7 +309,8 @@ __global__ __launch_bounds__(kFT) void gate_block_kernel(FusedArgs a) {
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const uint32_t t0 = d[2 * u], t1 = d[2 * u + 1];
-        const uint32_t e00 = tab[t0 & 0xFFFFu], e01 = tab[t0 >> 16], e10 = tab[t1 & 0xFFFFu], e11 = tab[t1 >> 16];
+        const uint32_t e00 = lds_read_u8((t0 & 0xFFFFu) | tb), e01 = lds_read_u8(__builtin_amdgcn_alignbit(tb >> 16, t0, 16));
+        const uint32_t e10 = lds_read_u8((t1 & 0xFFFFu) | tb), e11 = lds_read_u8(__builtin_amdgcn_alignbit(tb >> 16, t1, 16));
         v3[u] = e00 | (e10 << 8) | (e01 << 16) | (e11 << 24);                                 // conv3: rows x halves
         v4[u] = __builtin_amdgcn_perm(t1, t0, half ? 0x07030501u : 0x06020400u);              // raw input, own byte
       }
@@ -334,7 +351,7 @@ __global__ __launch_bounds__(kFT) void gate_block_kernel(FusedArgs a) {
   auto phase_b_lookup = [&](const uint8_t *tab, int sub, const TI (&rb)[4]) {
     if constexpr (kSkip & 4) return;
     const int tid = opaque_tid();
-    dw_row_both<W, WO>(rb, tab, (uint32_t)(tid & 3) * 8u, bacc[sub][0], bacc[sub][1]);
+    dw_row_both<W, WO>(rb, lds_addr(tab) | (uint32_t)(tid & 3) * 4u, bacc[sub][0], bacc[sub][1]);
   };
   auto phase_b_store = [&](int rn) {
     if constexpr (kSkip & 4) return;
@@ -342,9 +359,16 @@ __global__ __launch_bounds__(kFT) void gate_block_kernel(FusedArgs a) {
     const int j = tid & 15, gi = tid >> 4;
     const int im = gi / RG, rg = gi - im * RG;
     // 16-lane group = 4 channels x 4 output rows (lane = c + 4 r).  Transposed: lane j holds, for
-    // columns j (low half) and 16 + j (high half), nibble r = the 4 channels of output row 4 rg + r
-    uint32_t t[4] = {bacc[0][0], bacc[0][1], bacc[1][0], bacc[1][1]};
-    transpose16_multi<4>(t, lk);
+    // column 16 h + j, nibble r of each half = the 4 channels of output row 4 rg + r
+    // (bacc[sub][h]: columns 16 h .. 16 h + 15 of channels 4 sub .. 4 sub + 3, out1 in the low half, out2 in the high half)
+    constexpr int NT = WO > 16 ? 4 : 2;
+    uint32_t t[NT];
+    if constexpr (WO > 16) {
+      t[0] = bacc[0][0]; t[1] = bacc[1][0]; t[2] = bacc[0][1]; t[3] = bacc[1][1];
+    } else {
+      t[0] = bacc[0][0]; t[1] = bacc[1][0];
+    }
+    transpose16_multi<NT>(t, lk);
     uint8_t *dst = (uint8_t *)(S + im * PIX + 4 * rg * WO + j);
     auto put = [&](uint32_t w0, uint32_t w1, int col0) {      // w0 / w1: byte r = (out1 | out2 << 4) of channels 0-3 / 4-7
       if (im < rn && col0 + j < WO) {
@@ -355,10 +379,9 @@ __global__ __launch_bounds__(kFT) void gate_block_kernel(FusedArgs a) {
         if (4 * rg + 3 < HO) *(uint16_t *)(dst + (3 * WO + col0) * 4) = (uint16_t)(hi >> 16);
       }
     };
-    put(spread_nibbles(t[0] & 0xFFFFu) | (spread_nibbles(t[1] & 0xFFFFu) << 4),
-        spread_nibbles(t[2] & 0xFFFFu) | (spread_nibbles(t[3] & 0xFFFFu) << 4), 0);
+    put(spread_nibbles(t[0] & 0xFFFFu) | (spread_nibbles(t[0] >> 16) << 4), spread_nibbles(t[1] & 0xFFFFu) | (spread_nibbles(t[1] >> 16) << 4), 0);
     if constexpr (WO > 16)
-      put(spread_nibbles(t[0] >> 16) | (spread_nibbles(t[1] >> 16) << 4), spread_nibbles(t[2] >> 16) | (spread_nibbles(t[3] >> 16) << 4), 16);
+      put(spread_nibbles(t[2] & 0xFFFFu) | (spread_nibbles(t[2] >> 16) << 4), spread_nibbles(t[3] & 0xFFFFu) | (spread_nibbles(t[3] >> 16) << 4), 16);
   };
 
   // ---- phases C1 / C2: Block_convf group 2s + k -> output channels 16 s + 8 k .. + 7, as rows -----------------
@@ -373,7 +396,8 @@ __global__ __launch_bounds__(kFT) void gate_block_kernel(FusedArgs a) {
     TOut *const y = (TOut *)a.y;
     constexpr int CH2 = (HO + 2 * RPW - 1) / (2 * RPW);       // wave tasks per image (2 RPW rows each)
     constexpr int U = 2, NW = kFT / 64;                       // wave tasks per trip
-    const uint32_t sel = kgrp ? 0x0C0C0301u : 0x0C0C0200u;    // index of group k: bytes (k, 2 + k) of the branch dword
+    const uint32_t sel = kgrp ? 0x05040301u : 0x05040200u;    // index of group k: bytes (k, 2 + k) of the branch dword, under the table's address
+    const uint32_t tbh = lds_addr(tab) >> 16;
     if (kgrp == 0 && a.idx)                                   // parity tap: the branch dwords as the lookups see them
       for (int t = tid; t < rn * PIX; t += kFT) a.idx[((size_t)(n0 + i0 + t / PIX) * strands + st) * PIX + (t % PIX)] = S[t];
     for (int wt0 = wave; wt0 < rn * CH2; wt0 += U * NW) {
@@ -390,7 +414,7 @@ __global__ __launch_bounds__(kFT) void gate_block_kernel(FusedArgs a) {
       }
 #pragma unroll
       for (int u = 0; u < U; ++u)
-        w[u] = ox < WO ? (uint32_t)tab[__builtin_amdgcn_perm(0u, d0[u], sel)] | ((uint32_t)tab[__builtin_amdgcn_perm(0u, d1[u], sel)] << 8)
+        w[u] = ox < WO ? lds_read_u8(__builtin_amdgcn_perm(tbh, d0[u], sel)) | (lds_read_u8(__builtin_amdgcn_perm(tbh, d1[u], sel)) << 8)
                        : 0u;                                  // (pixels beyond the row stay zero: the next block's padding)
       // lane = pixel, bit = (row, channel) -> lane 8 q + j = channel j of row q, bit = pixel of the 16-lane group
       transpose16_multi<U>(w, lk);
@@ -478,14 +502,16 @@ __global__ void c3_image_kernel(const uint16_t *__restrict__ t_c3, uint8_t *__re
   const uint32_t idx = (uint32_t)(t & 0xFFFF);
   img[t] = (uint8_t)(t_c3[(size_t)(st >> 1) * 65536 + idx] >> (8 * (st & 1)));
 }
-// img_dw[strand][sub][row][ch][branch] (dwords) from the striped bit tables [C/16][2048][16]
+// img_dw[strand][sub][index >> 4][ch] (dwords) from the striped bit tables [C/16][2048][16]: bit (i & 31) of the dword
+// = conv1 of index i, bit ((i + 16) & 31) = conv2 of index i, for the 16 indices i that share i >> 4
 __global__ void dw_image_kernel(const uint32_t *__restrict__ t1, const uint32_t *__restrict__ t2, uint32_t *__restrict__ img, int C) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;       // one dword of the image
   if (t >= (size_t)C * 2048 * 2) return;
-  const int br = (int)(t & 1), ch = (int)((t >> 1) & 3), row = (int)((t >> 3) & 2047), ss = (int)(t >> 14);   // ss = 2 strand + sub
-  const int channel = 4 * ss + ch;
-  const uint32_t *src = br ? t2 : t1;
-  img[t] = src[((size_t)(channel >> 4) * 2048 + row) * 16 + (channel & 15)];
+  const int ch = (int)(t & 3), d = (int)((t >> 2) & 4095), ss = (int)(t >> 14);   // ss = 2 strand + sub
+  const int channel = 4 * ss + ch, row = d >> 1, up = d & 1;                      // up: index bit 4
+  const size_t src = ((size_t)(channel >> 4) * 2048 + row) * 16 + (channel & 15);
+  const uint32_t h1 = (t1[src] >> (16 * up)) & 0xFFFFu, h2 = (t2[src] >> (16 * up)) & 0xFFFFu;
+  img[t] = up ? (h1 << 16) | h2 : h1 | (h2 << 16);
 }
 
 // ---- parity taps ------------------------------------------------------------------------------------------

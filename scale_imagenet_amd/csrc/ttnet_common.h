@@ -108,7 +108,7 @@ __device__ inline uint32_t transpose16(uint32_t acc, const DwLaneConst &k) {
     constexpr int I = decltype(i)::value;
     const uint32_t partner = (uint32_t)__builtin_amdgcn_ds_swizzle((int)acc, 0x1F | (S[I] << 10));
     const uint32_t moved = __builtin_amdgcn_alignbit(partner, partner, k.rot[I]);
-    acc = moved ^ ((moved ^ acc) & k.keep[I]);            // keep ? acc : moved, one v_bitop3_b32
+    acc = __builtin_amdgcn_bitop3_b32(k.keep[I], acc, moved, 0xCA);      // keep ? acc : moved, one v_bitop3_b32
   });
   return acc;
 }
@@ -137,7 +137,7 @@ __device__ inline void transpose16_multi(uint32_t (&acc)[N], const DwLaneConst &
 #pragma unroll
     for (int n = 0; n < N; ++n) {
       const uint32_t moved = __builtin_amdgcn_alignbit(partner[n], partner[n], k.rot[I]);
-      acc[n] = moved ^ ((moved ^ acc[n]) & k.keep[I]);
+      acc[n] = __builtin_amdgcn_bitop3_b32(k.keep[I], acc[n], moved, 0xCA);      // keep ? acc : moved (written with ^ and & it compiles to two instructions)
     }
   });
 }
