@@ -407,6 +407,42 @@ int ttnet_plan_table_usage_reset(ttnet_plan *plan, void *stream);
 int ttnet_table_usage_add(ttnet_plan *plan, int lane, void *stream);
 int ttnet_plan_get_table_usage(ttnet_plan *plan, const char *name, int64_t *dst_host, size_t dst_bytes);
 
+/* Two-level minimisation of truth tables with don't-cares, on the device: a PRIME and IRREDUNDANT cover of every
+ * function of a batch (every cube is a prime implicant of ON u DC, no cube can be removed).  It is not a minimum cover.
+ *
+ * A function of n_bits inputs (1..16) is two bitmaps over its 2^n patterns, indexed in the canonical order of
+ * ttnet_plan_get_table (variable x_j is index bit n-1-j): `on`, where it must be 1, and `dc`, where it may take either
+ * value (a pattern in both counts as ON); OFF is the rest.  A cube is (mask, value): mask = the n-bit set of index bits
+ * that carry a literal, value & ~mask == 0, packed as the uint32 key mask << 16 | value; it holds the patterns p with
+ * p & mask == value.  The cover is defined by four steps, which the device code and scale_imagenet_amd.minimise's CPU
+ * twin both follow, so that they give the same keys in the same order:
+ *   1 expand       for every ON minterm m on its own: start from the cube with all n literals of m; for j = 0 .. n-1 in
+ *                  that order drop the literal of x_j iff the sibling half (the current cube with x_j complemented)
+ *                  holds no OFF pattern.  One pass leaves a prime: a cube only grows, so a refused drop stays refused.
+ *   2 order        the candidates by number of free variables, descending, then by generating minterm, ascending.
+ *   3 cover        walk that order; keep a cube iff it holds an ON minterm that no kept cube holds yet (duplicates drop
+ *                  out by themselves).
+ *   4 irredundant  walk the kept cubes in reverse; remove a cube iff every ON minterm in it also lies in another cube
+ *                  that is still kept.
+ * The output is the surviving cubes in the order of step 2.  An empty ON set gives no cube (constant 0); otherwise an
+ * empty OFF set gives the one cube with the empty mask, key 0 (constant 1).  The CNF of a function is the same
+ * procedure on on' = ~on & ~dc with the same dc, read by De Morgan: every cube becomes a clause of complemented literals.
+ *
+ * on_dev / dc_dev: uint32 [n_funcs][max(1, 2^n / 32)], bit i%32 of word i/32 is pattern i (unused high bits zero);
+ * dc_dev may be NULL (no don't-cares).  cubes_dev: uint32 [n_funcs][cube_cap] keys; counts_dev: int32 [n_funcs], the
+ * TRUE number of cubes of each cover.  The cap rule: cubes past cube_cap are not written, the caller sees
+ * counts > cube_cap and calls again; a cap >= the function's ON count never overflows; cube_cap 0 asks for the counts
+ * alone.  work_dev / work_bytes: scratch, at least ttnet_minimise_workspace(n_bits, n_funcs) bytes (8 * 2^n bytes,
+ * rounded up to 256, for each of min(n_funcs, 1024) workgroups), 16-byte aligned; the other buffers 4-byte aligned.
+ * One launch on `stream`: no plan, no host synchronisation, no allocation, capturable in a graph; integers only, so the
+ * same input gives the same bytes.  TTNET_E_INVALID (nothing launched) for a NULL pointer other than dc_dev, n_bits
+ * outside 1..16, n_funcs < 1, cube_cap < 0, a misaligned buffer or a workspace that is too small;
+ * ttnet_minimise_workspace returns TTNET_E_INVALID for arguments outside those ranges. */
+int64_t ttnet_minimise_workspace(int n_bits, int64_t n_funcs);
+int ttnet_minimise_covers(const uint32_t *on_dev, const uint32_t *dc_dev, int n_bits, int64_t n_funcs,
+                          uint32_t *cubes_dev, int64_t cube_cap, int32_t *counts_dev,
+                          void *work_dev, int64_t work_bytes, void *stream);
+
 /* Integer facts about the plan: "fcsize", "n_classes", "n_state_tensors", "max_batch",
  * "near_ties:<block_tt name>" (entries with |pre-activation| < 1e-5 found while building
  * that table), "table_bytes", "usage_bytes", "workspace_bytes", "graph_replays" (forwards replayed from a

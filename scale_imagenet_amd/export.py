@@ -22,6 +22,12 @@ minimisation: it goes to ``SOPform`` / ``POSform`` as ``dontcares``, so the expr
 pattern seen and are free elsewhere, which makes them smaller.  The CSV gains a ``count`` column, and a filter that is
 constant on the patterns seen is written as that constant.  ``dnf_literals`` / ``cnf_literals`` of the returned record
 are the literal counts of the two forms, to report the saving.  With ``usage=None`` every file is what it was.
+
+Minimiser: ``minimiser="sympy"`` (the default) is the path above and writes what it always wrote.  ``"device"`` and ``"cpu"``
+take the expressions from ``scale_imagenet_amd.minimise`` instead -- the HIP kernel, or its numpy twin -- for every
+n <= 16, so the 16-input tables of TT-small get their DNF / CNF / SAT-form files too; ``export_block`` minimises all its
+filters, both forms, in ONE device call.  Those covers are prime and irredundant, not minimum: an expression can carry more
+literals than sympy's for the same function (``profiles/minimise_bench.txt`` has the measured ratio).
 """
 from __future__ import annotations
 
@@ -68,10 +74,14 @@ def cnf_with_output(dnf, cnf) -> str:
 
 
 def export_filter(column: np.ndarray, n: int, filter_index: int, out_dir: str, block: int, sub_block: int,
-                  max_expr_bits: int = 9, usage: Optional[np.ndarray] = None) -> Dict[str, Optional[str]]:
+                  max_expr_bits: int = 9, usage: Optional[np.ndarray] = None, minimiser: str = "sympy", device=None,
+                  forms=None) -> Dict[str, Optional[str]]:
     """Files for one filter.  ``column``: its 2^n table entries (0/1), canonical order.  ``usage``: the lookup counts of
-    the filter's group, int64 [2^n] (module docstring)."""
+    the filter's group, int64 [2^n] (module docstring).  ``minimiser``: module docstring; ``forms``: this filter's
+    ``(DNF text, CNF text)`` when ``export_block`` has minimised it already."""
     import pandas as pd
+    if minimiser not in ("sympy", "device", "cpu"):
+        raise ValueError(f"minimiser {minimiser!r}: 'sympy', 'device' or 'cpu'")
     os.makedirs(out_dir, exist_ok=True)
     col = np.asarray(column).astype(np.float32)
     uniq = np.unique(col)
@@ -101,9 +111,13 @@ def export_filter(column: np.ndarray, n: int, filter_index: int, out_dir: str, b
         csv = f"{prefix}Truth_Table_block{block}_filter_{filter_index}_coefdefault_{value}_sousblock_{sub_block}.csv"
         frame.to_csv(csv)
         out["csv"] = csv
-        if n <= max_expr_bits:
-            minterms = frame["index"].values[answer if counts is None else answer & (counts > 0)].tolist()
-            dnf, cnf = minimal_forms(minterms, n, dontcares)
+        if n <= (max_expr_bits if minimiser == "sympy" else 16):
+            if minimiser == "sympy":
+                minterms = frame["index"].values[answer if counts is None else answer & (counts > 0)].tolist()
+                dnf, cnf = minimal_forms(minterms, n, dontcares)
+            else:
+                dnf, cnf = forms if forms is not None else _cover_forms(answer[None, :, None], n, None if counts is None else counts[None],
+                                                                        minimiser, device)[0]
             y = cnf_with_output(dnf, cnf)
             out.update(dnf=str(dnf), cnf=str(cnf), cnf_with_y=y, dnf_literals=literal_count(str(dnf)),
                        cnf_literals=literal_count(str(cnf)))
@@ -117,18 +131,39 @@ def export_filter(column: np.ndarray, n: int, filter_index: int, out_dir: str, b
 
 
 def export_block(table: np.ndarray, out_dir: str, block: int, sub_block: int, filters: Optional[Iterable[int]] = None,
-                 max_expr_bits: int = 9, usage: Optional[np.ndarray] = None) -> Dict[int, Dict[str, Optional[str]]]:
+                 max_expr_bits: int = 9, usage: Optional[np.ndarray] = None, minimiser: str = "sympy",
+                 device=None) -> Dict[int, Dict[str, Optional[str]]]:
     """``table``: [groups][2^n][cout_g] bits as returned by ``model.get_table(name)`` (or by the
     oracle's ``build_lut``).  Filter f = output channel f of the block = (group f // cout_g,
-    output f % cout_g).  ``usage``: int64 [groups][2^n] lookup counts of the block (module docstring)."""
+    output f % cout_g).  ``usage``: int64 [groups][2^n] lookup counts of the block (module docstring).
+    ``minimiser`` "device" / "cpu": all filters asked for are minimised at once (``device``: a torch device, default the
+    current one)."""
     g, size, cout_g = table.shape
     n = int(size).bit_length() - 1
     assert 2 ** n == size
     todo = range(g * cout_g) if filters is None else filters
     if usage is not None and tuple(np.shape(usage)) != (g, size):
         raise ValueError(f"usage has shape {tuple(np.shape(usage))}, the table has {g} groups of {size} entries")
+    todo = list(todo)
+    forms = {}
+    if minimiser in ("device", "cpu") and n <= 16 and todo:
+        from . import minimise
+        on, dc = minimise.pack_functions(np.asarray(table) == 1, usage)
+        forms = dict(zip(todo, _texts(minimise.minimal_covers(on[todo], dc[todo], n, minimiser, device), n)))
     return {f: export_filter(table[f // cout_g, :, f % cout_g], n, f, out_dir, block, sub_block, max_expr_bits,
-                             None if usage is None else usage[f // cout_g]) for f in todo}
+                             None if usage is None else usage[f // cout_g], minimiser, device, forms.get(f)) for f in todo}
+
+
+def _texts(covers, n: int):
+    from . import minimise
+    return [(minimise.dnf_text(d, n), minimise.cnf_text(c, n)) for d, c in covers]
+
+
+def _cover_forms(table: np.ndarray, n: int, usage, minimiser: str, device):
+    """``(DNF text, CNF text)`` of every filter of a ``[G, 2^n, cout_g]`` 0/1 table from ``minimise`` (one call)."""
+    from . import minimise
+    on, dc = minimise.pack_functions(table, usage)
+    return _texts(minimise.minimal_covers(on, dc, n, minimiser, device), n)
 
 
 def literal_count(expr_text: Optional[str]) -> int:

@@ -89,6 +89,10 @@ def build_parser() -> argparse.ArgumentParser:
                           "entry (counted on the device; 8 bytes of device memory per table entry)")
     out.add_argument("--table_coverage", type=str, default=None, metavar="FILE",
                      help="CSV block,groups,inputs,entries,seen,share_seen,constant_groups,top1pct_share (with --table_usage)")
+    out.add_argument("--table_gates", type=str, default=None, metavar="FILE",
+                     help="CSV, one row per binarised Block_TT: cubes and literals of its filters' DNF / CNF covers (prime and "
+                          "irredundant, minimised on the device), from the whole tables and, beside them, with the entries "
+                          "this run never read as don't-cares (counts the table usage, as --table_usage does)")
     ign = p.add_argument_group("accepted and ignored (training, logging and launcher flags of the reference)")
     for name, typ, default in _IGNORED:
         ign.add_argument(name, type=typ, default=default, help=argparse.SUPPRESS)
@@ -229,7 +233,7 @@ def run(args) -> int:
     extra = {}
     if args.topk or args.predictions or args.per_class or args.confusion:      # (otherwise the call is what it was)
         extra = dict(topk=args.topk, per_class=bool(args.per_class or args.confusion), confusion=bool(args.confusion))
-    if args.table_usage:
+    if args.table_usage or args.table_gates:
         extra["table_usage"] = True
     # a rank's own lines (running metrics, its shard's Acc..) go to stderr when there are several: stdout carries the result
     with contextlib.redirect_stdout(sys.stderr) if world > 1 else contextlib.nullcontext():
@@ -238,12 +242,15 @@ def run(args) -> int:
     res = all_reduce_metrics(part)
     if world > 1 and rank == 0:
         print("Acc..", res.top1, res.top5, flush=True)                 # main.py:284
-    if args.table_usage:
+    if args.table_usage or args.table_gates:
         usage = all_reduce_table_usage(part.table_usage)
-        if rank == 0:
+        if rank == 0 and args.table_usage:
             report.save_table_usage(args.table_usage, usage)
             if args.table_coverage:
                 report.write_coverage_csv(args.table_coverage, usage, {name: model.get_table(name) for name in usage})
+        if rank == 0 and args.table_gates:
+            report.write_gates_csv(args.table_gates, model.gate_counts(), model.gate_counts(usage),
+                                   {b.name: b.fan_in_bits for b in model.spec.block_tts()})
     if extra.get("topk") is not None:
         names = report.read_class_names(args.classes) if args.classes else None
         pred = all_gather_predictions(part.predictions) if args.predictions else None

@@ -1,0 +1,334 @@
+"""Two-level minimisation of truth tables with don't-cares: prime, irredundant covers (not minimum ones).
+
+The algorithm -- expand every ON minterm to a prime, order the primes by size, keep those that cover something new, drop
+the redundant ones in reverse -- is stated in ``include/ttnet.h`` (``ttnet_minimise_covers``).  It exists twice and both
+give the same cubes in the same order:
+
+  ``minimise_device``  the HIP kernel of ``csrc/minimise.hip``, all functions of a batch in one launch;
+  ``minimise_cpu``     its twin in numpy, with no device: the comparison in tests and benchmarks, never a fallback.
+
+A function of n inputs is two bitmaps over its 2^n patterns, uint32 ``[max(1, 2^n / 32)]``, bit ``i % 32`` of word
+``i // 32`` = pattern i in the canonical order of ``model.get_table`` (variable ``x_j`` is index bit ``n-1-j``): ``on``
+where it must be 1, ``dc`` where it may take either value.  A cube is the uint32 key ``mask << 16 | value``.
+``check_cover`` verifies a cover exhaustively on the host; ``dnf_text`` / ``cnf_text`` print covers the way sympy prints
+its forms, so ``export.cnf_with_output`` and ``export.literal_count`` take them unchanged.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import functools
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+
+def n_words(n: int) -> int:
+    return max(1, (1 << n) // 32)
+
+
+def _check_n(n: int):
+    if not 1 <= n <= 16:
+        raise ValueError(f"n = {n}: functions of 1 .. 16 inputs are served")
+
+
+def pack_bits(flags: np.ndarray) -> np.ndarray:
+    """bool ``[..., 2^n]`` -> uint32 ``[..., max(1, 2^n / 32)]`` bitmaps (unused high bits zero)."""
+    flags = np.asarray(flags, dtype=bool)
+    size = flags.shape[-1]
+    if size < 32:
+        flags = np.concatenate([flags, np.zeros(flags.shape[:-1] + (32 - size,), dtype=bool)], axis=-1)
+    packed = np.packbits(flags, axis=-1, bitorder="little")
+    return np.ascontiguousarray(packed).view("<u4").astype(np.uint32, copy=False)
+
+
+def unpack_bits(words: np.ndarray, n: int) -> np.ndarray:
+    """uint32 ``[..., words]`` bitmaps -> bool ``[..., 2^n]``."""
+    w = np.ascontiguousarray(np.asarray(words, dtype=np.uint32).astype("<u4", copy=False))
+    bits = np.unpackbits(w.view(np.uint8), axis=-1, bitorder="little")
+    return bits[..., : 1 << n].astype(bool)
+
+
+def pack_functions(table_bits: np.ndarray, usage: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """``(on, dc)`` bitmaps, uint32 ``[G * cout_g, words]``, of every filter of a ``get_table`` array ``[G, 2^n, cout_g]``
+    (filter f = group ``f // cout_g``, output ``f % cout_g``, as in ``export.export_block``).  With ``usage``
+    (``[G, 2^n]`` lookup counts) a pattern with count 0 is a don't-care, the rule of ``export.export_filter``."""
+    t = np.asarray(table_bits)
+    g, size, cout_g = t.shape
+    col = np.transpose(t != 0, (0, 2, 1)).reshape(g * cout_g, size)
+    if usage is None:
+        return pack_bits(col), np.zeros((g * cout_g, max(1, size // 32)), dtype=np.uint32)
+    u = np.asarray(usage)
+    if tuple(u.shape) != (g, size):
+        raise ValueError(f"usage has shape {tuple(u.shape)}, the table has {g} groups of {size} entries")
+    unseen = np.repeat(u == 0, cout_g, axis=0)
+    return pack_bits(col & ~unseen), pack_bits(unseen)
+
+
+def complement(on: np.ndarray, dc: np.ndarray, n: int) -> np.ndarray:
+    """The ON set of the complement, ``~on & ~dc``: minimised with the same ``dc`` it gives the CNF (``cnf_text``)."""
+    valid = np.uint32(0xFFFFFFFF if n >= 5 else (1 << (1 << n)) - 1)
+    return (~(np.asarray(on, dtype=np.uint32) | np.asarray(dc, dtype=np.uint32))) & valid
+
+
+# ---- the CPU twin ---------------------------------------------------------------------------------------------------------
+
+def _implicant_flags(not_off: np.ndarray, n: int) -> np.ndarray:
+    """bool ``(3,) * n``: digit j of an index is the state of x_j, 0 / 1 = literal, 2 = free; True iff that cube holds
+    no OFF pattern.  One vectorised pass per variable, ``flag[.., 2, ..] = flag[.., 0, ..] & flag[.., 1, ..]``, from the
+    last variable to the first so that every pass appends contiguous rows (43 M flags at n = 16)."""
+    flag = np.ascontiguousarray(not_off, dtype=bool).reshape((2,) * n)
+    for j in range(n - 1, -1, -1):
+        head = (slice(None),) * j
+        flag = np.concatenate([flag, flag[head + (slice(0, 1),)] & flag[head + (slice(1, 2),)]], axis=j)
+    return flag
+
+
+def _expand(on_idx: np.ndarray, flag: np.ndarray, n: int) -> np.ndarray:
+    """Step 1 for all ON minterms at once: their keys."""
+    flat = flag.reshape(-1)
+    pow3 = 3 ** np.arange(n - 1, -1, -1, dtype=np.int64)           # weight of digit j
+    bits = (on_idx[:, None] >> np.arange(n - 1, -1, -1)[None, :]) & 1
+    idx = (bits * pow3[None, :]).sum(axis=1)
+    mask = np.full(on_idx.shape, (1 << n) - 1, dtype=np.int64)
+    value = on_idx.astype(np.int64)
+    for j in range(n):
+        b = bits[:, j]
+        drop = flat[idx + (1 - 2 * b) * pow3[j]]                   # the sibling half holds no OFF pattern
+        idx = np.where(drop, idx + (2 - b) * pow3[j], idx)
+        bit = 1 << (n - 1 - j)
+        mask = np.where(drop, mask & ~bit, mask)
+        value = np.where(drop, value & ~bit, value)
+    return ((mask << 16) | value).astype(np.uint32)
+
+
+_POPCOUNT16 = np.unpackbits(np.arange(1 << 16, dtype="<u2").view(np.uint8).reshape(-1, 2), axis=1).sum(axis=1).astype(np.int64)
+
+
+@functools.lru_cache(maxsize=1 << 14)
+def _subset_sums(free_bits: int) -> np.ndarray:
+    """Every subset of the set bits of ``free_bits``, as an int64 array (shared: callers do not write to it)."""
+    out = np.zeros(1, dtype=np.int64)
+    b = 1
+    while b <= free_bits:
+        if free_bits & b:
+            out = np.concatenate([out, out | b])
+        b <<= 1
+    return out
+
+
+def minimise_cpu(on: np.ndarray, dc: Optional[np.ndarray], n: int) -> np.ndarray:
+    """The cover of one function (bitmaps, module docstring) as uint32 keys, by the four steps of ``include/ttnet.h``."""
+    _check_n(n)
+    on_b = unpack_bits(on, n)
+    dc_b = np.zeros_like(on_b) if dc is None else unpack_bits(dc, n) & ~on_b
+    on_idx = np.flatnonzero(on_b)
+    if len(on_idx) == 0:
+        return np.zeros(0, dtype=np.uint32)
+    if bool((on_b | dc_b).all()):
+        return np.zeros(1, dtype=np.uint32)
+    keys = _expand(on_idx, _implicant_flags(on_b | dc_b, n), n)
+    free = n - _POPCOUNT16[keys >> 16]
+    order = np.lexsort((on_idx, -free))                              # step 2
+    full = (1 << n) - 1
+    covered = np.zeros(1 << n, dtype=bool)
+    count = np.zeros(1 << n, dtype=np.int32)
+    kept: List[Tuple[int, np.ndarray]] = []
+    tried = set()
+    for key in keys[order].tolist():                                 # step 3 (a repeated cube covers nothing new)
+        if key in tried:
+            continue
+        tried.add(key)
+        mask, value = key >> 16, key & 0xFFFF
+        if (1 << (n - bin(mask).count("1"))) <= len(on_idx):
+            pts = value | _subset_sums(~mask & full)
+            pts = pts[on_b[pts]]
+        else:
+            pts = on_idx[(on_idx & mask) == value]
+        if covered[pts].all():
+            continue
+        covered[pts] = True
+        count[pts] += 1
+        kept.append((key, pts))
+    alive = [True] * len(kept)
+    for k in range(len(kept) - 1, -1, -1):                           # step 4
+        pts = kept[k][1]
+        if (count[pts] >= 2).all():
+            count[pts] -= 1
+            alive[k] = False
+    return np.array([key for (key, _), a in zip(kept, alive) if a], dtype=np.uint32)
+
+
+# ---- the device ------------------------------------------------------------------------------------------------------------
+
+def minimise_device(on, dc, n: int, device=None, cube_cap: Optional[int] = None) -> List[np.ndarray]:
+    """Covers of a batch of functions by ``ttnet_minimise_covers``: ``on`` / ``dc`` uint32 ``[F, words]`` (numpy, or torch
+    tensors on the device; ``dc`` None: no don't-cares) -> F arrays of uint32 keys.  One launch for the whole batch; the
+    functions whose cover has more cubes than the first cap (``cube_cap``; by default what 256 MB of keys allow the batch, at
+    least 1024 and at most 2^n, which never overflows) go through one more launch with the cap they need."""
+    import torch
+
+    from . import _lib
+    _check_n(n)
+    lib = _lib.load()
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+
+    def to_dev(a):
+        if a is None:
+            return None
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.uint32)).view(np.int32))
+        a = a.to(dev).contiguous()
+        if a.dim() != 2 or a.shape[1] != n_words(n) or a.element_size() != 4:
+            raise ValueError(f"bitmaps must be 32-bit [functions, {n_words(n)}], got {tuple(a.shape)} of {a.dtype}")
+        return a
+
+    on_t, dc_t = to_dev(on), to_dev(dc)
+    if dc_t is not None and dc_t.shape != on_t.shape:
+        raise ValueError("on and dc differ in shape")
+    total = on_t.shape[0]
+    out: List[Optional[np.ndarray]] = [None] * total
+
+    def run(sel: Optional[torch.Tensor], cap: int) -> Tuple[np.ndarray, np.ndarray]:
+        a = on_t if sel is None else on_t[sel].contiguous()
+        b = dc_t if (sel is None or dc_t is None) else dc_t[sel].contiguous()
+        f = a.shape[0]
+        with torch.cuda.device(dev):
+            work = torch.empty(_lib.check(lib.ttnet_minimise_workspace(n, f)), dtype=torch.uint8, device=dev)
+            cubes = torch.empty((f, max(cap, 1)), dtype=torch.int32, device=dev)
+            counts = torch.empty(f, dtype=torch.int32, device=dev)
+            _lib.check(lib.ttnet_minimise_covers(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr() if b is not None else None), n, f,
+                                                 C.c_void_p(cubes.data_ptr()), cubes.shape[1], C.c_void_p(counts.data_ptr()),
+                                                 C.c_void_p(work.data_ptr()), work.numel(),
+                                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            got = counts.cpu().numpy()
+            width = int(min(cap, max(int(got.max()), 1)))                # only the columns some cover reaches come back
+            return got, np.ascontiguousarray(cubes[:, :width].cpu().numpy()).view(np.uint32)
+
+    budget = 1 << 26                                                 # cube slots per launch (256 MB)
+    cap = min(1 << n, max(1024, budget // max(total, 1))) if cube_cap is None else int(cube_cap)
+    step = max(1, budget // max(cap, 1))
+    pending = [(None, cap)] if total <= step else [(torch.arange(lo, min(total, lo + step), device=dev), cap)
+                                                   for lo in range(0, total, step)]
+    while pending:
+        sel, cap = pending.pop()
+        ids = np.arange(total) if sel is None else sel.cpu().numpy()
+        counts, cubes = run(sel, cap)
+        over = []
+        for row, f in enumerate(ids.tolist()):
+            if counts[row] <= cap:
+                out[f] = cubes[row, : counts[row]].copy()
+            else:
+                over.append((f, int(counts[row])))
+        if over:
+            need = max(c for _, c in over)
+            step = max(1, budget // need)
+            for lo in range(0, len(over), step):
+                pending.append((torch.tensor([f for f, _ in over[lo:lo + step]], device=dev), need))
+    return out  # type: ignore[return-value]
+
+
+# ---- checking and printing ---------------------------------------------------------------------------------------------------
+
+def cube_patterns(keys: np.ndarray, n: int) -> List[np.ndarray]:
+    """The patterns of every cube, int64 arrays."""
+    full = (1 << n) - 1
+    return [(int(k) & 0xFFFF) | _subset_sums(~(int(k) >> 16) & full) for k in np.asarray(keys, dtype=np.uint32).tolist()]
+
+
+def check_cover(on: np.ndarray, dc: Optional[np.ndarray], n: int, cubes: Sequence[int]) -> None:
+    """Exhaustive check of a cover, by enumeration of every cube's patterns; raises AssertionError naming what fails:
+    the cover equals the function on every care pattern; every cube is well formed, an implicant of ON u DC and prime
+    (no single literal can be dropped); no cube is removable (each holds an ON pattern no other cube holds)."""
+    _check_n(n)
+    on_b = unpack_bits(on, n)
+    dc_b = np.zeros_like(on_b) if dc is None else unpack_bits(dc, n) & ~on_b
+    off_b = ~(on_b | dc_b)
+    keys = np.asarray(cubes, dtype=np.uint32)
+    full = (1 << n) - 1
+    assert len(set(keys.tolist())) == len(keys), "a cube appears twice"
+    times = np.zeros(1 << n, dtype=np.int64)
+    pats = cube_patterns(keys, n)
+    for key, pts in zip(keys.tolist(), pats):
+        mask, value = key >> 16, key & 0xFFFF
+        assert mask <= full and value & ~mask == 0, f"cube {key:#x} is malformed for n = {n}"
+        assert not off_b[pts].any(), f"cube {key:#x} holds an OFF pattern"
+        for b in range(n):
+            if mask >> b & 1:
+                assert off_b[pts ^ (1 << b)].any(), f"cube {key:#x} is not prime: the literal of x_{n - 1 - b} can be dropped"
+        times[pts] += 1
+    assert times[on_b].all(), f"{int((times[on_b] == 0).sum())} ON patterns are not covered"
+    assert not times[off_b].any(), "an OFF pattern is covered"
+    for key, pts in zip(keys.tolist(), pats):
+        mine = pts[on_b[pts]]
+        assert len(mine) and (times[mine] == 1).any(), f"cube {key:#x} can be removed"
+
+
+def _literals(key: int, n: int, complemented: bool) -> List[str]:
+    mask, value = key >> 16, key & 0xFFFF
+    out = []
+    for j in range(n):
+        b = n - 1 - j
+        if mask >> b & 1:
+            positive = bool(value >> b & 1) != complemented
+            out.append(f"x_{j}" if positive else f"~x_{j}")
+    return out
+
+
+def _text(cubes, n: int, complemented: bool) -> str:
+    inner, outer = (" | ", " & ") if complemented else (" & ", " | ")
+    empty, tautology = ("True", "False") if complemented else ("False", "True")
+    terms = [_literals(int(k), n, complemented) for k in np.asarray(cubes, dtype=np.uint32).tolist()]
+    if not terms:
+        return empty
+    if any(not t for t in terms):
+        return tautology
+    if len(terms) == 1:
+        return inner.join(terms[0])
+    return outer.join(t[0] if len(t) == 1 else "(" + inner.join(t) + ")" for t in terms)
+
+
+def dnf_text(cubes, n: int) -> str:
+    """A cover as a sum of products in sympy's print style: ``(x_0 & ~x_3) | x_5``; ``True`` / ``False`` for constants."""
+    return _text(cubes, n, False)
+
+
+def cnf_text(cubes, n: int) -> str:
+    """The cover of the COMPLEMENT (``complement``) read by De Morgan as a product of sums: ``(~x_0 | x_3) & ~x_5``."""
+    return _text(cubes, n, True)
+
+
+def literal_total(cubes) -> int:
+    """Literals of a cover: the set bits of its masks."""
+    return int(_POPCOUNT16[np.asarray(cubes, dtype=np.uint32) >> 16].sum())
+
+
+def minimal_covers(on: np.ndarray, dc: np.ndarray, n: int, minimiser: str, device=None) -> List[Tuple[np.ndarray, np.ndarray]]:
+    """``(DNF cover, cover of the complement)`` of every function of ``on`` / ``dc`` ``[F, words]``; with ``"device"`` both
+    covers of all functions come from one launch, with ``"cpu"`` from the twin."""
+    on = np.asarray(on, dtype=np.uint32)
+    dc = np.asarray(dc, dtype=np.uint32)
+    off = complement(on, dc, n)
+    if minimiser == "device":
+        both = minimise_device(np.concatenate([on, off]), np.concatenate([dc, dc]), n, device)
+    elif minimiser == "cpu":
+        both = [minimise_cpu(a, b, n) for a, b in zip(np.concatenate([on, off]), np.concatenate([dc, dc]))]
+    else:
+        raise ValueError(f"minimiser {minimiser!r}: 'device' or 'cpu' (sympy is export's own path)")
+    f = on.shape[0]
+    return [(both[i], both[f + i]) for i in range(f)]
+
+
+def gate_count_row(on: np.ndarray, dc: np.ndarray, n: int, minimiser: str = "device", device=None) -> dict:
+    """``{filters, constant, dnf_cubes, dnf_literals, cnf_cubes, cnf_literals}`` of one block's functions; a filter that is
+    constant on its care patterns counts under ``constant`` and has no cubes or literals in either form."""
+    covers = minimal_covers(on, dc, n, minimiser, device)
+    row = dict(filters=len(covers), constant=0, dnf_cubes=0, dnf_literals=0, cnf_cubes=0, cnf_literals=0)
+    for dnf, cnf in covers:
+        if literal_total(dnf) == 0 or literal_total(cnf) == 0:       # no cube, or the cube without a literal
+            row["constant"] += 1
+            continue
+        row["dnf_cubes"] += len(dnf)
+        row["dnf_literals"] += literal_total(dnf)
+        row["cnf_cubes"] += len(cnf)
+        row["cnf_literals"] += literal_total(cnf)
+    return row

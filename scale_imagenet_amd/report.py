@@ -10,6 +10,10 @@ Formats (fixed: tests and users' scripts read them):
   table usage  ``numpy.savez_compressed``: one int64 ``[groups, 2^n]`` array per ``Block_TT`` name (``EvalResult.table_usage``).
   coverage     ``block,groups,inputs,entries,seen,share_seen,constant_groups,top1pct_share`` per ``Block_TT``
                (``coverage_rows``).
+  gates        ``block,inputs,filters,constant,dnf_cubes,dnf_literals,cnf_cubes,cnf_literals,constant_seen,dnf_cubes_seen,
+               dnf_literals_seen,cnf_cubes_seen,cnf_literals_seen`` per binarised ``Block_TT`` (``gate_rows``): the counts of
+               ``model.gate_counts()`` on the full care set and, under ``*_seen``, with the entries the run never read as
+               don't-cares.  Prime, irredundant covers, not minimum ones.
 Every file is written to a temporary name beside its own and then renamed, so a reader never sees half of one.
 """
 from __future__ import annotations
@@ -150,3 +154,20 @@ def coverage_rows(usage, tables=None) -> List[list]:
 def write_coverage_csv(path: Optional[str], usage, tables=None):
     with _replacing(path) as f:
         csv.writer(f, lineterminator="\n").writerows(coverage_rows(usage, tables))
+
+
+GATE_FIELDS = ["constant", "dnf_cubes", "dnf_literals", "cnf_cubes", "cnf_literals"]
+
+
+def gate_rows(full, seen, inputs) -> List[list]:
+    """The rows of the gates file, header first.  ``full`` / ``seen``: ``model.gate_counts()`` /
+    ``model.gate_counts(usage)``; ``inputs``: ``{block name: n}``."""
+    rows = [["block", "inputs", "filters"] + GATE_FIELDS + [f + "_seen" for f in GATE_FIELDS]]
+    for name, a in full.items():
+        rows.append([name, int(inputs[name]), int(a["filters"])] + [int(a[f]) for f in GATE_FIELDS] + [int(seen[name][f]) for f in GATE_FIELDS])
+    return rows
+
+
+def write_gates_csv(path: Optional[str], full, seen, inputs):
+    with _replacing(path) as f:
+        csv.writer(f, lineterminator="\n").writerows(gate_rows(full, seen, inputs))
