@@ -167,6 +167,12 @@ int launch_va_stem(const float *x, const float *w, const float *bias, const floa
   return TTNET_OK;
 }
 
+int va_stem_kernel_arg_sizes(const int **sizes) {
+  using S = KernelArgSizes<decltype(&va_stem_kernel)>;
+  *sizes = S::sizes;
+  return S::n;
+}
+
 int launch_va_block(const uint64_t *x_rp, const void *t1, const void *t2, const void *t3, uint64_t *y, int n, hipStream_t s) {
   size_t t = (size_t)n * 64 * 11;
   hipLaunchKernelGGL(va_dw_kernel, dim3((unsigned)((t + 127) / 128)), dim3(128), 0, s, x_rp, (const uint32_t *)t1,

@@ -516,6 +516,12 @@ int launch_lin2_f16x2(const void *mid_frag, const void *w2f, const float *bias, 
   return TTNET_OK;
 }
 
+int lin2_kernel_arg_sizes(const int **sizes) {
+  using S = KernelArgSizes<decltype(&lin2_f16x2_kernel)>;
+  *sizes = S::sizes;
+  return S::n;
+}
+
 int launch_permute_lin1(const float *w1, float *w1p, int O, int G, int PP, hipStream_t s) {
   const size_t t = (size_t)O * G * PP * 16;
   hipLaunchKernelGGL(permute_lin1_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, w1, w1p, O, G, PP);

@@ -90,7 +90,7 @@ __global__ __launch_bounds__(kThreads) void lut_build_kernel(LutBuildArgs a) {
   } else if (cout_g == 1) {
     // 1-bit entries: dword w = idx>>5, bit idx&31; the dwords of 16 consecutive groups
     // (channels) are striped: [g/16][w][g%16], so that a workgroup's 16 tables interleave in
-    // LDS banks (gate.hip)
+    // LDS banks (gate.hip).  The host reads and writes all three layouts through table_entry (ttnet_common.h)
     const unsigned long long m = __ballot(live && (bits & 1u));
     const int lane = threadIdx.x & 63;
     const size_t words = entries >= 32 ? entries / 32 : 1;

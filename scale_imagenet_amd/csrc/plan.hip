@@ -5,9 +5,8 @@
 // models/model_utils/netbin.py:703-708).  No torch types, no CPU compute path: every
 // arithmetic step of forward() is a HIP kernel from stem.hip / gate.hip / head.hip, and the
 // derived tables are built by lut_build.hip.  Host code here only folds BatchNorm
-// parameters (a few thousand scalars, float64) and moves bytes.
+// parameters (a few thousand scalars, float64) and moves bytes.  (The RCCL all-gather of the same header: comm.hip.)
 
-#include <dlfcn.h>
 #include <math.h>
 #include <stdarg.h>
 #include <stdint.h>
@@ -18,8 +17,6 @@
 #include <algorithm>
 #include <array>
 #include <map>
-#include <memory>
-
 #include <mutex>
 #include <unordered_map>
 
@@ -143,12 +140,14 @@ struct ttnet_plan {
   struct GraphEntry {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
-    hipGraphNode_t first = nullptr, last = nullptr;     // the kernels that read x / write the logits
-    // own copies of those two kernels' launch parameters (argument values in 8-byte slots)
-    hipKernelNodeParams first_p{}, last_p{};
-    int first_nargs = 0;
-    uint64_t first_argv[12] = {}, last_argv[12] = {};
-    void *first_args[12] = {}, *last_args[12] = {};
+    // a kernel node and the plan's own copy of its launch parameters (argument values in 8-byte slots)
+    struct Kernel {
+      hipGraphNode_t node = nullptr;
+      hipKernelNodeParams p{};
+      uint64_t argv[12] = {};
+      void *args[12] = {};
+    };
+    Kernel first, last;               // the kernels that read x / write the logits
     const void *x = nullptr;
     void *out = nullptr;
   };
@@ -207,12 +206,6 @@ int ttnet::ensure_dynamic_lds(const void *kernel, size_t bytes) {
 }
 
 namespace {
-
-// Captured graphs bake in by-value kernel arguments derived from the weights (lin2's 1/prescale) and
-// the device addresses of tables: whenever a tensor, a table or the finalized state changes they are
-// all dropped (after a device synchronisation -- a replay may still be in flight) and re-captured
-// from the third forward on.
-int invalidate_graphs(ttnet_plan *pl);
 
 template <typename T>
 int dev_alloc(ttnet_plan *pl, T **out, size_t count, bool zero, size_t *account = nullptr) {
@@ -283,6 +276,12 @@ BlockGeom make_geom(const std::string &name, int in_planes, int out_planes, int 
   return g;
 }
 
+// internal index order of a table = the canonical column order
+void identity_perm(BlockTT &b) {
+  b.perm.resize(b.g.nbits());
+  for (int q = 0; q < b.g.nbits(); ++q) b.perm[q] = (uint8_t)q;
+}
+
 // Geometry of the network (mirrors make_small_network,
 // models/TT_general_imagenet_v2_small.py:159-203, and the shape-keyed branch padding of
 // the block forward, :98-139).
@@ -315,8 +314,7 @@ int build_geometry_valexnet(ttnet_plan *pl) {
   mh.c3.g = make_geom("features.5.Block_conv3", 64, 64, 1, 1, 1, 0, 8, false);
   for (BlockTT *b : {&mh.c1, &mh.c2, &mh.c3}) {
     add_block_tt(pl, b->g);
-    b->perm.resize(b->g.nbits());
-    for (int q = 0; q < b->g.nbits(); ++q) b->perm[q] = (uint8_t)q;
+    identity_perm(*b);
   }
   pl->blocks.push_back(mh);
   add_tensor(pl, "features.7.lin1.weight", {pl->inter, pl->fcsize}, TTNET_F32, true);
@@ -435,10 +433,7 @@ int build_geometry(ttnet_plan *pl) {
     add_block_tt(pl, mh.cf.g);
     // internal index orders (table variants only)
     if (!full_variant)
-    for (BlockTT *b : {&mh.c1, &mh.c2, &mh.c3}) {
-      b->perm.resize(b->g.nbits());
-      for (int q = 0; q < b->g.nbits(); ++q) b->perm[q] = (uint8_t)q;
-    }
+      for (BlockTT *b : {&mh.c1, &mh.c2, &mh.c3}) identity_perm(*b);
     // convf group = gsize/4 channels x 4 branches; reference interleave is channel 4c+branch (:144-147),
     // internal index bit = (gsize/4)*branch + channel-in-group
     const int nch = gsize / 4;
@@ -573,7 +568,7 @@ int allocate(ttnet_plan *pl) {
       TT_TRY(dev_alloc(pl, (uint8_t **)&mh.img_dw, (size_t)mh.C * 16384, false, tb));
       TT_TRY(dev_alloc(pl, (uint8_t **)&mh.img_c3, (size_t)(mh.C / 8) * 65536, false, tb));
     }
-  TT_TRY(dev_alloc(pl, &pl->w1f, frag_elems(valexnet ? 128 : (pl->inter + 127) / 128 * 128, pl->fcsize), false));
+  TT_TRY(dev_alloc(pl, &pl->w1f, frag_elems((pl->inter + 127) / 128 * 128, pl->fcsize), false));
   TT_TRY(dev_alloc(pl, &pl->bn_scale, pl->inter, false));
   TT_TRY(dev_alloc(pl, &pl->bn_shift, pl->inter, false));
   TT_TRY(dev_alloc(pl, &pl->w2f, frag_elems((pl->n_classes + 63) / 64 * 64, kpad), true));
@@ -602,6 +597,24 @@ int fold_bn(ttnet_plan *pl, const std::string &prefix, std::vector<double> &scal
   return TTNET_OK;
 }
 
+// stem: BN scale folded into the weights, which are split into two prescaled fp16 planes in MFMA
+// fragment order; BN shift as the weights of one more k-row (stem.hip)
+int prepare_stem(ttnet_plan *pl) {
+  std::vector<float> w;
+  TT_TRY(fetch(pl->tensors["features.1.weight"], w));
+  std::vector<uint16_t> wf(stem_split_weights_elems());
+  std::vector<double> sc, sh;
+  TT_TRY(fold_bn(pl, "features.2", sc, sh));
+  float init[64];
+  if (!stem_split_weights(w.data(), sc.data(), sh.data(), pl->p, wf.data(), init)) {
+    set_error("stem: the folded BatchNorm shift of features.2 is outside the range of the split operands");
+    return TTNET_E_UNSUPPORTED;
+  }
+  TT_HIP(hipMemcpy(pl->stem_wt, wf.data(), wf.size() * 2, hipMemcpyHostToDevice));
+  TT_HIP(hipMemcpy(pl->stem_init, init, sizeof(init), hipMemcpyHostToDevice));
+  return TTNET_OK;
+}
+
 // uint8 input: the stem's weights with ToTensor + Normalize folded in (stem.hip, U8).  From the loaded weights and the
 // plan's mean / std: at finalize and again whenever ttnet_plan_set_input_norm changes them.
 int prepare_stem_u8(ttnet_plan *pl) {
@@ -621,7 +634,6 @@ int prepare_stem_u8(ttnet_plan *pl) {
   TT_HIP(hipMemcpy(pl->norm_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
   return TTNET_OK;
 }
-
 
 int upload_f32(float *dst, const std::vector<double> &src) {
   std::vector<float> f(src.begin(), src.end());
@@ -661,8 +673,9 @@ int read_near_ties(ttnet_plan *pl) {
   return TTNET_OK;
 }
 
+// (name == nullptr: not timed)
 void begin_timing(ttnet_plan *pl, const char *name, hipStream_t s) {
-  if (!pl->profiling) return;
+  if (!pl->profiling || !name) return;
   if (pl->timing_used == pl->timings.size()) {
     Timing t{name, nullptr, nullptr};
     (void)hipEventCreate(&t.e0);
@@ -672,8 +685,8 @@ void begin_timing(ttnet_plan *pl, const char *name, hipStream_t s) {
   pl->timings[pl->timing_used].name = name;
   (void)hipEventRecord(pl->timings[pl->timing_used].e0, s);
 }
-void end_timing(ttnet_plan *pl, hipStream_t s) {
-  if (!pl->profiling) return;
+void end_timing(ttnet_plan *pl, const char *name, hipStream_t s) {
+  if (!pl->profiling || !name) return;
   (void)hipEventRecord(pl->timings[pl->timing_used].e1, s);
   pl->timing_used++;
 }
@@ -682,7 +695,7 @@ void end_timing(ttnet_plan *pl, hipStream_t s) {
   do {                              \
     begin_timing(pl, name, s);      \
     int r__ = (expr);               \
-    end_timing(pl, s);              \
+    end_timing(pl, name, s);        \
     if (r__ != TTNET_OK) return r__; \
   } while (0)
 
@@ -722,20 +735,68 @@ int run_two_launch_block(ttnet_plan *pl, const ttnet_plan::Lane &L, size_t i, in
   return TTNET_OK;
 }
 
-// One block in one launch (gate_fused.hip); a last block adds the pool + flatten launch
-int run_fused_block(ttnet_plan *pl, const ttnet_plan::Lane &L, size_t i, int n, hipStream_t s) {
-  static const char *kBlkNames[] = {"gate_block.f4", "gate_block.f5", "gate_block.f6", "gate_block.f7"};
+// Fused block i on the lane's buffers.  idx: where its branch dwords go -- the output of a last block, an optional tap
+// otherwise
+FusedBlockArgs fused_args(const ttnet_plan *pl, const ttnet_plan::Lane &L, size_t i, int n, uint32_t *idx) {
   const MultiHead &mh = pl->blocks[i];
-  uint32_t *idx = L.blk[i].idx;
   FusedBlockArgs f{};
   f.n = n; f.C = mh.C; f.H = mh.H; f.Ho = mh.Ho; f.off34 = mh.off34; f.last = mh.last ? 1 : 0;
   f.x = L.x_rp[i]; f.img_c3 = mh.img_c3; f.img_dw = mh.img_dw;
   f.t_cf = mh.last ? nullptr : (const uint8_t *)mh.cf.table;
   f.y = mh.last ? nullptr : (void *)L.x_rp[i + 1];
-  f.idx = mh.last ? idx : nullptr;
-  TT_TIMED(pl, kBlkNames[std::min<size_t>(i, 3)], s, launch_gate_block(f, s));
+  f.idx = idx;
+  return f;
+}
+
+// One block in one launch (gate_fused.hip); a last block adds the pool + flatten launch
+int run_fused_block(ttnet_plan *pl, const ttnet_plan::Lane &L, size_t i, int n, hipStream_t s) {
+  static const char *kBlkNames[] = {"gate_block.f4", "gate_block.f5", "gate_block.f6", "gate_block.f7"};
+  const MultiHead &mh = pl->blocks[i];
+  uint32_t *idx = mh.last ? L.blk[i].idx : nullptr;
+  TT_TIMED(pl, kBlkNames[std::min<size_t>(i, 3)], s, launch_gate_block(fused_args(pl, L, i, n, idx), s));
   if (mh.last)
     TT_TIMED(pl, "gate_last", s, launch_gate_last(gate_args(pl, L, i, n), (const float *)mh.cf.table, L.feat, pl->range_dev, s, idx));
+  return TTNET_OK;
+}
+
+// ---- a stage of the last forward as uint64 rows (ttnet_read_stage, ttnet_table_usage_add) ----
+// Each gate path keeps its activations in its own layout; these three answer in the one layout of the C ABI.
+// timing: the name the conversion launches are timed under (nullptr: not timed).
+
+// The branch dwords of fused block i, whose branch tensors never reach HBM: a last block's are its output; any other
+// block is run once more on its (still resident) input with `tap` attached -- it rewrites the next block's input with
+// the same bits
+int fused_branch_dwords(ttnet_plan *pl, const ttnet_plan::Lane &L, size_t i, int n, uint32_t *tap, const char *timing, hipStream_t s,
+                        const uint32_t **dwords) {
+  *dwords = pl->blocks[i].last ? L.blk[i].idx : tap;
+  if (!pl->blocks[i].last) TT_TIMED(pl, timing, s, launch_gate_block(fused_args(pl, L, i, n, tap), s));
+  return TTNET_OK;
+}
+
+// The input of block i as rows [n][C][H]: in place, but for the compact rows of the fused path (blocks after the
+// first), which are widened into buf
+int block_input_rows(ttnet_plan *pl, const ttnet_plan::Lane &L, size_t i, int n, uint64_t *buf, const char *timing, hipStream_t s,
+                     const uint64_t **rows) {
+  const MultiHead &mh = pl->blocks[i];
+  *rows = L.x_rp[i];
+  if (pl->path == GatePath::Fused && i > 0) {
+    TT_TIMED(pl, timing, s, launch_widen_rows(L.x_rp[i], buf, (size_t)n * mh.C * mh.H, mh.W, s));
+    *rows = buf;
+  }
+  return TTNET_OK;
+}
+
+// Branch k of block i after its padding as rows [n][C][Ho]: in place, or converted into buf (fused path: from the
+// dwords of fused_branch_dwords)
+int branch_as_rows(ttnet_plan *pl, const ttnet_plan::Lane &L, size_t i, int k, int n, const uint32_t *dwords, uint64_t *buf,
+                   const char *timing, hipStream_t s, const uint64_t **rows) {
+  const MultiHead &mh = pl->blocks[i];
+  *rows = buf;
+  switch (pl->path) {
+    case GatePath::TwoLaunch: TT_TIMED(pl, timing, s, launch_cp_to_rp(L.blk[i].o[k], buf, n, mh.C, mh.Ho, mh.Wo, s)); break;
+    case GatePath::Fused: TT_TIMED(pl, timing, s, launch_branch_rows(dwords, buf, n, mh.C, mh.Ho, k, s)); break;
+    default: *rows = (const uint64_t *)L.blk[i].o[k]; break;      // x-small and full keep row-packed branch tensors
+  }
   return TTNET_OK;
 }
 
@@ -766,6 +827,18 @@ int run_full_block(ttnet_plan *pl, const ttnet_plan::Lane &L, size_t i, int n, h
   const std::array<uint64_t *, 4> o64 = branch_rows(L, i);
   uint64_t *const c3_tmp = L.blk[i].c3_tmp;
   auto wts = [&](const BlockTT &b, const char *leaf) { return (const float *)pl->tensors[b.g.name + leaf].dev; };
+  // a grouped 1x1 block on an H x W pixel grid: everything but its sources and its output
+  auto pw_args = [&](const BlockTT &b, int H, int W) {
+    FullPwArgs a{};
+    a.n = n; a.H = H; a.W = W;
+    a.groups = b.g.groups; a.cin = b.g.cin_g(); a.mid = b.g.mid_g(); a.cout = b.g.cout_g(); a.Cout = b.g.out_planes;
+    a.Csrc = mh.C;
+    a.w1 = wts(b, ".conv1.weight"); a.w2 = wts(b, ".conv2.weight");
+    a.s1 = b.s1; a.t1 = b.t1; a.s2 = b.s2; a.t2 = b.t2;
+    a.gel = pl->full_gel ? pl->full_gel + full_gelu_tables_elems() / 2 : nullptr;
+    a.fix_count = L.full_fix; a.fix_list = L.full_fix ? L.full_fix + 64 : nullptr; a.range_flag = pl->range_dev;
+    return a;
+  };
   for (int br = 0; br < 2; ++br) {
     const BlockTT &b = br ? mh.c2 : mh.c1;
     FullDwArgs a{};
@@ -789,16 +862,9 @@ int run_full_block(ttnet_plan *pl, const ttnet_plan::Lane &L, size_t i, int n, h
     TT_TIMED(pl, kDw[br][std::min<size_t>(i, 3)], s, launch_full_dw(a, s));
   }
   {
-    const BlockTT &b = mh.c3;
-    FullPwArgs a{};
-    a.n = n; a.H = mh.H; a.W = mh.W;
-    a.groups = b.g.groups; a.cin = b.g.cin_g(); a.mid = b.g.mid_g(); a.cout = b.g.cout_g(); a.Cout = b.g.out_planes;
-    a.Csrc = mh.C; a.interleaved = 0; a.src[0] = L.x_rp[i];
-    a.w1 = wts(b, ".conv1.weight"); a.w2 = wts(b, ".conv2.weight");
-    a.s1 = b.s1; a.t1 = b.t1; a.s2 = b.s2; a.t2 = b.t2;
+    FullPwArgs a = pw_args(mh.c3, mh.H, mh.W);
+    a.interleaved = 0; a.src[0] = L.x_rp[i];
     a.out_rp = c3_tmp; a.out_float = nullptr;
-    a.gel = pl->full_gel ? pl->full_gel + full_gelu_tables_elems() / 2 : nullptr;
-    a.fix_count = L.full_fix; a.fix_list = L.full_fix ? L.full_fix + 64 : nullptr; a.range_flag = pl->range_dev;
     static const char *const kC3[4] = {"full.conv3.f4", "full.conv3.f5", "full.conv3.f6", "full.conv3.f7"};
     TT_TIMED(pl, kC3[std::min<size_t>(i, 3)], s, launch_full_pw(a, s));
     TT_TIMED(pl, "full.maj3", s,
@@ -807,20 +873,13 @@ int run_full_block(ttnet_plan *pl, const ttnet_plan::Lane &L, size_t i, int n, h
              launch_rp_majority(L.x_rp[i], o64[3], n, mh.C, mh.H, mh.W, mh.Ho, mh.off34, mh.off34, s));
   }
   {
-    const BlockTT &b = mh.cf;
-    FullPwArgs a{};
-    a.n = n; a.H = mh.Ho; a.W = mh.Wo;
-    a.groups = b.g.groups; a.cin = b.g.cin_g(); a.mid = b.g.mid_g(); a.cout = b.g.cout_g(); a.Cout = b.g.out_planes;
-    a.Csrc = mh.C; a.interleaved = 1;
+    FullPwArgs a = pw_args(mh.cf, mh.Ho, mh.Wo);
+    a.interleaved = 1;
     for (int k = 0; k < 4; ++k) a.src[k] = o64[k];
-    a.w1 = wts(b, ".conv1.weight"); a.w2 = wts(b, ".conv2.weight");
-    a.s1 = b.s1; a.t1 = b.t1; a.s2 = b.s2; a.t2 = b.t2;
-    a.gel = pl->full_gel ? pl->full_gel + full_gelu_tables_elems() / 2 : nullptr;
-    a.fix_count = L.full_fix; a.fix_list = L.full_fix ? L.full_fix + 64 : nullptr; a.range_flag = pl->range_dev;
     if (mh.last) {
       a.out_rp = nullptr; a.out_float = L.last_float;
       TT_TIMED(pl, "full.convf_last", s, launch_full_pw(a, s));
-      TT_TIMED(pl, "full.pool", s, launch_full_pool_split(L.last_float, L.feat, n, b.g.out_planes, mh.Ho, mh.Wo, pl->range_dev, s));
+      TT_TIMED(pl, "full.pool", s, launch_full_pool_split(L.last_float, L.feat, n, mh.cf.g.out_planes, mh.Ho, mh.Wo, pl->range_dev, s));
     } else {
       a.out_rp = L.x_rp[i + 1]; a.out_float = nullptr;
       static const char *const kCf[4] = {"full.convf.f4", "full.convf.f5", "full.convf.f6", "full.convf.f7"};
@@ -830,15 +889,30 @@ int run_full_block(ttnet_plan *pl, const ttnet_plan::Lane &L, size_t i, int n, h
   return TTNET_OK;
 }
 
-// split lin2.weight into w2f (finalize)
-int prepare_lin2(ttnet_plan *pl, const std::string &key, hipStream_t s) {
-  std::vector<float> w2;
-  TT_TRY(fetch(pl->tensors[key], w2));
-  const float ws2 = weight_prescale(w2.data(), w2.size());
+// The classifier's operands (finalize): BatchNorm1d folded, lin1's weights permuted to the feature order of the gate
+// kernels (vAlexnet's features already come in the reference's Flatten order) and split into w1f, lin2's into w2f
+int prepare_head(ttnet_plan *pl, hipStream_t s) {
+  const Tensor &t1 = pl->tensors[pl->head + ".lin1.weight"], &t2 = pl->tensors[pl->head + ".lin2.weight"];
+  std::vector<double> sc, sh;
+  TT_TRY(fold_bn(pl, pl->head + ".BN2", sc, sh));
+  std::vector<float> w;
+  TT_TRY(fetch(t1, w));
+  const float ws1 = weight_prescale(w.data(), w.size());
+  for (double &v : sc) v /= (double)ws1 * ACT_PRESCALE;      // operand prescales (powers of two) out of lin1's result
+  TT_TRY(upload_f32(pl->bn_scale, sc));
+  TT_TRY(upload_f32(pl->bn_shift, sh));
+  const float *w1 = (const float *)t1.dev;
+  if (pl->path != GatePath::VAlexnet) {
+    TT_TRY(launch_permute_lin1(w1, pl->w1p, pl->inter, pl->featC / 16, pl->featPP, s));
+    w1 = pl->w1p;
+  }
+  TT_TRY(launch_split_to_frag(w1, pl->w1f, pl->inter, pl->fcsize, (pl->inter + 127) / 128 * 128, ws1, s));
+  TT_TRY(fetch(t2, w));
+  const float ws2 = weight_prescale(w.data(), w.size());
   pl->lin2_inv = 1.0f / (ws2 * ACT_PRESCALE);
   const int kpad = (pl->inter + 15) / 16 * 16;
-  return launch_split_to_frag((const float *)pl->tensors[key].dev, pl->w2f, pl->n_classes, kpad, (pl->n_classes + 63) / 64 * 64, ws2, s,
-                              pl->inter, pl->inter);
+  return launch_split_to_frag((const float *)t2.dev, pl->w2f, pl->n_classes, kpad, (pl->n_classes + 63) / 64 * 64, ws2, s, pl->inter,
+                              pl->inter);
 }
 
 // Classifier_scale from the features in L.feat
@@ -915,6 +989,44 @@ inline uint32_t canonical_index(const BlockTT &b, uint32_t idx) {
   return ci;
 }
 
+// The Block_TT that ttnet_plan_get_table (get) / ttnet_plan_set_table names, whose host buffer must hold the table in
+// the canonical order
+int table_block(ttnet_plan *pl, const char *name, const void *host, size_t bytes, bool get, BlockTT **out) {
+  if (!pl || !name || !host) {
+    set_error("null argument");
+    return TTNET_E_INVALID;
+  }
+  BlockTT *b = find_block(pl, name);
+  if (!b) {
+    set_error("no Block_TT named %s", name);
+    return TTNET_E_INVALID;
+  }
+  if (pl->path == GatePath::Full) {
+    set_error("the full variant (fan-in 30) has no truth tables: 2^30 entries per output bit");
+    return TTNET_E_UNSUPPORTED;
+  }
+  if (get && !pl->finalized) {
+    set_error("get_table before finalize");
+    return TTNET_E_STATE;
+  }
+  if (bytes != b->g.canonical_bytes()) {
+    set_error("%s(%s): %s is %zu bytes, table is %zu", get ? "get_table" : "set_table", name, get ? "destination" : "source", bytes,
+              b->g.canonical_bytes());
+    return TTNET_E_INVALID;
+  }
+  *out = b;
+  return TTNET_OK;
+}
+
+// Every entry of b's table between the internal layout (raw) and the canonical order (canon); store: canon -> raw
+void walk_table(const BlockTT &b, void *raw, void *canon, bool store) {
+  const BlockGeom &g = b.g;
+  const size_t per = (size_t)1 << g.nbits(), entry_bytes = g.canonical_bytes() / g.entries();
+  for (int grp = 0; grp < g.groups; ++grp)
+    for (uint32_t idx = 0; idx < per; ++idx)
+      table_entry(g, raw, grp, idx, (uint8_t *)canon + ((size_t)grp * per + canonical_index(b, idx)) * entry_bytes, store);
+}
+
 // Per-lane scratch of ttnet_table_usage_add, sized for max_batch (a lane that has its scratch keeps it)
 int alloc_usage_scratch(ttnet_plan *pl, ttnet_plan::Lane &L) {
   if (L.u_br[0] || pl->path == GatePath::XSmall) return TTNET_OK;      // (x-small keeps everything as uint64 rows already)
@@ -949,6 +1061,210 @@ void free_usage(ttnet_plan *pl) {
   pl->usage_on = false;
 }
 
+int forward_eager(ttnet_plan *pl, ttnet_plan::Lane &L, const void *x_dev, bool u8, int64_t n, float *logits_dev, hipStream_t s) {
+  pl->timing_used = 0;
+  if (pl->path == GatePath::VAlexnet) {
+    if (u8) {
+      set_error("uint8 input is not implemented for the vAlexnet variant");
+      return TTNET_E_UNSUPPORTED;
+    }
+    TT_TIMED(pl, "va.stem", s,
+             launch_va_stem((const float *)x_dev, (const float *)pl->tensors["features.0.weight"].dev,
+                            (const float *)pl->tensors["features.0.bias"].dev, pl->va_scale, pl->va_shift, L.x_rp[0],
+                            (int)n, s));
+  } else {
+    TT_TIMED(pl, "stem", s,
+             launch_stem(x_dev, u8, pl->norm_tab, u8 ? pl->stem_wt_u8 : pl->stem_wt, u8 ? pl->stem_init_u8 : pl->stem_init, L.x_rp[0],
+                         pl->path == GatePath::TwoLaunch ? L.x_cp[0] : nullptr, (int)n, pl->p, pl->range_dev, s,
+                         (pl->lanes.size() >= 2 && !u8 && pl->path != GatePath::Full) ? 128 : 256));      // (stem.hip: half the CUs for float32 input with batches in flight)
+  }
+  return run_from_blocks(pl, L, (int)n, logits_dev, s);
+}
+
+// The forward is a fixed chain of ~11 launches whose host cost (~20 us each) equals the device
+// time at batch 256, so from the third call with a given batch size on it is replayed as a
+// hipGraph captured on a private stream.  Only two pointers change between calls: the input
+// (argument 0 of the first kernel) and the logits (argument 4 of lin2, the last kernel); they
+// are patched into the instantiated graph when they differ from the previous call.
+constexpr int kLastKernelOutArg = 4, kLastKernelBatchArg = 5;      // lin2_f16x2_kernel(A, B, bias, inv, out, M, ..)
+
+void drop_graph(ttnet_plan::GraphEntry &e) {
+  if (e.exec) (void)hipGraphExecDestroy(e.exec);
+  if (e.graph) (void)hipGraphDestroy(e.graph);
+  e = ttnet_plan::GraphEntry{};
+}
+
+// Captured graphs bake in by-value kernel arguments derived from the weights (lin2's 1/prescale) and
+// the device addresses of tables: whenever a tensor, a table or the finalized state changes they are
+// all dropped (after a device synchronisation -- a replay may still be in flight) and re-captured
+// from the third forward on.
+int invalidate_graphs(ttnet_plan *pl) {
+  bool any = false;
+  for (auto &l : pl->lanes) any = any || !l.graphs.empty();
+  if (any) TT_HIP(hipDeviceSynchronize());
+  for (auto &l : pl->lanes) {
+    for (auto &kv : l.graphs) {
+      drop_graph(kv.second);
+      pl->graph_drops++;
+    }
+    l.graphs.clear();
+    l.eager_calls.clear();
+  }
+  return TTNET_OK;
+}
+
+void graphs_off(ttnet_plan *pl, const char *why) {
+  pl->graphs_ok = false;
+  pl->graph_off_reason = why;
+  (void)hipGetLastError();
+}
+
+// Copy a kernel node's launch parameters into storage we own; arg_sizes: the kernel's own export of its argument sizes.
+// (The arrays returned by hipGraphKernelNodeGetParams belong to the node: they are read once,
+// here, and never handed back to the runtime.)
+bool own_params(hipGraphNode_t node, int (*arg_sizes)(const int **), ttnet_plan::GraphEntry::Kernel &k) {
+  const int *sizes = nullptr;
+  const int nargs = arg_sizes(&sizes);
+  hipGraphNodeType type;
+  hipKernelNodeParams q{};
+  if (nargs > (int)std::size(k.argv) || hipGraphNodeGetType(node, &type) != hipSuccess || type != hipGraphNodeTypeKernel ||
+      hipGraphKernelNodeGetParams(node, &q) != hipSuccess || !q.kernelParams || q.extra)
+    return false;
+  for (int i = 0; i < nargs; ++i) {
+    if (!q.kernelParams[i]) return false;
+    k.argv[i] = 0;
+    memcpy(&k.argv[i], q.kernelParams[i], (size_t)sizes[i]);
+  }
+  k.node = node;
+  k.p = q;
+  k.p.kernelParams = nullptr;          // (linked to k.args when an argument is patched)
+  k.p.extra = nullptr;
+  return true;
+}
+
+// Re-point argument `slot` of a captured kernel in the instantiated graph
+bool patch_pointer(hipGraphExec_t exec, ttnet_plan::GraphEntry::Kernel &k, int slot, const void *ptr) {
+  k.argv[slot] = (uint64_t)(uintptr_t)ptr;
+  k.p.kernelParams = k.args;          // (the entry may have been moved since capture)
+  for (size_t i = 0; i < std::size(k.args); ++i) k.args[i] = &k.argv[i];
+  return hipGraphExecKernelNodeSetParams(exec, k.node, &k.p) == hipSuccess;
+}
+
+// *status: what forward_eager returned inside the capture (a caller error -- bad argument, range flag -- is reported to
+// the caller as such and does not turn graph replay off for the plan; only a failure of the capture machinery does)
+bool capture_forward(ttnet_plan *pl, ttnet_plan::Lane &L, const void *x_dev, bool u8, int64_t n, float *logits_dev, ttnet_plan::GraphEntry &e, int *status) {
+  *status = TTNET_OK;
+  if (!pl->cap_stream && hipStreamCreateWithFlags(&pl->cap_stream, hipStreamNonBlocking) != hipSuccess) return false;
+  if (hipStreamBeginCapture(pl->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return false;
+  const int r = forward_eager(pl, L, x_dev, u8, n, logits_dev, pl->cap_stream);
+  hipGraph_t g = nullptr;
+  const hipError_t ee = hipStreamEndCapture(pl->cap_stream, &g);
+  if (r != TTNET_OK || ee != hipSuccess || !g) {
+    if (g) (void)hipGraphDestroy(g);
+    (void)hipGetLastError();
+    *status = r;
+    return false;
+  }
+  e.graph = g;
+  if (hipGraphInstantiate(&e.exec, g, nullptr, nullptr, 0) != hipSuccess) return false;
+  // a single chain: walk from the root to the leaf
+  hipGraphNode_t node = nullptr;
+  size_t cnt = 1;
+  if (hipGraphGetRootNodes(g, &node, &cnt) != hipSuccess || cnt != 1) return false;
+  const hipGraphNode_t first = node;
+  for (int guard = 0; guard < 1000; ++guard) {
+    size_t nd = 0;
+    if (hipGraphNodeGetDependentNodes(node, nullptr, &nd) != hipSuccess) return false;
+    if (nd == 0) break;
+    if (nd != 1) return false;
+    hipGraphNode_t next = nullptr;
+    if (hipGraphNodeGetDependentNodes(node, &next, &nd) != hipSuccess) return false;
+    node = next;
+  }
+  if (first == node || !own_params(first, pl->path == GatePath::VAlexnet ? va_stem_kernel_arg_sizes : stem_kernel_arg_sizes, e.first) ||
+      !own_params(node, lin2_kernel_arg_sizes, e.last))
+    return false;
+  // the two slots that will be patched must hold exactly the pointers this capture ran with
+  if (e.first.argv[0] != (uint64_t)(uintptr_t)x_dev || e.last.argv[kLastKernelOutArg] != (uint64_t)(uintptr_t)logits_dev ||
+      e.last.argv[kLastKernelBatchArg] != (uint64_t)n)
+    return false;
+  e.x = x_dev;
+  e.out = logits_dev;
+  return true;
+}
+
+int forward_impl(ttnet_plan *pl, int lane, const void *x_dev, bool u8, int64_t n, float *logits_dev, void *stream) {
+  TT_TRY(check_ready(pl, x_dev, n, logits_dev));
+  // The input contract of ttnet.h (16-byte aligned float32, 4-byte aligned uint8: the stem reads it with 16 / 12-byte
+  // buffer loads) is checked HERE, in front of the replay, the capture and the plain path alike: a cached graph
+  // only has its first argument re-pointed and would otherwise take any pointer.
+  if (pl->path != GatePath::VAlexnet && ((uintptr_t)x_dev & (u8 ? 3u : 15u)) != 0) {
+    set_error("forward: the input must be %d-byte aligned", u8 ? 4 : 16);
+    return TTNET_E_INVALID;
+  }
+  if (((uintptr_t)logits_dev & 3u) != 0) {
+    set_error("forward: the logits buffer must be 4-byte aligned");
+    return TTNET_E_INVALID;
+  }
+  if (lane < 0 || lane >= (int)pl->lanes.size()) {
+    set_error("forward: lane %d but the plan has %d (ttnet_plan_set_lanes)", lane, (int)pl->lanes.size());
+    return TTNET_E_INVALID;
+  }
+  pl->last_lane = lane;
+  ttnet_plan::Lane &L = pl->lanes[lane];
+  hipStream_t s = (hipStream_t)stream;
+  if (pl->profiling || !pl->graphs_ok) return forward_eager(pl, L, x_dev, u8, n, logits_dev, s);
+  const int64_t key = 2 * n + (u8 ? 1 : 0);               // one graph per (batch size, input kind)
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (s && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return forward_eager(pl, L, x_dev, u8, n, logits_dev, s);   // the caller is capturing us into a graph of their own
+  auto it = L.graphs.find(key);
+  if (it == L.graphs.end()) {
+    if (++L.eager_calls[key] <= 2) return forward_eager(pl, L, x_dev, u8, n, logits_dev, s);   // warm: attributes, lazy module load
+    ttnet_plan::GraphEntry e;
+    int cap_status = TTNET_OK;
+    if (!capture_forward(pl, L, x_dev, u8, n, logits_dev, e, &cap_status)) {
+      drop_graph(e);
+      if (cap_status != TTNET_OK) {          // the forward itself refused the call: the caller's error, graphs stay on
+        --L.eager_calls[key];
+        return cap_status;
+      }
+      graphs_off(pl, "capture or instantiation of the forward failed");   // stay on plain launches
+      return forward_eager(pl, L, x_dev, u8, n, logits_dev, s);
+    }
+    pl->graph_captures++;
+    if (L.graphs.size() >= 8) {                                // bound the cache: drop the smallest batch size
+      // its last replay may still be running on a stream this call knows nothing about
+      TT_HIP(hipDeviceSynchronize());
+      drop_graph(L.graphs.begin()->second);
+      L.graphs.erase(L.graphs.begin());
+      pl->graph_drops++;
+    }
+    it = L.graphs.emplace(key, e).first;
+  }
+  ttnet_plan::GraphEntry &e = it->second;
+  bool ok = true;
+  if (e.x != x_dev) {
+    ok = patch_pointer(e.exec, e.first, 0, x_dev);
+    e.x = x_dev;
+  }
+  if (ok && e.out != logits_dev) {
+    ok = patch_pointer(e.exec, e.last, kLastKernelOutArg, logits_dev);
+    e.out = logits_dev;
+  }
+  if (ok) ok = hipGraphLaunch(e.exec, s) == hipSuccess;
+  if (!ok) {
+    drop_graph(e);
+    L.graphs.erase(it);
+    graphs_off(pl, "hipGraphExecKernelNodeSetParams / hipGraphLaunch failed");
+    return forward_eager(pl, L, x_dev, u8, n, logits_dev, s);
+  }
+  L.last_n = n;
+  pl->timing_used = 0;
+  pl->graph_replays++;
+  return TTNET_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -972,16 +1288,16 @@ int ttnet_plan_create(const ttnet_net_desc *desc, int device, ttnet_plan **out) 
     return TTNET_E_INVALID;
   }
   TT_HIP(hipSetDevice(device));
-  std::unique_ptr<ttnet_plan> pl(new ttnet_plan());
+  ttnet_plan *pl = new ttnet_plan();
   pl->desc = *desc;
   pl->device = device;
-  int st = build_geometry(pl.get());
-  if (st == TTNET_OK) st = allocate(pl.get());
+  int st = build_geometry(pl);
+  if (st == TTNET_OK) st = allocate(pl);
   if (st != TTNET_OK) {
-    for (void *ptr : pl->owned) (void)hipFree(ptr);
+    ttnet_plan_destroy(pl);
     return st;
   }
-  *out = pl.release();
+  *out = pl;
   return TTNET_OK;
 }
 
@@ -1036,199 +1352,21 @@ int ttnet_plan_finalize(ttnet_plan *pl, void *stream) {
     TT_TRY(fold_bn(pl, "features.2", sc, sh));
     TT_TRY(upload_f32(pl->va_scale, sc));
     TT_TRY(upload_f32(pl->va_shift, sh));
-    for (BlockTT *b : all_block_tts(pl)) TT_TRY(build_table(pl, *b, s));
-    TT_TRY(fold_bn(pl, "features.7.BN2", sc, sh));
-    float ws1 = 1.f;
-    {
-      std::vector<float> w1;
-      TT_TRY(fetch(pl->tensors["features.7.lin1.weight"], w1));
-      ws1 = weight_prescale(w1.data(), w1.size());
-    }
-    for (double &v : sc) v /= (double)ws1 * ACT_PRESCALE;      // operand prescales (powers of two) out of lin1's result
-    TT_TRY(upload_f32(pl->bn_scale, sc));
-    TT_TRY(upload_f32(pl->bn_shift, sh));
-    TT_TRY(launch_split_to_frag((const float *)pl->tensors["features.7.lin1.weight"].dev, pl->w1f, pl->inter, pl->fcsize, 128, ws1,
-                                s));
-    TT_TRY(prepare_lin2(pl, "features.7.lin2.weight", s));
-    TT_HIP(hipStreamSynchronize(s));
-    TT_TRY(read_near_ties(pl));
-    pl->finalized = true;
-    return TTNET_OK;
-  }
-  // stem: BN scale folded into the weights, which are split into two prescaled fp16 planes in MFMA
-  // fragment order; BN shift as the weights of one more k-row (stem.hip)
-  {
-    std::vector<float> w;
-    TT_TRY(fetch(pl->tensors["features.1.weight"], w));
-    std::vector<uint16_t> wf(stem_split_weights_elems());
-    std::vector<double> sc, sh;
-    TT_TRY(fold_bn(pl, "features.2", sc, sh));
-    float init[64];
-    if (!stem_split_weights(w.data(), sc.data(), sh.data(), pl->p, wf.data(), init)) {
-      set_error("stem: the folded BatchNorm shift of features.2 is outside the range of the split operands");
-      return TTNET_E_UNSUPPORTED;
-    }
-    TT_HIP(hipMemcpy(pl->stem_wt, wf.data(), wf.size() * 2, hipMemcpyHostToDevice));
-    TT_HIP(hipMemcpy(pl->stem_init, init, sizeof(init), hipMemcpyHostToDevice));
+  } else {
+    TT_TRY(prepare_stem(pl));
     TT_TRY(prepare_stem_u8(pl));
   }
   for (auto &mh : pl->blocks) {
-    for (BlockTT *b : {&mh.c1, &mh.c2, &mh.c3, &mh.cf}) TT_TRY(build_table(pl, *b, s));
+    for (BlockTT *b : {&mh.c1, &mh.c2, &mh.c3, &mh.cf})
+      if (!b->g.name.empty()) TT_TRY(build_table(pl, *b, s));
     if (pl->path == GatePath::Fused) TT_TRY(launch_fused_images(mh.c1.table, mh.c2.table, mh.c3.table, mh.C, mh.img_dw, mh.img_c3, s));
   }
-  {
-    std::vector<double> sc, sh;
-    TT_TRY(fold_bn(pl, pl->head + ".BN2", sc, sh));
-    float ws1 = 1.f;
-    {
-      std::vector<float> w1;
-      TT_TRY(fetch(pl->tensors[pl->head + ".lin1.weight"], w1));
-      ws1 = weight_prescale(w1.data(), w1.size());
-    }
-    for (double &v : sc) v /= (double)ws1 * ACT_PRESCALE;      // operand prescales (powers of two) out of lin1's result
-    TT_TRY(upload_f32(pl->bn_scale, sc));
-    TT_TRY(upload_f32(pl->bn_shift, sh));
-    TT_TRY(launch_permute_lin1((const float *)pl->tensors[pl->head + ".lin1.weight"].dev, pl->w1p, pl->inter,
-                               pl->featC / 16, pl->featPP, s));
-    TT_TRY(launch_split_to_frag(pl->w1p, pl->w1f, pl->inter, pl->fcsize, (pl->inter + 127) / 128 * 128, ws1, s));
-    TT_TRY(prepare_lin2(pl, pl->head + ".lin2.weight", s));
-  }
+  TT_TRY(prepare_head(pl, s));
   TT_HIP(hipStreamSynchronize(s));
   TT_TRY(read_near_ties(pl));
   pl->finalized = true;
   return TTNET_OK;
 }
-
-namespace {
-
-int forward_eager(ttnet_plan *pl, ttnet_plan::Lane &L, const void *x_dev, bool u8, int64_t n, float *logits_dev, hipStream_t s) {
-  pl->timing_used = 0;
-  if (pl->path == GatePath::VAlexnet) {
-    if (u8) {
-      set_error("uint8 input is not implemented for the vAlexnet variant");
-      return TTNET_E_UNSUPPORTED;
-    }
-    TT_TIMED(pl, "va.stem", s,
-             launch_va_stem((const float *)x_dev, (const float *)pl->tensors["features.0.weight"].dev,
-                            (const float *)pl->tensors["features.0.bias"].dev, pl->va_scale, pl->va_shift, L.x_rp[0],
-                            (int)n, s));
-  } else {
-    TT_TIMED(pl, "stem", s,
-             launch_stem(x_dev, u8, pl->norm_tab, u8 ? pl->stem_wt_u8 : pl->stem_wt, u8 ? pl->stem_init_u8 : pl->stem_init, L.x_rp[0],
-                         pl->path == GatePath::TwoLaunch ? L.x_cp[0] : nullptr, (int)n, pl->p, pl->range_dev, s,
-                         (pl->lanes.size() >= 2 && !u8 && pl->path != GatePath::Full) ? 128 : 256));      // (stem.hip: half the CUs for float32 input with batches in flight)
-  }
-  return run_from_blocks(pl, L, (int)n, logits_dev, s);
-}
-
-// The forward is a fixed chain of ~11 launches whose host cost (~20 us each) equals the device
-// time at batch 256, so from the third call with a given batch size on it is replayed as a
-// hipGraph captured on a private stream.  Only two pointers change between calls: the input
-// (argument 0 of the first kernel) and the logits (argument 4 of lin2, the last kernel); they
-// are patched into the instantiated graph when they differ from the previous call.
-constexpr int kLastKernelArgs = 8, kLastKernelOutArg = 4;
-
-void drop_graph(ttnet_plan::GraphEntry &e) {
-  if (e.exec) (void)hipGraphExecDestroy(e.exec);
-  if (e.graph) (void)hipGraphDestroy(e.graph);
-  e = ttnet_plan::GraphEntry{};
-}
-
-int invalidate_graphs(ttnet_plan *pl) {
-  bool any = false;
-  for (auto &l : pl->lanes) any = any || !l.graphs.empty();
-  if (any) TT_HIP(hipDeviceSynchronize());
-  for (auto &l : pl->lanes) {
-    for (auto &kv : l.graphs) {
-      drop_graph(kv.second);
-      pl->graph_drops++;
-    }
-    l.graphs.clear();
-    l.eager_calls.clear();
-  }
-  return TTNET_OK;
-}
-
-void graphs_off(ttnet_plan *pl, const char *why) {
-  pl->graphs_ok = false;
-  pl->graph_off_reason = why;
-  (void)hipGetLastError();
-}
-
-// Copy a kernel node's launch parameters into storage we own.  sizes[i] = byte size of argument i.
-// (The arrays returned by hipGraphKernelNodeGetParams belong to the node: they are read once,
-// here, and never handed back to the runtime.)
-bool own_params(hipGraphNode_t node, const int *sizes, int nargs, hipKernelNodeParams &p, uint64_t *argv, void **args) {
-  hipKernelNodeParams q{};
-  if (hipGraphKernelNodeGetParams(node, &q) != hipSuccess || !q.kernelParams || q.extra) return false;
-  for (int i = 0; i < nargs; ++i) {
-    if (!q.kernelParams[i]) return false;
-    argv[i] = 0;
-    memcpy(&argv[i], q.kernelParams[i], (size_t)sizes[i]);
-    args[i] = &argv[i];
-  }
-  p = q;
-  p.kernelParams = args;
-  p.extra = nullptr;
-  return true;
-}
-
-// *status: what forward_eager returned inside the capture (a caller error -- bad argument, range flag -- is reported to
-// the caller as such and does not turn graph replay off for the plan; only a failure of the capture machinery does)
-bool capture_forward(ttnet_plan *pl, ttnet_plan::Lane &L, const void *x_dev, bool u8, int64_t n, float *logits_dev, ttnet_plan::GraphEntry &e, int *status) {
-  *status = TTNET_OK;
-  if (!pl->cap_stream && hipStreamCreateWithFlags(&pl->cap_stream, hipStreamNonBlocking) != hipSuccess) return false;
-  if (hipStreamBeginCapture(pl->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return false;
-  const int r = forward_eager(pl, L, x_dev, u8, n, logits_dev, pl->cap_stream);
-  hipGraph_t g = nullptr;
-  const hipError_t ee = hipStreamEndCapture(pl->cap_stream, &g);
-  if (r != TTNET_OK || ee != hipSuccess || !g) {
-    if (g) (void)hipGraphDestroy(g);
-    (void)hipGetLastError();
-    *status = r;
-    return false;
-  }
-  e.graph = g;
-  if (hipGraphInstantiate(&e.exec, g, nullptr, nullptr, 0) != hipSuccess) return false;
-  // a single chain: walk from the root to the leaf
-  hipGraphNode_t node = nullptr;
-  size_t cnt = 1;
-  if (hipGraphGetRootNodes(g, &node, &cnt) != hipSuccess || cnt != 1) return false;
-  e.first = node;
-  for (int guard = 0; guard < 1000; ++guard) {
-    size_t nd = 0;
-    if (hipGraphNodeGetDependentNodes(node, nullptr, &nd) != hipSuccess) return false;
-    if (nd == 0) break;
-    if (nd != 1) return false;
-    hipGraphNode_t next = nullptr;
-    if (hipGraphNodeGetDependentNodes(node, &next, &nd) != hipSuccess) return false;
-    node = next;
-  }
-  e.last = node;
-  hipGraphNodeType t0, t1;
-  if (hipGraphNodeGetType(e.first, &t0) != hipSuccess || hipGraphNodeGetType(e.last, &t1) != hipSuccess ||
-      t0 != hipGraphNodeTypeKernel || t1 != hipGraphNodeTypeKernel || e.first == e.last)
-    return false;
-  const int *first_sizes = nullptr;                               // stem_pc_kernel's arguments, from the file that declares it
-  const int first_n = stem_kernel_arg_sizes(&first_sizes);
-  static const int first_sizes_va[7] = {8, 8, 8, 8, 8, 8, 4};     // va_stem_kernel(x, w, bias, scale, shift, rp, n)
-  static const int last_sizes[8] = {8, 8, 8, 4, 8, 4, 4, 4};      // lin2_f16x2_kernel(A, B, bias, inv, out, M, N, KS)
-  const bool valexnet = pl->path == GatePath::VAlexnet;
-  e.first_nargs = valexnet ? 7 : first_n;
-  if (e.first_nargs > 12) return false;
-  if (!own_params(e.first, valexnet ? first_sizes_va : first_sizes, e.first_nargs, e.first_p, e.first_argv, e.first_args) ||
-      !own_params(e.last, last_sizes, kLastKernelArgs, e.last_p, e.last_argv, e.last_args))
-    return false;
-  // the two slots that will be patched must hold exactly the pointers this capture ran with
-  if (e.first_argv[0] != (uint64_t)(uintptr_t)x_dev || e.last_argv[kLastKernelOutArg] != (uint64_t)(uintptr_t)logits_dev ||
-      e.last_argv[5] != (uint64_t)n)
-    return false;
-  e.x = x_dev;
-  e.out = logits_dev;
-  return true;
-}
-
-}  // namespace
 
 int ttnet_plan_set_lanes(ttnet_plan *pl, int lanes) {
   if (!pl || lanes < 1 || lanes > 16) {
@@ -1273,7 +1411,7 @@ int ttnet_plan_table_usage_enable(ttnet_plan *pl, int enabled) {
     pl->usage_scheme_dw = pl->usage_scheme_pw = std::string(e) == "plain" ? kUsagePlain : kUsageMerged;
   int r = TTNET_OK;
   for (BlockTT *b : all_block_tts(pl)) {
-    if (r == TTNET_OK) r = dev_alloc(pl, &b->usage, (size_t)b->g.groups << b->g.nbits(), true, &pl->usage_bytes);
+    if (r == TTNET_OK) r = dev_alloc(pl, &b->usage, b->g.entries(), true, &pl->usage_bytes);
   }
   for (auto &l : pl->lanes)
     if (r == TTNET_OK) r = alloc_usage_scratch(pl, l);
@@ -1295,7 +1433,7 @@ int ttnet_plan_table_usage_reset(ttnet_plan *pl, void *stream) {
     return TTNET_E_STATE;
   }
   for (BlockTT *b : all_block_tts(pl))
-    TT_HIP(hipMemsetAsync(b->usage, 0, ((size_t)b->g.groups << b->g.nbits()) * sizeof(int64_t), (hipStream_t)stream));
+    TT_HIP(hipMemsetAsync(b->usage, 0, b->g.entries() * sizeof(int64_t), (hipStream_t)stream));
   return TTNET_OK;
 }
 
@@ -1321,12 +1459,8 @@ int ttnet_table_usage_add(ttnet_plan *pl, int lane, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   for (size_t i = 0; i < pl->blocks.size(); ++i) {
     const MultiHead &mh = pl->blocks[i];
-    // the block's input as uint64 rows
-    const uint64_t *xin = L.x_rp[i];
-    if (pl->path == GatePath::Fused && i > 0) {
-      TT_TIMED(pl, "usage.prep", s, launch_widen_rows(L.x_rp[i], L.u_rows, (size_t)n * mh.C * mh.H, mh.W, s));
-      xin = L.u_rows;
-    }
+    const uint64_t *xin = nullptr;
+    TT_TRY(block_input_rows(pl, L, i, n, L.u_rows, "usage.prep", s, &xin));
     for (const BlockTT *b : {&mh.c1, &mh.c2}) {
       const BlockGeom &g = b->g;
       const int ho = (mh.H + 2 * g.pad - g.kh) / g.stride + 1, wo = (mh.W + 2 * g.pad - g.kw) / g.stride + 1;
@@ -1335,33 +1469,13 @@ int ttnet_table_usage_add(ttnet_plan *pl, int lane, void *stream) {
     }
     TT_TIMED(pl, "usage.conv3", s,
              launch_usage_pw(&xin, 1, n, mh.C, mh.c3.g.groups, mh.c3.g.cin_g(), mh.H, mh.W, mh.c3.usage, pl->usage_scheme_pw, s));
-    // the four branch tensors after their padding, as uint64 rows [n][C][Ho]
-    std::array<uint64_t *, 4> br = branch_rows(L, i);
-    if (pl->path == GatePath::TwoLaunch) {
-      for (int k = 0; k < 4; ++k) {
-        TT_TIMED(pl, "usage.prep", s, launch_cp_to_rp(L.blk[i].o[k], L.u_br[k], n, mh.C, mh.Ho, mh.Wo, s));
-        br[k] = L.u_br[k];
-      }
-    } else if (pl->path == GatePath::Fused) {
-      // the branch tensors never reach HBM: a last block's dwords are its output, any other block is run once more
-      // on its (still resident) input with the lane's tap buffer attached -- it rewrites the next block's input
-      // with the same bits
-      const uint32_t *src = L.blk[i].idx;
-      if (!mh.last) {
-        FusedBlockArgs f{};
-        f.n = n; f.C = mh.C; f.H = mh.H; f.Ho = mh.Ho; f.off34 = mh.off34; f.last = 0;
-        f.x = L.x_rp[i]; f.img_c3 = mh.img_c3; f.img_dw = mh.img_dw; f.t_cf = (const uint8_t *)mh.cf.table;
-        f.y = L.x_rp[i + 1]; f.idx = L.u_tap;
-        TT_TIMED(pl, "usage.tap", s, launch_gate_block(f, s));
-        src = L.u_tap;
-      }
-      for (int k = 0; k < 4; ++k) {
-        TT_TIMED(pl, "usage.prep", s, launch_branch_rows(src, L.u_br[k], n, mh.C, mh.Ho, k, s));
-        br[k] = L.u_br[k];
-      }
-    }
+    // the four branch tensors after their padding (a non-last fused block is run again once, not once per branch)
+    const uint32_t *dwords = nullptr;
+    if (pl->path == GatePath::Fused) TT_TRY(fused_branch_dwords(pl, L, i, n, L.u_tap, "usage.tap", s, &dwords));
+    const uint64_t *br[4];
+    for (int k = 0; k < 4; ++k) TT_TRY(branch_as_rows(pl, L, i, k, n, dwords, L.u_br[k], "usage.prep", s, &br[k]));
     TT_TIMED(pl, "usage.convf", s,
-             launch_usage_pw(br.data(), 4, n, mh.C, mh.cf.g.groups, mh.cf.g.cin_g(), mh.Ho, mh.Wo, mh.cf.usage, pl->usage_scheme_pw, s));
+             launch_usage_pw(br, 4, n, mh.C, mh.cf.g.groups, mh.cf.g.cin_g(), mh.Ho, mh.Wo, mh.cf.usage, pl->usage_scheme_pw, s));
   }
   return TTNET_OK;
 }
@@ -1380,7 +1494,7 @@ int ttnet_plan_get_table_usage(ttnet_plan *pl, const char *name, int64_t *dst_ho
     set_error("no Block_TT named %s", name);
     return TTNET_E_INVALID;
   }
-  const size_t need = ((size_t)b->g.groups << b->g.nbits()) * sizeof(int64_t);
+  const size_t need = b->g.entries() * sizeof(int64_t);
   if (dst_bytes != need) {
     set_error("get_table_usage(%s): destination is %zu bytes, the counters are %zu", name, dst_bytes, need);
     return TTNET_E_INVALID;
@@ -1390,86 +1504,6 @@ int ttnet_plan_get_table_usage(ttnet_plan *pl, const char *name, int64_t *dst_ho
   TT_HIP(hipMemcpy(dst_host, b->usage, need, hipMemcpyDeviceToHost));
   return TTNET_OK;
 }
-
-namespace {
-int forward_impl(ttnet_plan *pl, int lane, const void *x_dev, bool u8, int64_t n, float *logits_dev, void *stream) {
-  TT_TRY(check_ready(pl, x_dev, n, logits_dev));
-  // The input contract of ttnet.h (16-byte aligned float32, 4-byte aligned uint8: the stem reads it with 16 / 12-byte
-  // buffer loads) is checked HERE, in front of the replay, the capture and the plain path alike: a cached graph
-  // only has its first argument re-pointed and would otherwise take any pointer.
-  if (pl->path != GatePath::VAlexnet && ((uintptr_t)x_dev & (u8 ? 3u : 15u)) != 0) {
-    set_error("forward: the input must be %d-byte aligned", u8 ? 4 : 16);
-    return TTNET_E_INVALID;
-  }
-  if (((uintptr_t)logits_dev & 3u) != 0) {
-    set_error("forward: the logits buffer must be 4-byte aligned");
-    return TTNET_E_INVALID;
-  }
-  if (lane < 0 || lane >= (int)pl->lanes.size()) {
-    set_error("forward: lane %d but the plan has %d (ttnet_plan_set_lanes)", lane, (int)pl->lanes.size());
-    return TTNET_E_INVALID;
-  }
-  pl->last_lane = lane;
-  ttnet_plan::Lane &L = pl->lanes[lane];
-  hipStream_t s = (hipStream_t)stream;
-  if (pl->profiling || !pl->graphs_ok) return forward_eager(pl, L, x_dev, u8, n, logits_dev, s);
-  const int64_t key = 2 * n + (u8 ? 1 : 0);               // one graph per (batch size, input kind)
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (s && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-    return forward_eager(pl, L, x_dev, u8, n, logits_dev, s);   // the caller is capturing us into a graph of their own
-  auto it = L.graphs.find(key);
-  if (it == L.graphs.end()) {
-    if (++L.eager_calls[key] <= 2) return forward_eager(pl, L, x_dev, u8, n, logits_dev, s);   // warm: attributes, lazy module load
-    ttnet_plan::GraphEntry e;
-    int cap_status = TTNET_OK;
-    if (!capture_forward(pl, L, x_dev, u8, n, logits_dev, e, &cap_status)) {
-      drop_graph(e);
-      if (cap_status != TTNET_OK) {          // the forward itself refused the call: the caller's error, graphs stay on
-        --L.eager_calls[key];
-        return cap_status;
-      }
-      graphs_off(pl, "capture or instantiation of the forward failed");   // stay on plain launches
-      return forward_eager(pl, L, x_dev, u8, n, logits_dev, s);
-    }
-    pl->graph_captures++;
-    if (L.graphs.size() >= 8) {                                // bound the cache: drop the smallest batch size
-      // its last replay may still be running on a stream this call knows nothing about
-      TT_HIP(hipDeviceSynchronize());
-      drop_graph(L.graphs.begin()->second);
-      L.graphs.erase(L.graphs.begin());
-      pl->graph_drops++;
-    }
-    it = L.graphs.emplace(key, e).first;
-  }
-  ttnet_plan::GraphEntry &e = it->second;
-  bool ok = true;
-  if (e.x != x_dev) {
-    e.first_argv[0] = (uint64_t)(uintptr_t)x_dev;
-    e.first_p.kernelParams = e.first_args;          // (the entry may have been moved since capture)
-    for (int i = 0; i < e.first_nargs; ++i) e.first_args[i] = &e.first_argv[i];
-    ok = hipGraphExecKernelNodeSetParams(e.exec, e.first, &e.first_p) == hipSuccess;
-    e.x = x_dev;
-  }
-  if (ok && e.out != logits_dev) {
-    e.last_argv[kLastKernelOutArg] = (uint64_t)(uintptr_t)logits_dev;
-    e.last_p.kernelParams = e.last_args;
-    for (int i = 0; i < kLastKernelArgs; ++i) e.last_args[i] = &e.last_argv[i];
-    ok = hipGraphExecKernelNodeSetParams(e.exec, e.last, &e.last_p) == hipSuccess;
-    e.out = logits_dev;
-  }
-  if (ok) ok = hipGraphLaunch(e.exec, s) == hipSuccess;
-  if (!ok) {
-    drop_graph(e);
-    L.graphs.erase(it);
-    graphs_off(pl, "hipGraphExecKernelNodeSetParams / hipGraphLaunch failed");
-    return forward_eager(pl, L, x_dev, u8, n, logits_dev, s);
-  }
-  L.last_n = n;
-  pl->timing_used = 0;
-  pl->graph_replays++;
-  return TTNET_OK;
-}
-}  // namespace
 
 int ttnet_forward_lane(ttnet_plan *pl, int lane, const float *x_dev, int64_t n, float *logits_dev, void *stream) {
   return forward_impl(pl, lane, x_dev, false, n, logits_dev, stream);
@@ -1537,61 +1571,52 @@ int ttnet_read_stage(ttnet_plan *pl, const char *stage, int64_t n, void *dst, si
     TT_HIP(hipStreamSynchronize(s));
     return check_range(pl);
   };
-  // a stage kept in another layout: convert(tmp) writes it in the ABI's layout into a temporary of `bytes`
-  auto convert_out = [&](size_t bytes, auto convert) -> int {
-    void *tmp = nullptr;
-    TT_HIP(hipMalloc(&tmp, bytes));
-    int r = convert(tmp);
-    if (r == TTNET_OK) r = copy_out(tmp, bytes);
-    (void)hipFree(tmp);
-    return r;
-  };
+  // a stage kept in another layout is converted to the ABI's into this temporary (copy_out synchronises before it goes)
+  struct Scratch {
+    void *p = nullptr;
+    ~Scratch() { (void)hipFree(p); }
+  } tmp;
   const GatePath path = pl->path;
-  if (st == "flatten")
-    return convert_out((size_t)n * pl->fcsize * 4, [&](void *tmp) {
-      return path == GatePath::VAlexnet ? launch_va_frag_to_flat(L.feat, (float *)tmp, (int)n, s)
-                                        : launch_frag_to_reference_order(L.feat, (float *)tmp, (int)n, pl->featC / 16, pl->featPP, s);
-    });
+  if (st == "flatten") {
+    const size_t bytes = (size_t)n * pl->fcsize * 4;
+    TT_HIP(hipMalloc(&tmp.p, bytes));
+    TT_TRY(path == GatePath::VAlexnet ? launch_va_frag_to_flat(L.feat, (float *)tmp.p, (int)n, s)
+                                      : launch_frag_to_reference_order(L.feat, (float *)tmp.p, (int)n, pl->featC / 16, pl->featPP, s));
+    return copy_out(tmp.p, bytes);
+  }
   if (path == GatePath::VAlexnet) {
     if (st == "features.4") return copy_out(L.x_rp[0], (size_t)n * 64 * 10 * 8);
     if (st == "features.5") return copy_out(L.va_y, (size_t)n * 256 * 11 * 8);
     set_error("unknown stage %s", stage);
     return TTNET_E_INVALID;
   }
+  const uint64_t *rows = nullptr;
   for (size_t i = 0; i < pl->blocks.size(); ++i) {
     const MultiHead &mh = pl->blocks[i];
     const std::string in_name = i == 0 ? std::string("features.3") : pl->blocks[i - 1].name;
     if (st == in_name) {
-      const size_t rows = (size_t)n * mh.C * mh.H;
-      if (path == GatePath::Fused && i > 0)           // compact rows -> the uint64 rows of the ABI
-        return convert_out(rows * 8, [&](void *tmp) { return launch_widen_rows(L.x_rp[i], (uint64_t *)tmp, rows, mh.W, s); });
-      return copy_out(L.x_rp[i], rows * 8);
+      const size_t bytes = (size_t)n * mh.C * mh.H * 8;
+      TT_HIP(hipMalloc(&tmp.p, bytes));
+      TT_TRY(block_input_rows(pl, L, i, (int)n, (uint64_t *)tmp.p, nullptr, s, &rows));
+      return copy_out(rows, bytes);
     }
     for (int b = 0; b < 4; ++b) {
       if (st != mh.name + ".out" + std::to_string(b + 1)) continue;
-      const size_t words = (size_t)n * mh.C * mh.Ho;
-      if (path == GatePath::XSmall || path == GatePath::Full) return copy_out(L.blk[i].o[b], words * 8);
-      if (path == GatePath::TwoLaunch)
-        return convert_out(words * 8, [&](void *tmp) { return launch_cp_to_rp(L.blk[i].o[b], (uint64_t *)tmp, (int)n, mh.C, mh.Ho, mh.Wo, s); });
-      // Fused: the branch tensors never reach HBM.  A last block's dwords are its output; for the others the
-      // block is run once more on its (still resident) input with the tap buffer attached
-      const uint32_t *src = L.blk[i].idx;
-      if (!mh.last) {
-        const size_t dwords = (size_t)pl->desc.max_batch * (mh.C / 8) * mh.Ho * mh.Wo;
-        if (pl->tap_elems < dwords) {
+      const uint32_t *dwords = nullptr;
+      if (path == GatePath::Fused) {
+        const size_t tap_elems = (size_t)pl->desc.max_batch * (mh.C / 8) * mh.Ho * mh.Wo;
+        if (!mh.last && pl->tap_elems < tap_elems) {
           uint32_t *t = nullptr;
-          TT_TRY(dev_alloc(pl, &t, dwords, true));
+          TT_TRY(dev_alloc(pl, &t, tap_elems, true));
           pl->tap = t;
-          pl->tap_elems = dwords;
+          pl->tap_elems = tap_elems;
         }
-        FusedBlockArgs f{};
-        f.n = (int)n; f.C = mh.C; f.H = mh.H; f.Ho = mh.Ho; f.off34 = mh.off34; f.last = 0;
-        f.x = L.x_rp[i]; f.img_c3 = mh.img_c3; f.img_dw = mh.img_dw; f.t_cf = (const uint8_t *)mh.cf.table;
-        f.y = L.x_rp[i + 1]; f.idx = pl->tap;
-        TT_TRY(launch_gate_block(f, s));
-        src = pl->tap;
+        TT_TRY(fused_branch_dwords(pl, L, i, (int)n, pl->tap, nullptr, s, &dwords));
       }
-      return convert_out(words * 8, [&](void *tmp) { return launch_branch_rows(src, (uint64_t *)tmp, (int)n, mh.C, mh.Ho, b, s); });
+      const size_t bytes = (size_t)n * mh.C * mh.Ho * 8;
+      TT_HIP(hipMalloc(&tmp.p, bytes));
+      TT_TRY(branch_as_rows(pl, L, i, b, (int)n, dwords, (uint64_t *)tmp.p, nullptr, s, &rows));
+      return copy_out(rows, bytes);
     }
   }
   set_error("unknown stage %s", stage);
@@ -1599,93 +1624,19 @@ int ttnet_read_stage(ttnet_plan *pl, const char *stage, int64_t n, void *dst, si
 }
 
 int ttnet_plan_get_table(ttnet_plan *pl, const char *name, void *dst_host, size_t dst_bytes) {
-  if (!pl || !name || !dst_host) {
-    set_error("null argument");
-    return TTNET_E_INVALID;
-  }
-  BlockTT *b = find_block(pl, name);
-  if (!b) {
-    set_error("no Block_TT named %s", name);
-    return TTNET_E_INVALID;
-  }
-  if (pl->path == GatePath::Full) {
-    set_error("the full variant (fan-in 30) has no truth tables: 2^30 entries per output bit");
-    return TTNET_E_UNSUPPORTED;
-  }
-  if (!pl->finalized) {
-    set_error("get_table before finalize");
-    return TTNET_E_STATE;
-  }
-  const BlockGeom &g = b->g;
-  const size_t entries = (size_t)1 << g.nbits();
-  const size_t need = (size_t)g.groups * entries * g.cout_g() * (g.last ? 4 : 1);
-  if (dst_bytes != need) {
-    set_error("get_table(%s): destination is %zu bytes, table is %zu", name, dst_bytes, need);
-    return TTNET_E_INVALID;
-  }
-  std::vector<uint8_t> raw(g.table_bytes());
+  BlockTT *b = nullptr;
+  TT_TRY(table_block(pl, name, dst_host, dst_bytes, true, &b));
+  std::vector<uint8_t> raw(b->g.table_bytes());
   TT_HIP(hipMemcpy(raw.data(), b->table, raw.size(), hipMemcpyDeviceToHost));
-  const int cg = g.cout_g(), eb = g.entry_bits();
-  const size_t words_1 = entries >= 32 ? entries / 32 : 1;   // striped 1-bit layout: [grp/16][w][grp%16]
-  const uint32_t *raw32 = (const uint32_t *)raw.data();
-  for (int grp = 0; grp < g.groups; ++grp)
-    for (uint32_t idx = 0; idx < entries; ++idx) {
-      const size_t ci = canonical_index(*b, idx);
-      if (g.last) {
-        memcpy((float *)dst_host + ((size_t)grp * entries + ci) * cg,
-               (const float *)raw.data() + ((size_t)grp * entries + idx) * cg, (size_t)cg * 4);
-        continue;
-      }
-      uint32_t bits;
-      if (eb == 1) bits = (raw32[((size_t)(grp >> 4) * words_1 + (idx >> 5)) * 16 + (grp & 15)] >> (idx & 31)) & 1u;
-      else if (eb == 8) bits = raw[(size_t)grp * entries + idx];
-      else bits = ((const uint16_t *)raw.data())[(size_t)grp * entries + idx];
-      uint8_t *d = (uint8_t *)dst_host + ((size_t)grp * entries + ci) * cg;
-      for (int o = 0; o < cg; ++o) d[o] = (bits >> o) & 1u;
-    }
+  walk_table(*b, raw.data(), dst_host, false);
   return TTNET_OK;
 }
 
 int ttnet_plan_set_table(ttnet_plan *pl, const char *name, const void *src_host, size_t src_bytes) {
-  if (!pl || !name || !src_host) {
-    set_error("null argument");
-    return TTNET_E_INVALID;
-  }
-  BlockTT *b = find_block(pl, name);
-  if (!b) {
-    set_error("no Block_TT named %s", name);
-    return TTNET_E_INVALID;
-  }
-  if (pl->path == GatePath::Full) {
-    set_error("the full variant (fan-in 30) has no truth tables: 2^30 entries per output bit");
-    return TTNET_E_UNSUPPORTED;
-  }
-  const BlockGeom &g = b->g;
-  const size_t entries = (size_t)1 << g.nbits();
-  const size_t need = (size_t)g.groups * entries * g.cout_g() * (g.last ? 4 : 1);
-  if (src_bytes != need) {
-    set_error("set_table(%s): source is %zu bytes, table is %zu", name, src_bytes, need);
-    return TTNET_E_INVALID;
-  }
-  std::vector<uint8_t> raw(g.table_bytes(), 0);
-  const int cg = g.cout_g(), eb = g.entry_bits();
-  const size_t words_1 = entries >= 32 ? entries / 32 : 1;
-  uint32_t *raw32 = (uint32_t *)raw.data();
-  for (int grp = 0; grp < g.groups; ++grp)
-    for (uint32_t idx = 0; idx < entries; ++idx) {
-      const size_t ci = canonical_index(*b, idx);
-      if (g.last) {
-        memcpy((float *)raw.data() + ((size_t)grp * entries + idx) * cg,
-               (const float *)src_host + ((size_t)grp * entries + ci) * cg, (size_t)cg * 4);
-        continue;
-      }
-      const uint8_t *sp = (const uint8_t *)src_host + ((size_t)grp * entries + ci) * cg;
-      uint32_t bits = 0;
-      for (int o = 0; o < cg; ++o) bits |= (uint32_t)(sp[o] & 1u) << o;
-      if (eb == 1) raw32[((size_t)(grp >> 4) * words_1 + (idx >> 5)) * 16 + (grp & 15)] |= bits << (idx & 31);
-      else if (eb == 8) raw[(size_t)grp * entries + idx] = (uint8_t)bits;
-      else ((uint16_t *)raw.data())[(size_t)grp * entries + idx] = (uint16_t)bits;
-    }
+  BlockTT *b = nullptr;
+  TT_TRY(table_block(pl, name, src_host, src_bytes, false, &b));
+  std::vector<uint8_t> raw(b->g.table_bytes(), 0);
+  walk_table(*b, raw.data(), const_cast<void *>(src_host), true);      // (storing only reads the canonical side)
   TT_HIP(hipSetDevice(pl->device));
   TT_TRY(invalidate_graphs(pl));
   TT_HIP(hipMemcpy(b->table, raw.data(), raw.size(), hipMemcpyHostToDevice));
@@ -1809,112 +1760,11 @@ void ttnet_plan_destroy(ttnet_plan *pl) {
     (void)hipEventDestroy(t.e1);
   }
   for (auto &l : pl->lanes)
-    for (auto &kv : l.graphs) {
-      if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-      if (kv.second.graph) (void)hipGraphDestroy(kv.second.graph);
-    }
+    for (auto &kv : l.graphs) drop_graph(kv.second);
   if (pl->cap_stream) (void)hipStreamDestroy(pl->cap_stream);
   if (pl->range_host) (void)hipHostFree(pl->range_host);
   for (void *ptr : pl->owned) (void)hipFree(ptr);
   delete pl;
-}
-
-// ---- logits all-gather over RCCL (xGMI) ------------------------------------------------------
-// librccl is resolved at first use so that a process which already carries an RCCL (e.g.
-// the one inside PyTorch-ROCm) keeps exactly one copy.
-
-struct ttnet_comm {
-  void *nccl = nullptr;
-  int rank = 0, world = 1, device = 0;
-};
-
-namespace {
-struct Id128 {
-  char b[128];   // ncclUniqueId, passed by value
-};
-struct Rccl {
-  void *lib = nullptr;
-  int (*GetUniqueId)(void *) = nullptr;
-  int (*CommInitRank)(void **, int, Id128, int) = nullptr;
-  int (*AllGather)(const void *, void *, size_t, int, void *, hipStream_t) = nullptr;
-  int (*CommDestroy)(void *) = nullptr;
-  const char *(*GetErrorString)(int) = nullptr;
-};
-Rccl g_rccl;
-
-int load_rccl() {
-  if (g_rccl.lib) return TTNET_OK;
-  const char *names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1", "/opt/rocm/lib/librccl.so"};
-  void *h = nullptr;
-  for (const char *nm : names) {
-    h = dlopen(nm, RTLD_NOW | RTLD_GLOBAL);
-    if (h) break;
-  }
-  if (!h) {
-    set_error("cannot load librccl: %s", dlerror());
-    return TTNET_E_UNSUPPORTED;
-  }
-  g_rccl.GetUniqueId = (decltype(g_rccl.GetUniqueId))dlsym(h, "ncclGetUniqueId");
-  g_rccl.CommInitRank = (decltype(g_rccl.CommInitRank))dlsym(h, "ncclCommInitRank");
-  g_rccl.AllGather = (decltype(g_rccl.AllGather))dlsym(h, "ncclAllGather");
-  g_rccl.CommDestroy = (decltype(g_rccl.CommDestroy))dlsym(h, "ncclCommDestroy");
-  g_rccl.GetErrorString = (decltype(g_rccl.GetErrorString))dlsym(h, "ncclGetErrorString");
-  if (!g_rccl.GetUniqueId || !g_rccl.CommInitRank || !g_rccl.AllGather || !g_rccl.CommDestroy) {
-    set_error("librccl lacks an expected symbol");
-    return TTNET_E_UNSUPPORTED;
-  }
-  g_rccl.lib = h;
-  return TTNET_OK;
-}
-
-int rccl_check(int r, const char *what) {
-  if (r == 0) return TTNET_OK;
-  set_error("%s failed: %s", what, g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "rccl error");
-  return TTNET_E_HIP;
-}
-}  // namespace
-
-int ttnet_comm_unique_id(void *id128) {
-  if (!id128) {
-    set_error("null argument");
-    return TTNET_E_INVALID;
-  }
-  TT_TRY(load_rccl());
-  return rccl_check(g_rccl.GetUniqueId(id128), "ncclGetUniqueId");
-}
-
-int ttnet_comm_create(const void *id128, int rank, int world, int device, ttnet_comm **out) {
-  if (!id128 || !out || world < 1 || rank < 0 || rank >= world) {
-    set_error("bad argument to ttnet_comm_create");
-    return TTNET_E_INVALID;
-  }
-  TT_TRY(load_rccl());
-  TT_HIP(hipSetDevice(device));
-  std::unique_ptr<ttnet_comm> c(new ttnet_comm());
-  c->rank = rank; c->world = world; c->device = device;
-  Id128 id;
-  memcpy(id.b, id128, 128);
-  TT_TRY(rccl_check(g_rccl.CommInitRank(&c->nccl, world, id, rank), "ncclCommInitRank"));
-  *out = c.release();
-  return TTNET_OK;
-}
-
-int ttnet_allgather_logits(ttnet_comm *comm, const float *local_dev, int64_t n_local, int64_t n_classes,
-                           float *all_dev, void *stream) {
-  if (!comm || !local_dev || !all_dev || n_local < 1 || n_classes < 1) {
-    set_error("bad argument to ttnet_allgather_logits");
-    return TTNET_E_INVALID;
-  }
-  // ncclFloat32 == 7
-  return rccl_check(g_rccl.AllGather(local_dev, all_dev, (size_t)(n_local * n_classes), 7, comm->nccl,
-                                     (hipStream_t)stream),
-                    "ncclAllGather");
-}
-
-void ttnet_comm_destroy(ttnet_comm *comm) {
-  if (!comm) return;
-  if (comm->nccl && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(comm->nccl);
-  delete comm;
 }
 
 }  // extern "C"

@@ -788,11 +788,11 @@ bool stem_split_weights_u8(const float *w, const double *scale, const double *sh
   return true;
 }
 
-// (x, wfrag, init, rp, cp, p, n, norm_tab, range_flag): keep in step with the kernel's signature
+// (every instantiation of stem_pc_kernel has the one signature)
 int stem_kernel_arg_sizes(const int **sizes) {
-  static const int kSizes[9] = {8, 8, 8, 8, 8, 4, 4, 8, 8};
-  *sizes = kSizes;
-  return 9;
+  using S = KernelArgSizes<decltype(&stem_pc_kernel<false, false, 1>)>;
+  *sizes = S::sizes;
+  return S::n;
 }
 
 int launch_stem(const void *x, bool x_is_u8, const uint32_t *norm_tab, const void *wfrag, const float *init, uint64_t *rp,

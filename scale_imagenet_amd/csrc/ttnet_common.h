@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 #include <algorithm>
 #include <string>
 #include <type_traits>
@@ -45,15 +46,59 @@ struct BlockGeom {
   int nbits() const { return cin_g() * kh * kw; }
   // internal table entry width in bits: 1 (bit-packed along the index), 8 or 16
   int entry_bits() const { return last ? 32 * cout_g() : (cout_g() == 1 ? 1 : (cout_g() <= 8 ? 8 : 16)); }
+  size_t entries() const { return (size_t)groups << nbits(); }      // table entries, all groups
+  // bytes of the table in the canonical order of the C ABI: [groups][2^n][cout_g] uint8 bits (float32 for a last block)
+  size_t canonical_bytes() const { return entries() * cout_g() * (last ? sizeof(float) : 1); }
   size_t table_bytes() const {
-    size_t entries = (size_t)groups << nbits();
-    if (last) return entries * cout_g() * sizeof(float);
+    if (last) return entries() * cout_g() * sizeof(float);
     if (entry_bits() == 1) {                       // one dword minimum per group (16-entry tables)
       const size_t per = ((size_t)1 << nbits()) / 8;
       return (size_t)groups * (per < 4 ? 4 : per);
     }
-    return entries * entry_bits() / 8;
+    return entries() * entry_bits() / 8;
   }
+};
+
+// The internal table layouts in one place (host; lut_build.hip's kernel writes them, the gate kernels read them):
+//   1-bit entries : dwords [grp / 16][idx / 32][grp % 16], bit idx % 32 -- 16 groups striped per dword row, one dword
+//                   minimum per group
+//   8 / 16 bits   : [grp][idx] uint8 / uint16, output o of the group in bit o
+//   last block    : [grp][idx][cout_g] float32
+// Entry (grp, internal index idx) of the table `raw`: its cout_g outputs are copied to `canon` (uint8 bits, floats for a
+// last block) or, with store, from it.  Storing ORs into a 1-bit table: start from a zeroed buffer.
+inline void table_entry(const BlockGeom &g, void *raw, int grp, uint32_t idx, void *canon, bool store) {
+  const int cg = g.cout_g(), eb = g.entry_bits();
+  const size_t per = (size_t)1 << g.nbits(), e = (size_t)grp * per + idx;
+  if (g.last) {
+    float *r = (float *)raw + e * cg;
+    if (store) memcpy(r, canon, (size_t)cg * sizeof(float));
+    else memcpy(canon, r, (size_t)cg * sizeof(float));
+    return;
+  }
+  const size_t w1 = ((size_t)(grp >> 4) * (per >= 32 ? per / 32 : 1) + (idx >> 5)) * 16 + (grp & 15);
+  uint8_t *c = (uint8_t *)canon;
+  if (store) {
+    uint32_t bits = 0;
+    for (int o = 0; o < cg; ++o) bits |= (uint32_t)(c[o] & 1u) << o;
+    if (eb == 1) ((uint32_t *)raw)[w1] |= bits << (idx & 31);
+    else if (eb == 8) ((uint8_t *)raw)[e] = (uint8_t)bits;
+    else ((uint16_t *)raw)[e] = (uint16_t)bits;
+  } else {
+    const uint32_t bits = eb == 1 ? (((const uint32_t *)raw)[w1] >> (idx & 31)) & 1u
+                                  : (eb == 8 ? ((const uint8_t *)raw)[e] : ((const uint16_t *)raw)[e]);
+    for (int o = 0; o < cg; ++o) c[o] = (bits >> o) & 1u;
+  }
+}
+
+// Byte sizes of a kernel's arguments, from its signature: KernelArgSizes<decltype(&kernel)>.  plan.hip re-points
+// arguments of captured graph nodes and must own a copy of every argument of those kernels; the files that define them
+// export their sizes through this (stem_kernel_arg_sizes, va_stem_kernel_arg_sizes, lin2_kernel_arg_sizes).
+template <typename F>
+struct KernelArgSizes;
+template <typename... A>
+struct KernelArgSizes<void (*)(A...)> {
+  static constexpr int n = (int)sizeof...(A);
+  static constexpr int sizes[sizeof...(A)] = {(int)sizeof(A)...};
 };
 
 #if defined(__HIPCC__)
@@ -221,8 +266,7 @@ bool stem_split_weights_u8(const float *w, const double *scale, const double *sh
 bool stem_split_weights(const float *w /*[p][3][7][7]*/, const double *scale, const double *shift, int p, uint16_t *out,
                         float *init /*[64]*/);
 size_t stem_split_weights_elems();
-// byte sizes of stem_pc_kernel's arguments, in order (plan.hip re-points the input of a captured graph node and
-// must own a copy of every argument); returns their number
+// byte sizes of stem_pc_kernel's arguments, in order (KernelArgSizes); returns their number
 int stem_kernel_arg_sizes(const int **sizes);
 
 // gate.hip
@@ -319,6 +363,7 @@ int launch_full_pool_split(const float *x, void *feat_frag, int n, int C, int H,
 // CIFAR vAlexnet variant (gate_va.hip)
 int launch_va_stem(const float *x, const float *w, const float *bias, const float *scale, const float *shift,
                    uint64_t *rp, int n, hipStream_t s);
+int va_stem_kernel_arg_sizes(const int **sizes);      // va_stem_kernel's, as stem_kernel_arg_sizes
 int launch_va_block(const uint64_t *x_rp, const void *t1, const void *t2, const void *t3, uint64_t *y, int n, hipStream_t s);
 int launch_va_feat(const uint64_t *y, void *feat_frag, int n, hipStream_t s);
 int launch_va_frag_to_flat(const void *af, float *out, int n, hipStream_t s);
@@ -343,6 +388,7 @@ int launch_head_mid(const float *part, int splits, const float *scale, const flo
 // logits[M][N] = mid[M][K] * W2[N][K]^T * inv + bias on split operands (w2f rows padded to 64)
 int launch_lin2_f16x2(const void *mid_frag, const void *w2f, const float *bias, float inv, float *out, int M, int N, int K,
                       hipStream_t s);
+int lin2_kernel_arg_sizes(const int **sizes);         // lin2_f16x2_kernel's, as stem_kernel_arg_sizes
 // W1p[o][(g*PP+pp)*16+k] = W1[o][(16g+k)*PP+pp]
 int launch_permute_lin1(const float *w1, float *w1p, int O, int G, int PP, hipStream_t s);
 

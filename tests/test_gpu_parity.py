@@ -490,6 +490,54 @@ def test_truth_table_export_from_gpu_tables(dev, tmp_path):
     assert compared >= 10
 
 
+@pytest.mark.parametrize("variant", ["small", "xsmall", "valexnet"])
+def test_table_round_trip_every_layout(dev, variant):
+    """get_table / set_table through every internal table layout: small at p = 16, --layers 0 has 1-bit striped
+    (conv1 / conv2), 16-bit (conv3), 8-bit (convf) and float (the last convf) tables, x-small at the same size the
+    16-entry 1-bit tables that are padded to one dword per group, vAlexnet its 64-entry 1-bit and 8-bit ones.  For
+    every Block_TT a seeded random table of the same shape and dtype must come back exactly as it was set; with
+    the originals set back the logits are bit-identical to those taken before the first set_table."""
+    from argparse import Namespace
+    from scale_imagenet_amd.spec import make_spec
+    if variant == "valexnet":
+        spec, st = spec_and_state("valexnet")
+        m = ttnet.TT_FHE_XSMALL_vAlexnet(args_for("valexnet"))
+        x = synth.synth_images(2, hw=(32, 32))
+    else:
+        spec = make_spec(variant, 2, 8, 0)
+        st = synth.synth_state_dict(spec, calibrated=False)
+        m = CLASSES[variant](Namespace(nfilter=2, tfilter=8, layers=0, groups=[1, None, 4, None]))
+        x = synth.synth_images(2)
+    m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in st.items()}, strict=True)
+    m = m.to(dev).eval().reserve(2)
+    x = torch.from_numpy(x).to(dev)
+    with torch.no_grad():
+        y0 = m(x).clone()
+    rng = np.random.default_rng(11)
+    seen = set()
+    for b in spec.block_tts():
+        orig = m.get_table(b.name)
+        assert orig.shape == (b.groups, 1 << b.fan_in_bits, b.cout_g)
+        if b.last:
+            rnd = rng.standard_normal(orig.shape).astype(np.float32)
+        else:
+            rnd = rng.integers(0, 2, size=orig.shape, dtype=np.uint8)
+        assert rnd.dtype == orig.dtype
+        m.set_table(b.name, rnd)
+        got = m.get_table(b.name)
+        assert got.dtype == rnd.dtype and np.array_equal(got, rnd), b.name
+        m.set_table(b.name, orig)
+        assert np.array_equal(m.get_table(b.name), orig), b.name
+        seen.add(("float" if b.last else 1 if b.cout_g == 1 else 8 if b.cout_g <= 8 else 16, 1 << b.fan_in_bits))
+    want = {"small": {(1, 65536), (16, 65536), (8, 65536), ("float", 65536)},
+            "xsmall": {(1, 16), (8, 16), ("float", 16)},
+            "valexnet": {(1, 64), (8, 256)}}[variant]
+    assert seen == want, seen                     # (entry width, entries per group) of the layouts walked
+    with torch.no_grad():
+        y1 = m(x).clone()
+    assert torch.equal(y1, y0)
+
+
 def test_ragged_batches_plan_regrowth_and_lanes(dev):
     """Batch sizes around the 32-image tile edges, a forward larger than the reserved workspace
     (the plan is rebuilt with the lanes it had), and both input kinds on both lanes: every result
