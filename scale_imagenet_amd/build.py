@@ -34,11 +34,12 @@ def build_lib(force: bool = False, verbose: bool = True) -> str:
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, "ttnet_common.h"), os.path.join(HERE, "..", "include", "ttnet.h")]
+    included = {"gate_full.hip": [os.path.join(CSRC, "erf_table.inc")]}
     jobs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
-        if force or _stale(o, [s] + headers):
+        if force or _stale(o, [s] + headers + included.get(src, [])):
             jobs.append([hipcc, *FLAGS, *EXTRA.get(src, []), "-c", s, "-o", o])
 
     def run(cmd):

@@ -9,7 +9,12 @@
 //
 // Everything stays on row-packed planes (uint64 per image row).  Bound: the float64 matrix pipe
 // (0.72 GFLOP per image in the two grouped convolutions of the 1x1 blocks: 4.7 ms per 512 images at
-// the 78.6 TFLOP/s FP64 peak) plus the GELU (a branch-free table erf, see gelu_exact).
+// the 78.6 TFLOP/s FP64 peak) plus the GELU (a branch-free table erf, see erf_abs).
+//
+// Each block kind has two evaluations: float64 throughout (full_dw_tab_kernel, full_pw_mfma_kernel<OT, false>;
+// TTNET_FULL_EXACT=1), and the default, a float32 / split-fp16 pass (full_dw_fast_kernel, full_pw_fast_kernel)
+// that lists the outputs whose sign it cannot vouch for, followed by a float64 pass over the list
+// (full_dw_fix_kernel, full_pw_mfma_kernel<OT, true>).  Both emit the same bits.
 
 #include <cstdlib>
 
@@ -18,6 +23,8 @@
 namespace ttnet {
 
 namespace {
+
+constexpr double kTwoM21 = 0x1p-21, kTwoM22 = 0x1p-22, kTwoM24 = 0x1p-24;
 
 // erf in float64 without branches: libm's erf picks one of five range-dependent algorithms per lane, so
 // a wave executes all of them (108 vector instructions per call, and the full model calls it 7.6 M times
@@ -32,8 +39,8 @@ __device__ const double kErfTable[kErfN][kErfC] = {
 __device__ inline void erf_table_to_lds(double *dst) {
   for (int i = threadIdx.x; i < kErfN * kErfC; i += blockDim.x) dst[i] = (&kErfTable[0][0])[i];
 }
-__device__ inline double gelu_exact(double z, const double *tab) {
-  const double x = z * 0.70710678118654752440, ax = __builtin_fabs(x);
+// erf(ax) for ax >= 0
+__device__ inline double erf_abs(double ax, const double *tab) {
   int i = (int)(ax * 8.0);
   i = i < kErfN - 1 ? i : kErfN - 1;
   const double t = ax - ((double)i + 0.5) * 0.125;
@@ -41,60 +48,42 @@ __device__ inline double gelu_exact(double z, const double *tab) {
   double p = c[8];
 #pragma unroll
   for (int k = 7; k >= 0; --k) p = fma(p, t, c[k]);
-  p = ax >= 6.0 ? 1.0 : p;
+  return ax >= 6.0 ? 1.0 : p;
+}
+__device__ inline double gelu_exact(double z, const double *tab) {
+  const double x = z * 0.70710678118654752440;
+  // (a statement of its own: called inside the return expression, the 0.5 z product is scheduled ahead of the polynomial
+  // in the float64 kernels' loops and lives through it)
+  const double p = erf_abs(__builtin_fabs(x), tab);
   return 0.5 * z * (1.0 + __builtin_copysign(p, x));
+}
+// the standard normal distribution function
+__device__ inline double Phi(double z, const double *tab) {
+  const double x = z * 0.70710678118654752440;
+  const double p = erf_abs(__builtin_fabs(x), tab);
+  return 0.5 * (1.0 + __builtin_copysign(p, x));
+}
+
+// sets (on) or clears one bit of a row word that other lanes are patching too
+__device__ inline void patch_bit(uint64_t *word, int bit, bool on) {
+  if (on) atomicOr((unsigned long long *)word, 1ull << bit);
+  else atomicAnd((unsigned long long *)word, ~(1ull << bit));
 }
 
 // ---- depthwise Block_TT: one input channel -> 8 mid -> 1 output ---------------------------------
 // grid (C, n-chunks); thread = (image, output row); weights of the channel in LDS.
-__global__ __launch_bounds__(256) void full_dw_kernel(FullDwArgs a) {
-  __shared__ double w1[8 * 36], s1[8], t1[8], w2[8], s2, t2;
-  __shared__ double erf_tab[kErfN * kErfC];
-  erf_table_to_lds(erf_tab);
-  const int c = blockIdx.x, nk = a.kh * a.kw;
-  for (int i = threadIdx.x; i < 8 * nk; i += blockDim.x) w1[i] = (double)a.w1[(size_t)c * 8 * nk + i];
-  if (threadIdx.x < 8) {
-    s1[threadIdx.x] = a.s1[c * 8 + threadIdx.x];
-    t1[threadIdx.x] = a.t1[c * 8 + threadIdx.x];
-    w2[threadIdx.x] = (double)a.w2[c * 8 + threadIdx.x];
-  }
-  if (threadIdx.x == 0) {
-    s2 = a.s2[c];
-    t2 = a.t2[c];
-  }
-  __syncthreads();
-  const int rows = a.n * a.ho;
-  for (int t = blockIdx.y * blockDim.x + threadIdx.x; t < rows; t += gridDim.y * blockDim.x) {
-    const int n = t / a.ho, oy = t % a.ho;
-    uint64_t r[6];
-    for (int kh = 0; kh < a.kh; ++kh) {
-      const int iy = oy * a.stride - a.pad + kh;
-      r[kh] = (iy >= 0 && iy < a.H) ? a.x_rp[((size_t)n * a.C + c) * a.H + iy] << a.pad : 0ull;   // bit 0 = column -pad
-    }
-    uint64_t out = 0;
-    for (int ox = 0; ox < a.wo; ++ox) {
-      double acc = 0.0;
-      for (int m = 0; m < 8; ++m) {
-        double s = 0.0;
-        for (int kh = 0; kh < a.kh; ++kh) {
-          const uint32_t bits = (uint32_t)(r[kh] >> (ox * a.stride));
-          for (int kw = 0; kw < a.kw; ++kw) s += ((bits >> kw) & 1u) ? w1[m * nk + kh * a.kw + kw] : 0.0;
-        }
-        acc = fma(gelu_exact(s * s1[m] + t1[m], erf_tab), w2[m], acc);
-      }
-      const double pre = acc * s2 + t2;
-      out |= (uint64_t)(pre >= 0.0) << (ox + a.pad_l);
-    }
-    a.out[((size_t)n * a.C + c) * a.Ho + oy + a.pad_t] = out;
-  }
+
+// row oy * stride - pad + kh of channel c, shifted so that bit 0 = column -pad; zero outside the image (or where !on)
+__device__ inline uint64_t window_row(const FullDwArgs &a, int n, int c, int oy, int kh, bool on = true) {
+  const int iy = oy * a.stride - a.pad + kh;
+  return (on && iy >= 0 && iy < a.H) ? a.x_rp[((size_t)n * a.C + c) * a.H + iy] << a.pad : 0ull;
 }
 
-// The same block with per-row partial sums from tables: the pre-activation of mid unit m is a sum
-// over the window rows of (sum over kw of w[m][kh][kw] x[kh][kw]), and a row has only KW <= 6 bits, so
-// that inner sum is a 2^KW-entry float64 table per (m, kh) (at most 20 KiB per channel, built in
-// LDS by the workgroup): KH lookups and adds per mid unit instead of KH*KW conditional adds.  (The
-// taps of a row are summed kw-ascending, the rows kh-ascending: another association than the
-// oracle's single running sum, a 1e-16 relative effect.)
+// Per-row partial sums from tables: the pre-activation of mid unit m is a sum over the window rows of
+// (sum over kw of w[m][kh][kw] x[kh][kw]), and a row has only KW <= 6 bits, so that inner sum is a 2^KW-entry
+// float64 table per (m, kh) (at most 20 KiB per channel, built in LDS by the workgroup): KH lookups and adds
+// per mid unit instead of KH*KW conditional adds.  (The taps of a row are summed kw-ascending, the rows
+// kh-ascending: another association than the oracle's single running sum, a 1e-16 relative effect.)
 template <int KH, int KW>
 __global__ __launch_bounds__(256) void full_dw_tab_kernel(FullDwArgs a) {
   __shared__ double tab[8][KH][1 << KW];
@@ -125,10 +114,7 @@ __global__ __launch_bounds__(256) void full_dw_tab_kernel(FullDwArgs a) {
     const int n = t / a.ho, oy = t % a.ho;
     uint64_t r[KH];
 #pragma unroll
-    for (int kh = 0; kh < KH; ++kh) {
-      const int iy = oy * a.stride - a.pad + kh;
-      r[kh] = (iy >= 0 && iy < a.H) ? a.x_rp[((size_t)n * a.C + c) * a.H + iy] << a.pad : 0ull;   // bit 0 = column -pad
-    }
+    for (int kh = 0; kh < KH; ++kh) r[kh] = window_row(a, n, c, oy, kh);
     uint64_t out = 0;
     for (int ox = 0; ox < a.wo; ++ox) {
       uint32_t idx[KH];
@@ -149,82 +135,35 @@ __global__ __launch_bounds__(256) void full_dw_tab_kernel(FullDwArgs a) {
   }
 }
 
-// ---- grouped 1x1 Block_TT with `cin` inputs per group ------------------------------------------
-// Input bit (group g, j): channel J = cin*g + j of either a plane tensor (conv3) or of the
+// ---- grouped 1x1 Block_TT: 30 inputs -> 240 hidden -> 30 or 15 outputs per group ------------------
+// Input bit (group g, j): channel J = 30 g + j of either a plane tensor (conv3) or of the
 // interleaved concat of four branch tensors (convf: channel J -> branch J%4, channel J/4;
-// models/TT_general_imagenet_v2.py:131-135).  One wave = one image row; lanes = columns.
-// Output: bits (ballot -> row words) or, for the last block, relu'd float32.
-// Generic version (any group shape that fits; the full model's 30 -> 240 -> 30 / 15 groups take the
-// matrix-instruction kernel below).  1024 threads share one copy of the group's weights in LDS (119 KiB for 30 -> 240 -> 30): sixteen
-// waves per CU hide the latency of the broadcast LDS reads that one wave per SIMD exposed (3x).
-// (Compile-time sizes with full unrolling were tried and were slower: more registers, same reads.)
-__global__ __launch_bounds__(1024) void full_pw_kernel(FullPwArgs a) {
-  extern __shared__ __align__(16) double lds[];
-  __shared__ double erf_tab[kErfN * kErfC];
-  erf_table_to_lds(erf_tab);
-  const int g = blockIdx.x, cin = a.cin, mid = a.mid, cout = a.cout;
-  double *w1 = lds;                      // [mid][cin]
-  double *w2 = w1 + mid * cin;           // [cout][mid]
-  double *s1 = w2 + cout * mid, *t1 = s1 + mid, *s2 = t1 + mid, *t2 = s2 + cout;
-  for (int i = threadIdx.x; i < mid * cin; i += blockDim.x) w1[i] = (double)a.w1[(size_t)g * mid * cin + i];
-  for (int i = threadIdx.x; i < cout * mid; i += blockDim.x) w2[i] = (double)a.w2[(size_t)g * cout * mid + i];
-  for (int i = threadIdx.x; i < mid; i += blockDim.x) {
-    s1[i] = a.s1[g * mid + i];
-    t1[i] = a.t1[g * mid + i];
+// models/TT_general_imagenet_v2.py:131-135).  Output: bits (ballots -> row words) or, for the last
+// block, relu'd float32.
+constexpr int kPwCin = 30, kPwMid = 240, kPwMT = kPwMid / 16;     // MT: tiles of 16 hidden units
+
+// A wave task covers as many whole image rows as fit its 64 lanes (one row of 56 pixels, two of 29,
+// four of 16, seven of 9): lane = (row r of the bundle, column x).  (One row per wave left 55-85 % of
+// the lanes idle in the later blocks.)
+struct RowBundle {
+  int W, rpw, bundles;                 // row width; rows per bundle, bundles per image
+  __host__ __device__ RowBundle(int H, int W_) : W(W_), rpw(64 / W_), bundles((H + rpw - 1) / rpw) {}
+  struct Pixel { int r, x; };          // row inside the bundle, column
+  __device__ Pixel pixel(int p) const {        // pixel p = 0 .. 63 of a bundle (r >= rpw: beyond it)
+    const int r = p / W;
+    return {r, p - r * W};
   }
-  for (int i = threadIdx.x; i < cout; i += blockDim.x) {
-    s2[i] = a.s2[g * cout + i];
-    t2[i] = a.t2[g * cout + i];
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-  // A wave covers as many whole image rows as fit its 64 lanes (one row of 56 pixels, two of 29,
-  // four of 16, seven of 9): lane = (row r of the bundle, column x).  (One row per wave left 55-85 % of
-  // the lanes idle in the later blocks.)
-  const int rpw = 64 / a.W, bundles = (a.H + rpw - 1) / rpw;
-  const int r = lane / a.W, x = lane - r * a.W;
-  const int tasks = a.n * bundles;
-  for (int t = blockIdx.y * nwaves + wave; t < tasks; t += gridDim.y * nwaves) {
-    const int n = t / bundles, y = (t % bundles) * rpw + r;
-    const bool live = r < rpw && y < a.H;
-    // this pixel's `cin` input bits
-    uint32_t in = 0;
-    if (live)
-      for (int j = 0; j < cin; ++j) {
-        const int J = cin * g + j;
-        uint64_t row;
-        if (a.interleaved) row = a.src[J & 3][((size_t)n * a.Csrc + (J >> 2)) * a.H + y];
-        else row = a.src[0][((size_t)n * a.Csrc + J) * a.H + y];
-        in |= (uint32_t)((row >> x) & 1ull) << j;
-      }
-    double acc[30];
-#pragma unroll
-    for (int o = 0; o < 30; ++o) acc[o] = 0.0;
-    for (int m = 0; m < mid; ++m) {
-      double s = 0.0;
-      const double *wr = w1 + m * cin;
-      for (int j = 0; j < cin; ++j) s += ((in >> j) & 1u) ? wr[j] : 0.0;
-      const double h = gelu_exact(s * s1[m] + t1[m], erf_tab);
-#pragma unroll
-      for (int o = 0; o < 30; ++o)
-        if (o < cout) acc[o] = fma(h, w2[o * mid + m], acc[o]);
-    }
-#pragma unroll
-    for (int o = 0; o < 30; ++o) {
-      if (o >= cout) break;
-      const double pre = acc[o] * s2[o] + t2[o];
-      if (a.out_float) {
-        if (live) a.out_float[(((size_t)n * a.Cout + g * cout + o) * a.H + y) * a.W + x] = (float)(pre > 0.0 ? pre : 0.0);
-      } else {
-        const uint64_t m64 = __ballot(live && pre >= 0.0);
-        if (live && x == 0)                               // the first lane of every row writes its row word
-          a.out_rp[((size_t)n * a.Cout + g * cout + o) * a.H + y] = (m64 >> (r * a.W)) & ((1ull << a.W) - 1ull);
-      }
-    }
-  }
+};
+
+// One ballot per pixel tile of 16: bits 16 q .. 16 q + 15 = member q of a channel quartet over the tile's pixels.
+// Lane (q = lg, bundle row ln) gets the row word of its channel: the W bits of row ln out of the 64 pixels.
+__device__ inline uint64_t row_word(const uint64_t (&bal)[4], int lg, int ln, int W) {
+  const uint64_t mine = ((bal[0] >> (16 * lg)) & 0xFFFFull) | (((bal[1] >> (16 * lg)) & 0xFFFFull) << 16) |
+                        (((bal[2] >> (16 * lg)) & 0xFFFFull) << 32) | (((bal[3] >> (16 * lg)) & 0xFFFFull) << 48);
+  return (mine >> (ln * W)) & ((1ull << W) - 1ull);
 }
 
-// The same block on the float64 matrix instruction v_mfma_f64_16x16x4_f64 (operand layouts probed in
+// The block on the float64 matrix instruction v_mfma_f64_16x16x4_f64 (operand layouts probed in
 // tools/ubench/mfma_f64_layout.hip: A lane l = A[l%16][l/16], B lane l = B[l/16][l%16], D register i of
 // lane l = D[4i + l/16][l%16]).  Both layers are small GEMMs over the 64 pixels of a task:
 //   layer 1   H[240 x 64] = W1[240 x 30] * X[30 x 64]      (X = the input bits as 0.0 / 1.0)
@@ -237,22 +176,35 @@ __global__ __launch_bounds__(1024) void full_pw_kernel(FullPwArgs a) {
 // an exact tie could turn.
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
-// FIX: the tasks are not image rows but the pixels full_pw_fast_kernel listed (64 per wave, any images, any
+// dynamic LDS of full_pw_mfma_kernel<OT, *>: byte offsets in declaration order
+template <int OT>
+struct MfmaLds {
+  static constexpr int KS1 = 8;                                                // layer-1 k-steps: K = 30 padded to 32
+  static constexpr size_t w1f = 0;                                             // double [MT][KS1][64]
+  static constexpr size_t w2f = w1f + sizeof(double) * kPwMT * KS1 * 64;       // double [MT][4][OT][64]
+  static constexpr size_t s1 = w2f + sizeof(double) * kPwMT * 4 * OT * 64;     // double [240]
+  static constexpr size_t t1 = s1 + sizeof(double) * kPwMid;                   // double [240]
+  static constexpr size_t bytes = t1 + sizeof(double) * kPwMid;
+};
+static_assert(MfmaLds<1>::bytes == 8 * (15 * 8 * 64 + 15 * 4 * 1 * 64 + 2 * 240), "LDS layout");
+static_assert(MfmaLds<2>::bytes == 8 * (15 * 8 * 64 + 15 * 4 * 2 * 64 + 2 * 240), "LDS layout");
+
+// FIX: the tasks are not image rows but the pixels full_pw_fast_kernel listed (16 per wave task, any images, any
 // positions); their bits are patched into the row words with atomics.
 template <int OT, bool FIX>      // 16-row output tiles: 2 (cout = 30) or 1 (cout = 15)
 __global__ __launch_bounds__(512) void full_pw_mfma_kernel(FullPwArgs a) {
-  extern __shared__ __align__(16) double lds[];
+  extern __shared__ __align__(16) uint8_t lds_raw[];
+  using L = MfmaLds<OT>;
   __shared__ double erf_tab[kErfN * kErfC];
   erf_table_to_lds(erf_tab);
-  constexpr int CIN = 30, MT = 15, KS1 = 8;              // 240 hidden units, K = 30 padded to 32
+  constexpr int CIN = kPwCin, MT = kPwMT, KS1 = L::KS1;
   constexpr int NTT = FIX ? 1 : 4;                       // pixel tiles of 16 per task (FIX: one, so that a short list still spreads over the chip)
   if constexpr (FIX) {                                   // nothing listed for this workgroup: skip the weight staging too
     const uint32_t capq = (uint32_t)a.n * (uint32_t)a.H * (uint32_t)a.W, cnt = min(a.fix_count[blockIdx.x], capq);
     if (blockIdx.y * (blockDim.x >> 6) >= (cnt + 15u) / 16u) return;
   }
-  double *w1f = lds;                                     // [MT][KS1][64]
-  double *w2f = w1f + MT * KS1 * 64;                     // [MT][4][OT][64]
-  double *s1 = w2f + MT * 4 * OT * 64, *t1 = s1 + 16 * MT;
+  double *w1f = (double *)(lds_raw + L::w1f), *w2f = (double *)(lds_raw + L::w2f);
+  double *s1 = (double *)(lds_raw + L::s1), *t1 = (double *)(lds_raw + L::t1);
   const int g = blockIdx.x, cout = a.cout, mid = 16 * MT;
   for (int i = threadIdx.x; i < MT * KS1 * 64; i += blockDim.x) {
     const int l = i & 63, ks = (i >> 6) % KS1, mt = i / (64 * KS1);
@@ -271,29 +223,27 @@ __global__ __launch_bounds__(512) void full_pw_mfma_kernel(FullPwArgs a) {
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = blockDim.x >> 6;
   const int lg = lane >> 4, ln = lane & 15;
-  const int rpw = 64 / a.W, bundles = (a.H + rpw - 1) / rpw;
+  const RowBundle rb(a.H, a.W);
   const uint32_t cap = (uint32_t)a.n * (uint32_t)a.H * (uint32_t)a.W;
   const uint32_t listed = FIX ? min(a.fix_count[g], cap) : 0u;
-  const int tasks = FIX ? (int)((listed + 15u) / 16u) : a.n * bundles;
+  const int tasks = FIX ? (int)((listed + 15u) / 16u) : a.n * rb.bundles;
   for (int t = blockIdx.y * nwaves + wave; t < tasks; t += gridDim.y * nwaves) {
-    int n, y0, y, x, r;
+    int n, y0, y, x;
     bool live;
-    uint32_t pid = 0;
     if constexpr (FIX) {
       live = (uint32_t)(16 * t + ln) < listed;           // lane l and its three lane-group twins: listed pixel 16 t + l%16
-      pid = live ? a.fix_list[(size_t)g * cap + 16 * t + ln] : 0u;
+      const uint32_t pid = live ? a.fix_list[(size_t)g * cap + 16 * t + ln] : 0u;
       x = (int)(pid % (uint32_t)a.W);
       y = (int)((pid / (uint32_t)a.W) % (uint32_t)a.H);
       n = (int)(pid / (uint32_t)(a.W * a.H));
       y0 = y;
-      r = 0;
     } else {
-      r = lane / a.W;
-      x = lane - r * a.W;
-      n = t / bundles;
-      y0 = (t % bundles) * rpw;
-      y = y0 + r;
-      live = r < rpw && y < a.H;
+      const RowBundle::Pixel me = rb.pixel(lane);
+      n = t / rb.bundles;
+      y0 = (t % rb.bundles) * rb.rpw;
+      y = y0 + me.r;
+      x = me.x;
+      live = me.r < rb.rpw && y < a.H;
     }
     uint32_t in = 0;                                     // this lane's pixel: its 30 input bits
     if (live)
@@ -351,29 +301,23 @@ __global__ __launch_bounds__(512) void full_pw_mfma_kernel(FullPwArgs a) {
         const double sc = o_ok ? a.s2[g * cout + o] : 0.0, sh = o_ok ? a.t2[g * cout + o] : -1.0;
         if constexpr (FIX) {
           // this lane's value belongs to its own listed pixel
-          if (o_ok && live) {
-            unsigned long long *word = (unsigned long long *)(a.out_rp + ((size_t)n * a.Cout + g * cout + o) * a.H + y);
-            if (acc[ot][0][i] * sc + sh >= 0.0) atomicOr(word, 1ull << x);
-            else atomicAnd(word, ~(1ull << x));
-          }
+          if (o_ok && live) patch_bit(a.out_rp + ((size_t)n * a.Cout + g * cout + o) * a.H + y, x, acc[ot][0][i] * sc + sh >= 0.0);
         } else if (a.out_float) {
 #pragma unroll
           for (int nt = 0; nt < NTT; ++nt) {
-            const int p = 16 * nt + ln, pr = p / a.W, px = p - pr * a.W, py = y0 + pr;
+            const RowBundle::Pixel q = rb.pixel(16 * nt + ln);
+            const int py = y0 + q.r;
             const double pre = acc[ot][nt][i] * sc + sh;
-            if (o_ok && pr < rpw && py < a.H)
-              a.out_float[(((size_t)n * a.Cout + g * cout + o) * a.H + py) * a.W + px] = (float)(pre > 0.0 ? pre : 0.0);
+            if (o_ok && q.r < rb.rpw && py < a.H)
+              a.out_float[(((size_t)n * a.Cout + g * cout + o) * a.H + py) * a.W + q.x] = (float)(pre > 0.0 ? pre : 0.0);
           }
         } else {
-          // one ballot per pixel tile: bits 16q .. 16q+15 = channel quartet member q over the tile's 16 pixels
           uint64_t bal[4] = {0, 0, 0, 0};
 #pragma unroll
           for (int nt = 0; nt < NTT; ++nt) bal[nt] = __ballot(acc[ot][nt][i] * sc + sh >= 0.0);
           // lane (q = l/16, row r' = l%16 < rpw) writes the row word of channel 16ot + 4i + q, image row y0 + r'
-          const uint64_t mine = ((bal[0] >> (16 * lg)) & 0xFFFFull) | (((bal[1] >> (16 * lg)) & 0xFFFFull) << 16) |
-                                (((bal[2] >> (16 * lg)) & 0xFFFFull) << 32) | (((bal[3] >> (16 * lg)) & 0xFFFFull) << 48);
-          if (o_ok && ln < rpw && y0 + ln < a.H)
-            a.out_rp[((size_t)n * a.Cout + g * cout + o) * a.H + y0 + ln] = (mine >> (ln * a.W)) & ((1ull << a.W) - 1ull);
+          if (o_ok && ln < rb.rpw && y0 + ln < a.H)
+            a.out_rp[((size_t)n * a.Cout + g * cout + o) * a.H + y0 + ln] = row_word(bal, lg, ln, a.W);
         }
       }
   }
@@ -391,7 +335,7 @@ __global__ __launch_bounds__(512) void full_pw_mfma_kernel(FullPwArgs a) {
 // float64 one -- provided tau really bounds the error.  tau (per output channel, computed by the kernel from
 // the weights it stages): with A_m = sum_c |w1[m][c]|, zmax_m = |s1_m| A_m + |t1_m| (no hidden unit can exceed it),
 //     ez_m = |s1_m| A_m (2^-21 + 16 x 2^-24) + 3 x 2^-24 zmax_m       layer 1: operand split, accumulation, BatchNorm fma
-//     eg_m = 1.13 ez_m + 1.6e-6 + 2e-7 zmax_m                          GELU: its slope, its own error (below: gelu_lin_node)
+//     eg_m = 1.13 ez_m + 1.6e-6 + 2e-7 zmax_m                          GELU: its slope, its own error (gelu_lin_err)
 //     E    = sum_m |w2[o][m]| eg_m + 3.2e-6 sum_m |w2[o][m]| |g_m|     layer 2: both operand splits, the dropped
 //                                                                      low x low product, 32 roundings of the sum
 //     tau  = 2 (|s2_o| E + 2^-22 |t2_o|)                               factor 2: margin
@@ -402,51 +346,13 @@ __global__ __launch_bounds__(512) void full_pw_mfma_kernel(FullPwArgs a) {
 // On the synthetic model about 1 in 1000 (pixel, group) pairs is listed.  The last block emits relu'd float32
 // features for a float32 head (tolerance 1e-5 on the logits): it takes the fast evaluation as it stands.
 //
-// gelu(z) = z Phi(z) with Phi from a table in LDS: 512 nodes z_i = i / 32 on [-8, 8), at each the value, the
-// slope and half the curvature of Phi (float64 -> float32), evaluated as a quadratic around the nearest node:
-// |dz| <= 1/64, so the neglected cubic term is <= (1/64)^3 / 6 x max |third derivative of Phi| (0.4) = 2.5e-7,
-// and with the float32 roundings |gelu_f32(z) - gelu(z)| <= 4e-7 (|z| + 0.1) (tests/test_full_fast_bounds.py
-// checks the formula in float32 against float64 on a dense grid).  Nine vector instructions and one 16-byte LDS
-// read; the Abramowitz-Stegun form it replaced (a reciprocal, an exponential, five fmas) cost twice that and set
-// the kernel's time.  Beyond the table Phi is 0 or 1 to 1e-15: the edge nodes hold exactly that, with no slope.
-constexpr int kPhiN = 512;
-// (slope and curvature are stored for an offset measured in the caller's units: z x scale)
-__device__ inline void phi_table_to_lds(float4 *dst, const double *erf_tab, double scale) {
-  for (int i = threadIdx.x; i < kPhiN; i += blockDim.x) {
-    const double z = (double)(i - kPhiN / 2) * (1.0 / 32.0);
-    const double x = z * 0.70710678118654752440, ax = __builtin_fabs(x);
-    int k = (int)(ax * 8.0);
-    k = k < kErfN - 1 ? k : kErfN - 1;
-    const double t = ax - ((double)k + 0.5) * 0.125;
-    const double *c = erf_tab + k * kErfC;
-    double p = c[8];
-    for (int q = 7; q >= 0; --q) p = fma(p, t, c[q]);
-    p = ax >= 6.0 ? 1.0 : p;
-    const double Phi = 0.5 * (1.0 + __builtin_copysign(p, x));
-    const double pdf = 0.39894228040143267794 * exp(-0.5 * z * z);
-    const bool edge = i == 0 || i == kPhiN - 1;
-    dst[i] = edge ? make_float4(i ? 1.f : 0.f, 0.f, 0.f, 0.f)
-                  : make_float4((float)Phi, (float)(pdf / scale), (float)(-0.5 * z * pdf / (scale * scale)), 0.f);
-  }
-}
-// z x SCALE in, gelu(z) x SCALE out (SCALE = ACT_PRESCALE: the prescale of layer 2's operand rides along for free).
-// In two steps so that a batch of table reads can be in flight before the first is needed.
-template <int SCALE>
-__device__ inline int gelu_node(float zs, float &dz) {
-  float r = __builtin_rintf(zs * (32.0f / (float)SCALE));               // nearest node, in units of 1/32
-  r = __builtin_fminf(__builtin_fmaxf(r, -(float)(kPhiN / 2)), (float)(kPhiN / 2 - 1));
-  dz = fmaf(r, -(float)SCALE / 32.0f, zs);                             // offset from the node, in units of 1 / SCALE
-  return (int)r + kPhiN / 2;
-}
-__device__ inline float gelu_eval(float zs, float dz, const float4 &c) { return zs * fmaf(dz, fmaf(dz, c.z, c.y), c.x); }
-// full_pw_fast_kernel's GELU (round 3): a table of gelu ITSELF, kGelN = 4096 nodes z_i = (i - 2048) / 256 on [-8, 8), evaluated
+// The fast kernels' GELU: a table of gelu itself, kGelN = 4096 nodes z_i = (i - 2048) / 256 on [-8, 8), evaluated
 // as the tangent at the NEAREST node.  |u - i| <= 1/2 node = 1/512 in z, so the neglected term is <= (1/512)^2 / 2 x
 // max |gelu''| (= 2 pdf(0) = 0.798) = 1.53e-6; an entry holds the tangent as a line in u itself, (intercept, slope) with
 // intercept = SCALE gelu(z_i) - i x slope (from the ROUNDED slope, so that the slope's rounding is not multiplied by u), and
 // g = fma(u, slope, intercept) has the roundings of the intercept and of the fma: 2^-24 (|intercept| + |g|) <= 2e-7 |z|.
 //   |gelu_lin(z) - gelu(z)| <= 1.6e-6 + 2e-7 |z|      (tests/test_full_fast_bounds.py restates it in float32 on a dense grid)
-// Five vector instructions and one 8-byte LDS read per hidden value where the quadratic in Phi of rounds 2 took nine and a
-// 12-byte read -- the kernel is bound by vector issue -- and a bound that no longer grows 2.4e-6 per unit of zmax:
+// Five vector instructions and one 8-byte LDS read per hidden value (the 1x1 kernel is bound by vector issue):
 //   u = fma(d, 256 sc, 256 sh)          the BatchNorm output in node widths
 //   t = med3(u + magic, lo, hi)         magic = 1.5 x 2^23: the float32 add rounds u to the nearest integer (ties to even),
 //                                       which then sits in the low mantissa bits; the clamp keeps it inside the table
@@ -455,22 +361,20 @@ __device__ inline float gelu_eval(float zs, float dz, const float4 &c) { return 
 // to 1e-14 for z >= 7.99, and that IS the line.
 constexpr float kNodeMagic = 12582912.0f;            // 1.5 x 2^23
 constexpr int kGelN = 4096;
+// (bits of t) << 3 = 8 x (node index i - 2048) + kNodeMagicAddr, so entry i of a table at byte address A sits at
+// ((bits of t) << 3) + addr_k with addr_k = A + kGelZero - kNodeMagicAddr (gelu_lin_node)
+constexpr uint32_t kNodeMagicAddr = __builtin_bit_cast(uint32_t, kNodeMagic) << 3;
+constexpr uint32_t kGelZero = 8u * (uint32_t)(kGelN / 2);      // byte offset of the node z = 0 inside a table
+// the table GELU's part of a hidden unit's error: ez through the slope of gelu (<= 1.13), the tangent line's own error
+__device__ inline double gelu_lin_err(double ez, double zmax) { return 1.13 * ez + 1.6e-6 + 2e-7 * zmax; }
 // (dst: LDS, or the plan's copy in global memory -- launch_full_gelu_tables -- which the kernels then only copy)
 __device__ inline void gelu_table_to_lds(float2 *dst, const double *erf_tab, double scale) {
   for (int i = threadIdx.x; i < kGelN; i += blockDim.x) {
     const double z = (double)(i - kGelN / 2) * (1.0 / 256.0);
-    const double x = z * 0.70710678118654752440, ax = __builtin_fabs(x);
-    int k = (int)(ax * 8.0);
-    k = k < kErfN - 1 ? k : kErfN - 1;
-    const double t = ax - ((double)k + 0.5) * 0.125;
-    const double *c = erf_tab + k * kErfC;
-    double p = c[8];
-    for (int q = 7; q >= 0; --q) p = fma(p, t, c[q]);
-    p = ax >= 6.0 ? 1.0 : p;
-    const double Phi = 0.5 * (1.0 + __builtin_copysign(p, x));
+    const double P = Phi(z, erf_tab);
     const double pdf = 0.39894228040143267794 * exp(-0.5 * z * z);
-    const float slope = (float)(scale * (Phi + z * pdf) * (1.0 / 256.0));
-    float2 e = make_float2((float)(scale * z * Phi - (double)(i - kGelN / 2) * (double)slope), slope);
+    const float slope = (float)(scale * (P + z * pdf) * (1.0 / 256.0));
+    float2 e = make_float2((float)(scale * z * P - (double)(i - kGelN / 2) * (double)slope), slope);
     if (i == 0) e = make_float2(0.f, 0.f);
     if (i == kGelN - 1) e = make_float2(0.f, (float)(scale * (1.0 / 256.0)));
     dst[i] = e;
@@ -485,15 +389,10 @@ __global__ void gelu_tables_kernel(float *dst) {
   __syncthreads();
   gelu_table_to_lds((float2 *)dst + (size_t)blockIdx.x * kGelN, erf_tab, blockIdx.x ? (double)ACT_PRESCALE : 1.0);
 }
+// u -> byte address of its table entry
 __device__ inline uint32_t gelu_lin_node(float u, uint32_t addr_k) {
   const float t = __builtin_amdgcn_fmed3f(u + kNodeMagic, kNodeMagic - (float)(kGelN / 2), kNodeMagic + (float)(kGelN / 2 - 1));
   return (__float_as_uint(t) << 3) + addr_k;
-}
-template <int SCALE>
-__device__ inline float gelu_f32(float zs, const float4 *tab) {
-  float dz;
-  const int i = gelu_node<SCALE>(zs, dz);
-  return gelu_eval(zs, dz, tab[i]);
 }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -514,7 +413,7 @@ __device__ inline void split_halves(float v, uint16_t &h1, uint16_t &h2) {
   h2 = __builtin_bit_cast(uint16_t, b);
 }
 
-constexpr int kFastMT = 15, kFastKP = 8, kFastMid = 240, kFastCin = 30;
+constexpr int kFastKP = 8;                           // layer-2 k-steps: pairs of hidden tiles
 
 // tools/ubench/full_pw_parts.hip builds this file with parts of full_pw_fast_kernel switched off (bit mask:
 // 1 no tasks (staging only), 2 no input gather, 4 no layer 1 / GELU, 8 no layer 2, 16 no epilogue).  0 in the library.
@@ -528,29 +427,42 @@ __device__ unsigned long long g_pw_stamps[8];        // ns spent by wave 0 of bl
 #else
 #define PW_STAMP(k) do {} while (0)
 #endif
-template <int OT>
-constexpr size_t fast_lds_bytes() {
-  return (size_t)kFastMT * 2 * 64 * 16 + (size_t)kFastKP * OT * 2 * 64 * 16 + 2 * 256 * sizeof(float) + 3 * 32 * sizeof(float) + 64 +
-         (size_t)kGelN * 8 + 32 * sizeof(float) + (size_t)kFastKP * OT * 64 * 16 + 2 * 256 * sizeof(float);
-}
-
-template <int OT>      // 16-row output tiles: 2 (cout = 30) or 1 (cout = 15)
 #ifndef TT_FULLPW_MINWAVES
 #define TT_FULLPW_MINWAVES 2      /* one workgroup per CU; 4 = two, at most 128 registers: spills, and no faster */
 #endif
+
+// dynamic LDS of full_pw_fast_kernel<OT>: byte offsets in declaration order
+template <int OT>
+struct FastLds {
+  static constexpr size_t w1f = 0;                                                  // uint4 [MT][plane][lane]: layer-1 A fragments
+  static constexpr size_t w2f = w1f + sizeof(uint4) * kPwMT * 2 * 64;               // uint4 [KP][OT][plane][lane]: layer-2 A fragments
+  static constexpr size_t zmx = w2f + sizeof(uint4) * kFastKP * OT * 2 * 64;        // float [256]: zmax_m
+  static constexpr size_t egm = zmx + sizeof(float) * 256;                          // float [256]: eg_m
+  static constexpr size_t s2f = egm + sizeof(float) * 256;                          // float [32]
+  static constexpr size_t t2f = s2f + sizeof(float) * 32;                           // float [32]
+  static constexpr size_t tau = t2f + sizeof(float) * 32;                           // float [32]: the part of the bound that does not depend on the pixel
+  static constexpr size_t tauk = tau + sizeof(float) * 32;                          // float [32]: bound per unit of the accumulated |w2| x |g|
+  static constexpr size_t red = tauk + sizeof(float) * 32;                          // float [16]: reductions
+  static constexpr size_t gel = red + sizeof(float) * 16;                           // float2 [4096]: GELU table, intercept and slope per node
+  static constexpr size_t w2a = gel + sizeof(float2) * kGelN;                       // uint4 [KP][OT][lane]: |w2|, high halves, layer-2 fragment order
+  static constexpr size_t s1n = w2a + sizeof(uint4) * kFastKP * OT * 64;            // float [256]: BatchNorm scale / layer-1 prescale, in node widths
+  static constexpr size_t t1n = s1n + sizeof(float) * 256;                          // float [256]: BatchNorm shift, in node widths
+  static constexpr size_t bytes = t1n + sizeof(float) * 256;
+};
+static_assert(FastLds<1>::bytes == 15 * 2 * 64 * 16 + 8 * 1 * 2 * 64 * 16 + 2 * 256 * 4 + 3 * 32 * 4 + 64 + 4096 * 8 + 32 * 4 + 8 * 1 * 64 * 16 + 2 * 256 * 4, "LDS layout");
+static_assert(FastLds<2>::bytes == 15 * 2 * 64 * 16 + 8 * 2 * 2 * 64 * 16 + 2 * 256 * 4 + 3 * 32 * 4 + 64 + 4096 * 8 + 32 * 4 + 8 * 2 * 64 * 16 + 2 * 256 * 4, "LDS layout");
+
+template <int OT>      // 16-row output tiles: 2 (cout = 30) or 1 (cout = 15)
 __global__ __launch_bounds__(512, TT_FULLPW_MINWAVES) void full_pw_fast_kernel(FullPwArgs a) {
   extern __shared__ __align__(16) uint8_t lds_raw[];
-  constexpr int CIN = kFastCin, MT = kFastMT, KP = kFastKP, MID = kFastMid;
-  uint4 *w1f = (uint4 *)lds_raw;                                // [MT][plane][lane]: layer-1 A fragments
-  uint4 *w2f = w1f + MT * 2 * 64;                               // [KP][OT][plane][lane]: layer-2 A fragments
-  float *zmx = (float *)(w2f + KP * OT * 2 * 64), *egm = zmx + 256;   // [256] each: zmax_m; eg_m
-
-  float *s2f = egm + 256, *t2f = s2f + 32, *tau = t2f + 32;     // [32] each (tau: the part of the bound that does not depend on the pixel)
-  float *tauk = tau + 32;                                       // [32] bound per unit of the accumulated |w2| x |g|
-  float *red = tauk + 32;                                       // [16] reductions
-  float2 *gel = (float2 *)(red + 16);                           // [4096] GELU table: value, slope per node
-  uint4 *w2a = (uint4 *)(gel + kGelN);                          // [KP][OT][lane]: |w2|, high halves, layer-2 fragment order
-  float *s1n = (float *)(w2a + KP * OT * 64), *t1n = s1n + 256; // [256] each: BatchNorm scale / layer-1 prescale and shift, in node widths (gelu_lin_node)
+  using L = FastLds<OT>;
+  constexpr int CIN = kPwCin, MT = kPwMT, KP = kFastKP, MID = kPwMid;
+  uint4 *w1f = (uint4 *)(lds_raw + L::w1f), *w2f = (uint4 *)(lds_raw + L::w2f), *w2a = (uint4 *)(lds_raw + L::w2a);
+  float *zmx = (float *)(lds_raw + L::zmx), *egm = (float *)(lds_raw + L::egm);
+  float *s2f = (float *)(lds_raw + L::s2f), *t2f = (float *)(lds_raw + L::t2f);
+  float *tau = (float *)(lds_raw + L::tau), *tauk = (float *)(lds_raw + L::tauk), *red = (float *)(lds_raw + L::red);
+  float2 *gel = (float2 *)(lds_raw + L::gel);
+  float *s1n = (float *)(lds_raw + L::s1n), *t1n = (float *)(lds_raw + L::t1n);
   __shared__ double erf_tab[kErfN * kErfC];
   erf_table_to_lds(erf_tab);
   const int g = blockIdx.x, cout = a.cout;
@@ -609,11 +521,11 @@ __global__ __launch_bounds__(512, TT_FULLPW_MINWAVES) void full_pw_fast_kernel(F
         for (int c = 0; c < CIN; ++c) A += fabs((double)a.w1[((size_t)g * MID + m) * CIN + c]);
         const double sc = a.s1[g * MID + m], sh = a.t1[g * MID + m];
         const double zmax = fabs(sc) * A + fabs(sh);
-        const double ez = fabs(sc) * A * (4.76837158203125e-7 + 16.0 * 5.9604644775390625e-8) + 3.0 * 5.9604644775390625e-8 * zmax;
+        const double ez = fabs(sc) * A * (kTwoM21 + 16.0 * kTwoM24) + 3.0 * kTwoM24 * zmax;
         s1n[m] = (float)(sc * 256.0 / (double)ws1);
         t1n[m] = (float)(sh * 256.0);
         zmx[m] = (float)zmax;
-        egm[m] = (float)(1.13 * ez + 1.6e-6 + 2e-7 * zmax);        // (gelu_lin_node)
+        egm[m] = (float)gelu_lin_err(ez, zmax);
         if (!(zmax * (double)ACT_PRESCALE < 65000.0)) red[15] = 1.0f;     // |gelu(z)| <= |z| <= zmax: only then can a split overflow
       } else {
         zmx[m] = 0.f; egm[m] = 0.f; s1n[m] = 0.f; t1n[m] = 0.f;
@@ -633,7 +545,7 @@ __global__ __launch_bounds__(512, TT_FULLPW_MINWAVES) void full_pw_fast_kernel(F
         s2f[o] = (float)(sc / ((double)ws2 * (double)ACT_PRESCALE));
         t2f[o] = (float)sh;
         // (the pixel's own sum |w2| |g| is accumulated as sum |w2| g <= that, plus at most 0.34 sum |w2|: gelu >= -0.17)
-        tau[o] = (float)(2.0 * (fabs(sc) * (E + 3.2e-6 * 0.35 * S1) + 2.384185791015625e-7 * fabs(sh))) * a.tau_scale;
+        tau[o] = (float)(2.0 * (fabs(sc) * (E + 3.2e-6 * 0.35 * S1) + kTwoM22 * fabs(sh))) * a.tau_scale;
         tauk[o] = (float)(2.0 * fabs(sc) * 3.2e-6 / ((double)ws2 * (double)ACT_PRESCALE)) * a.tau_scale;
       } else {
         s2f[o] = 0.f; t2f[o] = -1.0f; tau[o] = 0.f; tauk[o] = 0.f;
@@ -642,14 +554,13 @@ __global__ __launch_bounds__(512, TT_FULLPW_MINWAVES) void full_pw_fast_kernel(F
     __syncthreads();
   }
   const int lg = lane >> 4, ln = lane & 15;
-  const int rpw = 64 / a.W, bundles = (a.H + rpw - 1) / rpw;
-  const int r = lane / a.W, x = lane - r * a.W;
-  const int tasks = a.n * bundles;
+  const RowBundle rb(a.H, a.W);
+  const RowBundle::Pixel me = rb.pixel(lane);
+  const int tasks = a.n * rb.bundles;
   const uint32_t cap = (uint32_t)a.n * (uint32_t)a.H * (uint32_t)a.W;
   bool out_of_range = false;
   const bool check_range = red[15] != 0.f;               // (block-uniform; false for any sane BatchNorm)
-  // gelu_lin_node: byte address of table entry i = gel + 8 i, i = (bits of t) - (bits of the magic number) + 2048
-  const uint32_t gel_k = (uint32_t)((uint8_t *)gel - lds_raw) + 8u * (uint32_t)(kGelN / 2) - (0x4B400000u << 3);
+  const uint32_t gel_k = (uint32_t)((uint8_t *)gel - lds_raw) + kGelZero - kNodeMagicAddr;       // gelu_lin_node: byte addresses relative to lds_raw
 #ifdef TT_FULLPW_STAMP
   const bool stamping = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;
   unsigned long long stamp_t = 10ull * __builtin_amdgcn_s_memrealtime();
@@ -657,15 +568,15 @@ __global__ __launch_bounds__(512, TT_FULLPW_MINWAVES) void full_pw_fast_kernel(F
   for (int t = blockIdx.y * nwaves + wave; t < ((kPwSkip & 1) ? 0 : tasks); t += gridDim.y * nwaves) {
     PW_STAMP(5);
     // (the quotient of two wave-uniform values comes out of the vector unit: tell the compiler it is uniform)
-    const int n = __builtin_amdgcn_readfirstlane(t / bundles), y0 = __builtin_amdgcn_readfirstlane((t % bundles) * rpw), y = y0 + r;
-    const bool live = r < rpw && y < a.H;
+    const int n = __builtin_amdgcn_readfirstlane(t / rb.bundles), y0 = __builtin_amdgcn_readfirstlane((t % rb.bundles) * rb.rpw), y = y0 + me.r;
+    const bool live = me.r < rb.rpw && y < a.H;
     // this lane's pixel: its 30 input bits.  Thirty loads off wave-uniform bases (the lane's part of the address
     // is its row inside the bundle), issued together; written with a branch per channel they were issued and
     // waited for one by one, which was most of a task's time.
     uint32_t in = 0;
     if constexpr (kPwSkip & 2) in = (uint32_t)(lane * 0x9E3779B1u + t) & 0x3FFFFFFFu;
     else {
-      const int rc = live ? r : 0;
+      const int rc = live ? me.r : 0;
       uint64_t rows[CIN];
       const uint64_t *s0 = a.src[0], *s1 = a.src[1], *s2 = a.src[2], *s3 = a.src[3];
       const size_t img = (size_t)n * a.Csrc * a.H + y0 + rc;     // (the only 64-bit product of the task)
@@ -677,7 +588,7 @@ __global__ __launch_bounds__(512, TT_FULLPW_MINWAVES) void full_pw_fast_kernel(F
         rows[j] = a.interleaved ? sk[img + (uint32_t)((J >> 2) * a.H)] : s0[img + (uint32_t)(J * a.H)];
       }
 #pragma unroll
-      for (int j = 0; j < CIN; ++j) in |= (uint32_t)((rows[j] >> x) & 1ull) << j;
+      for (int j = 0; j < CIN; ++j) in |= (uint32_t)((rows[j] >> me.x) & 1ull) << j;
       in = live ? in : 0u;
     }
     // layer-1 B fragments: lane l of pixel tile nt = input bits 8 (l/16) .. + 7 of pixel 16 nt + l%16, as fp16 0 / 1
@@ -799,10 +710,11 @@ __global__ __launch_bounds__(512, TT_FULLPW_MINWAVES) void full_pw_fast_kernel(F
         if (a.out_float) {
 #pragma unroll
           for (int nt = 0; nt < 4; ++nt) {
-            const int p = 16 * nt + ln, pr = p / a.W, px = p - pr * a.W, py = y0 + pr;
+            const RowBundle::Pixel q = rb.pixel(16 * nt + ln);
+            const int py = y0 + q.r;
             const float pre = fmaf(acc[ot][nt][i], sc, sh);
-            if (o_ok && pr < rpw && py < a.H)
-              a.out_float[(((size_t)n * a.Cout + g * cout + o) * a.H + py) * a.W + px] = pre > 0.f ? pre : 0.f;
+            if (o_ok && q.r < rb.rpw && py < a.H)
+              a.out_float[(((size_t)n * a.Cout + g * cout + o) * a.H + py) * a.W + q.x] = pre > 0.f ? pre : 0.f;
           }
         } else {
           uint64_t bal[4];
@@ -812,12 +724,9 @@ __global__ __launch_bounds__(512, TT_FULLPW_MINWAVES) void full_pw_fast_kernel(F
             bal[nt] = __ballot(pre >= 0.f);
             doubt |= (o_ok && !(__builtin_fabsf(pre) >= fmaf(accb[ot][nt][i], tk, tb))) ? (1u << nt) : 0u;      // (a NaN is in doubt too)
           }
-          // bits 16 q .. 16 q + 15 of a ballot = channel 16 ot + 4 q + i over the tile's 16 pixels; lane (q, row r' = l%16 < rpw)
-          // writes the row word of that channel, image row y0 + r'
-          const uint64_t mine = ((bal[0] >> (16 * lg)) & 0xFFFFull) | (((bal[1] >> (16 * lg)) & 0xFFFFull) << 16) |
-                                (((bal[2] >> (16 * lg)) & 0xFFFFull) << 32) | (((bal[3] >> (16 * lg)) & 0xFFFFull) << 48);
-          if (o_ok && ln < rpw && y0 + ln < a.H)
-            a.out_rp[((size_t)n * a.Cout + g * cout + o) * a.H + y0 + ln] = (mine >> (ln * a.W)) & ((1ull << a.W) - 1ull);
+          // lane (q = l/16, row r' = l%16 < rpw) writes the row word of channel 16 ot + 4 q + i, image row y0 + r'
+          if (o_ok && ln < rb.rpw && y0 + ln < a.H)
+            a.out_rp[((size_t)n * a.Cout + g * cout + o) * a.H + y0 + ln] = row_word(bal, lg, ln, a.W);
         }
       }
     PW_STAMP(3);
@@ -834,8 +743,8 @@ __global__ __launch_bounds__(512, TT_FULLPW_MINWAVES) void full_pw_fast_kernel(F
       // drop the pixels beyond the bundle (idle lanes of the last rows)
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) {
-        const int p = 16 * nt + ln, pr = p / a.W;
-        if (!(pr < rpw && y0 + pr < a.H)) mine &= ~(1u << nt);
+        const int pr = rb.pixel(16 * nt + ln).r;
+        if (!(pr < rb.rpw && y0 + pr < a.H)) mine &= ~(1u << nt);
       }
       const int cnt = __popc(mine);
       int total = cnt;                                   // wave-wide sum, this lane's offset in it
@@ -858,8 +767,8 @@ __global__ __launch_bounds__(512, TT_FULLPW_MINWAVES) void full_pw_fast_kernel(F
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt)
           if ((mine >> nt) & 1u) {
-            const int p = 16 * nt + ln, pr = p / a.W, px = p - pr * a.W;
-            if (k < cap) a.fix_list[(size_t)g * cap + k] = ((uint32_t)n * (uint32_t)a.H + (uint32_t)(y0 + pr)) * (uint32_t)a.W + (uint32_t)px;
+            const RowBundle::Pixel q = rb.pixel(16 * nt + ln);
+            if (k < cap) a.fix_list[(size_t)g * cap + k] = ((uint32_t)n * (uint32_t)a.H + (uint32_t)(y0 + q.r)) * (uint32_t)a.W + (uint32_t)q.x;
             ++k;
           }
       }
@@ -877,13 +786,12 @@ __global__ __launch_bounds__(512, TT_FULLPW_MINWAVES) void full_pw_fast_kernel(F
 //                                                           BatchNorm output in node widths of the GELU table: KH entries
 //                                                           rounded once each and KH - 1 adds, each <= 2^-24 x 256 zmax_m
 //                                                           (the factor 2: margin)
-//     eg_m = 1.13 ez_m + 1.6e-6 + 2e-7 zmax_m               gelu_lin_node (the 1x1 kernel's tangent-line table, scale 1)
+//     eg_m = 1.13 ez_m + 1.6e-6 + 2e-7 zmax_m               gelu_lin_err (the tangent-line table at scale 1)
 //     E    = sum_m |w2_m| eg_m + 10 x 2^-24 sum_m |w2_m| zmax_m       eight fmas
 //     tau  = 2 (|s2| E + 2^-22 |t2|)
 // If the list overflows (it holds 1/16 of the outputs; about 1 in 10^5 is listed) the fix kernel recomputes
-// every output instead.  Round 3: the BatchNorm folded into the tables and the tangent-line GELU -- per hidden value
-// KH table reads, KH - 1 adds, add / med3 / shift-add for the node, one 8-byte read and two fmas, where the quadratic in
-// Phi took eighteen vector instructions.
+// every output instead.  Per hidden value: KH table reads, KH - 1 adds, add / med3 / shift-add for the node, one
+// 8-byte read and two fmas.
 template <int KH, int KW>
 __global__ __launch_bounds__(256) void full_dw_fast_kernel(FullDwArgs a) {
   __shared__ float tab[8][KH][1 << KW];
@@ -911,42 +819,38 @@ __global__ __launch_bounds__(256) void full_dw_fast_kernel(FullDwArgs a) {
       for (int k = 0; k < nk; ++k) A += fabs((double)a.w1[(size_t)c * 8 * nk + m * nk + k]);
       const double sc = a.s1[c * 8 + m], sh = a.t1[c * 8 + m], w = (double)a.w2[c * 8 + m];
       const double zmax = fabs(sc) * A + fabs(sh);
-      const double ez = (2.0 * KH) * 5.9604644775390625e-8 * zmax;
-      E += fabs(w) * (1.13 * ez + 1.6e-6 + 2e-7 * zmax);
+      const double ez = (2.0 * KH) * kTwoM24 * zmax;
+      E += fabs(w) * gelu_lin_err(ez, zmax);
       S2 += fabs(w) * zmax;
       w2f[m] = (float)w;
     }
-    E += 10.0 * 5.9604644775390625e-8 * S2;
+    E += 10.0 * kTwoM24 * S2;
     s2f = (float)a.s2[c];
     t2f = (float)a.t2[c];
-    tauf = (float)(2.0 * (fabs(a.s2[c]) * E + 2.384185791015625e-7 * fabs(a.t2[c]))) * a.tau_scale;
+    tauf = (float)(2.0 * (fabs(a.s2[c]) * E + kTwoM22 * fabs(a.t2[c]))) * a.tau_scale;
   }
   __syncthreads();
   const int rows = a.n * a.ho;
   const uint32_t cap = a.fix_cap;
-  const uint32_t gel_k = 8u * (uint32_t)(kGelN / 2) - (0x4B400000u << 3);        // byte offset of entry i inside gel = (bits of t) << 3 + this
   for (int t = blockIdx.y * blockDim.x + threadIdx.x; t < rows; t += gridDim.y * blockDim.x) {
     const int n = t / a.ho, oy = t % a.ho;
     uint64_t r[KH];
 #pragma unroll
-    for (int kh = 0; kh < KH; ++kh) {
-      const int iy = oy * a.stride - a.pad + kh;
-      r[kh] = (iy >= 0 && iy < a.H) ? a.x_rp[((size_t)n * a.C + c) * a.H + iy] << a.pad : 0ull;   // bit 0 = column -pad
-    }
+    for (int kh = 0; kh < KH; ++kh) r[kh] = window_row(a, n, c, oy, kh);
     uint64_t out = 0, doubt = 0;
     for (int ox = 0; ox < a.wo; ++ox) {
       uint32_t idx[KH];
 #pragma unroll
       for (int kh = 0; kh < KH; ++kh) idx[kh] = (uint32_t)(r[kh] >> (ox * a.stride)) & ((1u << KW) - 1u);
       float u[8];
-      uint32_t node[8];
+      uint32_t node[8];                                  // byte offset of the table entry inside gel
 #pragma unroll
       for (int m = 0; m < 8; ++m) {
         float sm = tab[m][0][idx[0]];
 #pragma unroll
         for (int kh = 1; kh < KH; ++kh) sm += tab[m][kh][idx[kh]];
         u[m] = sm;
-        node[m] = gelu_lin_node(sm, gel_k);
+        node[m] = gelu_lin_node(sm, kGelZero - kNodeMagicAddr);
       }
       float acc = 0.f;
 #pragma unroll
@@ -991,11 +895,7 @@ __global__ __launch_bounds__(256) void full_dw_fix_kernel(FullDwArgs a) {
     const int c = (int)((id / (uint32_t)(a.wo * a.ho)) % (uint32_t)a.C), n = (int)(id / (uint32_t)(a.wo * a.ho * a.C));
     uint32_t win[6];
 #pragma unroll
-    for (int kh = 0; kh < 6; ++kh) {
-      const int iy = oy * a.stride - a.pad + kh;
-      const uint64_t row = (kh < a.kh && iy >= 0 && iy < a.H) ? a.x_rp[((size_t)n * a.C + c) * a.H + iy] << a.pad : 0ull;
-      win[kh] = (uint32_t)(row >> (ox * a.stride)) & ((1u << a.kw) - 1u);
-    }
+    for (int kh = 0; kh < 6; ++kh) win[kh] = (uint32_t)(window_row(a, n, c, oy, kh, kh < a.kh) >> (ox * a.stride)) & ((1u << a.kw) - 1u);
     // full_dw_tab_kernel's order: the taps of a row kw-ascending, then the rows kh-ascending
     const float *w = a.w1 + (size_t)c * 8 * nk + (size_t)m * nk;
     float wv[36];
@@ -1018,12 +918,7 @@ __global__ __launch_bounds__(256) void full_dw_fix_kernel(FullDwArgs a) {
       const double gq = __shfl(gm, (threadIdx.x & 56) + q);           // (the lane index inside the wave: 8 outputs per wave)
       acc = fma(gq, (double)a.w2[c * 8 + q], acc);
     }
-    if (live && m == 0) {
-      const double pre = acc * a.s2[c] + a.t2[c];
-      unsigned long long *word = (unsigned long long *)(a.out + ((size_t)n * a.C + c) * a.Ho + oy + a.pad_t);
-      if (pre >= 0.0) atomicOr(word, 1ull << (ox + a.pad_l));
-      else atomicAnd(word, ~(1ull << (ox + a.pad_l)));
-    }
+    if (live && m == 0) patch_bit(a.out + ((size_t)n * a.C + c) * a.Ho + oy + a.pad_t, ox + a.pad_l, acc * a.s2[c] + a.t2[c] >= 0.0);
   }
 }
 
@@ -1057,20 +952,55 @@ __global__ void full_pool_split_kernel(const float *x, uint16_t *feat_frag, int 
   store_feature(feat_frag, img, KS, (ch / 16) * PP + pp, ch % 16, f, range_flag);
 }
 
-}  // namespace
+// raises the kernel's dynamic-LDS limit where `lds` needs it, launches, and reports a launch error
+template <class Args>
+int launch_kernel(void (*kernel)(Args), dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args &a) {
+  TT_TRY(ensure_dynamic_lds((const void *)kernel, lds));
+  hipLaunchKernelGGL(kernel, grid, block, lds, s, a);
+  TT_HIP(hipGetLastError());
+  return TTNET_OK;
+}
 
-// TTNET_FULL_EXACT=1: every output in float64 (the round-1 path; what the fast path is tested against).  Read at every
-// launch, so that a test can switch it between two forwards of one process (a captured graph keeps what it captured).
-static bool full_exact_only() {
+// TTNET_FULL_EXACT=1: every output in float64 (what the fast path is tested against).  Read at every launch, so that
+// a test can switch it between two forwards of one process (a captured graph keeps what it captured).
+bool full_exact_only() {
   const char *e = getenv("TTNET_FULL_EXACT");
   return e && e[0] == '1';
 }
 // TTNET_FULL_TAU_SCALE=<f>: multiplies the error bound of the fast path (tests measure its margin with f < 1)
-static float full_tau_scale() {
+float full_tau_scale() {
   const char *e = getenv("TTNET_FULL_TAU_SCALE");
   const float v = e ? (float)atof(e) : 1.0f;
   return v > 0.f ? v : 1.0f;
 }
+
+template <int KH, int KW>
+int launch_full_dw_window(const FullDwArgs &a, hipStream_t s) {
+  const int rows = a.n * a.ho;
+  const int chunks = std::max(1, std::min((rows + 255) / 256, std::max(1, 1024 / a.C)));
+  if (full_exact_only() || !(a.fix_list && a.fix_count && a.fix_cap))
+    return launch_kernel(full_dw_tab_kernel<KH, KW>, dim3(a.C, chunks), dim3(256), 0, s, a);
+  TT_HIP(hipMemsetAsync(a.fix_count, 0, sizeof(uint32_t), s));
+  TT_TRY(launch_kernel(full_dw_fast_kernel<KH, KW>, dim3(a.C, chunks), dim3(256), 0, s, a));
+  return launch_kernel(full_dw_fix_kernel, dim3(1024), dim3(256), 0, s, a);
+}
+
+template <int OT>
+int launch_full_pw_tiles(const FullPwArgs &a, hipStream_t s) {
+  const int tasks = a.n * RowBundle(a.H, a.W).bundles;
+  const int chunks = std::max(1, std::min((tasks + 7) / 8, std::max(1, 512 / a.groups)));
+  const bool fast = !full_exact_only() && (a.out_float || (a.fix_list && a.fix_count)) && a.groups <= 62;
+  if (!fast) return launch_kernel(full_pw_mfma_kernel<OT, false>, dim3(a.groups, chunks), dim3(512), MfmaLds<OT>::bytes, s, a);
+  if (!a.out_float) TT_HIP(hipMemsetAsync(a.fix_count, 0, 62 * sizeof(uint32_t), s));
+  TT_TRY(launch_kernel(full_pw_fast_kernel<OT>, dim3(a.groups, chunks), dim3(512), FastLds<OT>::bytes, s, a));
+  if (a.out_float) return TTNET_OK;
+  // the listed pixels in float64, 16 per wave task: one workgroup per CU (its float64 fragments fill the LDS);
+  // workgroups without listed pixels leave at once
+  const int xchunks = std::max(1, std::min((tasks / 4 + 7) / 8, std::max(1, 256 / a.groups)));
+  return launch_kernel(full_pw_mfma_kernel<OT, true>, dim3(a.groups, xchunks), dim3(512), MfmaLds<OT>::bytes, s, a);
+}
+
+}  // namespace
 
 size_t full_gelu_tables_elems() { return (size_t)2 * kGelN * 2; }
 int launch_full_gelu_tables(float *dst, hipStream_t s) {
@@ -1079,92 +1009,29 @@ int launch_full_gelu_tables(float *dst, hipStream_t s) {
   return TTNET_OK;
 }
 
+// The full variant's windows are (6,5) and (5,6) (spec.py _VARIANTS, plan.hip build_geometry); W + 2 pad <= 63: a padded
+// row is one 64-bit word.
 int launch_full_dw(const FullDwArgs &a_in, hipStream_t s) {
   FullDwArgs a = a_in;
   a.tau_scale = full_tau_scale();
-  if (a.kh > 6 || a.kw > 6 || a.kh * a.kw > 36 || a.W + 2 * a.pad > 63) {
+  const bool w65 = a.kh == 6 && a.kw == 5, w56 = a.kh == 5 && a.kw == 6;
+  if (!(w65 || w56) || a.W + 2 * a.pad > 63) {
     set_error("full_dw: unsupported window %dx%d", a.kh, a.kw);
     return TTNET_E_UNSUPPORTED;
   }
-  const int rows = a.n * a.ho;
-  const int chunks = std::max(1, std::min((rows + 255) / 256, std::max(1, 1024 / a.C)));
-  const bool w65 = a.kh == 6 && a.kw == 5, w56 = a.kh == 5 && a.kw == 6;
-  if (!full_exact_only() && (w65 || w56) && a.fix_list && a.fix_count && a.fix_cap) {
-    TT_HIP(hipMemsetAsync(a.fix_count, 0, sizeof(uint32_t), s));
-    if (w65) hipLaunchKernelGGL((full_dw_fast_kernel<6, 5>), dim3(a.C, chunks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((full_dw_fast_kernel<5, 6>), dim3(a.C, chunks), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(full_dw_fix_kernel, dim3(1024), dim3(256), 0, s, a);
-    TT_HIP(hipGetLastError());
-    return TTNET_OK;
-  }
-  if (a.kh == 6 && a.kw == 5) hipLaunchKernelGGL((full_dw_tab_kernel<6, 5>), dim3(a.C, chunks), dim3(256), 0, s, a);
-  else if (a.kh == 5 && a.kw == 6) hipLaunchKernelGGL((full_dw_tab_kernel<5, 6>), dim3(a.C, chunks), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(full_dw_kernel, dim3(a.C, chunks), dim3(256), 0, s, a);
-  TT_HIP(hipGetLastError());
-  return TTNET_OK;
+  return w65 ? launch_full_dw_window<6, 5>(a, s) : launch_full_dw_window<5, 6>(a, s);
 }
 
+// The plan builds the full variant only where every block's channels are a multiple of 30 (plan.hip build_geometry),
+// so every group is 30 -> 240 -> 30 (conv3, the last convf) or 30 -> 240 -> 15 (convf).
 int launch_full_pw(const FullPwArgs &a_in, hipStream_t s) {
   FullPwArgs a = a_in;
   a.tau_scale = full_tau_scale();
-  if (a.cin == 30 && a.mid == 240 && (a.cout == 30 || a.cout == 15) && a.W <= 64) {
-    const int ot = a.cout == 30 ? 2 : 1;
-    const size_t lds = sizeof(double) * ((size_t)15 * 8 * 64 + (size_t)15 * 4 * ot * 64 + 2 * 240);
-    const int rpw = 64 / a.W, tasks = a.n * ((a.H + rpw - 1) / rpw);
-    const int chunks = std::max(1, std::min((tasks + 7) / 8, std::max(1, 512 / a.groups)));
-    const bool fast = !full_exact_only() && (a.out_float || (a.fix_list && a.fix_count)) && a.groups <= 62;
-    if (fast) {
-      if (!a.out_float) TT_HIP(hipMemsetAsync(a.fix_count, 0, 62 * sizeof(uint32_t), s));
-      // two workgroups per CU (64 KiB of fragments each)
-      const int fchunks = std::max(1, std::min((tasks + 7) / 8, std::max(1, 512 / a.groups)));
-      if (ot == 2) {
-        TT_TRY(ensure_dynamic_lds((const void *)full_pw_fast_kernel<2>, fast_lds_bytes<2>()));
-        hipLaunchKernelGGL(full_pw_fast_kernel<2>, dim3(a.groups, fchunks), dim3(512), fast_lds_bytes<2>(), s, a);
-      } else {
-        TT_TRY(ensure_dynamic_lds((const void *)full_pw_fast_kernel<1>, fast_lds_bytes<1>()));
-        hipLaunchKernelGGL(full_pw_fast_kernel<1>, dim3(a.groups, fchunks), dim3(512), fast_lds_bytes<1>(), s, a);
-      }
-      TT_HIP(hipGetLastError());
-      if (a.out_float) return TTNET_OK;
-      // the listed pixels in float64, 16 per wave task: one workgroup per CU (its float64 fragments fill the LDS);
-      // workgroups without listed pixels leave at once
-      const int xchunks = std::max(1, std::min((tasks / 4 + 7) / 8, std::max(1, 256 / a.groups)));
-      if (ot == 2) {
-        TT_TRY(ensure_dynamic_lds((const void *)full_pw_mfma_kernel<2, true>, lds));
-        hipLaunchKernelGGL((full_pw_mfma_kernel<2, true>), dim3(a.groups, xchunks), dim3(512), lds, s, a);
-      } else {
-        TT_TRY(ensure_dynamic_lds((const void *)full_pw_mfma_kernel<1, true>, lds));
-        hipLaunchKernelGGL((full_pw_mfma_kernel<1, true>), dim3(a.groups, xchunks), dim3(512), lds, s, a);
-      }
-      TT_HIP(hipGetLastError());
-      return TTNET_OK;
-    }
-    if (ot == 2) {
-      TT_TRY(ensure_dynamic_lds((const void *)full_pw_mfma_kernel<2, false>, lds));
-      hipLaunchKernelGGL((full_pw_mfma_kernel<2, false>), dim3(a.groups, chunks), dim3(512), lds, s, a);
-    } else {
-      TT_TRY(ensure_dynamic_lds((const void *)full_pw_mfma_kernel<1, false>, lds));
-      hipLaunchKernelGGL((full_pw_mfma_kernel<1, false>), dim3(a.groups, chunks), dim3(512), lds, s, a);
-    }
-    TT_HIP(hipGetLastError());
-    return TTNET_OK;
-  }
-  if (a.cin > 32 || a.cout > 30 || a.W > 64) {
+  if (a.cin != kPwCin || a.mid != kPwMid || (a.cout != 30 && a.cout != 15) || a.W > 64) {
     set_error("full_pw: unsupported group %d -> %d", a.cin, a.cout);
     return TTNET_E_UNSUPPORTED;
   }
-  const size_t lds = sizeof(double) * ((size_t)a.mid * a.cin + (size_t)a.cout * a.mid + 2 * a.mid + 2 * a.cout);
-  if (lds > (size_t)kMaxLds) {
-    set_error("full_pw: weights (%zu B) exceed LDS", lds);
-    return TTNET_E_UNSUPPORTED;
-  }
-  if (lds > 64 * 1024)
-    TT_TRY(ensure_dynamic_lds((const void *)full_pw_kernel, lds));
-  const int rpw = 64 / a.W, rows = a.n * ((a.H + rpw - 1) / rpw);        // row bundles (tasks) of the launch
-  const int chunks = std::max(1, std::min((rows + 15) / 16, std::max(1, 512 / a.groups)));
-  hipLaunchKernelGGL(full_pw_kernel, dim3(a.groups, chunks), dim3(1024), lds, s, a);
-  TT_HIP(hipGetLastError());
-  return TTNET_OK;
+  return a.cout == 30 ? launch_full_pw_tiles<2>(a, s) : launch_full_pw_tiles<1>(a, s);
 }
 
 int launch_rp_majority(const uint64_t *x, uint64_t *out, int n, int C, int H, int W, int Ho, int pad_t, int pad_l,

@@ -43,6 +43,35 @@ def test_full_does_not_construct_at_p64():
         make_spec("full", nfilter=8, tfilter=8)
 
 
+def test_full_1x1_groups_are_the_matrix_kernels_shapes():
+    """launch_full_pw (gate_full.hip) has kernels for groups of 30 -> 240 -> 30 and 30 -> 240 -> 15 and refuses every
+    other shape.  Enumerated over every full model the constructor rule admits (p = 1..64, --layers 0..1):
+      * the models the plan builds (plan.hip build_geometry: every block's channels a multiple of 30) have no other
+        shape;
+      * in every other model the first 1x1 block in launch order (conv3, then convf, block by block) that has
+        another shape is one launch_full_pw refused before it lost its generic kernel too (cin > 32 or cout > 30).
+        Not every shape is: convf of the first block is 31 -> 248 -> 15 at p = 31 and 62 and 32 -> 256 -> 16 at
+        p = 32, 40 and 48, but conv3 of the same block (31 -> 31, 32 -> 32, 40 -> 40, 48 -> 48) comes first."""
+    matrix = {(30, 240, 30), (30, 240, 15)}
+    built, late = [], set()
+    for layers in (0, 1):
+        for p in range(1, 65):
+            try:
+                spec = make_spec("full", nfilter=p, tfilter=1, layers=layers)
+            except (ValueError, ZeroDivisionError):         # p < 30: no group at all
+                continue
+            order = [(c.cin_g, c.mid_g, c.cout_g) for b in spec.blocks for c in (b.conv3, b.convf)]
+            if all(b.in_planes % 30 == 0 for b in spec.blocks):
+                built.append((p, layers))
+                assert set(order) <= matrix, (p, layers, order)
+                continue
+            first = next(s for s in order if s not in matrix)
+            assert first[0] > 32 or first[2] > 30, (p, layers, first)
+            late |= {s for s in order if s not in matrix and not (s[0] > 32 or s[2] > 30)}
+    assert built == [(30, 0), (60, 0), (30, 1), (60, 1)]
+    assert late == {(31, 248, 15), (32, 256, 16)}
+
+
 @pytest.mark.parametrize("variant", ["small", "xsmall"])
 def test_module_state_dict_is_drop_in(variant):
     from scale_imagenet_amd import ttnet
