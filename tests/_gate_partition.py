@@ -19,6 +19,15 @@ and the tasks per image of the flat grids (``xs_kernels``, ``VA_KERNELS``).  If 
 kernels, the bit comparison still holds for every size that is run, but a size may stop reaching the case it was
 derived for; whoever changes them updates this file, and tests/test_gate_batch_sizes_cpu.py then says whether the
 sizes still reach every case.
+
+The full variant (gate_full.hip, the last section below) is not pinned to its launchers by any plan query:
+``gate_grid:`` serves gate paths 0 and 1 only.  Its grids are ``chunks = min(ceil(work / per chunk), cap / units)`` with
+the literals 256 rows per chunk and 1024 workgroups (launch_full_dw_window), 8 wave tasks per chunk and 512 workgroups
+(launch_full_pw_tiles), 256 / groups chunks for the float64 pass over the list and 16 listed pixels per wave task of
+that pass (full_pw_mfma_kernel<OT, true>), and the list capacity of plan.hip (``full_fix_cap``).  All of them are
+restated here by hand: whoever changes one of them in gate_full.hip or plan.hip updates that section, and
+tests/test_gate_batch_sizes_cpu.py then says whether ``full_sizes`` and the forced-list cases of
+tests/test_gpu_full_fallback.py still reach every branch.
 """
 from __future__ import annotations
 
@@ -295,6 +304,151 @@ def flat_edge_images(kernels: List[FlatKernel], sizes: List[int]) -> List[int]:
                 out |= {m - 1, m}
     return sorted(out)
 
+
+# ---- gate_full.hip: grid-stride loops over rows (depthwise) and over wave tasks (grouped 1x1) ---------------------
+
+FULL_DW_ROWS, FULL_DW_GRID = 256, 1024        # launch_full_dw_window: threads (= output rows) per chunk, workgroups at most
+FULL_PW_WAVES, FULL_PW_GRID = 8, 512          # launch_full_pw_tiles: wave tasks per chunk (512 threads), workgroups at most
+FULL_FIX_GRID, FULL_FIX_PIXELS = 256, 16      # the float64 pass over the list: workgroups at most, listed pixels per wave task
+
+
+def _ceil(a: int, b: int) -> int:
+    return -(-a // b)
+
+
+def full_dw_chunks(n: int, C: int, ho: int) -> int:
+    """launch_full_dw_window: grid (C, chunks), one thread per (image, output row)."""
+    return max(1, min(_ceil(n * ho, FULL_DW_ROWS), max(1, FULL_DW_GRID // C)))
+
+
+def full_dw_sweeps(n: int, C: int, ho: int) -> int:
+    return _ceil(n * ho, FULL_DW_ROWS * full_dw_chunks(n, C, ho))
+
+
+def row_bundle(H: int, W: int) -> Tuple[int, int]:
+    """RowBundle: (rows per 64-lane wave task, tasks per image)."""
+    rpw = 64 // W
+    return rpw, _ceil(H, rpw)
+
+
+def full_pw_chunks(n: int, groups: int, H: int, W: int) -> int:
+    """launch_full_pw_tiles: grid (groups, chunks), 8 waves per workgroup, one task per wave and sweep."""
+    return max(1, min(_ceil(n * row_bundle(H, W)[1], FULL_PW_WAVES), max(1, FULL_PW_GRID // groups)))
+
+
+def full_pw_sweeps(n: int, groups: int, H: int, W: int) -> int:
+    return _ceil(n * row_bundle(H, W)[1], FULL_PW_WAVES * full_pw_chunks(n, groups, H, W))
+
+
+def full_fix_xchunks(n: int, groups: int, H: int, W: int) -> int:
+    """launch_full_pw_tiles: the y extent of full_pw_mfma_kernel<OT, true>'s grid."""
+    tasks = n * row_bundle(H, W)[1]
+    return max(1, min((tasks // 4 + 7) // 8, max(1, FULL_FIX_GRID // groups)))
+
+
+def full_fix_sweeps(n: int, groups: int, H: int, W: int, listed: int) -> int:
+    """Sweeps of the float64 pass of one group that has ``listed`` pixels on its list (at most all n * H * W)."""
+    tasks = _ceil(min(listed, n * H * W), FULL_FIX_PIXELS)
+    return _ceil(tasks, FULL_PW_WAVES * full_fix_xchunks(n, groups, H, W))
+
+
+class FullKernel(NamedTuple):
+    """One main kernel launch of a block of the full variant: chunks = min(ceil(n * unit / per_chunk), cap)."""
+    name: str
+    block: int
+    kind: str           # "dw" (conv1, conv2) or "pw" (conv3, convf)
+    unit: int           # rows (dw) or wave tasks (pw) per image
+    per_chunk: int
+    cap: int            # chunks at most
+    outputs: int        # what the kernel may list, per image: C * ho * wo outputs (dw), groups * H * W pairs (pw); 0: lists nothing
+    groups: int
+    hw: Tuple[int, int]  # pixel grid (pw) or output size (dw)
+
+    def chunks(self, n: int) -> int:
+        return max(1, min(_ceil(n * self.unit, self.per_chunk), self.cap))
+
+    def sweeps(self, n: int) -> int:
+        return _ceil(n * self.unit, self.per_chunk * self.chunks(n))
+
+
+def full_kernels(spec) -> List[FullKernel]:
+    """conv1, conv2, conv3 and convf of every block, as run_full_block (plan.hip) launches them."""
+    out = []
+    for i, b in enumerate(spec.blocks):
+        H, W = b.in_hw
+        for c in (b.conv1, b.conv2):
+            ho, wo = c.out_hw(H, W)
+            out.append(FullKernel(f"{b.name} {c.name.rsplit('_', 1)[1]}", i, "dw", ho, FULL_DW_ROWS, max(1, FULL_DW_GRID // b.in_planes),
+                                  b.in_planes * ho * wo, b.in_planes, (ho, wo)))
+        for c, (h, w) in ((b.conv3, (H, W)), (b.convf, b.out_hw)):
+            out.append(FullKernel(f"{b.name} {c.name.rsplit('_', 1)[1]}", i, "pw", row_bundle(h, w)[1], FULL_PW_WAVES,
+                                  max(1, FULL_PW_GRID // c.groups), 0 if c.last else c.groups * h * w, c.groups, (h, w)))
+    for k in out:                                     # the two statements of each grid agree
+        for n in (1, 7, 40, 200):
+            if k.kind == "dw":
+                assert (k.chunks(n), k.sweeps(n)) == (full_dw_chunks(n, k.groups, k.unit), full_dw_sweeps(n, k.groups, k.unit))
+            else:
+                assert (k.chunks(n), k.sweeps(n)) == (full_pw_chunks(n, k.groups, *k.hw), full_pw_sweeps(n, k.groups, *k.hw))
+    return out
+
+
+def full_dw_outputs(spec) -> int:
+    """Depthwise outputs per image: C * ho * wo over conv1 and conv2 of every block (ho and wo differ: (6,5) / (5,6) windows)."""
+    return sum(k.outputs for k in full_kernels(spec) if k.kind == "dw")
+
+
+def full_pw_pairs(spec) -> int:
+    """(pixel, group) pairs per image over every binarised 1x1 block (the last convf emits floats and lists nothing)."""
+    return sum(k.outputs for k in full_kernels(spec) if k.kind == "pw")
+
+
+def full_fix_cap(spec, max_batch: int) -> int:
+    """plan.hip: list entries of a lane: the largest groups * H * W of a binarised 1x1 block, times the reserved batch.
+    The depthwise kernels share that area, so it also caps their list (Lane::full_fix, FullDwArgs::fix_cap)."""
+    return max(k.outputs for k in full_kernels(spec) if k.kind == "pw") * max_batch
+
+
+def full_last_single_sweep(k: FullKernel) -> int:
+    """The largest batch that kernel k finishes in one sweep (n * unit <= per_chunk * cap; below the cap there is one sweep)."""
+    return k.per_chunk * k.cap // k.unit
+
+
+def full_sizes(spec) -> List[int]:
+    """Batch sizes for the full variant: 1, 2, 3 (every grid below its cap); per kernel of every block the last batch of
+    one sweep and the first of two; and the largest of these plus 13 (N_max: several kernels deep in their second sweep)."""
+    sizes = {1, 2, 3}
+    for k in full_kernels(spec):
+        n1 = full_last_single_sweep(k)
+        sizes |= {n1, n1 + 1}
+    sizes.add(max(sizes) + 13)
+    return sorted(sizes)
+
+
+def full_second_sweep(k: FullKernel, n: int) -> Tuple[int, int]:
+    """(first, last) image that kernel k touches in its second sweep at batch n, or () if it has none.  Work item t (row or
+    wave task) belongs to image t // unit, and sweep s covers items [s, s + 1) * per_chunk * chunks."""
+    if k.sweeps(n) < 2:
+        return ()
+    per_sweep = k.per_chunk * k.chunks(n)
+    return per_sweep // k.unit, (min(2 * per_sweep, n * k.unit) - 1) // k.unit
+
+
+def full_edge_images(spec, sizes: List[int]) -> List[int]:
+    """Where the constant images of the sweep go: first and last image of the second sweep of every kernel, at its first
+    two-sweep size and at the largest size; and images 0 and N_max - 1."""
+    n_max, out = max(sizes), {0, max(sizes) - 1}
+    for k in full_kernels(spec):
+        for n in (full_last_single_sweep(k) + 1, n_max):
+            if n <= n_max:
+                out |= set(full_second_sweep(k, n))
+    return sorted(out)
+
+
+FULL = [(6, 10, 1)]                                                      # the shipped full model: p = 60 --layers 1
+FULL_CPU_ONLY = [(6, 10, 0)]                                             # sizes asserted on the CPU only
+# tests/test_gpu_full_fallback.py, every output listed: (reserved batch, n whose depthwise lists hold everything, n at which
+# features.4 alone overflows, n at which every block overflows); test_gate_batch_sizes_cpu.py asserts that they do
+FULL_FALLBACK = (40, 5, 6, 40)
 
 # ---- the geometries of the sweep: (nfilter, tfilter, --layers) ---------------------------------------------------
 FUSED_ONLY = [(2, 8, 1), (6, 8, 1), (12, 8, 1), (16, 8, 1)]             # TT-small p = 16, 48, 96, 128

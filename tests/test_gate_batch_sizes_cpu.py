@@ -175,3 +175,112 @@ def test_constant_images_sit_on_slice_and_round_edges(g, both):
         assert rounds == [R, R, 1]
         # first and last image of each of the three rounds of that workgroup
         assert {n0, n0 + R - 1, n0 + R, n0 + 2 * R - 1, n0 + 2 * R} <= set(edges)
+
+
+# ---- the full variant (gate_full.hip): test_full_batches and tests/test_gpu_full_fallback.py ------------------------
+
+FULL_GEOMETRIES = GP.FULL + GP.FULL_CPU_ONLY
+# what tests/test_gpu_full_fallback.py runs (it reads the same four numbers)
+FALLBACK_MAX_BATCH, FALLBACK_LISTS_ALL, FALLBACK_MIXED, FALLBACK_OVERFLOW = GP.FULL_FALLBACK
+
+
+def _full(g):
+    return make_spec("full", *g)
+
+
+def test_full_geometries_and_shipped_counts():
+    assert sorted((a * b, l) for a, b, l in FULL_GEOMETRIES) == [(60, 0), (60, 1)] and GP.FULL == [(6, 10, 1)]
+    spec = _full(GP.FULL[0])
+    assert [b.name for b in spec.blocks] == ["features.4", "features.5", "features.6"]
+    # (6,5) and (5,6) windows: the two depthwise outputs of features.5 are 15 x 16 and 16 x 15
+    k = {x.name: x for x in GP.full_kernels(spec)}
+    assert k["features.5 conv1"].hw == (15, 16) and k["features.5 conv2"].hw == (16, 15)
+    assert (GP.full_dw_outputs(spec), GP.full_pw_pairs(spec), GP.full_fix_cap(spec, 1)) == (197400, 22508, 6728)
+    assert k["features.6 convf"].outputs == 0 and all(x.outputs > 0 for x in k.values() if x.name != "features.6 convf")
+    assert GP.full_sizes(spec) == [1, 2, 3, 34, 35, 36, 37, 64, 65, 68, 69, 113, 114, 128, 129, 136, 137, 150, 151, 164]
+    # the row bundles of a 64-lane wave task: 29 x 29 leaves the last bundle half empty, 9 x 9 puts 2 of 7 rows into it
+    assert GP.row_bundle(56, 56) == (1, 56) and GP.row_bundle(16, 16) == (4, 4)
+    assert GP.row_bundle(29, 29) == (2, 15) and 29 - 14 * 2 == 1
+    assert GP.row_bundle(9, 9) == (7, 2) and 9 - 7 == 2
+    assert {x.hw for x in k.values() if x.kind == "pw"} == {(56, 56), (29, 29), (16, 16), (9, 9)}
+
+
+@pytest.mark.parametrize("g", FULL_GEOMETRIES)
+def test_full_sizes_reach_one_and_two_sweeps_of_every_kernel(g):
+    spec = _full(g)
+    sizes = GP.full_sizes(spec)
+    assert sizes == sorted(set(sizes)) and {1, 2, 3} <= set(sizes) and sizes[-1] == sizes[-2] + 13
+    kernels = GP.full_kernels(spec)
+    assert len(kernels) == 4 * len(spec.blocks)
+    for k in kernels:
+        tag = f"p={g[0] * g[1]} --layers {g[2]} {k.name}"
+        walk = {n: (k.chunks(n), k.sweeps(n)) for n in sizes}
+        # a grid below its cap; the first batch of two sweeps, right after the last one of one sweep
+        assert any(c < k.cap for c, _ in walk.values()), tag
+        two = min(n for n in range(1, 4096) if k.sweeps(n) == 2)
+        assert walk.get(two) == (k.cap, 2) and walk.get(two - 1, (0, 0))[1] == 1, tag
+        # one sweep with the grid AT its cap.  Where an image has more work items than a chunk takes per sweep (conv3 of
+        # features.4: 56 wave tasks per image, 8 per chunk) the step from n to n + 1 can jump from below the cap straight
+        # into the second sweep, and no batch has that case: then the last one-sweep batch must at least be the largest
+        # one-sweep grid there is.
+        at_cap = [n for n in range(1, two) if k.chunks(n) == k.cap]
+        if at_cap:
+            assert any(walk.get(n) == (k.cap, 1) for n in at_cap), tag
+        else:
+            assert k.unit > k.per_chunk and walk[two - 1] == (GP._ceil((two - 1) * k.unit, k.per_chunk), 1), tag
+            assert k.cap - walk[two - 1][0] < GP._ceil(k.unit, k.per_chunk), tag
+        # N_max is past the first sweep of every kernel, and some kernel walks three or more
+        assert walk[sizes[-1]][1] >= 2, tag
+    assert max(k.sweeps(sizes[-1]) for k in kernels) >= 3
+    assert sum(1 for k in kernels if not [n for n in range(1, 4096) if k.sweeps(n) == 1 and k.chunks(n) == k.cap]) <= 1
+
+
+@pytest.mark.parametrize("g", FULL_GEOMETRIES)
+def test_full_constant_images_sit_on_second_sweep_edges(g):
+    spec = _full(g)
+    sizes = GP.full_sizes(spec)
+    edges = set(GP.full_edge_images(spec, sizes))
+    assert 0 in edges and max(sizes) - 1 in edges and len(edges) < max(sizes) // 4
+    for k in GP.full_kernels(spec):
+        two = GP.full_last_single_sweep(k) + 1
+        first, last = GP.full_second_sweep(k, two)
+        assert last == two - 1 and first <= last and {first, last} <= edges, k.name     # the second sweep at its first size: the tail of the batch
+        assert GP.full_second_sweep(k, two - 1) == ()
+        first, last = GP.full_second_sweep(k, max(sizes))
+        assert first < last <= max(sizes) - 1 and {first, last} <= edges, k.name
+
+
+def test_full_run_order_goes_up_down_and_up():
+    sizes = GP.full_sizes(_full(GP.FULL[0]))
+    order = GP.run_order(sizes)
+    assert set(order) == set(sizes) and order[0] == 1 and order[1] == order[-1] == max(sizes) and sum(order) == 1800
+
+
+def test_forced_list_cases_reach_every_branch_of_the_float64_pass():
+    """tests/test_gpu_full_fallback.py lists EVERY output (TTNET_FULL_TAU_SCALE=1e30) on a plan reserved for 40 images:
+    whether the depthwise list then holds them (``all == false`` of full_dw_fix_kernel) or overflows (recompute all)
+    follows from n alone."""
+    spec = _full(GP.FULL[0])
+    cap = GP.full_fix_cap(spec, FALLBACK_MAX_BATCH)
+    assert cap == FALLBACK_MAX_BATCH * 6728
+    dw = [k for k in GP.full_kernels(spec) if k.kind == "dw"]
+    pw = [k for k in GP.full_kernels(spec) if k.kind == "pw" and k.outputs]
+    assert len(dw) == 6 and len(pw) == 5
+    over = lambda n: [k.block for k in dw if n * k.outputs > cap]       # (the kernel's test: listed > fix_cap)
+    assert over(FALLBACK_LISTS_ALL) == []                               # the list holds every output of every block
+    assert over(FALLBACK_MIXED) == [0, 0]                               # features.4 overflows, features.5 and .6 do not
+    assert over(FALLBACK_OVERFLOW) == [0, 0, 1, 1, 2, 2]                # every block recomputes all
+    assert FALLBACK_LISTS_ALL + 1 == FALLBACK_MIXED                     # (the two sides of the threshold)
+    for k in pw:
+        # a group's list never outgrows its share of the area, whatever is listed: groups * n * H * W <= cap
+        for n in (FALLBACK_LISTS_ALL, FALLBACK_MIXED, FALLBACK_OVERFLOW):
+            assert n * k.outputs <= cap, k.name
+        # with every pixel listed the float64 pass walks each group in several sweeps, already at n = 5
+        H, W = k.hw
+        assert GP.full_fix_sweeps(FALLBACK_LISTS_ALL, k.groups, H, W, FALLBACK_LISTS_ALL * H * W) >= 2, k.name
+        assert GP.full_fix_sweeps(FALLBACK_LISTS_ALL, k.groups, H, W, 10 ** 9) == GP.full_fix_sweeps(FALLBACK_LISTS_ALL, k.groups, H, W, FALLBACK_LISTS_ALL * H * W)
+        assert GP.full_fix_sweeps(FALLBACK_LISTS_ALL, k.groups, H, W, 16) == 1 and GP.full_fix_xchunks(1, k.groups, H, W) >= 1
+    # n = 40: the 1x1 main kernels of features.4 take two sweeps
+    assert [k.sweeps(FALLBACK_OVERFLOW) for k in pw if k.block == 0] == [2, 2]
+    # the depthwise counter counts past the cap, and neither running total wraps its 32 bits within the test file
+    assert 20 * FALLBACK_OVERFLOW * GP.full_dw_outputs(spec) < 2 ** 32

@@ -9,10 +9,15 @@ up, down and up again; before each size the whole workspace is overwritten by a 
 image that a kernel fails to write cannot read back the right answer of an earlier run.  The oracle (oracle/ttnet_bits.py on the GPU's own tables, which other tests pin to float64)
 evaluates all N_max images once; a batch of n is the prefix bits[:n].  Nothing is sampled: every stage of every image
 of every batch is compared.
+
+The full variant (fan-in 30, gate_full.hip) has no tables: the oracle evaluates every block directly in float64
+(OB.apply_direct), and the sweep runs twice, on the default path (split-fp16 / float32 with a float64 pass over the
+listed outputs) and with TTNET_FULL_EXACT=1, at sizes that put every grid-stride loop of its kernels into a second sweep.
 """
 import hashlib
 import os
 import time
+from contextlib import contextmanager
 from argparse import Namespace
 from concurrent.futures import ThreadPoolExecutor
 
@@ -29,7 +34,7 @@ from scale_imagenet_amd.spec import VAlexSpec, make_spec
 pytestmark = pytest.mark.gpu
 
 CLASSES = {"small": ttnet.TT_vf_19lv3_imgnet_small, "xsmall": ttnet.TT_vf_19lv3_imgnet_xsmall,
-           "valexnet": ttnet.TT_FHE_XSMALL_vAlexnet}
+           "valexnet": ttnet.TT_FHE_XSMALL_vAlexnet, "full": ttnet.TT_vf_19lv3_imgnet}
 PATH_TWO_LAUNCH, PATH_FUSED, PATH_XSMALL, PATH_FULL, PATH_VALEXNET = range(5)      # "gate_path" of ttnet_plan_query
 WORKERS = min(16, os.cpu_count() or 1)
 
@@ -116,17 +121,58 @@ def first_bad(mask):
     return int(bad[0]), len(bad)
 
 
-def run_and_check(tag, m, spec, rows_dev, scrub_dev, n, stages, feat, exact, blocks, path):
+@contextmanager
+def env_set(monkeypatch, env):
+    """Environment variables that gate_full.hip reads at every launch, set around one model's forwards."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    try:
+        yield
+    finally:
+        for k in env:
+            monkeypatch.delenv(k, raising=False)
+
+
+def tie_report(image_bits, st, spec, stage):
+    """For the failure text of a full-variant mismatch: how many outputs of the float64 oracle sit at |pre| < 1e-12 and
+    below OB.NEAR_TIE in the Block_TTs of the stage's block, for that one image.  The GPU sums in another order than the
+    oracle (a 1e-16 relative effect), so a differing bit at |pre| < 1e-12 is an exact tie turned by summation order; the
+    assertion is not loosened for it, the text only says so."""
+    blk = [b for b in spec.blocks if stage.startswith(b.name)][0]
+    out, keep = [], OB.NEAR_TIE
+    try:
+        for bound in (1e-12, keep):
+            OB.NEAR_TIE = bound                           # (apply_direct reads it when it fills ``near``)
+            near = {}
+            OB.features_from_stem_bits(image_bits[None], st, spec, None, None, near)
+            out.append(", ".join(f"{k.rsplit('_', 1)[1]} {int(v.sum())}" for k, v in near.items() if k.startswith(blk.name)))
+    finally:
+        OB.NEAR_TIE = keep
+    return (f" [float64 oracle, this image, outputs with |pre| < 1e-12: {out[0]}; with |pre| < {keep:g}: {out[1]}.  A bit that differs "
+            f"only at |pre| < 1e-12 is an exact tie turned by summation order, not a kernel fault]")
+
+
+def run_and_check(tag, m, spec, rows_dev, scrub_dev, n, stages, feat, exact, blocks, path, listed=None, ties=None):
     """One batch of n images on model m against the oracle.  Returns (stage rows, flatten, logits) of the GPU.
 
     The buffers of a plan are image-major from a fixed base and nothing clears them between forwards, so after a run
     of the same images every slot would already hold its right answer, and an image that a kernel fails to write would
     read back correct.  Before each size the whole workspace is therefore overwritten by a forward of N_max OTHER
-    images (``scrub_dev``): what a kernel does not write at this n then holds another image's result."""
+    images (``scrub_dev``): what a kernel does not write at this n then holds another image's result.
+
+    ``listed`` (full variant): receives the growth of the plan's running totals "full_listed_pw" / "full_listed_dw" across
+    the forward of the n images alone (the scrub forward excluded), and the seconds that forward took.  ``ties``: called
+    with (first differing image, stage) for a note in the failure text."""
     plan = m._any_plan()
     with torch.no_grad():
         m.forward_from_stem_bits(scrub_dev)
+        if listed is not None:
+            before = plan.query("full_listed_pw"), plan.query("full_listed_dw")       # (synchronises)
+            t0 = time.time()
         y_dev = m.forward_from_stem_bits(rows_dev[:n])
+    if listed is not None:
+        listed["pw"], listed["dw"] = plan.query("full_listed_pw") - before[0], plan.query("full_listed_dw") - before[1]
+        listed["seconds"] = time.time() - t0
     y = y_dev.cpu().numpy()
     if path in (PATH_FUSED, PATH_TWO_LAUNCH):             # the restated partition against the launchers' own arithmetic
         for i, b in enumerate(blocks):
@@ -142,6 +188,8 @@ def run_and_check(tag, m, spec, rows_dev, scrub_dev, n, stages, feat, exact, blo
             if path == PATH_FUSED:
                 bi = [k for k, b in enumerate(spec.blocks) if stage.startswith(b.name)][0]
                 where = f" [fused block {bi}: {GP.fused_locate(i, n, blocks[bi].C, blocks[bi].HO)}]"
+            if ties is not None:
+                where = ties(i, stage)
             pytest.fail(f"{tag} n={n}: stage {stage} differs from the bit oracle in {cnt} of {n} images, first image {i}{where}")
     flat = m.read_stage("flatten", n)
     if spec.variant == "valexnet":
@@ -171,18 +219,32 @@ def run_and_check(tag, m, spec, rows_dev, scrub_dev, n, stages, feat, exact, blo
     return got, flat, y_dev
 
 
-def sweep(tag, dev, variant, nfilter, tfilter, layers, sizes, monkeypatch=None, both_paths=False, expect_path=None):
+def sweep(tag, dev, variant, nfilter, tfilter, layers, sizes, monkeypatch=None, both_paths=False, expect_path=None,
+          full_modes=False):
     """Build the model(s) of a geometry on plans reserved for max(sizes), run the oracle once over all images, then
     every size in GP.run_order.  ``both_paths``: a two-launch plan (TTNET_GATE_UNFUSED=1, read at plan creation) and a
-    fused plan of the same geometry; each is checked against the oracle and they are compared with each other."""
+    fused plan of the same geometry; each is checked against the oracle and they are compared with each other.
+    ``full_modes`` (full variant): a plan on the default path and one that runs under TTNET_FULL_EXACT=1, both created
+    under TTNET_NO_GRAPH=1 (read once, at plan creation) so that no captured graph freezes what gate_full.hip reads from
+    the environment at every launch; the stages of the two must be the same bytes, and the float64 list counters are
+    bounded (default) or still (exact)."""
     t0 = time.time()
     n_max = max(sizes)
-    models = []
+    models, envs = [], [{}, {}]
     if both_paths:
         monkeypatch.setenv("TTNET_GATE_UNFUSED", "1")
         models.append(("two-launch by switch", PATH_TWO_LAUNCH) + build_model(variant, nfilter, tfilter, layers, dev, n_max))
         monkeypatch.delenv("TTNET_GATE_UNFUSED")
         models.append(("fused", PATH_FUSED) + build_model(variant, nfilter, tfilter, layers, dev, n_max))
+    elif full_modes:
+        monkeypatch.setenv("TTNET_NO_GRAPH", "1")
+        for name in ("TTNET_FULL_EXACT", "TTNET_FULL_TAU_SCALE"):
+            monkeypatch.delenv(name, raising=False)
+        envs = [{}, {"TTNET_FULL_EXACT": "1"}]
+        for label, env in zip(("default", "TTNET_FULL_EXACT=1"), envs):
+            with env_set(monkeypatch, env):
+                models.append((label, PATH_FULL) + build_model(variant, nfilter, tfilter, layers, dev, n_max))
+            assert models[-1][2]._any_plan().query("graphs_enabled") == 0, f"{tag}: {label}: the plan would capture graphs"
     else:
         assert os.environ.get("TTNET_GATE_UNFUSED") is None
         models.append((tag, expect_path) + build_model(variant, nfilter, tfilter, layers, dev, n_max))
@@ -192,13 +254,16 @@ def sweep(tag, dev, variant, nfilter, tfilter, layers, sizes, monkeypatch=None, 
         assert got_path == path, f"{tag}: {label} runs on gate path {got_path}, expected {path}"
     _, _, m0, spec, st = models[0]
     blocks = [] if variant == "valexnet" else GP.blocks_of(spec)
-    luts = {b.name: m0.get_table(b.name) for b in spec.block_tts()}
-    for _, _, m, _, _ in models[1:]:
+    # (the full variant has no tables, get_table refuses: the oracle evaluates every block directly in float64)
+    luts = None if variant == "full" else {b.name: m0.get_table(b.name) for b in spec.block_tts()}
+    for _, _, m, _, _ in models[1:] if luts is not None else ():
         for b in spec.block_tts():
             assert np.array_equal(m.get_table(b.name), luts[b.name]), f"{tag}: the two plans built different tables for {b.name}"
     hw = 10 if variant == "valexnet" else 56
     if variant == "valexnet":
         edges = GP.flat_edge_images(GP.VA_KERNELS, sizes)
+    elif variant == "full":
+        edges = GP.full_edge_images(spec, sizes)
     elif variant == "xsmall":
         edges = GP.flat_edge_images(GP.xs_kernels(blocks), sizes)
     else:
@@ -212,9 +277,30 @@ def sweep(tag, dev, variant, nfilter, tfilter, layers, sizes, monkeypatch=None, 
     # slot i of the scrub batch: the inverse of image i - 1, so no slot holds its own image or a constant one's twin
     scrub_dev = torch.from_numpy(OB.pack_rows(np.roll(1 - bits, 1, axis=0)).view(np.int64)).to(dev)
     order = GP.run_order(sizes)
+    seen, gpu_s = {}, 0.0                                  # full_modes: (mode, n) -> (list growth, logits) of the first run of n
     for n in order:
-        res = [run_and_check(f"{tag} [{label}]", m, spec, rows_dev, scrub_dev, n, stages, feat, exact, blocks, path)
-               for label, path, m, _, _ in models]
+        res = []
+        for k, (label, path, m, _, _) in enumerate(models):
+            if not full_modes:
+                res.append(run_and_check(f"{tag} [{label}]", m, spec, rows_dev, scrub_dev, n, stages, feat, exact, blocks, path))
+                continue
+            listed = {}
+            with env_set(monkeypatch, envs[k]):
+                res.append(run_and_check(f"{tag} [{label}]", m, spec, rows_dev, scrub_dev, n, stages, feat, exact, blocks, path,
+                                         listed=listed, ties=lambda i, stage: tie_report(bits[i], st, spec, stage)))
+            gpu_s += listed.pop("seconds")
+            pairs, outputs = n * GP.full_pw_pairs(spec), n * GP.full_dw_outputs(spec)
+            print(f"{tag} [{label}] n={n}: {listed['pw']} of {pairs} (pixel, group) pairs and {listed['dw']} of {outputs} depthwise outputs listed")
+            if envs[k]:
+                assert listed == {"pw": 0, "dw": 0}, f"{tag} [{label}] n={n}: the float64 path listed {listed}"
+            else:
+                assert 0 < listed["pw"] < pairs / 8 and 0 <= listed["dw"] < outputs / 100, (tag, n, listed, pairs, outputs)
+            first = seen.setdefault((k, n), (listed, res[-1][2]))
+            assert first[0] == listed, f"{tag} [{label}] n={n}: listed {listed} now, {first[0]} the first time"
+            assert torch.equal(first[1], res[-1][2]), f"{tag} [{label}] n={n}: logits differ between two runs of the same batch"
+        if full_modes:
+            for stage in res[0][0]:
+                assert np.array_equal(res[0][0][stage], res[1][0][stage]), f"{tag} n={n}: {stage} differs between the default and the float64 path"
         if both_paths:
             (s_u, f_u, y_u), (s_f, f_f, y_f) = res
             for stage in s_u:
@@ -222,7 +308,10 @@ def sweep(tag, dev, variant, nfilter, tfilter, layers, sizes, monkeypatch=None, 
             assert np.array_equal(f_u, f_f), f"{tag} n={n}: flatten differs between the two-launch and the fused plan"
             assert torch.equal(y_u, y_f), f"{tag} n={n}: logits differ between the two-launch and the fused plan"
     print(f"{tag}: sizes {order}: {sum(order) * len(models)} images compared with the oracle over {len(stages)} stages, flatten and "
-          f"logits; oracle pass over {n_max} images {t2 - t1:.1f} s on {WORKERS} threads, whole sweep {time.time() - t0:.1f} s")
+          f"logits; oracle pass over {n_max} images {t2 - t1:.1f} s on {WORKERS} threads, whole sweep {time.time() - t0:.1f} s"
+          + (f", of which {gpu_s:.1f} s in the forwards of the compared batches" if full_modes else ""))
+    if full_modes:
+        assert order.count(n_max) == 2 and all((k, n_max) in seen for k in range(2))
 
 
 def small_sizes(nfilter, tfilter, layers, both=False):
@@ -269,3 +358,12 @@ def test_xsmall_batches(dev, nfilter, tfilter, layers):
 def test_valexnet_batches(dev):
     """gate_va.hip through forward_from_stem_bits with rows [n][64][10], against OB.valexnet_from_stem_bits."""
     sweep("valexnet", dev, "valexnet", 8, 8, 1, GP.flat_sizes(GP.VA_KERNELS), expect_path=PATH_VALEXNET)
+
+
+def test_full_batches(dev, monkeypatch):
+    """gate_full.hip (fan-in 30, p = 60 --layers 1): the sizes of GP.full_sizes put every grid-stride loop of full_dw_* and
+    full_pw_* on both sides of its second sweep.  Default path and TTNET_FULL_EXACT=1, each against the float64 oracle
+    (OB.apply_direct, no tables) and against each other; the list counters of the default path stay a small share."""
+    nfilter, tfilter, layers = GP.FULL[0]
+    sweep(f"full p={nfilter * tfilter} --layers {layers}", dev, "full", nfilter, tfilter, layers,
+          GP.full_sizes(make_spec("full", nfilter, tfilter, layers)), monkeypatch=monkeypatch, expect_path=PATH_FULL, full_modes=True)
