@@ -443,6 +443,31 @@ int ttnet_minimise_covers(const uint32_t *on_dev, const uint32_t *dc_dev, int n_
                           uint32_t *cubes_dev, int64_t cube_cap, int32_t *counts_dev,
                           void *work_dev, int64_t work_bytes, void *stream);
 
+/* The same covers made smaller by `rounds` (0..8) reduce / expand rounds on the device; everything said above holds, and
+ * rounds = 0 gives the bytes of ttnet_minimise_covers.  Round 0 is the four steps and yields the cover K_0, an ordered list
+ * of keys.  Round r = 1 .. rounds turns K_{r-1} into K_r:
+ *   5 count        for every ON pattern, how many cubes of K_{r-1} hold it (what step 4 left behind).
+ *   6 reduce       walk the cubes of K_{r-1} from the last to the first.  E = the ON patterns of cube c whose count is 1;
+ *                  E is never empty, because K_{r-1} is irredundant and a count only falls for patterns that a cube
+ *                  leaves.  Replace c by the smallest cube that holds E (mask = the index bits on which all of E agree,
+ *                  value = their common bits) and decrement the count of every ON pattern of c that the smaller cube no
+ *                  longer holds.  Sequential by definition: the cubes walked later see the lowered counts.
+ *   7 expand       every reduced cube on its own, as in step 1, to a prime again; it keeps its position.  The literals
+ *                  are tried in the order x_{n-1} .. x_0 when r is odd and x_0 .. x_{n-1} when r is even.
+ *   8 order        by number of free variables, descending, then by position in K_{r-1}, ascending; then steps 3 and 4
+ *                  unchanged (a repeated key drops out in step 3 by itself).  The result is K_r.
+ *   9 best         the call returns the K_r, r = 0 .. rounds, with the smallest (literals, cubes), compared in that
+ *                  order; the earliest r wins a tie.  All rounds run, and round r+1 starts from K_r, not from the best.
+ * So the result is prime and irredundant, never carries more literals than the cover of ttnet_minimise_covers, and is
+ * deterministic.  A constant function and a K_0 of one cube are returned before any round.
+ * work_dev: at least ttnet_minimise_rounds_workspace(n_bits, n_funcs) bytes for every `rounds`: 16 * 2^n bytes, rounded up
+ * to 256, for each of min(n_funcs, 1024) workgroups (the 8 of ttnet_minimise_covers, a key list for the cover in hand and
+ * one for the best).  TTNET_E_INVALID (nothing launched) also for rounds outside 0..8. */
+int64_t ttnet_minimise_rounds_workspace(int n_bits, int64_t n_funcs);
+int ttnet_minimise_covers_rounds(const uint32_t *on_dev, const uint32_t *dc_dev, int n_bits, int64_t n_funcs, int rounds,
+                                 uint32_t *cubes_dev, int64_t cube_cap, int32_t *counts_dev,
+                                 void *work_dev, int64_t work_bytes, void *stream);
+
 /* Integer facts about the plan: "fcsize", "n_classes", "n_state_tensors", "max_batch",
  * "near_ties:<block_tt name>" (entries with |pre-activation| < 1e-5 found while building
  * that table), "table_bytes", "usage_bytes", "workspace_bytes", "graph_replays" (forwards replayed from a

@@ -27,7 +27,9 @@ Minimiser: ``minimiser="sympy"`` (the default) is the path above and writes what
 take the expressions from ``scale_imagenet_amd.minimise`` instead -- the HIP kernel, or its numpy twin -- for every
 n <= 16, so the 16-input tables of TT-small get their DNF / CNF / SAT-form files too; ``export_block`` minimises all its
 filters, both forms, in ONE device call.  Those covers are prime and irredundant, not minimum: an expression can carry more
-literals than sympy's for the same function (``profiles/minimise_bench.txt`` has the measured ratio).
+literals than sympy's for the same function (``profiles/minimise_bench.txt`` has the measured ratio).  ``rounds`` (0 .. 8,
+default 0: what it always was) adds that many reduce / expand rounds to "device" and "cpu", which shrink the covers
+(``profiles/minimise_rounds_bench.txt``: ratios and times per round count); "sympy" ignores it.
 """
 from __future__ import annotations
 
@@ -75,10 +77,11 @@ def cnf_with_output(dnf, cnf) -> str:
 
 def export_filter(column: np.ndarray, n: int, filter_index: int, out_dir: str, block: int, sub_block: int,
                   max_expr_bits: int = 9, usage: Optional[np.ndarray] = None, minimiser: str = "sympy", device=None,
-                  forms=None) -> Dict[str, Optional[str]]:
+                  forms=None, rounds: int = 0) -> Dict[str, Optional[str]]:
     """Files for one filter.  ``column``: its 2^n table entries (0/1), canonical order.  ``usage``: the lookup counts of
     the filter's group, int64 [2^n] (module docstring).  ``minimiser``: module docstring; ``forms``: this filter's
-    ``(DNF text, CNF text)`` when ``export_block`` has minimised it already."""
+    ``(DNF text, CNF text)`` when ``export_block`` has minimised it already.  ``rounds``: module docstring (ignored by
+    "sympy")."""
     import pandas as pd
     if minimiser not in ("sympy", "device", "cpu"):
         raise ValueError(f"minimiser {minimiser!r}: 'sympy', 'device' or 'cpu'")
@@ -117,7 +120,7 @@ def export_filter(column: np.ndarray, n: int, filter_index: int, out_dir: str, b
                 dnf, cnf = minimal_forms(minterms, n, dontcares)
             else:
                 dnf, cnf = forms if forms is not None else _cover_forms(answer[None, :, None], n, None if counts is None else counts[None],
-                                                                        minimiser, device)[0]
+                                                                        minimiser, device, rounds)[0]
             y = cnf_with_output(dnf, cnf)
             out.update(dnf=str(dnf), cnf=str(cnf), cnf_with_y=y, dnf_literals=literal_count(str(dnf)),
                        cnf_literals=literal_count(str(cnf)))
@@ -132,12 +135,12 @@ def export_filter(column: np.ndarray, n: int, filter_index: int, out_dir: str, b
 
 def export_block(table: np.ndarray, out_dir: str, block: int, sub_block: int, filters: Optional[Iterable[int]] = None,
                  max_expr_bits: int = 9, usage: Optional[np.ndarray] = None, minimiser: str = "sympy",
-                 device=None) -> Dict[int, Dict[str, Optional[str]]]:
+                 device=None, rounds: int = 0) -> Dict[int, Dict[str, Optional[str]]]:
     """``table``: [groups][2^n][cout_g] bits as returned by ``model.get_table(name)`` (or by the
     oracle's ``build_lut``).  Filter f = output channel f of the block = (group f // cout_g,
     output f % cout_g).  ``usage``: int64 [groups][2^n] lookup counts of the block (module docstring).
     ``minimiser`` "device" / "cpu": all filters asked for are minimised at once (``device``: a torch device, default the
-    current one)."""
+    current one), with ``rounds`` reduce / expand rounds (module docstring; ignored by "sympy")."""
     g, size, cout_g = table.shape
     n = int(size).bit_length() - 1
     assert 2 ** n == size
@@ -149,9 +152,9 @@ def export_block(table: np.ndarray, out_dir: str, block: int, sub_block: int, fi
     if minimiser in ("device", "cpu") and n <= 16 and todo:
         from . import minimise
         on, dc = minimise.pack_functions(np.asarray(table) == 1, usage)
-        forms = dict(zip(todo, _texts(minimise.minimal_covers(on[todo], dc[todo], n, minimiser, device), n)))
+        forms = dict(zip(todo, _texts(minimise.minimal_covers(on[todo], dc[todo], n, minimiser, device, rounds), n)))
     return {f: export_filter(table[f // cout_g, :, f % cout_g], n, f, out_dir, block, sub_block, max_expr_bits,
-                             None if usage is None else usage[f // cout_g], minimiser, device, forms.get(f)) for f in todo}
+                             None if usage is None else usage[f // cout_g], minimiser, device, forms.get(f), rounds) for f in todo}
 
 
 def _texts(covers, n: int):
@@ -159,11 +162,11 @@ def _texts(covers, n: int):
     return [(minimise.dnf_text(d, n), minimise.cnf_text(c, n)) for d, c in covers]
 
 
-def _cover_forms(table: np.ndarray, n: int, usage, minimiser: str, device):
+def _cover_forms(table: np.ndarray, n: int, usage, minimiser: str, device, rounds: int = 0):
     """``(DNF text, CNF text)`` of every filter of a ``[G, 2^n, cout_g]`` 0/1 table from ``minimise`` (one call)."""
     from . import minimise
     on, dc = minimise.pack_functions(table, usage)
-    return _texts(minimise.minimal_covers(on, dc, n, minimiser, device), n)
+    return _texts(minimise.minimal_covers(on, dc, n, minimiser, device, rounds), n)
 
 
 def literal_count(expr_text: Optional[str]) -> int:

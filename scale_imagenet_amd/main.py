@@ -93,6 +93,9 @@ def build_parser() -> argparse.ArgumentParser:
                      help="CSV, one row per binarised Block_TT: cubes and literals of its filters' DNF / CNF covers (prime and "
                           "irredundant, minimised on the device), from the whole tables and, beside them, with the entries "
                           "this run never read as don't-cares (counts the table usage, as --table_usage does)")
+    out.add_argument("--table_gates_rounds", type=int, default=0, metavar="R", choices=range(9),
+                     help="reduce / expand rounds (0 .. 8) of the minimiser behind both columns of --table_gates; more rounds, "
+                          "smaller covers, longer minimisation; 0: the covers it always gave")
     ign = p.add_argument_group("accepted and ignored (training, logging and launcher flags of the reference)")
     for name, typ, default in _IGNORED:
         ign.add_argument(name, type=typ, default=default, help=argparse.SUPPRESS)
@@ -249,7 +252,8 @@ def run(args) -> int:
             if args.table_coverage:
                 report.write_coverage_csv(args.table_coverage, usage, {name: model.get_table(name) for name in usage})
         if rank == 0 and args.table_gates:
-            report.write_gates_csv(args.table_gates, model.gate_counts(), model.gate_counts(usage),
+            report.write_gates_csv(args.table_gates, model.gate_counts(rounds=args.table_gates_rounds),
+                                   model.gate_counts(usage, rounds=args.table_gates_rounds),
                                    {b.name: b.fan_in_bits for b in model.spec.block_tts()})
     if extra.get("topk") is not None:
         names = report.read_class_names(args.classes) if args.classes else None
@@ -272,6 +276,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     check_topk(args, needed=bool(args.predictions))
     if args.table_coverage and not args.table_usage:
         raise SystemExit("--table_coverage needs --table_usage")
+    if args.table_gates_rounds and not args.table_gates:
+        raise SystemExit("--table_gates_rounds needs --table_gates")
     return launch(args, argv, "scale_imagenet_amd.main", _check_paths, run)
 
 

@@ -1,8 +1,10 @@
 """Two-level minimisation of truth tables with don't-cares: prime, irredundant covers (not minimum ones).
 
 The algorithm -- expand every ON minterm to a prime, order the primes by size, keep those that cover something new, drop
-the redundant ones in reverse -- is stated in ``include/ttnet.h`` (``ttnet_minimise_covers``).  It exists twice and both
-give the same cubes in the same order:
+the redundant ones in reverse -- is stated in ``include/ttnet.h`` (``ttnet_minimise_covers``), and so are the optional
+``rounds`` on top of it (``ttnet_minimise_covers_rounds``): each reduces every cube of the cover to the patterns only it
+holds, expands it again in another order of the variables and runs the last two steps once more; the smallest cover
+met goes out.  It exists twice and both give the same cubes in the same order for every ``rounds``:
 
   ``minimise_device``  the HIP kernel of ``csrc/minimise.hip``, all functions of a batch in one launch;
   ``minimise_cpu``     its twin in numpy, with no device: the comparison in tests and benchmarks, never a fallback.
@@ -83,17 +85,20 @@ def _implicant_flags(not_off: np.ndarray, n: int) -> np.ndarray:
     return flag
 
 
-def _expand(on_idx: np.ndarray, flag: np.ndarray, n: int) -> np.ndarray:
-    """Step 1 for all ON minterms at once: their keys."""
+def _expand(keys: np.ndarray, flag: np.ndarray, n: int, order: Sequence[int]) -> np.ndarray:
+    """Steps 1 and 7 for all cubes at once: every literal of x_j, j in ``order``, is dropped iff the sibling half of the
+    cube as it then is holds no OFF pattern (``flag`` of ``_implicant_flags``); the grown keys."""
     flat = flag.reshape(-1)
     pow3 = 3 ** np.arange(n - 1, -1, -1, dtype=np.int64)           # weight of digit j
-    bits = (on_idx[:, None] >> np.arange(n - 1, -1, -1)[None, :]) & 1
-    idx = (bits * pow3[None, :]).sum(axis=1)
-    mask = np.full(on_idx.shape, (1 << n) - 1, dtype=np.int64)
-    value = on_idx.astype(np.int64)
-    for j in range(n):
-        b = bits[:, j]
-        drop = flat[idx + (1 - 2 * b) * pow3[j]]                   # the sibling half holds no OFF pattern
+    shifts = np.arange(n - 1, -1, -1)[None, :]
+    mask = (keys >> 16).astype(np.int64)
+    value = (keys & 0xFFFF).astype(np.int64)
+    digits = np.where((mask[:, None] >> shifts) & 1, (value[:, None] >> shifts) & 1, 2)
+    idx = (digits * pow3[None, :]).sum(axis=1)
+    for j in order:
+        b = digits[:, j]
+        literal = b != 2
+        drop = literal & flat[np.where(literal, idx + (1 - 2 * b) * pow3[j], 0)]                   # the sibling half
         idx = np.where(drop, idx + (2 - b) * pow3[j], idx)
         bit = 1 << (n - 1 - j)
         mask = np.where(drop, mask & ~bit, mask)
@@ -116,35 +121,27 @@ def _subset_sums(free_bits: int) -> np.ndarray:
     return out
 
 
-def minimise_cpu(on: np.ndarray, dc: Optional[np.ndarray], n: int) -> np.ndarray:
-    """The cover of one function (bitmaps, module docstring) as uint32 keys, by the four steps of ``include/ttnet.h``."""
-    _check_n(n)
-    on_b = unpack_bits(on, n)
-    dc_b = np.zeros_like(on_b) if dc is None else unpack_bits(dc, n) & ~on_b
-    on_idx = np.flatnonzero(on_b)
-    if len(on_idx) == 0:
-        return np.zeros(0, dtype=np.uint32)
-    if bool((on_b | dc_b).all()):
-        return np.zeros(1, dtype=np.uint32)
-    keys = _expand(on_idx, _implicant_flags(on_b | dc_b, n), n)
-    free = n - _POPCOUNT16[keys >> 16]
-    order = np.lexsort((on_idx, -free))                              # step 2
-    full = (1 << n) - 1
+def _cover_points(key: int, n: int, on_b: np.ndarray, on_idx: np.ndarray) -> np.ndarray:
+    """The ON patterns of a cube, ascending or not: whichever of the cube and the ON set is cheaper to enumerate."""
+    mask, value = key >> 16, key & 0xFFFF
+    if (1 << (n - bin(mask).count("1"))) <= len(on_idx):
+        pts = value | _subset_sums(~mask & ((1 << n) - 1))
+        return pts[on_b[pts]]
+    return on_idx[(on_idx & mask) == value]
+
+
+def _cover_irredundant(ordered: List[int], n: int, on_b: np.ndarray, on_idx: np.ndarray):
+    """Steps 3 and 4 on keys in step-2 order: ``(kept keys, their ON patterns, cover count of every pattern)``."""
     covered = np.zeros(1 << n, dtype=bool)
     count = np.zeros(1 << n, dtype=np.int32)
     kept: List[Tuple[int, np.ndarray]] = []
     tried = set()
-    for key in keys[order].tolist():                                 # step 3 (a repeated cube covers nothing new)
+    for key in ordered:                                              # step 3 (a repeated cube covers nothing new)
         if key in tried:
             continue
         tried.add(key)
-        mask, value = key >> 16, key & 0xFFFF
-        if (1 << (n - bin(mask).count("1"))) <= len(on_idx):
-            pts = value | _subset_sums(~mask & full)
-            pts = pts[on_b[pts]]
-        else:
-            pts = on_idx[(on_idx & mask) == value]
-        if covered[pts].all():
+        pts = _cover_points(key, n, on_b, on_idx)
+        if np.count_nonzero(covered[pts]) == len(pts):
             continue
         covered[pts] = True
         count[pts] += 1
@@ -152,16 +149,62 @@ def minimise_cpu(on: np.ndarray, dc: Optional[np.ndarray], n: int) -> np.ndarray
     alive = [True] * len(kept)
     for k in range(len(kept) - 1, -1, -1):                           # step 4
         pts = kept[k][1]
-        if (count[pts] >= 2).all():
+        if count[pts].min() >= 2:
             count[pts] -= 1
             alive[k] = False
-    return np.array([key for (key, _), a in zip(kept, alive) if a], dtype=np.uint32)
+    kept = [kp for kp, a in zip(kept, alive) if a]
+    return [k for k, _ in kept], [p for _, p in kept], count
+
+
+def minimise_cpu(on: np.ndarray, dc: Optional[np.ndarray], n: int, rounds: int = 0) -> np.ndarray:
+    """The cover of one function (bitmaps, module docstring) as uint32 keys, by the steps of ``include/ttnet.h``: the four
+    of ``ttnet_minimise_covers`` and, for ``rounds`` in 1 .. 8, the reduce / expand rounds of
+    ``ttnet_minimise_covers_rounds``, of which the cover with the fewest (literals, cubes) is returned."""
+    _check_n(n)
+    rounds = _check_rounds(rounds)
+    on_b = unpack_bits(on, n)
+    dc_b = np.zeros_like(on_b) if dc is None else unpack_bits(dc, n) & ~on_b
+    on_idx = np.flatnonzero(on_b)
+    if len(on_idx) == 0:
+        return np.zeros(0, dtype=np.uint32)
+    if bool((on_b | dc_b).all()):
+        return np.zeros(1, dtype=np.uint32)
+    flag = _implicant_flags(on_b | dc_b, n)
+    full = (1 << n) - 1
+    keys = _expand((full << 16) | on_idx.astype(np.uint32), flag, n, range(n))
+    free = n - _POPCOUNT16[keys >> 16]
+    order = np.lexsort((on_idx, -free))                              # step 2
+    cover, points, count = _cover_irredundant(keys[order].tolist(), n, on_b, on_idx)
+    best = cover
+    for r in range(1, int(rounds) + 1 if len(cover) > 1 else 0):
+        cover = list(cover)                                          # (``best`` may be this list)
+        for k in range(len(cover) - 1, -1, -1):                      # step 6 (step 5: ``count`` is what step 4 left)
+            pts = points[k]
+            lone = pts[count[pts] == 1]
+            assert len(lone), "an irredundant cover: every cube holds an ON pattern that no other cube holds"
+            agree = ~(int(np.bitwise_or.reduce(lone)) ^ int(np.bitwise_and.reduce(lone))) & full
+            value = int(lone[0]) & agree
+            count[pts[(pts & agree) != value]] -= 1
+            cover[k] = (agree << 16) | value
+        grown = _expand(np.array(cover, dtype=np.uint32), flag, n, range(n - 1, -1, -1) if r % 2 else range(n))       # step 7
+        order = np.argsort(_POPCOUNT16[grown >> 16], kind="stable")                                                 # step 8
+        cover, points, count = _cover_irredundant(grown[order].tolist(), n, on_b, on_idx)
+        if (literal_total(cover), len(cover)) < (literal_total(best), len(best)):                  # step 9
+            best = cover
+    return np.array(best, dtype=np.uint32)
 
 
 # ---- the device ------------------------------------------------------------------------------------------------------------
 
-def minimise_device(on, dc, n: int, device=None, cube_cap: Optional[int] = None) -> List[np.ndarray]:
-    """Covers of a batch of functions by ``ttnet_minimise_covers``: ``on`` / ``dc`` uint32 ``[F, words]`` (numpy, or torch
+def _check_rounds(rounds: int) -> int:
+    if not 0 <= int(rounds) <= 8:
+        raise ValueError(f"rounds = {rounds}: 0 .. 8 rounds are served")
+    return int(rounds)
+
+
+def minimise_device(on, dc, n: int, device=None, cube_cap: Optional[int] = None, rounds: int = 0) -> List[np.ndarray]:
+    """Covers of a batch of functions by ``ttnet_minimise_covers`` (``rounds`` = 0) or ``ttnet_minimise_covers_rounds``
+    (1 .. 8): ``on`` / ``dc`` uint32 ``[F, words]`` (numpy, or torch
     tensors on the device; ``dc`` None: no don't-cares) -> F arrays of uint32 keys.  One launch for the whole batch; the
     functions whose cover has more cubes than the first cap (``cube_cap``; by default what 256 MB of keys allow the batch, at
     least 1024 and at most 2^n, which never overflows) go through one more launch with the cap they need."""
@@ -169,6 +212,7 @@ def minimise_device(on, dc, n: int, device=None, cube_cap: Optional[int] = None)
 
     from . import _lib
     _check_n(n)
+    rounds = _check_rounds(rounds)
     lib = _lib.load()
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
 
@@ -193,13 +237,14 @@ def minimise_device(on, dc, n: int, device=None, cube_cap: Optional[int] = None)
         b = dc_t if (sel is None or dc_t is None) else dc_t[sel].contiguous()
         f = a.shape[0]
         with torch.cuda.device(dev):
-            work = torch.empty(_lib.check(lib.ttnet_minimise_workspace(n, f)), dtype=torch.uint8, device=dev)
+            sizer = lib.ttnet_minimise_rounds_workspace if rounds else lib.ttnet_minimise_workspace
+            work = torch.empty(_lib.check(sizer(n, f)), dtype=torch.uint8, device=dev)
             cubes = torch.empty((f, max(cap, 1)), dtype=torch.int32, device=dev)
             counts = torch.empty(f, dtype=torch.int32, device=dev)
-            _lib.check(lib.ttnet_minimise_covers(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr() if b is not None else None), n, f,
-                                                 C.c_void_p(cubes.data_ptr()), cubes.shape[1], C.c_void_p(counts.data_ptr()),
-                                                 C.c_void_p(work.data_ptr()), work.numel(),
-                                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            head = (C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr() if b is not None else None), n, f)
+            tail = (C.c_void_p(cubes.data_ptr()), cubes.shape[1], C.c_void_p(counts.data_ptr()), C.c_void_p(work.data_ptr()),
+                    work.numel(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            _lib.check(lib.ttnet_minimise_covers_rounds(*head, rounds, *tail) if rounds else lib.ttnet_minimise_covers(*head, *tail))
             got = counts.cpu().numpy()
             width = int(min(cap, max(int(got.max()), 1)))                # only the columns some cover reaches come back
             return got, np.ascontiguousarray(cubes[:, :width].cpu().numpy()).view(np.uint32)
@@ -302,26 +347,28 @@ def literal_total(cubes) -> int:
     return int(_POPCOUNT16[np.asarray(cubes, dtype=np.uint32) >> 16].sum())
 
 
-def minimal_covers(on: np.ndarray, dc: np.ndarray, n: int, minimiser: str, device=None) -> List[Tuple[np.ndarray, np.ndarray]]:
+def minimal_covers(on: np.ndarray, dc: np.ndarray, n: int, minimiser: str, device=None,
+                   rounds: int = 0) -> List[Tuple[np.ndarray, np.ndarray]]:
     """``(DNF cover, cover of the complement)`` of every function of ``on`` / ``dc`` ``[F, words]``; with ``"device"`` both
-    covers of all functions come from one launch, with ``"cpu"`` from the twin."""
+    covers of all functions come from one launch, with ``"cpu"`` from the twin.  ``rounds``: reduce / expand rounds, 0 .. 8."""
     on = np.asarray(on, dtype=np.uint32)
     dc = np.asarray(dc, dtype=np.uint32)
     off = complement(on, dc, n)
     if minimiser == "device":
-        both = minimise_device(np.concatenate([on, off]), np.concatenate([dc, dc]), n, device)
+        both = minimise_device(np.concatenate([on, off]), np.concatenate([dc, dc]), n, device, rounds=rounds)
     elif minimiser == "cpu":
-        both = [minimise_cpu(a, b, n) for a, b in zip(np.concatenate([on, off]), np.concatenate([dc, dc]))]
+        both = [minimise_cpu(a, b, n, rounds) for a, b in zip(np.concatenate([on, off]), np.concatenate([dc, dc]))]
     else:
         raise ValueError(f"minimiser {minimiser!r}: 'device' or 'cpu' (sympy is export's own path)")
     f = on.shape[0]
     return [(both[i], both[f + i]) for i in range(f)]
 
 
-def gate_count_row(on: np.ndarray, dc: np.ndarray, n: int, minimiser: str = "device", device=None) -> dict:
+def gate_count_row(on: np.ndarray, dc: np.ndarray, n: int, minimiser: str = "device", device=None, rounds: int = 0) -> dict:
     """``{filters, constant, dnf_cubes, dnf_literals, cnf_cubes, cnf_literals}`` of one block's functions; a filter that is
-    constant on its care patterns counts under ``constant`` and has no cubes or literals in either form."""
-    covers = minimal_covers(on, dc, n, minimiser, device)
+    constant on its care patterns counts under ``constant`` and has no cubes or literals in either form.  ``rounds``: as in
+    ``minimal_covers``."""
+    covers = minimal_covers(on, dc, n, minimiser, device, rounds)
     row = dict(filters=len(covers), constant=0, dnf_cubes=0, dnf_literals=0, cnf_cubes=0, cnf_literals=0)
     for dnf, cnf in covers:
         if literal_total(dnf) == 0 or literal_total(cnf) == 0:       # no cube, or the cube without a literal

@@ -348,23 +348,26 @@ class _TTNetBase(nn.Module):
         return out
 
     def export_truth_tables(self, block_name: str, out_dir: str, block: int = 0, sub_block: int = 0, filters=None,
-                            max_expr_bits: int = 9, usage=None, minimiser: str = "sympy"):
+                            max_expr_bits: int = 9, usage=None, minimiser: str = "sympy", rounds: int = 0):
         """Write the reference's truth-table files (CSV, DNF / CNF, SAT form) for one
         ``Block_TT`` from the table the plan built on the GPU.  ``usage``: that block's lookup counts
         (``table_usage()[block_name]``), whose zero entries become don't-care terms.  ``minimiser``: "sympy" (n <= 9), or
         "device" / "cpu" for prime, irredundant covers of every n <= 16 (the 16-input tables of TT-small), all filters of
-        the block in one launch on the plan's device.  See ``scale_imagenet_amd.export``."""
+        the block in one launch on the plan's device; ``rounds`` (0 .. 8) reduce / expand rounds make those covers smaller,
+        "sympy" ignores it.  See ``scale_imagenet_amd.export``."""
         from . import export
         table = self.get_table(block_name)
         device = torch.device("cuda", self._any_plan().device_index)
-        return export.export_block(table, out_dir, block, sub_block, filters, max_expr_bits, usage, minimiser, device)
+        return export.export_block(table, out_dir, block, sub_block, filters, max_expr_bits, usage, minimiser, device, rounds)
 
-    def gate_counts(self, usage=None, minimiser: str = "device") -> "OrderedDict[str, dict]":
+    def gate_counts(self, usage=None, minimiser: str = "device", rounds: int = 0) -> "OrderedDict[str, dict]":
         """Two-level gate counts of every binarised ``Block_TT`` (the float last block is skipped), without writing files:
         ``{name: {filters, constant, dnf_cubes, dnf_literals, cnf_cubes, cnf_literals}}`` from prime, irredundant covers
         (``scale_imagenet_amd.minimise``; not minimum ones), one launch per block for all its filters and both forms.
         ``usage``: ``table_usage()``; the entries never looked up become don't-cares.  ``constant`` counts the filters that
-        are constant on their care patterns; they add no cubes.  The full variant has no tables: ``get_table`` refuses."""
+        are constant on their care patterns; they add no cubes.  ``rounds``: 0 .. 8 reduce / expand rounds of the minimiser
+        ("device" or "cpu", the only ones served here), which make the covers smaller.  The full variant has no tables:
+        ``get_table`` refuses."""
         from . import minimise
         out: "OrderedDict[str, dict]" = OrderedDict()
         for b in self.spec.block_tts():
@@ -372,7 +375,8 @@ class _TTNetBase(nn.Module):
                 continue
             table = self.get_table(b.name)
             on, dc = minimise.pack_functions(table, None if usage is None else usage[b.name])
-            out[b.name] = minimise.gate_count_row(on, dc, b.fan_in_bits, minimiser, torch.device("cuda", self._any_plan().device_index))
+            out[b.name] = minimise.gate_count_row(on, dc, b.fan_in_bits, minimiser, torch.device("cuda", self._any_plan().device_index),
+                                                  rounds)
         return out
 
     def set_input_norm(self, mean, std):

@@ -7,6 +7,12 @@
                                                      p = 64 --layers 1 (DNF and CNF, synthetic weights), with and without
                                                      the don't-cares of N synthetic images; cubes and literals per block;
                                                      the CPU twin on K functions per block in 16 processes beside it
+  python tools/minimise_bench.py --rounds 0,1,2,4 [--quality] [--device] [--images N] [--repeats K]
+                                                     the same two measurements per number of reduce / expand rounds (the text
+                                                     goes to profiles/minimise_rounds_bench.txt): the literal ratios of
+                                                     --quality for every round count; the time of the --device job (all
+                                                     blocks, K alternating passes after a warm one, the best and the worst
+                                                     pass) and its gate totals.  Rounds 0 is ttnet_minimise_covers itself.
 """
 import argparse
 import os
@@ -28,10 +34,6 @@ def _twin_job(job):
 
 
 def quality():
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
-    from _util import spec_and_state
-    from oracle import ttnet_bits as OB
-
     def ratios(functions, n):
         out = []
         for on_b, dc_b in functions:
@@ -43,10 +45,17 @@ def quality():
             out.append(ours / (E.literal_count(str(dnf)) + E.literal_count(str(cnf))))
         return np.array(out)
 
-    def line(tag, r):
+    for tag, n, fns in quality_sets():
+        r = ratios(fns, n)
         print(f"{tag:<46} functions {len(r):4d}  literals ours / sympy: mean {r.mean():.3f}  median {np.median(r):.3f}  "
               f"min {r.min():.3f}  max {r.max():.3f}  p90 {np.quantile(r, 0.9):.3f}")
 
+
+def quality_sets():
+    """``[(tag, n, [(on flags, dc flags)])]``: the x-small tables and the seeded random functions of --quality."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from _util import spec_and_state
+    from oracle import ttnet_bits as OB
     spec, st = spec_and_state("xsmall")
     fns = []
     for blk in spec.blocks:
@@ -57,7 +66,7 @@ def quality():
             for g in range(table.shape[0]):
                 for o in range(table.shape[2]):
                     fns.append((table[g, :, o] == 1, np.zeros(16, dtype=bool)))
-    line("x-small tables (n = 4, synthetic weights)", ratios(fns, 4))
+    sets = [("x-small tables (n = 4, synthetic weights)", 4, fns)]
     for n, count in ((6, 200), (8, 40)):
         for p_on, p_dc in ((0.5, 0.0), (0.3, 0.4)):
             rng = np.random.default_rng(1000 * n + int(100 * p_dc))
@@ -65,12 +74,33 @@ def quality():
             for _ in range(count):
                 r = rng.random(1 << n)
                 fns.append((r < p_on, (r >= p_on) & (r < p_on + p_dc)))
-            line(f"random n = {n}, ON {p_on:.0%}, don't-care {p_dc:.0%}", ratios(fns, n))
+            sets.append((f"random n = {n}, ON {p_on:.0%}, don't-care {p_dc:.0%}", n, fns))
+    return sets
 
 
-def device(images: int, sample: int):
-    import multiprocessing as mp
+def quality_rounds(rounds):
+    """The ratios of ``quality`` for every round count: sympy minimises each function once."""
+    for tag, n, fns in quality_sets():
+        ours = {r: [] for r in rounds}
+        theirs = []
+        for on_b, dc_b in fns:
+            if not on_b.any() or (on_b | dc_b).all() or not (~on_b & ~dc_b).any():
+                continue
+            on, dc = M.pack_bits(on_b), M.pack_bits(dc_b)
+            dnf, cnf = E.minimal_forms(np.flatnonzero(on_b).tolist(), n, np.flatnonzero(dc_b).tolist())
+            theirs.append(E.literal_count(str(dnf)) + E.literal_count(str(cnf)))
+            for r in rounds:
+                ours[r].append(M.literal_total(M.minimise_cpu(on, dc, n, r))
+                               + M.literal_total(M.minimise_cpu(M.complement(on, dc, n), dc, n, r)))
+        for r in rounds:
+            q = np.array(ours[r]) / np.array(theirs)
+            print(f"{tag:<46} rounds {r}  functions {len(q):4d}  literals ours / sympy: mean {q.mean():.3f}  median {np.median(q):.3f}  "
+                  f"min {q.min():.3f}  max {q.max():.3f}  p90 {np.quantile(q, 0.9):.3f}  total {sum(ours[r])} / {sum(theirs)} = "
+                  f"{sum(ours[r]) / sum(theirs):.3f}", flush=True)
 
+
+def small_p64(images: int):
+    """TT-small p = 64 --layers 1 on device 0 with synthetic weights and the table usage of ``images`` synthetic images."""
     import torch
 
     from scale_imagenet_amd import synth, ttnet
@@ -89,6 +119,67 @@ def device(images: int, sample: int):
     usage = m.table_usage()
     m.count_table_usage(False)
     print(f"TT-small p = 64 --layers 1, synthetic weights; don't-cares: entries not read by {images} synthetic images")
+    return dev, spec, m, usage
+
+
+def device_rounds(rounds, images: int, repeats: int):
+    """Per round count: the time of the whole job (every binarised block, DNF + CNF of every filter, host time around
+    ``minimise_device``, which ends in the copy back), on the whole tables and with don't-cares, and its gate totals.  One warm
+    pass over every round count, then ``repeats`` passes that alternate the round counts."""
+    import torch
+    dev, spec, m, usage = small_p64(images)
+    jobs = []
+    for b in spec.block_tts():
+        if b.last:
+            continue
+        table = m.get_table(b.name)
+        for with_dc in (False, True):
+            on, dc = M.pack_functions(table, usage[b.name] if with_dc else None)
+            both_on, both_dc = np.concatenate([on, M.complement(on, dc, b.fan_in_bits)]), np.concatenate([dc, dc])
+            jobs.append((with_dc, b.fan_in_bits, len(on), torch.from_numpy(both_on.view(np.int32)).to(dev),
+                         torch.from_numpy(both_dc.view(np.int32)).to(dev)))
+    times = {(r, d): [] for r in rounds for d in (False, True)}
+    totals = {}
+    for rep in range(repeats + 1):
+        for r in rounds:
+            spent = {False: 0.0, True: 0.0}
+            row = {d: dict(functions=0, constant=0, cubes=0, literals=0) for d in (False, True)}
+            for with_dc, n, f, on_t, dc_t in jobs:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                covers = M.minimise_device(on_t, dc_t, n, dev, rounds=r)
+                spent[with_dc] += (time.perf_counter() - t0) * 1e3
+                if rep:
+                    continue                                                    # the totals are the same in every pass
+                for d, c in zip(covers[:f], covers[f:]):
+                    row[with_dc]["functions"] += 2
+                    if M.literal_total(d) == 0 or M.literal_total(c) == 0:
+                        row[with_dc]["constant"] += 1
+                        continue
+                    row[with_dc]["cubes"] += len(d) + len(c)
+                    row[with_dc]["literals"] += M.literal_total(d) + M.literal_total(c)
+            print(f"pass {rep} rounds {r}: {spent[False]:.0f} ms whole tables, {spent[True]:.0f} ms with don't-cares", file=sys.stderr,
+                  flush=True)
+            if rep:
+                for d in (False, True):
+                    times[r, d].append(spent[d])
+            else:
+                totals[r] = row
+    print(f"{'rounds':<8}{'dc':>4}{'functions':>10}{'constant':>9}{'cubes':>10}{'literals':>11}{'lits / rounds 0':>17}"
+          f"{'best ms':>10}{'worst ms':>10}{'best / rounds 0':>17}   ({repeats} passes after a warm one, DNF + CNF, all blocks)")
+    for d in (False, True):
+        for r in rounds:
+            t, base = totals[r][d], totals[rounds[0]][d]
+            print(f"{r:<8}{'yes' if d else 'no':>4}{t['functions']:>10}{t['constant']:>9}{t['cubes']:>10}{t['literals']:>11}"
+                  f"{t['literals'] / base['literals']:>17.4f}{min(times[r, d]):>10.0f}{max(times[r, d]):>10.0f}"
+                  f"{min(times[r, d]) / min(times[rounds[0], d]):>17.2f}", flush=True)
+
+
+def device(images: int, sample: int):
+    import multiprocessing as mp
+
+    import torch
+    dev, spec, m, usage = small_p64(images)
     print(f"{'block':<24}{'dc':>3}{'functions':>10}{'device ms':>11}{'dnf cubes':>11}{'dnf lits':>11}{'cnf cubes':>11}{'cnf lits':>11}"
           f"{'constant':>9}{'twin s/function':>17}{'twin functions':>15}")
     pool = mp.get_context("spawn").Pool(16)
@@ -137,8 +228,11 @@ if __name__ == "__main__":
     ap.add_argument("--device", action="store_true")
     ap.add_argument("--images", type=int, default=300)
     ap.add_argument("--sample", type=int, default=32)
+    ap.add_argument("--rounds", type=str, default=None, metavar="R,R,..", help="report per number of reduce / expand rounds")
+    ap.add_argument("--repeats", type=int, default=3)
     a = ap.parse_args()
+    rounds = None if a.rounds is None else [int(r) for r in a.rounds.split(",")]
     if a.quality:
-        quality()
+        quality() if rounds is None else quality_rounds(rounds)
     if a.device:
-        device(a.images, a.sample)
+        device(a.images, a.sample) if rounds is None else device_rounds(rounds, a.images, a.repeats)
