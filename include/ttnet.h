@@ -407,6 +407,34 @@ int ttnet_plan_table_usage_reset(ttnet_plan *plan, void *stream);
 int ttnet_table_usage_add(ttnet_plan *plan, int lane, void *stream);
 int ttnet_plan_get_table_usage(ttnet_plan *plan, const char *name, int64_t *dst_host, size_t dst_bytes);
 
+/* Care-set misses: per image, how many lookups of a forward fell outside a chosen set of table entries.  A care set for
+ * Block_TT `name` (G groups, n input bits) is a bitmap uint32 [G][max(1, 2^n / 32)]: entries in the canonical order of
+ * ttnet_plan_get_table, bit i % 32 of word i / 32 = entry i of the group, unused high bits zero (the bitmap format of
+ * ttnet_minimise_covers).  A miss is a lookup whose entry has bit 0.  The lookups are those ttnet_table_usage_add counts:
+ * every Ho x Wo output position of the block's own convolution, positions a later floor-cropped pool discards included.
+ * An image without a miss in any block gets the same stage bits, hence bit-identical logits, from ANY tables that agree
+ * with the plan's on the care sets -- e.g. a circuit minimised with the other entries as don't-cares.
+ *   set_care     installs or replaces the bitmap of one block (bytes = G * max(1, 2^n / 32) * 4); bits_host == NULL removes
+ *                it.  The first install also allocates the per-lane scratch of ttnet_table_usage_add (ttnet_plan_set_lanes
+ *                grows it with the lanes), never the usage counters: care sets and usage counts are independent, on together
+ *                or separately, and share that scratch.  Synchronises the device: call it outside graph capture.
+ *   clear_care   removes every bitmap, and frees the scratch unless the usage counters are on.
+ *   care_misses  rows_dev = int32 [n][B] for the n images of the forward last issued on `lane` (whichever entry point issued
+ *                it, plain launches or a replayed graph), B = ttnet_plan_query("care_blocks") = the Block_TTs of the plan in
+ *                the order conv1, conv2, conv3, convf per block: rows_dev[i][b] = misses of image i in Block_TT b, 0 for a
+ *                block without a bitmap.  It zeroes the rows itself.  Asynchronous on `stream`, ordered by the caller after
+ *                that lane's forward and before the lane is reused; its own launches only, no allocation, no host
+ *                synchronisation, capturable.  On the block-fused path every non-last block whose convf has a bitmap is run
+ *                once more with a tap buffer, as the usage add does.  int32 adds only: the rows do not depend on launch
+ *                geometry, lane or stream.
+ * "care_bytes" (ttnet_plan_query) is what the bitmaps hold; the shared scratch is part of "usage_bytes" while either
+ * feature is on.  Errors: care_misses before any set_care (or after clear_care) and a lane without a forward TTNET_E_STATE;
+ * a bad lane, a NULL or misaligned rows_dev, an unknown block name, a wrong `bytes` TTNET_E_INVALID.  Served and refused
+ * variants (TTNET_E_UNSUPPORTED from set_care) as for ttnet_plan_table_usage_enable. */
+int ttnet_plan_set_care(ttnet_plan *plan, const char *name, const uint32_t *bits_host, size_t bytes);
+int ttnet_plan_clear_care(ttnet_plan *plan);
+int ttnet_care_misses(ttnet_plan *plan, int lane, int32_t *rows_dev, void *stream);
+
 /* Two-level minimisation of truth tables with don't-cares, on the device: a PRIME and IRREDUNDANT cover of every
  * function of a batch (every cube is a prime implicant of ON u DC, no cube can be removed).  It is not a minimum cover.
  *
@@ -470,7 +498,8 @@ int ttnet_minimise_covers_rounds(const uint32_t *on_dev, const uint32_t *dc_dev,
 
 /* Integer facts about the plan: "fcsize", "n_classes", "n_state_tensors", "max_batch",
  * "near_ties:<block_tt name>" (entries with |pre-activation| < 1e-5 found while building
- * that table), "table_bytes", "usage_bytes", "workspace_bytes", "graph_replays" (forwards replayed from a
+ * that table), "table_bytes", "usage_bytes", "care_bytes", "care_blocks", "last_n:<lane>" (images of the
+ * forward last issued on that lane), "workspace_bytes", "graph_replays" (forwards replayed from a
  * captured hipGraph so far), "graphs_enabled" (0: ttnet_last_error() then says why), "graph_captures",
  * "graph_drops", "graphs_cached", "lanes", "range_overflow" (synchronises; 1 if a forward since the last
  * query left the fp16 x 2 range, and clears the flag), "gate_path" (which kernels evaluate the blocks, fixed at

@@ -85,6 +85,9 @@ SYMBOLS: List[Tuple[str, object, list]] = [
     ("ttnet_plan_table_usage_reset", C.c_int, [_P, _P]),
     ("ttnet_table_usage_add", C.c_int, [_P, C.c_int, _P]),
     ("ttnet_plan_get_table_usage", C.c_int, [_P, C.c_char_p, _P, C.c_size_t]),
+    ("ttnet_plan_set_care", C.c_int, [_P, C.c_char_p, _P, C.c_size_t]),
+    ("ttnet_plan_clear_care", C.c_int, [_P]),
+    ("ttnet_care_misses", C.c_int, [_P, C.c_int, _P, _P]),
     ("ttnet_minimise_workspace", C.c_int64, [C.c_int, C.c_int64]),
     ("ttnet_minimise_covers", C.c_int, [_P, _P, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P]),
     ("ttnet_minimise_rounds_workspace", C.c_int64, [C.c_int, C.c_int64]),

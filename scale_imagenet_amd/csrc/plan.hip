@@ -56,6 +56,7 @@ struct BlockTT {
   int64_t near_ties = -1;
   bool user_table = false;
   int64_t *usage = nullptr;      // [groups][2^n] lookups per entry, canonical order (ttnet_plan_table_usage_enable)
+  uint32_t *care = nullptr;      // [groups][max(1, 2^n / 32)] care bitmap, canonical order (ttnet_plan_set_care); null: none
 };
 
 struct MultiHead {
@@ -134,6 +135,10 @@ struct ttnet_plan {
   bool usage_on = false;
   size_t usage_bytes = 0;
   int usage_scheme_dw = kUsageMerged, usage_scheme_pw = kUsageMerged;   // per table shape: depthwise / grouped 1x1 (DESIGN: table usage)
+  // care sets (ttnet_plan_set_care): the bitmaps live in the BlockTTs; the lanes' scratch is the usage add's, kept while
+  // either of the two is on and accounted in scratch_bytes
+  bool care_on = false;
+  size_t care_bytes = 0, scratch_bytes = 0;
 
   bool profiling = false;
   // captured forward per batch size (hipGraph): one launch instead of ~11 on the host side
@@ -1027,7 +1032,7 @@ void walk_table(const BlockTT &b, void *raw, void *canon, bool store) {
       table_entry(g, raw, grp, idx, (uint8_t *)canon + ((size_t)grp * per + canonical_index(b, idx)) * entry_bytes, store);
 }
 
-// Per-lane scratch of ttnet_table_usage_add, sized for max_batch (a lane that has its scratch keeps it)
+// Per-lane scratch of ttnet_table_usage_add and ttnet_care_misses, sized for max_batch (a lane that has its scratch keeps it)
 int alloc_usage_scratch(ttnet_plan *pl, ttnet_plan::Lane &L) {
   if (L.u_br[0] || pl->path == GatePath::XSmall) return TTNET_OK;      // (x-small keeps everything as uint64 rows already)
   const size_t nb = (size_t)pl->desc.max_batch;
@@ -1038,7 +1043,7 @@ int alloc_usage_scratch(ttnet_plan *pl, ttnet_plan::Lane &L) {
     br = std::max(br, nb * mh.C * mh.Ho);
     if (!mh.last) tap = std::max(tap, nb * (mh.C / 8) * mh.Ho * mh.Wo);
   }
-  size_t *acc = &pl->usage_bytes;
+  size_t *acc = &pl->scratch_bytes;
   for (int k = 0; k < 4; ++k) TT_TRY(dev_alloc(pl, &L.u_br[k], br, true, acc));
   if (pl->path == GatePath::Fused) {
     TT_TRY(dev_alloc(pl, &L.u_rows, rows, true, acc));
@@ -1047,18 +1052,67 @@ int alloc_usage_scratch(ttnet_plan *pl, ttnet_plan::Lane &L) {
   return TTNET_OK;
 }
 
-void free_usage(ttnet_plan *pl) {
-  for (BlockTT *b : all_block_tts(pl)) {
-    dev_free(pl, b->usage);
-    b->usage = nullptr;
-  }
+// the lanes' scratch goes once neither the usage counters nor a care set need it
+void free_usage_scratch(ttnet_plan *pl) {
+  if (pl->usage_on || pl->care_on) return;
   for (auto &l : pl->lanes) {
     for (auto &p : l.u_br) { dev_free(pl, p); p = nullptr; }
     dev_free(pl, l.u_rows); l.u_rows = nullptr;
     dev_free(pl, l.u_tap); l.u_tap = nullptr;
   }
+  pl->scratch_bytes = 0;
+}
+
+void free_usage(ttnet_plan *pl) {
+  for (BlockTT *b : all_block_tts(pl)) {
+    dev_free(pl, b->usage);
+    b->usage = nullptr;
+  }
   pl->usage_bytes = 0;
   pl->usage_on = false;
+  free_usage_scratch(pl);
+}
+
+void free_care(ttnet_plan *pl) {
+  for (BlockTT *b : all_block_tts(pl)) {
+    dev_free(pl, b->care);
+    b->care = nullptr;
+  }
+  pl->care_bytes = 0;
+  pl->care_on = false;
+  free_usage_scratch(pl);
+}
+
+// words of b's care bitmap
+size_t care_words(const BlockTT &b) {
+  return (size_t)b.g.groups * std::max<size_t>(1, ((size_t)1 << b.g.nbits()) / 32);
+}
+
+// TTNET_E_UNSUPPORTED for the variants that table usage and care sets do not serve
+int check_usage_served(ttnet_plan *pl, const char *what) {
+  if (pl->path == GatePath::Full) {
+    set_error("the full variant (fan-in 30) has no truth tables: 2^30 entries per output bit");
+    return TTNET_E_UNSUPPORTED;
+  }
+  if (pl->path == GatePath::VAlexnet) {
+    set_error("%s is not built for the vAlexnet variant", what);
+    return TTNET_E_UNSUPPORTED;
+  }
+  return TTNET_OK;
+}
+
+// The lane whose last forward ttnet_table_usage_add / ttnet_care_misses read
+int usage_lane(ttnet_plan *pl, const char *who, int lane, const ttnet_plan::Lane **out) {
+  if (lane < 0 || lane >= (int)pl->lanes.size()) {
+    set_error("%s: lane %d but the plan has %d (ttnet_plan_set_lanes)", who, lane, (int)pl->lanes.size());
+    return TTNET_E_INVALID;
+  }
+  if (pl->lanes[lane].last_n < 1) {
+    set_error("%s: no forward has run on lane %d", who, lane);
+    return TTNET_E_STATE;
+  }
+  *out = &pl->lanes[lane];
+  return TTNET_OK;
 }
 
 int forward_eager(ttnet_plan *pl, ttnet_plan::Lane &L, const void *x_dev, bool u8, int64_t n, float *logits_dev, hipStream_t s) {
@@ -1382,7 +1436,7 @@ int ttnet_plan_set_lanes(ttnet_plan *pl, int lanes) {
       return r;
     }
   }
-  if (pl->usage_on)
+  if (pl->usage_on || pl->care_on)
     for (auto &l : pl->lanes) TT_TRY(alloc_usage_scratch(pl, l));     // (lanes that have theirs keep it)
   return TTNET_OK;
 }
@@ -1392,14 +1446,7 @@ int ttnet_plan_table_usage_enable(ttnet_plan *pl, int enabled) {
     set_error("null plan");
     return TTNET_E_INVALID;
   }
-  if (pl->path == GatePath::Full) {
-    set_error("the full variant (fan-in 30) has no truth tables: 2^30 entries per output bit");
-    return TTNET_E_UNSUPPORTED;
-  }
-  if (pl->path == GatePath::VAlexnet) {
-    set_error("table usage is not built for the vAlexnet variant");
-    return TTNET_E_UNSUPPORTED;
-  }
+  TT_TRY(check_usage_served(pl, "table usage"));
   TT_HIP(hipSetDevice(pl->device));
   if ((enabled != 0) == pl->usage_on) return TTNET_OK;
   TT_HIP(hipDeviceSynchronize());
@@ -1446,15 +1493,9 @@ int ttnet_table_usage_add(ttnet_plan *pl, int lane, void *stream) {
     set_error("table_usage_add before ttnet_plan_table_usage_enable");
     return TTNET_E_STATE;
   }
-  if (lane < 0 || lane >= (int)pl->lanes.size()) {
-    set_error("table_usage_add: lane %d but the plan has %d (ttnet_plan_set_lanes)", lane, (int)pl->lanes.size());
-    return TTNET_E_INVALID;
-  }
-  const ttnet_plan::Lane &L = pl->lanes[lane];
-  if (L.last_n < 1) {
-    set_error("table_usage_add: no forward has run on lane %d", lane);
-    return TTNET_E_STATE;
-  }
+  const ttnet_plan::Lane *lp = nullptr;
+  TT_TRY(usage_lane(pl, "table_usage_add", lane, &lp));
+  const ttnet_plan::Lane &L = *lp;
   const int n = (int)L.last_n;
   hipStream_t s = (hipStream_t)stream;
   for (size_t i = 0; i < pl->blocks.size(); ++i) {
@@ -1502,6 +1543,106 @@ int ttnet_plan_get_table_usage(ttnet_plan *pl, const char *name, int64_t *dst_ho
   TT_HIP(hipSetDevice(pl->device));
   TT_HIP(hipDeviceSynchronize());
   TT_HIP(hipMemcpy(dst_host, b->usage, need, hipMemcpyDeviceToHost));
+  return TTNET_OK;
+}
+
+int ttnet_plan_set_care(ttnet_plan *pl, const char *name, const uint32_t *bits_host, size_t bytes) {
+  if (!pl || !name) {
+    set_error("null argument");
+    return TTNET_E_INVALID;
+  }
+  TT_TRY(check_usage_served(pl, "the care set"));
+  BlockTT *b = find_block(pl, name);
+  if (!b) {
+    set_error("no Block_TT named %s", name);
+    return TTNET_E_INVALID;
+  }
+  const size_t words = care_words(*b);
+  if (bits_host && bytes != words * sizeof(uint32_t)) {
+    set_error("set_care(%s): source is %zu bytes, the bitmap is %zu", name, bytes, words * sizeof(uint32_t));
+    return TTNET_E_INVALID;
+  }
+  TT_HIP(hipSetDevice(pl->device));
+  TT_HIP(hipDeviceSynchronize());                      // no care_misses may be reading the bitmap that is replaced
+  if (!bits_host) {
+    if (b->care) pl->care_bytes -= std::max<size_t>(words * sizeof(uint32_t), 16);
+    dev_free(pl, b->care);
+    b->care = nullptr;
+    return TTNET_OK;
+  }
+  const bool was_on = pl->care_on;
+  pl->care_on = true;
+  int r = TTNET_OK;
+  for (auto &l : pl->lanes)
+    if (r == TTNET_OK) r = alloc_usage_scratch(pl, l);
+  if (r == TTNET_OK && !b->care) r = dev_alloc(pl, &b->care, words, false, &pl->care_bytes);
+  if (r != TTNET_OK) {
+    if (!was_on) free_care(pl);
+    return r;
+  }
+  TT_HIP(hipMemcpy(b->care, bits_host, bytes, hipMemcpyHostToDevice));
+  return TTNET_OK;
+}
+
+int ttnet_plan_clear_care(ttnet_plan *pl) {
+  if (!pl) {
+    set_error("null plan");
+    return TTNET_E_INVALID;
+  }
+  if (!pl->care_on) return TTNET_OK;
+  TT_HIP(hipSetDevice(pl->device));
+  TT_HIP(hipDeviceSynchronize());
+  free_care(pl);
+  return TTNET_OK;
+}
+
+int ttnet_care_misses(ttnet_plan *pl, int lane, int32_t *rows_dev, void *stream) {
+  if (!pl) {
+    set_error("null plan");
+    return TTNET_E_INVALID;
+  }
+  if (!pl->care_on) {
+    set_error("care_misses before ttnet_plan_set_care");
+    return TTNET_E_STATE;
+  }
+  if (!rows_dev || ((uintptr_t)rows_dev & 3)) {
+    set_error("care_misses: rows_dev is null or not 4-byte aligned");
+    return TTNET_E_INVALID;
+  }
+  const ttnet_plan::Lane *lp = nullptr;
+  TT_TRY(usage_lane(pl, "care_misses", lane, &lp));
+  const ttnet_plan::Lane &L = *lp;
+  const int n = (int)L.last_n;
+  const int nb = (int)pl->blocks.size() * 4;           // row length: the Block_TTs in the order of all_block_tts
+  hipStream_t s = (hipStream_t)stream;
+  TT_HIP(hipMemsetAsync(rows_dev, 0, (size_t)n * nb * sizeof(int32_t), s));
+  for (size_t i = 0; i < pl->blocks.size(); ++i) {
+    const MultiHead &mh = pl->blocks[i];
+    int32_t *rows = rows_dev + 4 * i;                  // this block's four columns
+    if (mh.c1.care || mh.c2.care || mh.c3.care) {
+      const uint64_t *xin = nullptr;
+      TT_TRY(block_input_rows(pl, L, i, n, L.u_rows, "care.prep", s, &xin));
+      int col = 0;
+      for (const BlockTT *b : {&mh.c1, &mh.c2}) {
+        const BlockGeom &g = b->g;
+        const int ho = (mh.H + 2 * g.pad - g.kh) / g.stride + 1, wo = (mh.W + 2 * g.pad - g.kw) / g.stride + 1;
+        if (b->care)
+          TT_TIMED(pl, "care.dw", s,
+                   launch_care_dw(xin, n, mh.C, mh.H, mh.W, ho, wo, g.kh, g.kw, g.stride, g.pad, b->care, rows + col, nb, s));
+        ++col;
+      }
+      if (mh.c3.care)
+        TT_TIMED(pl, "care.conv3", s,
+                 launch_care_pw(&xin, 1, n, mh.C, mh.c3.g.groups, mh.c3.g.cin_g(), mh.H, mh.W, mh.c3.care, rows + 2, nb, s));
+    }
+    if (!mh.cf.care) continue;
+    const uint32_t *dwords = nullptr;
+    if (pl->path == GatePath::Fused) TT_TRY(fused_branch_dwords(pl, L, i, n, L.u_tap, "care.tap", s, &dwords));
+    const uint64_t *br[4];
+    for (int k = 0; k < 4; ++k) TT_TRY(branch_as_rows(pl, L, i, k, n, dwords, L.u_br[k], "care.prep", s, &br[k]));
+    TT_TIMED(pl, "care.convf", s,
+             launch_care_pw(br, 4, n, mh.C, mh.cf.g.groups, mh.cf.g.cin_g(), mh.Ho, mh.Wo, mh.cf.care, rows + 3, nb, s));
+  }
   return TTNET_OK;
 }
 
@@ -1663,7 +1804,17 @@ int ttnet_plan_query(ttnet_plan *pl, const char *what, int64_t *out) {
   else if (w == "max_batch") *out = pl->desc.max_batch;
   else if (w == "table_bytes") *out = (int64_t)pl->table_bytes;
   else if (w == "workspace_bytes") *out = (int64_t)pl->workspace_bytes;
-  else if (w == "usage_bytes") *out = (int64_t)pl->usage_bytes;
+  else if (w == "usage_bytes") *out = (int64_t)(pl->usage_bytes + pl->scratch_bytes);
+  else if (w == "care_bytes") *out = (int64_t)pl->care_bytes;
+  else if (w == "care_blocks") *out = (int64_t)all_block_tts(pl).size();
+  else if (w.rfind("last_n:", 0) == 0) {                      // images of the forward last issued on that lane (0: none yet)
+    const int lane = atoi(w.c_str() + 7);
+    if (lane < 0 || lane >= (int)pl->lanes.size()) {
+      set_error("last_n: lane %d but the plan has %d (ttnet_plan_set_lanes)", lane, (int)pl->lanes.size());
+      return TTNET_E_INVALID;
+    }
+    *out = pl->lanes[lane].last_n;
+  }
   else if (w == "p") *out = pl->p;
   else if (w == "graph_replays") *out = pl->graph_replays;
   else if (w == "graphs_enabled") {

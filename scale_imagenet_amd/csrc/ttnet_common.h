@@ -401,5 +401,11 @@ int launch_usage_dw(const uint64_t *x_rp, int n, int C, int H, int W, int Ho, in
 // grouped 1x1 block on the H x W positions of nsrc (1, or 4 = the interleaved branch concat) tensors [n][Csrc][H]
 int launch_usage_pw(const uint64_t *const *src, int nsrc, int n, int Csrc, int groups, int cin_g, int H, int W, int64_t *counters,
                     int scheme, hipStream_t s);
+// care-set misses of the same lookups: care = uint32 bitmap [groups][max(1, 2^n / 32)] (bit i % 32 of word i / 32 = entry i),
+// rows[img * row_stride] += the lookups of image img whose bit is 0 (int32; the caller zeroes the rows)
+int launch_care_dw(const uint64_t *x_rp, int n, int C, int H, int W, int Ho, int Wo, int kh, int kw, int stride, int pad,
+                   const uint32_t *care, int32_t *rows, int row_stride, hipStream_t s);
+int launch_care_pw(const uint64_t *const *src, int nsrc, int n, int Csrc, int groups, int cin_g, int H, int W, const uint32_t *care,
+                   int32_t *rows, int row_stride, hipStream_t s);
 
 }  // namespace ttnet

@@ -10,7 +10,7 @@ all-gather of ``[B/world, 1000]`` fp32.
 Evaluating a dataset needs less still: every rank evaluates its ``ShardedSampler`` slice and one
 ``all_reduce_metrics`` sums four numbers (loss sum, images, top-1 hits, top-5 hits).  Per-image predictions are
 joined in rank order (``all_gather_predictions``), per-class counters summed (``all_reduce_counts``), truth-table
-usage counters summed (``all_reduce_table_usage``).
+usage counters summed (``all_reduce_table_usage``), the care-set rows joined (``all_gather_care``).
 """
 from __future__ import annotations
 
@@ -136,6 +136,29 @@ def all_gather_predictions(pred, group=None):
     dist.all_gather_into_tensor(out, _wire(local, group), group=group)
     out = out.cpu().numpy()
     return Predictions.join([Predictions.from_records(out[r * width: r * width + counts[r]]) for r in range(world)])
+
+
+def all_gather_care(care, group=None):
+    """Every rank's ``evaluate.CareResult`` joined in rank order (dataset order for ``ShardedSampler`` shards), as
+    ``all_gather_predictions`` joins the predictions: the int32 rows, with the two hit flags of a labelled run as two more
+    columns, padded to the longest shard.  Every rank returns the whole; a single process returns its input."""
+    from .evaluate import CareResult
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return care
+    import numpy as np
+    world = dist.get_world_size(group)
+    n, b = care.rows.shape
+    counts = _wire(torch.zeros(world, dtype=torch.int64), group)
+    dist.all_gather_into_tensor(counts, _wire(torch.tensor([n], dtype=torch.int64), group), group=group)
+    counts = counts.cpu().tolist()
+    width = max(max(counts), 1)
+    local = torch.zeros((width, b + 2), dtype=torch.int32)
+    local[:n, :b] = torch.from_numpy(np.ascontiguousarray(care.rows, dtype=np.int32))
+    local[:n, b:] = -1 if care.hits is None else torch.from_numpy(np.ascontiguousarray(care.hits, dtype=np.int32))
+    out = _wire(torch.empty((world * width, b + 2), dtype=torch.int32), group)
+    dist.all_gather_into_tensor(out, _wire(local, group), group=group)
+    out = np.concatenate([out.cpu().numpy()[r * width: r * width + counts[r]] for r in range(world)])
+    return CareResult(list(care.blocks), out[:, :b].copy(), None if care.hits is None else out[:, b:] == 1)
 
 
 def all_reduce_counts(counts, confusion=None, group=None):

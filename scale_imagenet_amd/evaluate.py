@@ -30,6 +30,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Callable, Iterable, List, Optional, Tuple
 
@@ -93,6 +94,7 @@ class EvalResult:
     per_class = None    # (not a field) int64 [n_classes, 4] {images, hits1, hits5, predicted}, with ``per_class=True``
     confusion = None    # (not a field) int64 [n_classes, n_classes] indexed [target][top-1 class], with ``confusion=True``
     table_usage = None  # (not a field) {Block_TT name: int64 [groups, 2^n]} lookups per table entry, with ``table_usage=True``
+    care = None         # (not a field) ``CareResult``: per-image care-set misses in dataset order, with ``care=``
 
     def to_parts(self) -> EvalParts:
         """The sums behind this result: exact when ``parts`` is set, otherwise recovered from the means (the hit
@@ -140,6 +142,62 @@ class Predictions:
         """Shards in dataset order -> one ``Predictions`` (``ShardedSampler`` shards are contiguous: rank order)."""
         return Predictions(np.concatenate([p.classes for p in parts]), np.concatenate([p.logit for p in parts]),
                            np.concatenate([p.logprob for p in parts]))
+
+
+def care_bounds(covered: np.ndarray, hits: np.ndarray) -> Tuple[float, float]:
+    """The bracket, in percent, on the accuracy of ANY circuit that agrees with the network's tables on the care sets:
+    ``covered`` bool [N] (no miss in any block: that image's logits are the network's, bit for bit), ``hits`` bool [N]
+    (the network is right on that image).  With C covered images of which h are hits, ``h / N <= accuracy <=
+    (h + N - C) / N``: a covered image counts as it does for the network, an uncovered one may go either way."""
+    covered, hits = np.asarray(covered, dtype=bool), np.asarray(hits, dtype=bool)
+    n = covered.size
+    if hits.shape != covered.shape:
+        raise ValueError(f"care_bounds: {covered.size} covered flags but hits of shape {tuple(hits.shape)}")
+    if n == 0:
+        return 0.0, 0.0
+    h, c = int((covered & hits).sum()), int(covered.sum())
+    return 100.0 * h / n, 100.0 * (h + n - c) / n
+
+
+@dataclass
+class CareResult:
+    """Care-set misses of an evaluation (``evaluate(care=)``): ``rows[i][b]`` = lookups of image i (dataset order) in
+    ``Block_TT`` ``blocks[b]`` that fell outside its care set."""
+    blocks: List[str]
+    rows: np.ndarray                    # int32 [N, B]
+    hits: Optional[np.ndarray] = None   # bool [N, 2]: the target is the network's best class / among its 5 best (labelled runs)
+
+    @property
+    def covered(self) -> np.ndarray:
+        """bool [N]: no miss in any block."""
+        return ~(self.rows != 0).any(axis=1)
+
+    @property
+    def covered_images(self) -> int:
+        return int(self.covered.sum())
+
+    @property
+    def images_with_misses(self) -> "OrderedDict[str, int]":
+        return OrderedDict(zip(self.blocks, (self.rows != 0).sum(axis=0).tolist()))
+
+    @property
+    def misses(self) -> "OrderedDict[str, int]":
+        return OrderedDict(zip(self.blocks, self.rows.astype(np.int64).sum(axis=0).tolist()))
+
+    @property
+    def top1_bounds(self) -> Optional[Tuple[float, float]]:
+        return None if self.hits is None else care_bounds(self.covered, self.hits[:, 0])
+
+    @property
+    def top5_bounds(self) -> Optional[Tuple[float, float]]:
+        return None if self.hits is None else care_bounds(self.covered, self.hits[:, 1])
+
+    def line(self) -> str:
+        """``Care.. covered/N top1 [lo, hi] top5 [lo, hi]`` (the bounds only for a labelled run)."""
+        text = f"Care.. {self.covered_images}/{len(self.rows)}"
+        if self.hits is not None:
+            text += " top1 [%.3f, %.3f] top5 [%.3f, %.3f]" % (self.top1_bounds + self.top5_bounds)
+        return text
 
 
 def _check_k(k: int, n_classes: int):
@@ -336,6 +394,38 @@ class _OnDeviceMetrics:
         return res
 
 
+class _Care:
+    """``care=``: ``model.care_misses(lane)`` after every forward on the batch's stream, its ``n * B * 4`` bytes copied to
+    the lane's pinned buffer on that stream and collected when the batch retires, as ``_TopK`` does with its records."""
+
+    def __init__(self, lanes: int):
+        self.pinned = [None] * lanes
+        self.rows: List[np.ndarray] = []
+        self.hits: List[np.ndarray] = []
+
+    def add(self, model, lane: int, asynchronous: bool):
+        rows = model.care_misses(lane)
+        if not rows.is_cuda:                              # (a stub model in a test)
+            return rows
+        n = rows.shape[0]
+        if self.pinned[lane] is None or self.pinned[lane].shape[0] < n:
+            self.pinned[lane] = torch.empty((n, rows.shape[1]), dtype=torch.int32, pin_memory=True)
+        host = self.pinned[lane][:n]
+        host.copy_(rows, non_blocking=asynchronous)
+        return host
+
+    def retire(self, host, pred: "Predictions", targets):
+        self.rows.append(host.numpy().copy())
+        if targets is not None:
+            t = targets.cpu().numpy().reshape(-1, 1)
+            eq = pred.classes[:, :5] == t
+            self.hits.append(np.stack([eq[:, 0], eq.any(axis=1)], axis=1))
+
+    def result(self, blocks) -> CareResult:
+        rows = np.concatenate(self.rows) if self.rows else np.empty((0, len(blocks)), np.int32)
+        return CareResult(list(blocks), rows.astype(np.int32, copy=False), np.concatenate(self.hits) if self.hits else None)
+
+
 class _TopK:
     """``topk=k``: one ``ttnet_topk_rows`` call per batch on the batch's stream, its ``n * k * 16`` bytes copied to the
     lane's pinned buffer on that stream and collected when the batch retires (by then the lane's event has passed).
@@ -371,7 +461,7 @@ class _TopK:
 def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]],
              device: torch.device, log_every: int = 0, inflight: int = 1, *,
              forward: Optional[Callable] = None, metrics: str = "torch", topk: int = 0, per_class: bool = False,
-             confusion: bool = False, table_usage: bool = False) -> EvalResult:
+             confusion: bool = False, table_usage: bool = False, care=None, care_min_count: int = 1) -> EvalResult:
     """main.py:242-284: ``model.eval()``, no_grad, per batch loss / top-1 / top-5.
 
     ``inflight`` > 1 keeps that many batches in flight on separate HIP streams and model lanes
@@ -401,7 +491,15 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
     table (``{Block_TT name: int64 [groups, 2^n]}``, canonical order; include/ttnet.h).  The counters are enabled and
     zeroed first and ``model.add_table_usage(lane)`` follows every forward on the batch's stream, whatever the input
     type and ``inflight``; nothing is read back before the end.  Size the plan first (``model.reserve``): a plan that has
-    to grow for a larger batch would start its counters again, which raises here."""
+    to grow for a larger batch would start its counters again, which raises here.
+
+    ``care=``: care-set bitmaps or usage counts, as ``model.set_care(care, care_min_count)`` takes them.  The result's
+    ``care`` (``CareResult``) holds, for every image in dataset order whatever ``inflight`` is, the lookups of every
+    ``Block_TT`` that fell outside its care set, which images are covered (no miss anywhere: a circuit minimised with the
+    other entries as don't-cares classifies them exactly as the network does) and, for a labelled run, the bracket that
+    puts on the circuit's top-1 / top-5 accuracy (``care_bounds``).  The bounds come from per-image top-5 records, so the
+    evaluation keeps at least 5 predictions per image internally; ``predictions`` is returned only for ``topk > 0``, with
+    the k asked for.  The care set stays installed afterwards (``model.clear_care()``)."""
     if topk < 0 or topk > _lib.TOPK_MAX:
         raise ValueError(f"topk must be in [0, {_lib.TOPK_MAX}], got {topk}")
     per_class = per_class or confusion
@@ -418,12 +516,20 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
     if table_usage and not all(hasattr(inner, a) for a in ("count_table_usage", "add_table_usage", "table_usage")):
         raise RuntimeError(f"evaluate(table_usage=True): {type(inner).__name__} keeps no truth-table usage counters (it needs "
                            "count_table_usage / add_table_usage / table_usage, as the TTNet models have)")
+    if care is not None and not all(hasattr(inner, a) for a in ("set_care", "care_misses", "care_blocks")):
+        raise RuntimeError(f"evaluate(care=): {type(inner).__name__} keeps no care sets (it needs set_care / care_misses / "
+                           "care_blocks, as the TTNet models have)")
     use_lanes = inflight > 1 and device.type == "cuda" and hasattr(model, "set_lanes")
     lanes = inflight if use_lanes else 1
     if use_lanes:
         model.set_lanes(inflight)
     streams = [torch.cuda.Stream(device) for _ in range(lanes)] if use_lanes else []
     acc = _OnDeviceMetrics(device, lanes, streams, per_class, confusion) if metrics == "device" else _TorchMetrics()
+    asked_k = topk
+    if care is not None:
+        topk = max(topk, 5)                                # (the hits behind the bounds are read from the records)
+        inner.set_care(care, care_min_count)
+        cares = _Care(lanes)
     top = _TopK(topk, lanes) if topk else None
     usage_plan = None
     if table_usage:
@@ -460,13 +566,15 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
     pending = []                                           # batches in flight, oldest first: (index, event, metrics, images)
 
     def retire():
-        index, event, batch, n, kept = pending.pop(0)
+        index, event, batch, n, kept, care_kept = pending.pop(0)
         if event is not None:
             event.synchronize()
         if labelled:
             acc.retire(batch, n)
         if top is not None:
             top.retire(kept)
+        if care is not None:
+            cares.retire(care_kept[0], top.parts[-1], care_kept[1])
         if log_every and labelled:
             log(index, "retired")
 
@@ -494,7 +602,9 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
                 elif usage_plan is not inner._any_plan():
                     raise RuntimeError("evaluate(table_usage=True): the plan was rebuilt for a larger batch and its counters "
                                        "started again; call model.reserve(<largest batch>) first")
-            batch = kept = None
+            batch = kept = care_kept = None
+            if care is not None:
+                care_kept = (cares.add(inner, lane, use_lanes), targets if labelled else None)
             if top is None:
                 batch = acc.add(outputs, targets, lane)
             else:
@@ -504,7 +614,8 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
             event = torch.cuda.Event() if use_lanes else None
             if use_lanes:
                 event.record(streams[lane])
-        pending.append((i, event, batch, inputs.size(0) if isinstance(inputs, torch.Tensor) else len(inputs), kept))
+        pending.append((i, event, batch, inputs.size(0) if isinstance(inputs, torch.Tensor) else len(inputs), kept,
+                        care_kept))
         if not use_lanes:                                  # nothing in flight: read the batch now, as the reference does
             retire()
         if log_every and labelled:
@@ -525,10 +636,17 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
         res = EvalResult(None, None, None, sum(len(p) for p in top.parts))
     else:
         res = acc.result()
-    if top is not None:
+    if asked_k:
         res.predictions = top.result()
+        if asked_k < topk:
+            pr = res.predictions
+            res.predictions = Predictions(pr.classes[:, :asked_k], pr.logit[:, :asked_k], pr.logprob[:, :asked_k])
+    if care is not None:
+        res.care = cares.result(inner.care_blocks)
     if table_usage:
         res.table_usage = inner.table_usage()             # (synchronises the device)
     if labelled is not False:
         print("Acc..", res.top1, res.top5)
+    if care is not None:
+        print(res.care.line())
     return res

@@ -77,11 +77,11 @@ def cnf_with_output(dnf, cnf) -> str:
 
 def export_filter(column: np.ndarray, n: int, filter_index: int, out_dir: str, block: int, sub_block: int,
                   max_expr_bits: int = 9, usage: Optional[np.ndarray] = None, minimiser: str = "sympy", device=None,
-                  forms=None, rounds: int = 0) -> Dict[str, Optional[str]]:
+                  forms=None, rounds: int = 0, min_count: int = 1) -> Dict[str, Optional[str]]:
     """Files for one filter.  ``column``: its 2^n table entries (0/1), canonical order.  ``usage``: the lookup counts of
     the filter's group, int64 [2^n] (module docstring).  ``minimiser``: module docstring; ``forms``: this filter's
     ``(DNF text, CNF text)`` when ``export_block`` has minimised it already.  ``rounds``: module docstring (ignored by
-    "sympy")."""
+    "sympy").  ``min_count``: an entry looked up fewer times than this is a don't-care (default 1: the entries never read)."""
     import pandas as pd
     if minimiser not in ("sympy", "device", "cpu"):
         raise ValueError(f"minimiser {minimiser!r}: 'sympy', 'device' or 'cpu'")
@@ -96,7 +96,7 @@ def export_filter(column: np.ndarray, n: int, filter_index: int, out_dir: str, b
         counts = np.asarray(usage, dtype=np.int64).reshape(-1)
         if counts.shape != col.shape:
             raise ValueError(f"usage has {counts.size} counts, the filter has {col.size} entries")
-        seen = counts > 0
+        seen = counts >= max(1, int(min_count))
         dontcares = np.flatnonzero(~seen).tolist()
         on_seen = np.unique(col[seen]) if seen.any() else uniq[:1]       # (never looked up: any constant will do)
         if len(on_seen) == 1:
@@ -116,11 +116,11 @@ def export_filter(column: np.ndarray, n: int, filter_index: int, out_dir: str, b
         out["csv"] = csv
         if n <= (max_expr_bits if minimiser == "sympy" else 16):
             if minimiser == "sympy":
-                minterms = frame["index"].values[answer if counts is None else answer & (counts > 0)].tolist()
+                minterms = frame["index"].values[answer if counts is None else answer & seen].tolist()
                 dnf, cnf = minimal_forms(minterms, n, dontcares)
             else:
                 dnf, cnf = forms if forms is not None else _cover_forms(answer[None, :, None], n, None if counts is None else counts[None],
-                                                                        minimiser, device, rounds)[0]
+                                                                        minimiser, device, rounds, min_count)[0]
             y = cnf_with_output(dnf, cnf)
             out.update(dnf=str(dnf), cnf=str(cnf), cnf_with_y=y, dnf_literals=literal_count(str(dnf)),
                        cnf_literals=literal_count(str(cnf)))
@@ -135,12 +135,13 @@ def export_filter(column: np.ndarray, n: int, filter_index: int, out_dir: str, b
 
 def export_block(table: np.ndarray, out_dir: str, block: int, sub_block: int, filters: Optional[Iterable[int]] = None,
                  max_expr_bits: int = 9, usage: Optional[np.ndarray] = None, minimiser: str = "sympy",
-                 device=None, rounds: int = 0) -> Dict[int, Dict[str, Optional[str]]]:
+                 device=None, rounds: int = 0, min_count: int = 1) -> Dict[int, Dict[str, Optional[str]]]:
     """``table``: [groups][2^n][cout_g] bits as returned by ``model.get_table(name)`` (or by the
     oracle's ``build_lut``).  Filter f = output channel f of the block = (group f // cout_g,
     output f % cout_g).  ``usage``: int64 [groups][2^n] lookup counts of the block (module docstring).
     ``minimiser`` "device" / "cpu": all filters asked for are minimised at once (``device``: a torch device, default the
-    current one), with ``rounds`` reduce / expand rounds (module docstring; ignored by "sympy")."""
+    current one), with ``rounds`` reduce / expand rounds (module docstring; ignored by "sympy").  ``min_count``: the entries
+    looked up fewer times than this are the don't-cares (the complement of ``minimise.care_masks(usage, min_count)``)."""
     g, size, cout_g = table.shape
     n = int(size).bit_length() - 1
     assert 2 ** n == size
@@ -151,10 +152,10 @@ def export_block(table: np.ndarray, out_dir: str, block: int, sub_block: int, fi
     forms = {}
     if minimiser in ("device", "cpu") and n <= 16 and todo:
         from . import minimise
-        on, dc = minimise.pack_functions(np.asarray(table) == 1, usage)
+        on, dc = minimise.pack_functions(np.asarray(table) == 1, usage, min_count)
         forms = dict(zip(todo, _texts(minimise.minimal_covers(on[todo], dc[todo], n, minimiser, device, rounds), n)))
     return {f: export_filter(table[f // cout_g, :, f % cout_g], n, f, out_dir, block, sub_block, max_expr_bits,
-                             None if usage is None else usage[f // cout_g], minimiser, device, forms.get(f), rounds) for f in todo}
+                             None if usage is None else usage[f // cout_g], minimiser, device, forms.get(f), rounds, min_count) for f in todo}
 
 
 def _texts(covers, n: int):
@@ -162,10 +163,10 @@ def _texts(covers, n: int):
     return [(minimise.dnf_text(d, n), minimise.cnf_text(c, n)) for d, c in covers]
 
 
-def _cover_forms(table: np.ndarray, n: int, usage, minimiser: str, device, rounds: int = 0):
+def _cover_forms(table: np.ndarray, n: int, usage, minimiser: str, device, rounds: int = 0, min_count: int = 1):
     """``(DNF text, CNF text)`` of every filter of a ``[G, 2^n, cout_g]`` 0/1 table from ``minimise`` (one call)."""
     from . import minimise
-    on, dc = minimise.pack_functions(table, usage)
+    on, dc = minimise.pack_functions(table, usage, min_count)
     return _texts(minimise.minimal_covers(on, dc, n, minimiser, device, rounds), n)
 
 

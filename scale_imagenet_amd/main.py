@@ -66,6 +66,36 @@ def add_topk_flags(group, default: int):
                        help="class names, one per line in index order: written instead of the indices")
 
 
+def add_care_flags(group):
+    group.add_argument("--care_from", type=str, default=None, metavar="FILE",
+                       help=".npz written by --table_usage: the entries that run read are the care set; every image is then "
+                            "tested for lookups outside it, and `Care.. covered/N top1 [lo, hi] top5 [lo, hi]` brackets the "
+                            "accuracy of any circuit minimised with the other entries as don't-cares")
+    group.add_argument("--care_min_count", type=int, default=1, metavar="T",
+                       help="keep only the entries read at least T times (default 1)")
+
+
+def care_args(args) -> dict:
+    """The ``evaluate`` keywords of --care_from."""
+    if not args.care_from:
+        return {}
+    from . import report
+    return dict(care=report.load_table_usage(args.care_from), care_min_count=args.care_min_count)
+
+
+def check_care_flags(args):
+    if args.care_min_count < 1:
+        raise SystemExit("--care_min_count must be at least 1")
+    if not args.care_from:
+        for flag in ("care_rows", "care_summary"):
+            if getattr(args, flag, None):
+                raise SystemExit(f"--{flag} needs --care_from")
+        if args.care_min_count != 1:
+            raise SystemExit("--care_min_count needs --care_from")
+    elif not os.path.isfile(args.care_from):
+        raise SystemExit(f"--care_from: {args.care_from} does not exist (write it with --table_usage)")
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(
         prog="python -m scale_imagenet_amd.main",
@@ -96,6 +126,11 @@ def build_parser() -> argparse.ArgumentParser:
     out.add_argument("--table_gates_rounds", type=int, default=0, metavar="R", choices=range(9),
                      help="reduce / expand rounds (0 .. 8) of the minimiser behind both columns of --table_gates; more rounds, "
                           "smaller covers, longer minimisation; 0: the covers it always gave")
+    add_care_flags(out)
+    out.add_argument("--care_rows", type=str, default=None, metavar="FILE",
+                     help="CSV index,covered,<one column per Block_TT>: every image's care-set misses (with --care_from)")
+    out.add_argument("--care_summary", type=str, default=None, metavar="FILE",
+                     help="CSV block,lookups,misses,images_with_misses and a total row (with --care_from)")
     ign = p.add_argument_group("accepted and ignored (training, logging and launcher flags of the reference)")
     for name, typ, default in _IGNORED:
         ign.add_argument(name, type=typ, default=default, help=argparse.SUPPRESS)
@@ -225,7 +260,7 @@ def end_ranks(world: int):
 def run(args) -> int:
     """One rank (or the only process): evaluate this rank's shard, sum over the ranks, rank 0 prints the line."""
     from . import jpeg, report
-    from .dist import all_gather_predictions, all_reduce_counts, all_reduce_metrics, all_reduce_table_usage
+    from .dist import all_gather_care, all_gather_predictions, all_reduce_counts, all_reduce_metrics, all_reduce_table_usage
     from .evaluate import evaluate
 
     rank, world, device = start_rank(args)
@@ -238,6 +273,7 @@ def run(args) -> int:
         extra = dict(topk=args.topk, per_class=bool(args.per_class or args.confusion), confusion=bool(args.confusion))
     if args.table_usage or args.table_gates:
         extra["table_usage"] = True
+    extra.update(care_args(args))
     # a rank's own lines (running metrics, its shard's Acc..) go to stderr when there are several: stdout carries the result
     with contextlib.redirect_stdout(sys.stderr) if world > 1 else contextlib.nullcontext():
         part = evaluate(model, loader, device, log_every=args.log_interval, inflight=max(1, args.inflight), metrics="device",
@@ -245,6 +281,14 @@ def run(args) -> int:
     res = all_reduce_metrics(part)
     if world > 1 and rank == 0:
         print("Acc..", res.top1, res.top5, flush=True)                 # main.py:284
+    if args.care_from:
+        care = all_gather_care(part.care)
+        if world > 1 and rank == 0:
+            print(care.line(), flush=True)
+        if rank == 0 and args.care_rows:
+            report.write_care_rows_csv(args.care_rows, care)
+        if rank == 0 and args.care_summary:
+            report.write_care_summary_csv(args.care_summary, care, model.care_lookups())
     if args.table_usage or args.table_gates:
         usage = all_reduce_table_usage(part.table_usage)
         if rank == 0 and args.table_usage:
@@ -278,6 +322,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         raise SystemExit("--table_coverage needs --table_usage")
     if args.table_gates_rounds and not args.table_gates:
         raise SystemExit("--table_gates_rounds needs --table_gates")
+    check_care_flags(args)
     return launch(args, argv, "scale_imagenet_amd.main", _check_paths, run)
 
 

@@ -50,10 +50,32 @@ def unpack_bits(words: np.ndarray, n: int) -> np.ndarray:
     return bits[..., : 1 << n].astype(bool)
 
 
-def pack_functions(table_bits: np.ndarray, usage: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+def _kept(usage: np.ndarray, min_count: int) -> np.ndarray:
+    """bool, the shape of ``usage``: the entries looked up at least ``min_count`` times (the care set)."""
+    if int(min_count) != min_count or min_count < 1:
+        raise ValueError(f"min_count must be an integer >= 1, got {min_count!r}")
+    return np.asarray(usage) >= int(min_count)
+
+
+def care_masks(usage, min_count: int = 1) -> "dict":
+    """The care sets of a ``table_usage()`` dict: ``{Block_TT name: uint32 [G, words]}`` bitmaps (``pack_bits``; the format
+    of ``ttnet_plan_set_care``) in which an entry is kept iff its count is at least ``min_count``.  The complement is the
+    ``dc`` of ``pack_functions(table, usage, min_count)`` before its repeat over ``cout_g``."""
+    out = {}
+    for name, u in usage.items():
+        u = np.asarray(u)
+        size = u.shape[-1] if u.ndim == 2 else 0
+        if u.ndim != 2 or size < 2 or size & (size - 1) or size > 1 << 16:
+            raise ValueError(f"usage[{name!r}] has shape {tuple(u.shape)}, expected [groups, 2^n] with 1 <= n <= 16")
+        out[name] = pack_bits(_kept(u, min_count))
+    return out
+
+
+def pack_functions(table_bits: np.ndarray, usage: Optional[np.ndarray] = None, min_count: int = 1) -> Tuple[np.ndarray, np.ndarray]:
     """``(on, dc)`` bitmaps, uint32 ``[G * cout_g, words]``, of every filter of a ``get_table`` array ``[G, 2^n, cout_g]``
     (filter f = group ``f // cout_g``, output ``f % cout_g``, as in ``export.export_block``).  With ``usage``
-    (``[G, 2^n]`` lookup counts) a pattern with count 0 is a don't-care, the rule of ``export.export_filter``."""
+    (``[G, 2^n]`` lookup counts) a pattern with count 0 is a don't-care, the rule of ``export.export_filter``; ``min_count``
+    raises that to every pattern looked up fewer than ``min_count`` times (the complement of ``care_masks``)."""
     t = np.asarray(table_bits)
     g, size, cout_g = t.shape
     col = np.transpose(t != 0, (0, 2, 1)).reshape(g * cout_g, size)
@@ -62,7 +84,7 @@ def pack_functions(table_bits: np.ndarray, usage: Optional[np.ndarray] = None) -
     u = np.asarray(usage)
     if tuple(u.shape) != (g, size):
         raise ValueError(f"usage has shape {tuple(u.shape)}, the table has {g} groups of {size} entries")
-    unseen = np.repeat(u == 0, cout_g, axis=0)
+    unseen = np.repeat(~_kept(u, min_count), cout_g, axis=0)
     return pack_bits(col & ~unseen), pack_bits(unseen)
 
 

@@ -14,6 +14,10 @@ Formats (fixed: tests and users' scripts read them):
                dnf_literals_seen,cnf_cubes_seen,cnf_literals_seen`` per binarised ``Block_TT`` (``gate_rows``): the counts of
                ``model.gate_counts()`` on the full care set and, under ``*_seen``, with the entries the run never read as
                don't-cares.  Prime, irredundant covers, not minimum ones.
+  care rows    ``index,covered,<one column per Block_TT>``: per image in dataset order, whether it is covered (1: no miss
+               in any block) and its care-set misses per block (``evaluate.CareResult.rows``).
+  care summary ``block,lookups,misses,images_with_misses`` per ``Block_TT`` and a last row ``total`` whose
+               ``images_with_misses`` is the number of images that are not covered (``care_summary_rows``).
 Every file is written to a temporary name beside its own and then renamed, so a reader never sees half of one.
 """
 from __future__ import annotations
@@ -64,19 +68,64 @@ def _name(index: int, names: Optional[Sequence[str]]) -> str:
 
 
 def write_predictions_csv(path: Optional[str], paths: Sequence[str], targets: Optional[Sequence[int]], pred,
-                          names: Optional[Sequence[str]] = None):
-    """``pred``: ``evaluate.Predictions`` of ``len(paths)`` images in the order of ``paths``; ``targets`` None: unlabelled."""
+                          names: Optional[Sequence[str]] = None, covered=None):
+    """``pred``: ``evaluate.Predictions`` of ``len(paths)`` images in the order of ``paths``; ``targets`` None: unlabelled.
+    ``covered`` (bool per image, ``evaluate.CareResult.covered``) adds a last column ``covered`` of 0 / 1."""
     if len(pred) != len(paths) or (targets is not None and len(targets) != len(paths)):
         raise ValueError(f"{len(paths)} paths, {len(pred)} predictions, {None if targets is None else len(targets)} targets")
+    if covered is not None and len(covered) != len(paths):
+        raise ValueError(f"{len(paths)} paths, {len(covered)} covered flags")
     k = pred.k
     with _replacing(path) as f:
         w = csv.writer(f, lineterminator="\n")
-        w.writerow(["path", "target"] + [c for i in range(1, k + 1) for c in (f"class_{i}", f"logprob_{i}")])
+        w.writerow(["path", "target"] + [c for i in range(1, k + 1) for c in (f"class_{i}", f"logprob_{i}")] +
+                   (["covered"] if covered is not None else []))
         for n, p in enumerate(paths):
             row = [p, "" if targets is None else _name(int(targets[n]), names)]
             for i in range(k):
                 row += [_name(int(pred.classes[n, i]), names), repr(float(pred.logprob[n, i]))]
+            if covered is not None:
+                row.append(int(bool(covered[n])))
             w.writerow(row)
+
+
+def write_care_rows_csv(path: Optional[str], care):
+    """``care``: ``evaluate.CareResult``."""
+    rows, covered = np.asarray(care.rows), care.covered
+    with _replacing(path) as f:
+        w = csv.writer(f, lineterminator="\n")
+        w.writerow(["index", "covered"] + list(care.blocks))
+        for i in range(rows.shape[0]):
+            w.writerow([i, int(covered[i])] + rows[i].tolist())
+
+
+def read_care_rows_csv(path: str) -> Tuple[List[str], np.ndarray, np.ndarray]:
+    """``(blocks, covered bool [N], rows int32 [N, B])`` as written."""
+    with open(path, newline="", encoding="utf-8") as f:
+        lines = list(csv.reader(f))
+    head, lines = lines[0], lines[1:]
+    if head[:2] != ["index", "covered"] or [r[0] for r in lines] != [str(i) for i in range(len(lines))]:
+        raise ValueError(f"{path}: not a care rows file (header {head})")
+    blocks = head[2:]
+    rows = np.array([[int(v) for v in r[2:]] for r in lines], dtype=np.int32).reshape(len(lines), len(blocks))
+    return blocks, np.array([r[1] == "1" for r in lines], dtype=bool), rows
+
+
+def care_summary_rows(care, lookups_per_image) -> List[list]:
+    """The rows of the care summary, header first.  ``lookups_per_image``: ``{Block_TT name: groups * Ho * Wo}``
+    (``model.care_lookups()``), the lookups one image makes in that block."""
+    n = len(care.rows)
+    out = [["block", "lookups", "misses", "images_with_misses"]]
+    misses, images = care.misses, care.images_with_misses
+    for name in care.blocks:
+        out.append([name, n * int(lookups_per_image[name]), misses[name], images[name]])
+    out.append(["total", sum(r[1] for r in out[1:]), sum(r[2] for r in out[1:]), n - care.covered_images])
+    return out
+
+
+def write_care_summary_csv(path: Optional[str], care, lookups_per_image):
+    with _replacing(path) as f:
+        csv.writer(f, lineterminator="\n").writerows(care_summary_rows(care, lookups_per_image))
 
 
 def read_predictions_csv(path: str) -> Tuple[List[str], List[str], List[List[str]], np.ndarray]:
@@ -85,6 +134,8 @@ def read_predictions_csv(path: str) -> Tuple[List[str], List[str], List[List[str
     with open(path, newline="", encoding="utf-8") as f:
         rows = list(csv.reader(f))
     head, rows = rows[0], rows[1:]
+    if head[-1:] == ["covered"]:                          # (the optional last column of a run with a care set)
+        head, rows = head[:-1], [r[:-1] for r in rows]
     k = (len(head) - 2) // 2
     if head != ["path", "target"] + [c for i in range(1, k + 1) for c in (f"class_{i}", f"logprob_{i}")]:
         raise ValueError(f"{path}: not a predictions file (header {head})")

@@ -19,7 +19,7 @@ from __future__ import annotations
 import ctypes as C
 import threading
 from collections import OrderedDict
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -280,6 +280,7 @@ class _TTNetBase(nn.Module):
                 self._apply_input_norm(plan)
                 if self.__dict__.get("_count_usage"):
                     _lib.check(plan.lib.ttnet_plan_table_usage_enable(plan.handle, 1))
+                self._install_care(plan)
                 self._plans[idx] = plan
             sig = self._state_signature()
             if plan.signature != sig:
@@ -348,25 +349,28 @@ class _TTNetBase(nn.Module):
         return out
 
     def export_truth_tables(self, block_name: str, out_dir: str, block: int = 0, sub_block: int = 0, filters=None,
-                            max_expr_bits: int = 9, usage=None, minimiser: str = "sympy", rounds: int = 0):
+                            max_expr_bits: int = 9, usage=None, minimiser: str = "sympy", rounds: int = 0,
+                            min_count: int = 1):
         """Write the reference's truth-table files (CSV, DNF / CNF, SAT form) for one
         ``Block_TT`` from the table the plan built on the GPU.  ``usage``: that block's lookup counts
         (``table_usage()[block_name]``), whose zero entries become don't-care terms.  ``minimiser``: "sympy" (n <= 9), or
         "device" / "cpu" for prime, irredundant covers of every n <= 16 (the 16-input tables of TT-small), all filters of
         the block in one launch on the plan's device; ``rounds`` (0 .. 8) reduce / expand rounds make those covers smaller,
-        "sympy" ignores it.  See ``scale_imagenet_amd.export``."""
+        "sympy" ignores it.  ``min_count``: entries looked up fewer times than this become don't-cares too.  See
+        ``scale_imagenet_amd.export``."""
         from . import export
         table = self.get_table(block_name)
         device = torch.device("cuda", self._any_plan().device_index)
-        return export.export_block(table, out_dir, block, sub_block, filters, max_expr_bits, usage, minimiser, device, rounds)
+        return export.export_block(table, out_dir, block, sub_block, filters, max_expr_bits, usage, minimiser, device, rounds, min_count)
 
-    def gate_counts(self, usage=None, minimiser: str = "device", rounds: int = 0) -> "OrderedDict[str, dict]":
+    def gate_counts(self, usage=None, minimiser: str = "device", rounds: int = 0, min_count: int = 1) -> "OrderedDict[str, dict]":
         """Two-level gate counts of every binarised ``Block_TT`` (the float last block is skipped), without writing files:
         ``{name: {filters, constant, dnf_cubes, dnf_literals, cnf_cubes, cnf_literals}}`` from prime, irredundant covers
         (``scale_imagenet_amd.minimise``; not minimum ones), one launch per block for all its filters and both forms.
         ``usage``: ``table_usage()``; the entries never looked up become don't-cares.  ``constant`` counts the filters that
         are constant on their care patterns; they add no cubes.  ``rounds``: 0 .. 8 reduce / expand rounds of the minimiser
-        ("device" or "cpu", the only ones served here), which make the covers smaller.  The full variant has no tables:
+        ("device" or "cpu", the only ones served here), which make the covers smaller.  ``min_count``: the entries looked up
+        fewer times than this are the don't-cares (the complement of ``set_care(usage, min_count)``).  The full variant has no tables:
         ``get_table`` refuses."""
         from . import minimise
         out: "OrderedDict[str, dict]" = OrderedDict()
@@ -374,7 +378,7 @@ class _TTNetBase(nn.Module):
             if b.last:
                 continue
             table = self.get_table(b.name)
-            on, dc = minimise.pack_functions(table, None if usage is None else usage[b.name])
+            on, dc = minimise.pack_functions(table, None if usage is None else usage[b.name], min_count)
             out[b.name] = minimise.gate_count_row(on, dc, b.fan_in_bits, minimiser, torch.device("cuda", self._any_plan().device_index),
                                                   rounds)
         return out
@@ -490,6 +494,74 @@ class _TTNetBase(nn.Module):
             _lib.check(plan.lib.ttnet_plan_get_table_usage(plan.handle, b.name.encode(), a.ctypes.data_as(C.c_void_p), a.nbytes))
             out[b.name] = a
         return out
+
+    # -- care sets (include/ttnet.h: ttnet_plan_set_care ..) ------------------------------------------
+    @property
+    def care_blocks(self) -> List[str]:
+        """The ``Block_TT`` names, in the column order of ``care_misses``."""
+        return [b.name for b in self.spec.block_tts()]
+
+    def care_lookups(self) -> "OrderedDict[str, int]":
+        """``{Block_TT name: groups * Ho * Wo}``: the lookups one image makes in that block (the most its column of
+        ``care_misses`` can hold)."""
+        out: "OrderedDict[str, int]" = OrderedDict()
+        for blk in self.spec.blocks:
+            for b in (blk.conv1, blk.conv2, blk.conv3):
+                ho, wo = b.out_hw(*blk.in_hw)
+                out[b.name] = b.groups * ho * wo
+            out[blk.convf.name] = blk.convf.groups * blk.out_hw[0] * blk.out_hw[1]
+        return out
+
+    def set_care(self, masks_or_usage, min_count: int = 1):
+        """Install care sets: ``{Block_TT name: uint32 [G, words]}`` bitmaps (``minimise.care_masks``), or the int64
+        ``table_usage()`` counts themselves, from which the entries looked up at least ``min_count`` times are kept.  A
+        name that is left out has no care set (its column of ``care_misses`` is 0).  Replaces what was installed; holds for
+        the plans that exist and for those made later (a plan rebuilt for a larger batch gets the same bitmaps)."""
+        from . import minimise
+        blocks = {b.name: b for b in self.spec.block_tts()}
+        unknown = sorted(set(masks_or_usage) - set(blocks))
+        if unknown:
+            raise KeyError(f"set_care: no Block_TT named {unknown[0]!r}")
+        counts = {k: v for k, v in masks_or_usage.items() if np.asarray(v).dtype != np.uint32}
+        masks = {k: np.asarray(v) for k, v in masks_or_usage.items() if k not in counts}
+        masks.update(minimise.care_masks(counts, min_count))
+        for name, m in masks.items():
+            b = blocks[name]
+            want = (b.groups, minimise.n_words(b.fan_in_bits))
+            if tuple(m.shape) != want:
+                raise ValueError(f"set_care: the bitmap of {name} has shape {tuple(m.shape)}, expected {want}")
+        self.__dict__["_care"] = {k: np.ascontiguousarray(masks[k], dtype=np.uint32) for k in blocks if k in masks}
+        try:
+            for plan in self._plans.values():
+                _lib.check(plan.lib.ttnet_plan_clear_care(plan.handle))
+                self._install_care(plan)
+        except _lib.TTNetError:                           # (a refused variant: nothing stays installed)
+            self.clear_care()
+            raise
+        return self
+
+    def _install_care(self, plan):
+        for name, m in (self.__dict__.get("_care") or {}).items():
+            _lib.check(plan.lib.ttnet_plan_set_care(plan.handle, name.encode(), m.ctypes.data_as(C.c_void_p), m.nbytes))
+
+    def clear_care(self):
+        self.__dict__["_care"] = None
+        for plan in self._plans.values():
+            _lib.check(plan.lib.ttnet_plan_clear_care(plan.handle))
+        return self
+
+    def care_misses(self, lane: int = 0) -> torch.Tensor:
+        """int32 ``[n, len(care_blocks)]`` on the device: per image of the forward last issued on ``lane``, the lookups
+        of every ``Block_TT`` that fell outside its care set.  Asynchronous on the current stream, which must be the one
+        that forward was issued on (or be ordered after it).  An all-zero row proves that any circuit which agrees with the
+        tables on the care sets gives that image the same logits, bit for bit."""
+        plan = self._any_plan()
+        dev = torch.device("cuda", plan.device_index)
+        n = max(plan.query(f"last_n:{int(lane)}"), 1)       # (no forward yet: the call below says so)
+        rows = torch.empty((n, len(self.spec.block_tts())), dtype=torch.int32, device=dev)
+        _lib.check(plan.lib.ttnet_care_misses(plan.handle, int(lane), C.c_void_p(rows.data_ptr()),
+                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return rows
 
     def near_ties(self) -> Dict[str, int]:
         plan = self._any_plan()
