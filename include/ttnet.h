@@ -195,6 +195,69 @@ int ttnet_resize_center_crop_u8_ragged(const uint8_t *src_dev, int64_t src_bytes
                                        int64_t n, int max_h, int max_w, int resize, int crop, uint8_t *dst_dev,
                                        int32_t *bad_dev, void *stream);
 
+/* Views: crops of a ragged batch other than the one centre crop -- corner crops, mirrored crops, boxes the caller chose.
+ * A view is one crop x crop output cut from one image.  Its 48-byte descriptor is int32[12] =
+ * {image, flags, bx, by, bw, bh, nw, nh, x0, y0, 0, 0}; arrays of them are 16-byte aligned.  Its pixels:
+ *     B   = img[image][by : by + bh, bx : bx + bw]            the box, in source pixels
+ *     R   = Pillow's BILINEAR resize of B to (nw, nh)         8-bit, horizontal pass then vertical pass, a pass skipped
+ *                                                             when that size is unchanged (as ttnet_resize_center_crop_u8)
+ *     out = R[y0 : y0 + crop, x0 : x0 + crop]                 columns reversed when flags & 1
+ * The flip acts on the output window: it is hflip AFTER the resize, as in TenCrop and RandomHorizontalFlip.
+ * A view is valid iff 0 <= image < n_images; that image's descriptor is valid (1 <= h, w <= 65536, its bytes inside the
+ * buffer); the box lies inside the image with bw, bh >= 1; 1 <= nw, nh <= 65536; 0 <= x0, x0 + crop <= nw, likewise y0;
+ * flags has no bit but bit 0 and the two reserved words are zero; bw / nw and bh / nh do not exceed the call's max_scale. */
+typedef struct ttnet_view_desc {
+  int32_t image, flags;
+  int32_t bx, by, bw, bh;
+  int32_t nw, nh;
+  int32_t x0, y0;
+  int32_t reserved[2];
+} ttnet_view_desc;                                    /* 48 bytes */
+#define TTNET_VIEW_FLIP 1                             /* flags */
+
+/* n_views views of the n_images images of a ragged batch (buffer and image descriptors as for
+ * ttnet_resize_center_crop_u8_ragged; view descriptors in DEVICE memory) -> uint8 [n_views][crop][crop][3] in view order.
+ * Several views may name the same image.  One kernel launch -- the ragged kernel's own staging, horizontal pass and
+ * vertical fold, handed another geometry -- asynchronous on `stream`; nothing is allocated, uploaded or cached, so the
+ * call can be captured into a graph and replayed with new images and new descriptors.
+ *   - src_dev and view_desc_dev 16-byte aligned, image_desc_dev 8-byte aligned, dst_dev 4-byte aligned, crop * 3 a
+ *     multiple of 4, 1 <= n_images, n_views <= 65535.
+ *   - max_scale >= 1 bounds bw / nw and bh / nh of every view: it sizes the coefficient tables and the staged input row
+ *     as max_h / max_w do for the centre crop.  Bounds the 160 KB of LDS or the staging area cannot serve are
+ *     TTNET_E_UNSUPPORTED (nothing launched).
+ *   - an invalid view yields a zero crop and adds 1 to *bad_dev (when not NULL), once per view.  Whatever the
+ *     descriptors hold, nothing outside [src_dev, src_dev + src_bytes) is read and a view writes only its own crop. */
+int ttnet_resize_views_u8_ragged(const uint8_t *src_dev, int64_t src_bytes, const ttnet_image_desc *image_desc_dev,
+                                 int64_t n_images, const ttnet_view_desc *view_desc_dev, int64_t n_views, double max_scale,
+                                 int crop, uint8_t *dst_dev, int32_t *bad_dev, void *stream);
+
+/* The evaluation families of views, written ON THE DEVICE from the image descriptors (those of
+ * ttnet_jpeg_decode_ragged for instance: the host need not know any size): V descriptors per image, image-major (view
+ * i * V + v).  The box is the whole image and (nw, nh) follow torchvision's Resize(resize), the rule of
+ * ttnet_resize_center_crop_u8.  With mx = nw - crop, my = nh - crop, cx = round_half_even(mx / 2), cy likewise, the windows
+ * (x0, y0, flip) are
+ *     TTNET_VIEWS_CENTER  V = 1   (cx, cy, 0)                                          Resize + CenterCrop
+ *     TTNET_VIEWS_FLIP    V = 2   (cx, cy, 0), (mx - cx, cy, 1)                        .. and the centre crop of the mirrored image
+ *     TTNET_VIEWS_FIVE    V = 5   (0, 0, 0), (mx, 0, 0), (0, my, 0), (mx, my, 0), (cx, cy, 0)            FiveCrop
+ *     TTNET_VIEWS_TEN     V = 10  FIVE, then (mx, 0, 1), (0, 0, 1), (mx, my, 1), (0, my, 1), (mx - cx, cy, 1)   TenCrop
+ * (with an odd margin the mirrored image's centre crop is not the mirror of the centre crop).  An image with h < 1 or
+ * w < 1 -- one that was not decoded -- gets invalid views.  resize >= crop; n_images * V <= 65535; image_desc_dev 8-byte,
+ * view_desc_dev 16-byte aligned.  One launch, asynchronous, capturable.
+ * ttnet_eval_views_max_scale is the max_scale these families need for images within max_h x max_w (host arithmetic only;
+ * ttnet_resize_center_crop_u8_ragged sizes itself by the same function). */
+enum { TTNET_VIEWS_CENTER = 0, TTNET_VIEWS_FLIP = 1, TTNET_VIEWS_FIVE = 2, TTNET_VIEWS_TEN = 3 };
+int ttnet_make_eval_views(const ttnet_image_desc *image_desc_dev, int64_t n_images, int resize, int crop, int family,
+                          ttnet_view_desc *view_desc_dev, void *stream);
+double ttnet_eval_views_max_scale(int max_h, int max_w, int resize);
+
+/* The mean of the views' outputs, torchvision's `outputs.view(n, V, -1).mean(1)`:
+ *     out[i][c] = float32((sum over v of double(logits[i * V + v][c])) / V)
+ * logits_dev float32 [n * V][C] -> out_dev float32 [n][C]; the sum in ascending v, in float64, so the result does not
+ * depend on the launch; NaN propagates; V = 1 copies.  1 <= V <= 32, 1 <= n, n * V <= 65535 * 32, 1 <= C <= 65536; both
+ * 4-byte aligned.  One launch, asynchronous, no allocation, capturable.  (The mean of the probabilities is left out.) */
+#define TTNET_VIEWS_MAX 32
+int ttnet_mean_views(const float *logits_dev, int64_t n, int64_t V, int64_t C, float *out_dev, void *stream);
+
 /* JPEG decoding in front of the ragged resize: PIL.Image.open(path).convert("RGB"), the default loader of
  * torchvision.datasets.ImageFolder (main.py:208) that feeds the eval transform (utils/preprocess.py:104), on a batch of
  * compressed files.  Decoded on the device: Huffman-coded sequential 8-bit JPEG (SOF0, SOF1) with one scan holding

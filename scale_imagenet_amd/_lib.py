@@ -15,6 +15,8 @@ LIB_PATH = os.path.join(_HERE, "libttnet.so")
 
 TTNET_F32, TTNET_I64, TTNET_U8, TTNET_U16, TTNET_U64 = 0, 1, 2, 3, 4
 TOPK_MAX = 32                                              # TTNET_TOPK_MAX
+VIEWS_MAX = 32                                             # TTNET_VIEWS_MAX
+VIEW_FAMILIES = {"center": (0, 1), "flip": (1, 2), "five": (2, 5), "ten": (3, 10)}     # TTNET_VIEWS_*: (code, views per image)
 VARIANTS = {"small": 0, "xsmall": 1, "full": 2, "valexnet": 3}
 
 
@@ -70,6 +72,10 @@ SYMBOLS: List[Tuple[str, object, list]] = [
     ("ttnet_resize_center_crop_u8", C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     ("ttnet_resize_center_crop_u8_ragged", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                                      _P, _P, _P]),
+    ("ttnet_resize_views_u8_ragged", C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_double, C.c_int, _P, _P, _P]),
+    ("ttnet_make_eval_views", C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P]),
+    ("ttnet_eval_views_max_scale", C.c_double, [C.c_int, C.c_int, C.c_int]),
+    ("ttnet_mean_views", C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P]),
     ("ttnet_jpeg_ctx_create", C.c_int, [C.c_int, C.POINTER(_P)]),
     ("ttnet_jpeg_ctx_reserve", C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64]),
     ("ttnet_jpeg_decode_ragged", C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, _P]),

@@ -260,6 +260,19 @@ __global__ __launch_bounds__(256) void class_counts_kernel(const int64_t *__rest
   if (confusion) atomicAdd(&confusion[(size_t)t * C + c], 1ull);
 }
 
+// ttnet_mean_views: one thread per (image, class); the V addends are read in ascending v (consecutive threads read
+// consecutive floats of a row) and summed in float64.
+__global__ __launch_bounds__(256) void mean_views_kernel(const float *__restrict__ logits, int64_t total, int V, int C,
+                                                         float *__restrict__ out) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;      // i * C + c
+  if (j >= total) return;
+  const int64_t i = j / C;
+  const float *p = logits + (i * V) * C + (j - i * C);
+  double s = 0.0;
+  for (int v = 0; v < V; ++v) s += (double)p[(int64_t)v * C];
+  out[j] = (float)(s / (double)V);
+}
+
 __global__ __launch_bounds__(kReduceThreads) void eval_reduce_kernel(const PerImage *__restrict__ pi, int n,
                                                                      ttnet_eval_acc *acc) {
   __shared__ double s_loss[kReduceThreads / 64];
@@ -403,6 +416,24 @@ extern "C" int ttnet_class_counts(const int64_t *targets_dev, const void *per_im
   hipLaunchKernelGGL(class_counts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, targets_dev,
                      (const PerImage *)per_image_dev, (const TopkRecord *)topk_dev, (int)n, (int)k, (int)n_classes,
                      (unsigned long long *)counts_dev, (unsigned long long *)confusion_dev);
+  TT_HIP(hipGetLastError());
+  return TTNET_OK;
+}
+
+extern "C" int ttnet_mean_views(const float *logits_dev, int64_t n, int64_t V, int64_t C, float *out_dev, void *stream) {
+  if (!logits_dev || !out_dev || n < 1 || V < 1 || V > TTNET_VIEWS_MAX || n * V > (int64_t)65535 * TTNET_VIEWS_MAX || C < 1 ||
+      C > 65536) {
+    set_error("mean_views: bad argument (n %lld >= 1, V %lld in [1, %d], C %lld in [1, 65536], no NULL)", (long long)n,
+              (long long)V, TTNET_VIEWS_MAX, (long long)C);
+    return TTNET_E_INVALID;
+  }
+  if (((uintptr_t)logits_dev & 3) || ((uintptr_t)out_dev & 3)) {
+    set_error("mean_views: both buffers must be 4-byte aligned");
+    return TTNET_E_INVALID;
+  }
+  const int64_t total = n * C;
+  hipLaunchKernelGGL(mean_views_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits_dev,
+                     total, (int)V, (int)C, out_dev);
   TT_HIP(hipGetLastError());
   return TTNET_OK;
 }

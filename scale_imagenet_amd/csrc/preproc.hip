@@ -333,6 +333,8 @@ extern "C" int ttnet_resize_center_crop_u8(const uint8_t *src_dev, int64_t n, in
 //     item), so only one chunk of intermediate rows is ever kept.  Integer sums do not depend on their order: the
 //     result is the byte of the two-pass form.
 // The next chunk's global loads are issued before the fold of the current one.
+// Views (ttnet_resize_views_u8_ragged) are the same kernel handed another geometry: a box of the image instead of the whole
+// image, any resized size and crop window instead of torchvision's, the window's columns optionally reversed.
 namespace ttnet {
 namespace {
 
@@ -349,7 +351,73 @@ struct RaggedArgs {
   int ty;          // output rows per workgroup: RG_ITEMS / ceil(crop * 3 / 4 / RG_THREADS)
   int kmax;        // most taps per window any image within max_h x max_w can need (stride room of the tables)
   int stage_q;     // 16-byte pieces of the staged-input area
+  // ttnet_resize_views_u8_ragged only: one workgroup column per view instead of per image
+  const ttnet_view_desc *views;
+  int n_images;
+  double max_scale;
 };
+
+// torchvision.transforms.functional.resize with an int size: the shorter side becomes `resize`, the longer one
+// int(resize * long / short); an image whose shorter side already matches is kept.  The one statement of that rule on
+// the device: the ragged kernel and the view generator both call it.
+__device__ inline void resized_size(int h, int w, int resize, int &nh, int &nw) {
+  nw = w, nh = h;
+  if ((w <= h && w == resize) || (h <= w && h == resize)) return;
+  if (w <= h) { nw = resize; nh = (int)((double)resize * h / w); }
+  else { nh = resize; nw = (int)((double)resize * w / h); }
+}
+// CenterCrop's offset, int(round(margin / 2.0)) with Python's round()
+__device__ inline int center_offset(int margin) { return (int)nearbyint(margin / 2.0); }
+
+__device__ inline bool image_ok(const ttnet_image_desc &d, int max_h, int max_w, int64_t src_bytes) {
+  return d.h >= 1 && d.h <= max_h && d.w >= 1 && d.w <= max_w && d.offset >= 0 && d.offset <= src_bytes &&
+         (int64_t)d.h * d.w * 3 <= src_bytes - d.offset;
+}
+
+// What a workgroup column resizes: the box [by, by + bh) x [bx, bx + bw) of an image of row pitch w at byte `offset`,
+// resampled to nw x nh, of which the crop x crop window at (x0, y0) is kept, its columns reversed when `flip`.
+struct Geo {
+  int64_t offset;
+  int w, bx, by, bw, bh, nw, nh, x0, y0;
+  bool flip, ok;
+};
+
+// Resize(resize) + CenterCrop(crop) of image im: the whole image is the box
+__device__ inline Geo center_geo(const RaggedArgs &a, int im) {
+  const ttnet_image_desc d = a.desc[im];
+  Geo g;
+  g.ok = image_ok(d, a.max_h, a.max_w, a.src_bytes);
+  g.offset = d.offset;
+  g.w = d.w; g.bx = 0; g.by = 0; g.bw = d.w; g.bh = d.h; g.nw = d.w; g.nh = d.h;
+  if (g.ok) resized_size(d.h, d.w, a.resize, g.nh, g.nw);
+  g.x0 = center_offset(g.nw - a.crop);
+  g.y0 = center_offset(g.nh - a.crop);
+  g.flip = false;
+  return g;
+}
+
+constexpr int kMaxSide = 65536;      // of an image a view names, and of the size a box is resampled to
+
+// view v as its descriptor states it (ttnet.h: when a view is valid)
+__device__ inline Geo view_geo(const RaggedArgs &a, int v) {
+  const int4 *p = (const int4 *)(a.views + v);
+  const int4 q0 = p[0], q1 = p[1], q2 = p[2];      // {image, flags, bx, by} {bw, bh, nw, nh} {x0, y0, 0, 0}
+  Geo g;
+  g.bx = q0.z; g.by = q0.w; g.bw = q1.x; g.bh = q1.y; g.nw = q1.z; g.nh = q1.w; g.x0 = q2.x; g.y0 = q2.y;
+  g.flip = (q0.y & 1) != 0;
+  g.ok = q0.x >= 0 && q0.x < a.n_images && (q0.y & ~1) == 0 && q2.z == 0 && q2.w == 0;
+  ttnet_image_desc d;
+  d.offset = 0; d.h = 0; d.w = 0;
+  if (g.ok) d = a.desc[q0.x];
+  g.offset = d.offset;
+  g.w = d.w;
+  g.ok = g.ok && image_ok(d, kMaxSide, kMaxSide, a.src_bytes) &&
+         g.bx >= 0 && g.bw >= 1 && g.bw <= d.w && g.bx <= d.w - g.bw && g.by >= 0 && g.bh >= 1 && g.bh <= d.h && g.by <= d.h - g.bh &&
+         g.nw >= 1 && g.nw <= kMaxSide && g.nh >= 1 && g.nh <= kMaxSide &&
+         g.x0 >= 0 && g.x0 <= g.nw - a.crop && g.y0 >= 0 && g.y0 <= g.nh - a.crop;
+  g.ok = g.ok && (double)g.bw / g.nw <= a.max_scale && (double)g.bh / g.nh <= a.max_scale;
+  return g;
+}
 
 // One axis of Pillow's resampling, as precompute() sets it up; `ident`: a pass Pillow skips (size unchanged).
 struct Axis {
@@ -438,26 +506,22 @@ __device__ inline void ragged_hpass(const uint8_t *s_in, uint8_t *s_mid, const i
   }
 }
 
-// WIDE: crop * 3 / 4 > RG_THREADS, several dword columns per thread (fewer rows per tile); otherwise item e is row e, column tid
-template <bool WIDE>
+// WIDE: crop * 3 / 4 > RG_THREADS, several dword columns per thread (fewer rows per tile); otherwise item e is row e, column tid.
+// VIEWS: blockIdx.y is a view and the geometry is its descriptor's (ttnet_resize_views_u8_ragged); otherwise it is an image
+// and the geometry is torchvision's Resize + CenterCrop.  Everything after the geometry is the same code.
+template <bool WIDE, bool VIEWS>
 __global__ __launch_bounds__(RG_THREADS) void resize_crop_ragged_kernel(RaggedArgs a) {
   extern __shared__ __align__(16) uint8_t lds[];
   const int im = blockIdx.y, tid = threadIdx.x, crop = a.crop, ow = crop * 3, owq = ow >> 2;
   const int y_lo = blockIdx.x * a.ty, rows_out = min(a.ty, crop - y_lo), items = rows_out * owq;
   const int ncol = (owq + RG_THREADS - 1) / RG_THREADS;
   uint32_t *dst = (uint32_t *)(a.dst + ((size_t)im * crop + y_lo) * ow);      // this tile's rows, contiguous
-  const ttnet_image_desc d = a.desc[im];
-  const int h = d.h, w = d.w;
-  bool ok = h >= 1 && h <= a.max_h && w >= 1 && w <= a.max_w && d.offset >= 0 && d.offset <= a.src_bytes &&
-            (int64_t)h * w * 3 <= a.src_bytes - d.offset;
-  // torchvision: the shorter side becomes `resize`, the longer int(resize * long / short); kept if the shorter side matches
-  int nw = w, nh = h;
-  if (ok && !((w <= h && w == a.resize) || (h <= w && h == a.resize))) {
-    if (w <= h) { nw = a.resize; nh = (int)((double)a.resize * h / w); }
-    else { nh = a.resize; nw = (int)((double)a.resize * w / h); }
-  }
-  const int x0 = (int)nearbyint((nw - crop) / 2.0), y0 = (int)nearbyint((nh - crop) / 2.0);     // Python's round()
-  const Axis ax = make_axis(w, nw), ay = make_axis(h, nh);
+  Geo g;
+  if constexpr (VIEWS) g = view_geo(a, im);
+  else g = center_geo(a, im);
+  bool ok = g.ok;
+  const int w = g.w, x0 = g.x0, y0 = g.y0;
+  const Axis ax = make_axis(g.bw, g.nw), ay = make_axis(g.bh, g.nh);
   const int ksh = ax.ksize, ksv = ay.ksize;
   double c;
   int c0, cl, nl, r0, rl, rn;
@@ -483,10 +547,11 @@ __global__ __launch_bounds__(RG_THREADS) void resize_crop_ragged_kernel(RaggedAr
   int *s_bv = s_kh + (size_t)crop * a.kmax;                                             // [RG_TY][2]: first row (tile-relative), count
   int *s_kv = s_bv + 2 * RG_TY;                                                         // [RG_TY][ksv]
   for (int xc = tid; xc < crop; xc += RG_THREADS) {
+    const int xo = x0 + (g.flip ? crop - 1 - xc : xc);      // the flip acts on the window: output column xc is resized column xo
     int xmin, cnt;
-    axis_window(ax, x0 + xc, c, xmin, cnt);
+    axis_window(ax, xo, c, xmin, cnt);
     s_xb[xc] = (xmin - c0) * 3;
-    axis_coeffs(ax, x0 + xc, s_kh + xc * ksh);
+    axis_coeffs(ax, xo, s_kh + xc * ksh);
   }
   const int yc_t = RG_THREADS - 1 - tid;                   // the vertical rows on the last threads (idle above at crop 224)
   if (yc_t < rows_out) {
@@ -499,7 +564,7 @@ __global__ __launch_bounds__(RG_THREADS) void resize_crop_ragged_kernel(RaggedAr
   const size_t whole_q = (size_t)a.src_bytes >> 4;
   const uint32_t pitch = (uint32_t)w * 3u, row_bytes = (uint32_t)row_q * 16u;
   const float inv_rowq = 1.0f / (float)row_q;
-  auto first_byte = [&](int rc) { return (size_t)d.offset + ((size_t)(r0 + rc) * w + c0) * 3; };
+  auto first_byte = [&](int rc) { return (size_t)g.offset + ((size_t)(g.by + r0 + rc) * w + g.bx + c0) * 3; };
   uint4 v[RG_STAGE_LOADS];
   // stage: the 16-byte pieces of the buffer from the one that holds byte (row, c0), never past src_bytes
   auto load = [&](int rc) {
@@ -580,6 +645,54 @@ __global__ __launch_bounds__(RG_THREADS) void resize_crop_ragged_kernel(RaggedAr
 }  // namespace
 }  // namespace ttnet
 
+// The bound on bw / nw and bh / nh that the CENTER / FLIP / FIVE / TEN views (and the ragged Resize + CenterCrop, whose
+// geometry is the CENTER view's) need for images within max_h x max_w.  Scale of an axis (w / nw or h / nh): the shorter
+// side s goes to `resize` (scale s / resize), the longer side l to int(resize * l / s) > resize * l / s - 1
+// (scale < s / (resize - 1)); s <= min(max_h, max_w).
+extern "C" double ttnet_eval_views_max_scale(int max_h, int max_w, int resize) {
+  if (max_h < 1 || max_w < 1 || resize < 1) return 1.0;
+  return std::max(1.0, (double)std::min(max_h, max_w) / (resize > 1 ? resize - 1.0 : 1.0));
+}
+
+namespace {
+// Sizes a launch for axis scales up to smax (taps 2 * ceil(max(scale, 1)) + 1; input columns of the crop
+// < (crop + 1) * max(scale, 1) + 3) and launches it: `columns` images or views.  The one place both ragged entry points
+// get their tap stride, staging area and LDS from.
+template <bool VIEWS>
+int launch_ragged(const char *who, RaggedArgs a, double smax, int64_t columns, hipStream_t stream) {
+  const int crop = a.crop, ow = crop * 3, owq = ow / 4;
+  const int ty = std::min(RG_TY, RG_ITEMS / ((owq + RG_THREADS - 1) / RG_THREADS));
+  if (ty < 1 || !(smax <= 1e4)) {
+    set_error("%s: crop %d or axis scales up to %g are beyond this kernel", who, crop, smax);
+    return TTNET_E_UNSUPPORTED;
+  }
+  a.ty = ty;
+  a.kmax = 2 * (int)ceil(smax) + 3;                                  // (+2: slack over the rounding of the bound)
+  const int64_t cw_max = (int64_t)ceil((crop + 1) * smax) + 4, row_q_max = (cw_max * 3 + 30) / 16;
+  if (row_q_max > RG_STAGE_Q) {
+    set_error("%s: axis scales up to %g at crop %d need %lld input bytes per row, more than the %d a workgroup stages", who,
+              smax, crop, (long long)(cw_max * 3), RG_STAGE_Q * 16);
+    return TTNET_E_UNSUPPORTED;
+  }
+  a.stage_q = (int)std::min<int64_t>((int64_t)RG_CHUNK * row_q_max, RG_STAGE_Q);
+  const size_t lds = (size_t)a.stage_q * 16 + (size_t)RG_CHUNK * ow + ((3 * a.kmax + 31) & ~15) +
+                     ((size_t)crop + (size_t)crop * a.kmax + 2 * RG_TY + (size_t)RG_TY * a.kmax) * sizeof(int);
+  if (lds > 160 * 1024) {
+    set_error("%s: axis scales up to %g at crop %d need %zu bytes of LDS per workgroup", who, smax, crop, lds);
+    return TTNET_E_UNSUPPORTED;
+  }
+  auto launch = [&](auto kernel) -> int {
+    TT_TRY(ensure_dynamic_lds((const void *)kernel, lds));
+    hipLaunchKernelGGL(kernel, dim3((crop + ty - 1) / ty, (unsigned)columns), dim3(RG_THREADS), lds, stream, a);
+    return TTNET_OK;
+  };
+  if (owq <= RG_THREADS) TT_TRY(launch(resize_crop_ragged_kernel<false, VIEWS>));
+  else TT_TRY(launch(resize_crop_ragged_kernel<true, VIEWS>));
+  TT_HIP(hipGetLastError());
+  return TTNET_OK;
+}
+}  // namespace
+
 extern "C" int ttnet_resize_center_crop_u8_ragged(const uint8_t *src_dev, int64_t src_bytes, const ttnet_image_desc *desc_dev,
                                                   int64_t n, int max_h, int max_w, int resize, int crop, uint8_t *dst_dev,
                                                   int32_t *bad_dev, void *stream) {
@@ -594,42 +707,92 @@ extern "C" int ttnet_resize_center_crop_u8_ragged(const uint8_t *src_dev, int64_
               "4-byte aligned and crop * 3 a multiple of 4");
     return TTNET_E_INVALID;
   }
-  // Bounds over every image within max_h x max_w.  Scale of an axis (w / nw or h / nh): the shorter side s goes to
-  // `resize` (scale s / resize), the longer side l to int(resize * l / s) > resize * l / s - 1 (scale < s / (resize - 1));
-  // s <= min(max_h, max_w).  Taps 2 * ceil(max(scale, 1)) + 1; input columns of the crop < (crop + 1) * max(scale, 1) + 3.
-  const int ow = crop * 3, owq = ow / 4;
-  const int ty = std::min(RG_TY, RG_ITEMS / ((owq + RG_THREADS - 1) / RG_THREADS));
-  const double smax = std::max(1.0, (double)std::min(max_h, max_w) / (resize > 1 ? resize - 1.0 : 1.0));
-  if (ty < 1 || smax > 1e4 || max_h > 65536 || max_w > 65536 || resize > 65536) {
-    set_error("resize_center_crop_ragged: crop %d or images up to %dx%d at resize %d are beyond this kernel", crop, max_w,
-              max_h, resize);
+  if (max_h > 65536 || max_w > 65536 || resize > 65536) {
+    set_error("resize_center_crop_ragged: images up to %dx%d at resize %d are beyond this kernel", max_w, max_h, resize);
     return TTNET_E_UNSUPPORTED;
   }
   RaggedArgs a{};
   a.src = src_dev; a.src_bytes = src_bytes; a.desc = desc_dev; a.dst = dst_dev; a.bad = bad_dev;
-  a.max_h = max_h; a.max_w = max_w; a.resize = resize; a.crop = crop; a.ty = ty;
-  a.kmax = 2 * (int)ceil(smax) + 3;                                  // (+2: slack over the rounding of the bound)
-  const int64_t cw_max = (int64_t)ceil((crop + 1) * smax) + 4, row_q_max = (cw_max * 3 + 30) / 16;
-  if (row_q_max > RG_STAGE_Q) {
-    set_error("resize_center_crop_ragged: images up to %dx%d at resize %d / crop %d need %lld input bytes per row, more than "
-              "the %d a workgroup stages", max_w, max_h, resize, crop, (long long)(cw_max * 3), RG_STAGE_Q * 16);
-    return TTNET_E_UNSUPPORTED;
+  a.max_h = max_h; a.max_w = max_w; a.resize = resize; a.crop = crop;
+  return launch_ragged<false>("resize_center_crop_ragged", a, ttnet_eval_views_max_scale(max_h, max_w, resize), n,
+                              (hipStream_t)stream);
+}
+
+static_assert(sizeof(ttnet_view_desc) == 48, "a view descriptor is 48 bytes (ttnet.h)");
+
+extern "C" int ttnet_resize_views_u8_ragged(const uint8_t *src_dev, int64_t src_bytes, const ttnet_image_desc *image_desc_dev,
+                                            int64_t n_images, const ttnet_view_desc *view_desc_dev, int64_t n_views,
+                                            double max_scale, int crop, uint8_t *dst_dev, int32_t *bad_dev, void *stream) {
+  if (!src_dev || !image_desc_dev || !view_desc_dev || !dst_dev || src_bytes < 1 || n_images < 1 || n_images > 65535 ||
+      n_views < 1 || n_views > 65535 || crop < 1 || crop > kMaxSide || !(max_scale >= 1.0)) {
+    set_error("resize_views_ragged: bad argument (n_images %lld, n_views %lld in [1, 65535], src_bytes %lld, crop %d, "
+              "max_scale %g >= 1)", (long long)n_images, (long long)n_views, (long long)src_bytes, crop, max_scale);
+    return TTNET_E_INVALID;
   }
-  a.stage_q = (int)std::min<int64_t>((int64_t)RG_CHUNK * row_q_max, RG_STAGE_Q);
-  const size_t lds = (size_t)a.stage_q * 16 + (size_t)RG_CHUNK * ow + ((3 * a.kmax + 31) & ~15) +
-                     ((size_t)crop + (size_t)crop * a.kmax + 2 * RG_TY + (size_t)RG_TY * a.kmax) * sizeof(int);
-  if (lds > 160 * 1024) {
-    set_error("resize_center_crop_ragged: images up to %dx%d at resize %d / crop %d need %zu bytes of LDS per workgroup",
-              max_w, max_h, resize, crop, lds);
-    return TTNET_E_UNSUPPORTED;
+  if (((uintptr_t)src_dev & 15) || ((uintptr_t)image_desc_dev & 7) || ((uintptr_t)view_desc_dev & 15) || ((uintptr_t)dst_dev & 3) ||
+      (crop * 3) % 4) {
+    set_error("resize_views_ragged: the input and the view descriptors must be 16-byte aligned, the image descriptors 8-byte "
+              "aligned, the output 4-byte aligned and crop * 3 a multiple of 4");
+    return TTNET_E_INVALID;
   }
-  auto launch = [&](auto kernel) -> int {
-    TT_TRY(ensure_dynamic_lds((const void *)kernel, lds));
-    hipLaunchKernelGGL(kernel, dim3((crop + ty - 1) / ty, (unsigned)n), dim3(RG_THREADS), lds, (hipStream_t)stream, a);
-    return TTNET_OK;
+  RaggedArgs a{};
+  a.src = src_dev; a.src_bytes = src_bytes; a.desc = image_desc_dev; a.dst = dst_dev; a.bad = bad_dev; a.crop = crop;
+  a.views = view_desc_dev; a.n_images = (int)n_images; a.max_scale = max_scale;
+  return launch_ragged<true>("resize_views_ragged", a, max_scale, n_views, (hipStream_t)stream);
+}
+
+// ttnet_make_eval_views: one thread per image writes its V view descriptors, image-major.
+namespace {
+constexpr int kFamilyViews[4] = {1, 2, 5, 10};      // TTNET_VIEWS_CENTER, _FLIP, _FIVE, _TEN
+
+__global__ __launch_bounds__(256) void make_eval_views_kernel(const ttnet_image_desc *desc, int n, int resize, int crop, int family,
+                                                              int V, ttnet_view_desc *out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const ttnet_image_desc d = desc[i];
+  // (an image that was not decoded, h = w = 0, or any other size the resize refuses: its views are refused too, by their box)
+  const bool ok = d.h >= 1 && d.w >= 1;
+  int nh = 0, nw = 0;
+  if (ok) resized_size(d.h, d.w, resize, nh, nw);
+  const int mx = nw - crop, my = nh - crop, cx = center_offset(mx), cy = center_offset(my);
+  // the windows in torchvision's order: five_crop is (tl, tr, bl, br, center); ten_crop adds five_crop of the flipped image,
+  // whose windows read mirrored: tl <-> tr, bl <-> br, and the centre crop at mx - cx
+  auto window = [&](int v, int &x, int &y, int &flip) {
+    flip = 0;
+    if (family == TTNET_VIEWS_CENTER || (family == TTNET_VIEWS_FLIP && v == 0)) { x = cx; y = cy; return; }
+    if (family == TTNET_VIEWS_FLIP) { x = mx - cx; y = cy; flip = 1; return; }
+    const int u = v % 5;
+    flip = v >= 5;
+    if (u == 4) { x = flip ? mx - cx : cx; y = cy; return; }
+    const bool right = ((u & 1) != 0) != (flip != 0);
+    x = right ? mx : 0;
+    y = (u & 2) ? my : 0;
   };
-  if (owq <= RG_THREADS) TT_TRY(launch(resize_crop_ragged_kernel<false>));
-  else TT_TRY(launch(resize_crop_ragged_kernel<true>));
+  for (int v = 0; v < V; ++v) {
+    int x = 0, y = 0, flip = 0;
+    window(v, x, y, flip);
+    int4 *p = (int4 *)(out + (size_t)i * V + v);
+    p[0] = ok ? make_int4(i, flip, 0, 0) : make_int4(i, 0, 0, 0);
+    p[1] = ok ? make_int4(d.w, d.h, nw, nh) : make_int4(0, 0, 0, 0);
+    p[2] = ok ? make_int4(x, y, 0, 0) : make_int4(0, 0, 0, 0);
+  }
+}
+}  // namespace
+
+extern "C" int ttnet_make_eval_views(const ttnet_image_desc *image_desc_dev, int64_t n_images, int resize, int crop, int family,
+                                     ttnet_view_desc *view_desc_dev, void *stream) {
+  if (!image_desc_dev || !view_desc_dev || n_images < 1 || crop < 1 || resize < crop || resize > kMaxSide ||
+      family < TTNET_VIEWS_CENTER || family > TTNET_VIEWS_TEN || n_images * kFamilyViews[family] > 65535) {
+    set_error("make_eval_views: bad argument (n_images %lld, resize %d >= crop %d, family %d in [0, 3], n_images * views <= 65535)",
+              (long long)n_images, resize, crop, family);
+    return TTNET_E_INVALID;
+  }
+  if (((uintptr_t)image_desc_dev & 7) || ((uintptr_t)view_desc_dev & 15)) {
+    set_error("make_eval_views: the image descriptors must be 8-byte aligned, the view descriptors 16-byte aligned");
+    return TTNET_E_INVALID;
+  }
+  hipLaunchKernelGGL(make_eval_views_kernel, dim3((unsigned)((n_images + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     image_desc_dev, (int)n_images, resize, crop, family, kFamilyViews[family], view_desc_dev);
   TT_HIP(hipGetLastError());
   return TTNET_OK;
 }

@@ -461,7 +461,8 @@ class _TopK:
 def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]],
              device: torch.device, log_every: int = 0, inflight: int = 1, *,
              forward: Optional[Callable] = None, metrics: str = "torch", topk: int = 0, per_class: bool = False,
-             confusion: bool = False, table_usage: bool = False, care=None, care_min_count: int = 1) -> EvalResult:
+             confusion: bool = False, table_usage: bool = False, care=None, care_min_count: int = 1,
+             views: Optional[str] = None) -> EvalResult:
     """main.py:242-284: ``model.eval()``, no_grad, per batch loss / top-1 / top-5.
 
     ``inflight`` > 1 keeps that many batches in flight on separate HIP streams and model lanes
@@ -499,7 +500,25 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
     other entries as don't-cares classifies them exactly as the network does) and, for a labelled run, the bracket that
     puts on the circuit's top-1 / top-5 accuracy (``care_bounds``).  The bounds come from per-image top-5 records, so the
     evaluation keeps at least 5 predictions per image internally; ``predictions`` is returned only for ``topk > 0``, with
-    the k asked for.  The care set stays installed afterwards (``model.clear_care()``)."""
+    the k asked for.  The care set stays installed afterwards (``model.clear_care()``).
+
+    ``views="flip" | "five" | "ten"``: multi-crop evaluation, torchvision's ``Resize(256)`` -> ``FiveCrop(224)`` /
+    ``TenCrop(224)`` (or centre crop + its flip) -> ``outputs.view(n, V, -1).mean(1)``.  ``RaggedU8`` and ``RaggedJpeg``
+    batches go through ``preprocess.imgnet_views_forward`` / ``jpeg.jpeg_views_forward``: every image is uploaded (and
+    decoded) once, its V crops are cut on the device, ``n * V`` crops are forwarded -- size the plan for that
+    (``model.reserve``) -- and the V rows of logits are averaged on the device (``ttnet_mean_views``).  Metrics, top-k and
+    per-class counters see ``[n, n_classes]`` as ever.  ``table_usage=True`` then counts the lookups of ALL ``n * V``
+    crops: that is how more views widen what a usage run sees.  ``care=`` with ``views`` raises ValueError (the miss rows
+    would be per crop, not per image), and so does a float or already-cropped uint8 tensor batch (RuntimeError: there is
+    no image left to cut other views from); ``forward=`` with ``views`` raises ValueError as well, since a forward of
+    the caller's own decides its views itself.  ``views=None``: nothing changes."""
+    if views is not None and views not in ("flip", "five", "ten"):
+        raise ValueError(f"views must be None, \"flip\", \"five\" or \"ten\", got {views!r}")
+    if views is not None and care is not None:
+        raise ValueError("evaluate(care=, views=): the care-set misses are counted per forwarded crop, V rows per image; "
+                         "evaluate the care set with views=None")
+    if views is not None and forward is not None:
+        raise ValueError("evaluate(forward=, views=): a forward of the caller's own decides its views itself")
     if topk < 0 or topk > _lib.TOPK_MAX:
         raise ValueError(f"topk must be in [0, {_lib.TOPK_MAX}], got {topk}")
     per_class = per_class or confusion
@@ -547,15 +566,22 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
         if forward is not None:
             return forward(model, inputs, lane or 0)
         if isinstance(inputs, torch.Tensor):
+            if views is not None:
+                raise RuntimeError(f"evaluate(views={views!r}) needs RaggedU8 or RaggedJpeg batches (whole images to cut the "
+                                   f"views from), got a {inputs.dtype} tensor {tuple(inputs.shape)}")
             if inputs.dtype == torch.uint8:
                 return model.forward_u8(inputs, lane=lane or 0)
             return model(inputs) if lane is None else model(inputs, lane=lane)
         from . import jpeg, preprocess                    # (not needed by the float path)
         if isinstance(inputs, jpeg.RaggedJpeg):
             seen.update(("jpeg", "ragged"))
+            if views is not None:
+                return jpeg.jpeg_views_forward(model, inputs, views, lane=lane or 0)
             return jpeg.jpeg_eval_forward(model, inputs, lane=lane or 0)
         if isinstance(inputs, preprocess.RaggedU8):
             seen.add("ragged")
+            if views is not None:
+                return preprocess.imgnet_views_forward(model, inputs, views, lane=lane or 0)
             return preprocess.imgnet_eval_forward(model, inputs, lane=lane or 0)
         raise RuntimeError(f"evaluate: no forward for a batch of type {type(inputs).__name__}; pass forward=")
 

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .preprocess import MAX_SIDE, RaggedU8, _StickyCount, resize_center_crop_u8_ragged
+from .preprocess import MAX_SIDE, RaggedU8, _StickyCount, imgnet_views_forward, resize_center_crop_u8_ragged
 
 KIND_JPEG, KIND_RAW, KIND_PROGRESSIVE = 0, 1, 2
 TABLE_BYTES = 2048        # per-image table block: uint16 quant[3][64] (zig-zag) + [3][dc, ac] x (counts[16], symbols[256])
@@ -904,3 +904,10 @@ def jpeg_eval_forward(model, rj: RaggedJpeg, lane: int = 0) -> torch.Tensor:
     """``model(imgnet_transform(False)(Image.open(f).convert("RGB")))`` for a batch of files: decode ->
     resize_center_crop_u8_ragged -> forward_u8, all on the current stream, no host synchronisation."""
     return model.forward_u8(resize_center_crop_u8_ragged(decode_ragged(rj, lane=lane)), lane=lane)
+
+
+def jpeg_views_forward(model, rj: RaggedJpeg, family: str, lane: int = 0) -> torch.Tensor:
+    """``jpeg_eval_forward`` with several views per file (``preprocess.imgnet_views_forward``): every file is decoded
+    ONCE, then the ``family`` of crops is cut from the decoded image on the device, all ``n * V`` crops are forwarded and
+    each image's logits are averaged.  No host synchronisation."""
+    return imgnet_views_forward(model, decode_ragged(rj, lane=lane), family, lane=lane)

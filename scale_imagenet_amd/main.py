@@ -54,6 +54,10 @@ def add_own_flags(p: argparse.ArgumentParser):
                      help="jpeg: files decoded on the device (progressive ones by Pillow in the workers); "
                           "jpeg-progressive: progressive files on the device too; pillow: everything decoded by Pillow "
                           "in the workers (slow; for cross-checking a folder)")
+    own.add_argument("--views", choices=["flip", "five", "ten"], default=None,
+                     help="multi-crop evaluation: Resize(256), then the centre crop and its flip (2 views), FiveCrop(224) or "
+                          "TenCrop(224); every file is decoded once, the views are cut and forwarded on the device and their "
+                          "logits averaged (default: the one centre crop).  Not with --care_from")
     own.add_argument("--inflight", type=int, default=2, help="batches in flight on separate streams / lanes")
     own.add_argument("--gpus", type=int, default=1, help="evaluate on N GPUs: starts one rank per GPU itself")
     return own
@@ -225,7 +229,23 @@ def load_model(args, device, rank: int):
     model = getattr(ttnet, VARIANT_CLASSES[args.variant])(argparse.Namespace(
         nfilter=args.nfilter, tfilter=args.tfilter, layers=args.layers, groups=parse_groups(args.groups)))
     model.load_state_dict(_state_dict(args, model.spec, rank), strict=True)
-    return model.to(device).eval().reserve(max(1, args.eval_batch_size))
+    return model.to(device).eval().reserve(max(1, args.eval_batch_size) * views_per_image(args))
+
+
+def views_per_image(args) -> int:
+    """How many crops --views forwards per image (1 without the flag)."""
+    from ._lib import VIEW_FAMILIES
+    views = getattr(args, "views", None)
+    return VIEW_FAMILIES[views][1] if views else 1
+
+
+def views_args(args) -> dict:
+    """The ``evaluate`` keyword of --views (none without the flag: the call is what it was)."""
+    if not getattr(args, "views", None):
+        return {}
+    if args.care_from:
+        raise SystemExit("--views does not go with --care_from: the care-set misses are per forwarded crop")
+    return dict(views=args.views)
 
 
 def shard_loader(args, folder, rank: int, world: int):
@@ -274,6 +294,7 @@ def run(args) -> int:
     if args.table_usage or args.table_gates:
         extra["table_usage"] = True
     extra.update(care_args(args))
+    extra.update(views_args(args))
     # a rank's own lines (running metrics, its shard's Acc..) go to stderr when there are several: stdout carries the result
     with contextlib.redirect_stdout(sys.stderr) if world > 1 else contextlib.nullcontext():
         part = evaluate(model, loader, device, log_every=args.log_interval, inflight=max(1, args.inflight), metrics="device",
@@ -323,6 +344,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     if args.table_gates_rounds and not args.table_gates:
         raise SystemExit("--table_gates_rounds needs --table_gates")
     check_care_flags(args)
+    views_args(args)
     return launch(args, argv, "scale_imagenet_amd.main", _check_paths, run)
 
 

@@ -14,7 +14,7 @@ import sys
 from typing import Optional, Sequence
 
 from .main import _check_ckpt, add_care_flags, add_model_flags, add_own_flags, add_topk_flags, care_args, check_care_flags, \
-    check_topk, end_ranks, launch, load_model, shard_loader, start_rank
+    check_topk, end_ranks, launch, load_model, shard_loader, start_rank, views_args
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -51,7 +51,7 @@ def run(args) -> int:
     loader = shard_loader(args, files, rank, world)
     with contextlib.redirect_stdout(sys.stderr):          # stdout carries the CSV (or nothing)
         part = evaluate(model, ((inputs, None) for inputs, _ in loader), device, inflight=max(1, args.inflight), topk=args.topk,
-                        **care_args(args))
+                        **care_args(args), **views_args(args))
     pred = all_gather_predictions(part.predictions)
     covered = all_gather_care(part.care).covered if args.care_from else None
     if rank == 0:
@@ -66,6 +66,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     args = build_parser().parse_args(argv)
     check_topk(args, needed=True)
     check_care_flags(args)
+    views_args(args)
     return launch(args, argv, "scale_imagenet_amd.predict", _check_paths, run)
 
 
