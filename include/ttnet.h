@@ -117,7 +117,7 @@ int ttnet_plan_finalize(ttnet_plan *plan, void *stream);
  * Asynchronous on `stream`.  From the third call with the same n the launches are replayed from a
  * hipGraph captured on a private stream (the input / logits pointers are patched per call);
  * TTNET_NO_GRAPH=1 in the environment keeps plain launches.  Results are identical either way.
- * Setting a tensor, a table or finalizing drops every captured graph (they are re-captured).
+ * Setting a tensor, a table, the input normalisation or finalizing drops every captured graph (they are re-captured).
  * Range.  The float stages run on the 16-bit matrix cores with every float32 operand carried as two
  * fp16 terms after a power-of-two prescale (x16 for activations): inputs, pooled features and
  * classifier activations must satisfy |v| < 4094 (the reference's float32 path has no such limit;
@@ -148,7 +148,15 @@ int ttnet_forward_lane(ttnet_plan *plan, int lane, const float *x_dev, int64_t n
  * ttnet_plan_set_input_norm replaces them) in front of the stem's average pool.  Same result as
  * ttnet_forward on the normalised float32 tensor up to stem near ties (the stem works on the exact integer byte
  * sums, with the normalisation folded into its weights: two matrix products per output instead of the three the
- * float32 input needs).  Not available for TTNET_VALEXNET. */
+ * float32 input needs).
+ * TTNET_VALEXNET takes the CIFAR bytes the same way: uint8 [n][32][32][3], 4-byte aligned, any lane.  Its defaults are
+ * the reference's CIFAR constants (cifar_transform, utils/preprocess.py:82-87: mean 0.4914, 0.4822, 0.4465, std 0.2023,
+ * 0.1994, 0.2010).  Its stem kernel accumulates centred bytes b - round(255 mean_c), exact in float32, on weights scaled
+ * by 1 / (255 std_c); the remainder of the normalisation joins the bias in one constant per border class of the
+ * convolution output (interior, top row, left column, corner), because the zero padding is zero in normalised space
+ * and not byte 0.  Same bits as ttnet_forward on the normalised float32 tensor up to stem near ties.
+ * ttnet_plan_set_input_norm rebuilds the folded operands (at once on a finalized plan, otherwise at finalize) and
+ * drops every captured graph, as setting a tensor does; std must be positive (TTNET_E_INVALID). */
 int ttnet_plan_set_input_norm(ttnet_plan *plan, const float *mean3, const float *std3);
 int ttnet_forward_u8(ttnet_plan *plan, int lane, const uint8_t *x_nhwc_dev, int64_t n, float *logits_dev, void *stream);
 

@@ -1,0 +1,263 @@
+"""CIFAR-10 for ``TT_FHE_XSMALL_vAlexnet``: the dataset's files, batches that live on the device, and the command
+``python -m scale_imagenet_amd.cifar``.
+
+The reference feeds this model ``cifar_transform(False)`` (utils/preprocess.py:82-87): ``ToTensor`` and
+``Normalize(CIFAR_MEAN, CIFAR_STD)``, nothing else -- no decoding, resizing or cropping.  So the images stay what the
+dataset holds, bytes: ``read_cifar10`` transposes the files' planar CHW records to HWC once on the host,
+``device_batches`` uploads the whole split once (30 MB for the test set) and hands out slices of it, and
+``model.forward_u8`` normalises inside the stem kernel (include/ttnet.h: ttnet_forward_u8).  ``evaluate`` sends uint8
+tensors there by itself.
+
+Both published layouts are read: ``cifar-10-batches-py`` (pickles ``test_batch`` / ``data_batch_1..5``, ``batches.meta``)
+and ``cifar-10-batches-bin`` (``*.bin`` records of 1 label byte + 3072 planar bytes, ``batches.meta.txt``).  The pickles go
+through a restricted unpickler: a dataset file cannot name a callable other than numpy's array reconstruction.
+Nothing is parsed, created or written at import time.
+"""
+from __future__ import annotations
+
+import argparse
+import io
+import os
+import pickle
+import sys
+from typing import Iterator, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+# cifar_transform, utils/preprocess.py:82-87 (the defaults of a vAlexnet plan, include/ttnet.h)
+CIFAR_MEAN = (0.4914, 0.4822, 0.4465)
+CIFAR_STD = (0.2023, 0.1994, 0.2010)
+N_CLASSES = 10
+RECORD_BYTES = 1 + 3072                       # cifar-10-batches-bin: label, then 1024 R, 1024 G, 1024 B bytes
+LAYOUT_DIRS = ("cifar-10-batches-py", "cifar-10-batches-bin")
+SPLIT_FILES = {"test": ["test_batch"], "train": [f"data_batch_{i}" for i in range(1, 6)]}
+
+
+def _numpy_globals():
+    """The globals a pickled numpy array names: ``_reconstruct`` (under numpy.core or numpy._core, by the numpy that wrote
+    the file), ``ndarray``, ``dtype``, and ``_codecs.encode``, through which Python 3 writes an array's bytes at pickle
+    protocol 2 (it turns a str into bytes and does nothing else).  Resolved here, never imported by name from the file."""
+    import _codecs
+    reconstruct = np.zeros(0, dtype=np.uint8).__reduce__()[0]
+    return {("numpy.core.multiarray", "_reconstruct"): reconstruct, ("numpy._core.multiarray", "_reconstruct"): reconstruct,
+            ("numpy", "ndarray"): np.ndarray, ("numpy", "dtype"): np.dtype, ("_codecs", "encode"): _codecs.encode}
+
+
+class RefusedGlobal(pickle.UnpicklingError):
+    """A dataset pickle named a global that a CIFAR file has no use for."""
+
+
+class _ArrayUnpickler(pickle.Unpickler):
+    """Unpickles containers, numbers, strings and numpy arrays; any other global is refused."""
+
+    def __init__(self, f, name: str):
+        super().__init__(f, encoding="bytes")
+        self._name = name
+        self._allowed = _numpy_globals()
+
+    def find_class(self, module, name):
+        try:
+            return self._allowed[(module, name)]
+        except KeyError:
+            raise RefusedGlobal(f"{self._name}: the pickle names the global {module}.{name}; a CIFAR file holds only lists, "
+                                "numbers, strings and numpy arrays, so it is refused") from None
+
+
+def load_pickle(path: str):
+    """A dataset pickle through the restricted unpickler (keys come back as bytes, as the files have them)."""
+    with open(path, "rb") as f:
+        data = f.read()
+    try:
+        return _ArrayUnpickler(io.BytesIO(data), path).load()
+    except RefusedGlobal:
+        raise
+    except Exception as e:                                  # (a truncated or foreign file)
+        raise ValueError(f"{path}: not a readable pickle ({type(e).__name__}: {e})") from e
+
+
+def _dataset_dir(path: str, names: Sequence[str]) -> str:
+    """``path`` itself or the one published directory under it that holds any of ``names``."""
+    tried = [path] + [os.path.join(path, d) for d in LAYOUT_DIRS]
+    for d in tried:
+        if any(os.path.isfile(os.path.join(d, n)) for n in names):
+            return d
+    raise FileNotFoundError(f"{path}: none of {', '.join(names)} here or under {' / '.join(LAYOUT_DIRS)}")
+
+
+def _check_labels(labels: np.ndarray, n: int, file: str) -> np.ndarray:
+    if labels.shape != (n,):
+        raise ValueError(f"{file}: {labels.size} labels for {n} images")
+    if n and (labels.min() < 0 or labels.max() >= N_CLASSES):
+        bad = int(labels[(labels < 0) | (labels >= N_CLASSES)][0])
+        raise ValueError(f"{file}: label {bad} is outside [0, {N_CLASSES - 1}]")
+    return labels.astype(np.int64)
+
+
+def _read_py(file: str) -> Tuple[np.ndarray, np.ndarray]:
+    d = load_pickle(file)
+    if not isinstance(d, dict) or b"data" not in d or b"labels" not in d:
+        raise ValueError(f"{file}: expected a dict with b'data' and b'labels'")
+    data = d[b"data"]
+    if not isinstance(data, np.ndarray) or data.dtype != np.uint8 or data.ndim != 2 or data.shape[1] != 3072:
+        what = f"{data.dtype} {tuple(data.shape)}" if isinstance(data, np.ndarray) else type(data).__name__
+        raise ValueError(f"{file}: b'data' must be uint8 [N, 3072], got {what}")
+    return data, _check_labels(np.asarray(d[b"labels"], dtype=np.int64).reshape(-1), data.shape[0], file)
+
+
+def _read_bin(file: str) -> Tuple[np.ndarray, np.ndarray]:
+    raw = np.fromfile(file, dtype=np.uint8)
+    if raw.size % RECORD_BYTES:
+        raise ValueError(f"{file}: {raw.size} bytes is not a whole number of {RECORD_BYTES}-byte records "
+                         f"({raw.size % RECORD_BYTES} left over)")
+    rec = raw.reshape(-1, RECORD_BYTES)
+    return rec[:, 1:], _check_labels(rec[:, 0].astype(np.int64), rec.shape[0], file)
+
+
+def read_cifar10(path: str, split: str = "test") -> Tuple[np.ndarray, np.ndarray]:
+    """``(uint8 [N, 32, 32, 3], int64 [N])`` of ``split`` ("test" or "train") from ``path``: a ``cifar-10-batches-py`` or
+    ``cifar-10-batches-bin`` directory, or the directory that holds one.  The train split is ``data_batch_1``, ``_2``, ..
+    in order, as many as are there without a gap.  Pixel ``[r, q, c]`` is byte ``c * 1024 + r * 32 + q`` of its record."""
+    if split not in SPLIT_FILES:
+        raise ValueError(f"split must be \"test\" or \"train\", got {split!r}")
+    stems = SPLIT_FILES[split]
+    d = _dataset_dir(path, [s + ext for s in stems for ext in ("", ".bin")])
+    binary = not os.path.isfile(os.path.join(d, stems[0]))
+    files = [os.path.join(d, s + (".bin" if binary else "")) for s in stems]
+    if not os.path.isfile(files[0]):
+        raise FileNotFoundError(f"{files[0]}: the {split} split starts with this file")
+    present = [os.path.isfile(f) for f in files]
+    count = present.index(False) if False in present else len(files)
+    if any(present[count:]):
+        raise FileNotFoundError(f"{files[count]}: missing, but a later batch of the {split} split is there")
+    parts = [(_read_bin if binary else _read_py)(f) for f in files[:count]]
+    planar = np.concatenate([p[0] for p in parts])
+    images = np.ascontiguousarray(planar.reshape(-1, 3, 32, 32).transpose(0, 2, 3, 1))     # CHW -> HWC, once
+    return images, np.concatenate([p[1] for p in parts])
+
+
+def read_label_names(path: str) -> List[str]:
+    """The ten class names from ``batches.meta`` (pickle, ``b'label_names'``) or ``batches.meta.txt`` (one per line)."""
+    d = _dataset_dir(path, ["batches.meta", "batches.meta.txt"])
+    file = os.path.join(d, "batches.meta")
+    if os.path.isfile(file):
+        meta = load_pickle(file)
+        if not isinstance(meta, dict) or b"label_names" not in meta:
+            raise ValueError(f"{file}: expected a dict with b'label_names'")
+        names = [n.decode("utf-8") if isinstance(n, bytes) else str(n) for n in meta[b"label_names"]]
+    else:
+        from .report import read_class_names
+        file += ".txt"
+        names = read_class_names(file)
+    if len(names) != N_CLASSES:
+        raise ValueError(f"{file}: {len(names)} class names, expected {N_CLASSES}")
+    return names
+
+
+def device_batches(images, targets, batch_size: int, device) -> Iterator[Tuple["torch.Tensor", "torch.Tensor"]]:
+    """Upload ``images`` (uint8 ``[N, 32, 32, 3]``) and ``targets`` (int64 ``[N]``) to ``device`` once, then yield
+    ``(images[a:b], targets[a:b])`` in order, ``batch_size`` at a time (the last pair may be shorter): the batches
+    ``evaluate`` sends to ``model.forward_u8``.  No loader, no worker, no host copy per batch."""
+    import torch
+    if batch_size < 1:
+        raise ValueError("batch_size must be positive")
+    x = torch.as_tensor(images)
+    t = torch.as_tensor(targets)
+    if x.dtype != torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (32, 32, 3):
+        raise ValueError(f"expected uint8 images [N, 32, 32, 3], got {x.dtype} {tuple(x.shape)}")
+    if t.dtype != torch.int64 or tuple(t.shape) != (x.shape[0],):
+        raise ValueError(f"expected int64 targets [{x.shape[0]}], got {t.dtype} {tuple(t.shape)}")
+    x, t = x.contiguous().to(device), t.to(device)
+    for a in range(0, x.shape[0], batch_size):
+        yield x[a:a + batch_size], t[a:a + batch_size]
+
+
+# ---- python -m scale_imagenet_amd.cifar ------------------------------------------------------------------------------
+
+def build_parser() -> argparse.ArgumentParser:
+    from .main import add_topk_flags
+    p = argparse.ArgumentParser(
+        prog="python -m scale_imagenet_amd.cifar",
+        description="Evaluate a CIFAR-10 split with TT_FHE_XSMALL_vAlexnet on the HIP path and print the reference's final "
+                    "line, `Acc.. <top-1> <top-5>`.  The split is uploaded once as bytes and normalised inside the stem kernel.",
+        epilog="No trained checkpoint is published with the reference for this model; --synthetic-ckpt runs the command on "
+               "deterministic synthetic weights (the accuracy is then that of chance).")
+    p.add_argument("--data_dir", type=str, default="./../datasets/", help="cifar-10-batches-py or cifar-10-batches-bin, or the "
+                   "directory that holds one of them")
+    p.add_argument("--split", choices=sorted(SPLIT_FILES), default="test")
+    p.add_argument("--ckpt", type=str, default=None,
+                   help="checkpoint with a 'model_state_dict' entry, bare or 'module.'-prefixed keys (default ./ckpt/last.pth)")
+    p.add_argument("--synthetic-ckpt", action="store_true",
+                   help="use synth.synth_state_dict's deterministic weights instead of a trained checkpoint; when --ckpt names "
+                        "a file that does not exist yet, the synthetic checkpoint is written there first")
+    p.add_argument("--eval_batch_size", type=int, default=256)
+    p.add_argument("--inflight", type=int, default=2, help="batches in flight on separate streams / lanes")
+    p.add_argument("--gpu", type=int, default=None, help="GPU id to use (default 0)")
+    out = p.add_argument_group("per-image and per-class results (stdout is unchanged)")
+    add_topk_flags(out, 0)
+    out.add_argument("--predictions", type=str, default=None, metavar="FILE",
+                     help="CSV path,target,class_1,logprob_1,.. of every image in dataset order, path = <split>/<index> "
+                          "(--topk, default 5 here)")
+    out.add_argument("--per_class", type=str, default=None, metavar="FILE", help="CSV class,images,hits1,hits5,predicted,acc1,acc5")
+    out.add_argument("--confusion", type=str, default=None, metavar="FILE",
+                     help=".npy, int64 [10][10] indexed [target][top-1 class]")
+    return p
+
+
+def _class_names(args) -> Optional[List[str]]:
+    """--classes FILE, else the dataset's own batches.meta when it is there."""
+    from . import report
+    if args.classes:
+        return report.read_class_names(args.classes)
+    try:
+        return read_label_names(args.data_dir)
+    except FileNotFoundError:
+        return None
+
+
+def run(args) -> int:
+    import torch
+
+    from . import report, ttnet
+    from .evaluate import evaluate
+    from .main import _check_ckpt, _state_dict
+    if not os.path.isdir(args.data_dir):
+        raise SystemExit(f"--data_dir: {args.data_dir} is not a directory")
+    _check_ckpt(args)
+    if args.eval_batch_size < 1:
+        raise SystemExit("--eval_batch_size must be positive")
+    images, targets = read_cifar10(args.data_dir, args.split)
+    if not torch.cuda.is_available():
+        raise SystemExit("scale_imagenet_amd.cifar needs a HIP device (the product has no CPU path)")
+    device = torch.device("cuda", args.gpu or 0)
+    torch.cuda.set_device(device)
+    model = ttnet.TT_FHE_XSMALL_vAlexnet(argparse.Namespace(nfilter=8, tfilter=8, layers=1, groups=[1, None, 4, None]))
+    model.load_state_dict(_state_dict(args, model.spec, 0), strict=True)
+    model = model.to(device).eval().reserve(args.eval_batch_size)
+    extra = {}
+    if args.topk or args.predictions or args.per_class or args.confusion:
+        extra = dict(topk=args.topk, per_class=bool(args.per_class or args.confusion), confusion=bool(args.confusion))
+    res = evaluate(model, device_batches(images, targets, args.eval_batch_size, device), device, inflight=max(1, args.inflight),
+                   metrics="device", **extra)                   # prints `Acc.. top1 top5` (main.py:284)
+    if extra:
+        names = _class_names(args)
+        if args.predictions:
+            report.write_predictions_csv(args.predictions, [f"{args.split}/{i}" for i in range(len(targets))], targets.tolist(),
+                                         res.predictions, names)
+        if args.per_class:
+            report.write_per_class_csv(args.per_class, res.per_class, names)
+        if args.confusion:
+            report.write_confusion(args.confusion, res.confusion)
+    return 0
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    from .main import check_topk
+    args = build_parser().parse_args(list(sys.argv[1:] if argv is None else argv))
+    check_topk(args, needed=bool(args.predictions))
+    if args.topk > N_CLASSES:
+        raise SystemExit(f"--topk must be in [1, {N_CLASSES}]")
+    return run(args)
+
+
+if __name__ == "__main__":
+    sys.exit(main())

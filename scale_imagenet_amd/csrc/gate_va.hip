@@ -10,6 +10,8 @@
 // activation on row-packed planes and favour clarity.  The head reuses head.hip (the 0/1
 // features are exact in the split-operand format).
 
+#include <math.h>
+
 #include "ttnet_common.h"
 
 namespace ttnet {
@@ -69,6 +71,84 @@ __global__ __launch_bounds__(640) void va_stem_kernel(const float *__restrict__ 
     out |= (uint64_t)(best >= 0.f) << px;
   }
   if (img < n) rp[((size_t)img * 64 + ch) * 10 + py] = out;
+}
+
+// stem from the dataset's bytes: uint8 [n][32][32][3] (HWC) in, the same bits out.  ToTensor + Normalize are folded in
+// (va_stem_u8_fold): a byte b of channel c is x = (b - m_c) * a_c + e_c with the integer centre m_c = round(255 mean_c),
+// a_c = 1 / (255 std_c) and the remainder e_c = (m_c - 255 mean_c) * a_c.  The centred byte b - m_c is exact in float32
+// and is what LDS holds (zero in the padding), a_c is folded into the weights, and e_c -- which only the taps inside the
+// image carry, since the padding is zero in NORMALISED space -- goes with the bias into one constant per border class
+// of the convolution output (interior, top row, left column, corner; the pooled outputs never touch the bottom or right
+// padding).  Taps are accumulated in (c, kh, kw) order as in va_stem_kernel.
+// One workgroup = 32 channels of one image: lane = (channel, half of the pooled row), wave = pooled row, so a CU holds
+// two workgroups (20 waves) where the float kernel has 10; the two halves of a row word meet through one shuffle.
+constexpr int kVaU8TabW = 0, kVaU8TabK = 64 * 27, kVaU8TabCentre = kVaU8TabK + 64 * 4, kVaU8TabElems = kVaU8TabCentre + 4;
+
+__global__ __launch_bounds__(640) void va_stem_u8_kernel(const uint8_t *__restrict__ x, const float *__restrict__ tab,
+                                                         const float *__restrict__ scale, const float *__restrict__ shift,
+                                                         uint64_t *__restrict__ rp, int n) {
+  __shared__ float img_s[3][34][34];
+  const int img = blockIdx.x >> 1, ch = ((blockIdx.x & 1) << 5) | (threadIdx.x & 31);
+  if (img >= n) return;                                              // (whole workgroups: no barrier is left behind)
+  const float centre[3] = {tab[kVaU8TabCentre], tab[kVaU8TabCentre + 1], tab[kVaU8TabCentre + 2]};
+  float wr[27];                                                      // (in flight while the image is staged)
+#pragma unroll
+  for (int i = 0; i < 27; ++i) wr[i] = tab[kVaU8TabW + i * 64 + ch];
+  const float4 kc = *(const float4 *)(tab + kVaU8TabK + ch * 4);     // interior, top, left, corner
+  const float sc = scale[ch], sh = shift[ch];
+  for (int i = threadIdx.x; i < 3 * 34 * 34; i += blockDim.x) {      // the zero border
+    const int r = (i / 34) % 34, q = i % 34;
+    if (r == 0 || r == 33 || q == 0 || q == 33) (&img_s[0][0][0])[i] = 0.f;
+  }
+  const uint32_t *src = (const uint32_t *)(x + (size_t)img * 3072);   // (4-byte aligned: checked by the plan)
+  for (int i = threadIdx.x; i < 768; i += blockDim.x) {
+    const uint32_t v = src[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int e = 4 * i + k, p = e / 3, c = e - 3 * p;
+      img_s[c][(p >> 5) + 1][(p & 31) + 1] = (float)((v >> (8 * k)) & 0xFFu) - centre[c];
+    }
+  }
+  __syncthreads();
+  const int half = (threadIdx.x >> 5) & 1, py = threadIdx.x >> 6;    // 10 waves: one pooled row each
+  uint32_t out = 0;
+  for (int j = 0; j < 5; ++j) {
+    const int px = 5 * half + j;
+    float acc[3][3];
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 3; ++dx) acc[dy][dx] = 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float patch[5][5];
+#pragma unroll
+      for (int r = 0; r < 5; ++r)
+#pragma unroll
+        for (int q = 0; q < 5; ++q) patch[r][q] = img_s[c][3 * py + r][3 * px + q];
+#pragma unroll
+      for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw)
+#pragma unroll
+          for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx)
+              acc[dy][dx] = fmaf(patch[dy + kh][dx + kw], wr[(c * 3 + kh) * 3 + kw], acc[dy][dx]);
+    }
+    float best = -INFINITY;
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 3; ++dx) {
+        const bool top = dy == 0 && py == 0, left = dx == 0 && px == 0;
+        const float b = top ? (left ? kc.w : kc.y) : (left ? kc.z : kc.x);
+        best = fmaxf(best, fmaf(fmaxf(acc[dy][dx] + b, 0.f), sc, sh));   // ReLU, eval BatchNorm, MaxPool2d(3)
+      }
+    out |= (uint32_t)(best >= 0.f) << px;
+  }
+  out |= (uint32_t)__shfl_xor((int)out, 32);                         // columns 0..4 and 5..9 of the row word
+  if (half == 0) rp[((size_t)img * 64 + ch) * 10 + py] = out;
 }
 
 // Block_conv1 / Block_conv2 / out4: thread = (image, channel, output row of the 11x11 plane).
@@ -173,7 +253,51 @@ int va_stem_kernel_arg_sizes(const int **sizes) {
   return S::n;
 }
 
-int launch_va_block(const uint64_t *x_rp, const void *t1, const void *t2, const void *t3, uint64_t *y, int n, hipStream_t s) {
+size_t va_stem_u8_table_elems() { return kVaU8TabElems; }
+
+// The table of va_stem_u8_kernel, in float64 from the stem's weights [64][3][3][3], its bias and the normalisation
+// constants: weights times a_c as [27 taps][64 channels], the four border-class constants per channel, the integer centres.  (A centre is kept
+// inside [0, 255]: b - m_c stays exact whatever mean is given, the remainder e_c takes the rest.)
+void va_stem_u8_fold(const float *w, const float *bias, const float *mean3, const float *std3, float *tab) {
+  double a[3], e[3];
+  for (int c = 0; c < 3; ++c) {
+    const double m255 = 255.0 * (double)mean3[c];
+    const double centre = std::min(255.0, std::max(0.0, nearbyint(m255)));
+    a[c] = 1.0 / (255.0 * (double)std3[c]);
+    e[c] = (centre - m255) * a[c];
+    tab[kVaU8TabCentre + c] = (float)centre;
+  }
+  tab[kVaU8TabCentre + 3] = 0.f;
+  for (int ch = 0; ch < 64; ++ch) {
+    double k[4] = {(double)bias[ch], (double)bias[ch], (double)bias[ch], (double)bias[ch]};
+    for (int c = 0; c < 3; ++c)
+      for (int kh = 0; kh < 3; ++kh)
+        for (int kw = 0; kw < 3; ++kw) {
+          const int i = (c * 3 + kh) * 3 + kw;
+          const double wv = (double)w[ch * 27 + i];
+          tab[kVaU8TabW + i * 64 + ch] = (float)(wv * a[c]);       // [tap][channel]: a wave's loads are contiguous
+          // class bit 0: the output is in convolution row 0 (tap row kh = 0 is padding); bit 1: column 0 (kw = 0 is)
+          for (int cls = 0; cls < 4; ++cls)
+            if (!((cls & 1) && kh == 0) && !((cls & 2) && kw == 0)) k[cls] += wv * e[c];
+        }
+    for (int cls = 0; cls < 4; ++cls) tab[kVaU8TabK + ch * 4 + cls] = (float)k[cls];
+  }
+}
+
+int launch_va_stem_u8(const uint8_t *x, const float *tab, const float *scale, const float *shift, uint64_t *rp, int n,
+                      hipStream_t s) {
+  hipLaunchKernelGGL(va_stem_u8_kernel, dim3(2 * (unsigned)n), dim3(640), 0, s, x, tab, scale, shift, rp, n);
+  TT_HIP(hipGetLastError());
+  return TTNET_OK;
+}
+
+int va_stem_u8_kernel_arg_sizes(const int **sizes) {
+  using S = KernelArgSizes<decltype(&va_stem_u8_kernel)>;
+  *sizes = S::sizes;
+  return S::n;
+}
+
+int launch_va_block(const uint64_t *x_rp,const void *t1, const void *t2, const void *t3, uint64_t *y, int n, hipStream_t s) {
   size_t t = (size_t)n * 64 * 11;
   hipLaunchKernelGGL(va_dw_kernel, dim3((unsigned)((t + 127) / 128)), dim3(128), 0, s, x_rp, (const uint32_t *)t1,
                      (const uint32_t *)t2, y, n);

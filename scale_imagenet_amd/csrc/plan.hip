@@ -113,6 +113,7 @@ struct ttnet_plan {
   uint32_t *tap = nullptr;          // fused path: branch dwords of a non-last block, filled on demand by ttnet_read_stage
   size_t tap_elems = 0;
   float *va_scale = nullptr, *va_shift = nullptr;   // vAlexnet stem BatchNorm folded
+  float *va_u8_tab = nullptr;       // vAlexnet, uint8 input: folded weights, border-class constants, centres (va_stem_u8_fold)
   size_t full_fix_cap = 0;          // full variant: list entries of Lane::full_fix
   float *full_gel = nullptr;        // full variant: GELU tables of the fast kernels (launch_full_gelu_tables), shared by all lanes
 
@@ -122,7 +123,8 @@ struct ttnet_plan {
   uint32_t *norm_tab = nullptr;     // uint8 input: centres and border corrections (stem_split_weights_u8)
   uint16_t *stem_wt_u8 = nullptr;   // uint8 input: split weights with the normalisation folded in
   float *stem_init_u8 = nullptr;
-  float in_mean[3] = {0.485f, 0.456f, 0.406f}, in_std[3] = {0.229f, 0.224f, 0.225f};   // utils/preprocess.py:107-108
+  // Normalize of the uint8 input: utils/preprocess.py:107-108 (ImageNet); a vAlexnet plan starts from the CIFAR ones
+  float in_mean[3] = {0.485f, 0.456f, 0.406f}, in_std[3] = {0.229f, 0.224f, 0.225f};
   // head
   float *w1p = nullptr;             // scratch for the permuted lin1 weights (finalize only)
   uint16_t *w1f = nullptr;          // lin1 weights, two fp16 planes in fragment order
@@ -305,6 +307,9 @@ int build_geometry_valexnet(ttnet_plan *pl) {
   pl->p = 64;
   pl->n_classes = 10; pl->inter = 100; pl->fcsize = 256 * 11 * 11;
   pl->head = "features.7";
+  const float mean[3] = {0.4914f, 0.4822f, 0.4465f}, std[3] = {0.2023f, 0.1994f, 0.2010f};   // cifar_transform, utils/preprocess.py:82-87
+  std::copy(mean, mean + 3, pl->in_mean);
+  std::copy(std, std + 3, pl->in_std);
   for (const char *pre : {"VGG_Model16_0", "features.0"}) {      // one conv module registered under two names
     add_tensor(pl, std::string(pre) + ".weight", {64, 3, 3, 3}, TTNET_F32, std::string(pre) == "features.0");
     add_tensor(pl, std::string(pre) + ".bias", {64}, TTNET_F32, std::string(pre) == "features.0");
@@ -544,6 +549,7 @@ int allocate(ttnet_plan *pl) {
   if (valexnet) {
     TT_TRY(dev_alloc(pl, &pl->va_scale, 64, false));
     TT_TRY(dev_alloc(pl, &pl->va_shift, 64, false));
+    TT_TRY(dev_alloc(pl, &pl->va_u8_tab, va_stem_u8_table_elems(), true));
   } else {
     TT_TRY(dev_alloc(pl, &pl->stem_wt, stem_split_weights_elems(), false));
     TT_TRY(dev_alloc(pl, &pl->stem_init, 64, false));
@@ -637,6 +643,18 @@ int prepare_stem_u8(ttnet_plan *pl) {
   TT_HIP(hipMemcpy(pl->stem_wt_u8, wf.data(), wf.size() * 2, hipMemcpyHostToDevice));
   TT_HIP(hipMemcpy(pl->stem_init_u8, init, sizeof(init), hipMemcpyHostToDevice));
   TT_HIP(hipMemcpy(pl->norm_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+  return TTNET_OK;
+}
+
+// vAlexnet, uint8 input: the stem's weights and bias with ToTensor + Normalize folded in, one constant per border class
+// (gate_va.hip).  From the loaded tensors and the plan's mean / std: at finalize and again whenever
+// ttnet_plan_set_input_norm changes them.
+int prepare_va_stem_u8(ttnet_plan *pl) {
+  std::vector<float> w, b, tab(va_stem_u8_table_elems());
+  TT_TRY(fetch(pl->tensors["features.0.weight"], w));
+  TT_TRY(fetch(pl->tensors["features.0.bias"], b));
+  va_stem_u8_fold(w.data(), b.data(), pl->in_mean, pl->in_std, tab.data());
+  TT_HIP(hipMemcpy(pl->va_u8_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
   return TTNET_OK;
 }
 
@@ -1118,14 +1136,14 @@ int usage_lane(ttnet_plan *pl, const char *who, int lane, const ttnet_plan::Lane
 int forward_eager(ttnet_plan *pl, ttnet_plan::Lane &L, const void *x_dev, bool u8, int64_t n, float *logits_dev, hipStream_t s) {
   pl->timing_used = 0;
   if (pl->path == GatePath::VAlexnet) {
-    if (u8) {
-      set_error("uint8 input is not implemented for the vAlexnet variant");
-      return TTNET_E_UNSUPPORTED;
-    }
-    TT_TIMED(pl, "va.stem", s,
-             launch_va_stem((const float *)x_dev, (const float *)pl->tensors["features.0.weight"].dev,
-                            (const float *)pl->tensors["features.0.bias"].dev, pl->va_scale, pl->va_shift, L.x_rp[0],
-                            (int)n, s));
+    if (u8)
+      TT_TIMED(pl, "va.stem_u8", s,
+               launch_va_stem_u8((const uint8_t *)x_dev, pl->va_u8_tab, pl->va_scale, pl->va_shift, L.x_rp[0], (int)n, s));
+    else
+      TT_TIMED(pl, "va.stem", s,
+               launch_va_stem((const float *)x_dev, (const float *)pl->tensors["features.0.weight"].dev,
+                              (const float *)pl->tensors["features.0.bias"].dev, pl->va_scale, pl->va_shift, L.x_rp[0],
+                              (int)n, s));
   } else {
     TT_TIMED(pl, "stem", s,
              launch_stem(x_dev, u8, pl->norm_tab, u8 ? pl->stem_wt_u8 : pl->stem_wt, u8 ? pl->stem_init_u8 : pl->stem_init, L.x_rp[0],
@@ -1235,7 +1253,10 @@ bool capture_forward(ttnet_plan *pl, ttnet_plan::Lane &L, const void *x_dev, boo
     if (hipGraphNodeGetDependentNodes(node, &next, &nd) != hipSuccess) return false;
     node = next;
   }
-  if (first == node || !own_params(first, pl->path == GatePath::VAlexnet ? va_stem_kernel_arg_sizes : stem_kernel_arg_sizes, e.first) ||
+  // the first kernel of the chain, by (path, input kind): its argument 0 is the input
+  int (*const first_sizes)(const int **) =
+      pl->path != GatePath::VAlexnet ? stem_kernel_arg_sizes : u8 ? va_stem_u8_kernel_arg_sizes : va_stem_kernel_arg_sizes;
+  if (first == node || !own_params(first, first_sizes, e.first) ||
       !own_params(node, lin2_kernel_arg_sizes, e.last))
     return false;
   // the two slots that will be patched must hold exactly the pointers this capture ran with
@@ -1252,7 +1273,7 @@ int forward_impl(ttnet_plan *pl, int lane, const void *x_dev, bool u8, int64_t n
   // The input contract of ttnet.h (16-byte aligned float32, 4-byte aligned uint8: the stem reads it with 16 / 12-byte
   // buffer loads) is checked HERE, in front of the replay, the capture and the plain path alike: a cached graph
   // only has its first argument re-pointed and would otherwise take any pointer.
-  if (pl->path != GatePath::VAlexnet && ((uintptr_t)x_dev & (u8 ? 3u : 15u)) != 0) {
+  if ((pl->path != GatePath::VAlexnet || u8) && ((uintptr_t)x_dev & (u8 ? 3u : 15u)) != 0) {
     set_error("forward: the input must be %d-byte aligned", u8 ? 4 : 16);
     return TTNET_E_INVALID;
   }
@@ -1406,6 +1427,7 @@ int ttnet_plan_finalize(ttnet_plan *pl, void *stream) {
     TT_TRY(fold_bn(pl, "features.2", sc, sh));
     TT_TRY(upload_f32(pl->va_scale, sc));
     TT_TRY(upload_f32(pl->va_shift, sh));
+    TT_TRY(prepare_va_stem_u8(pl));
   } else {
     TT_TRY(prepare_stem(pl));
     TT_TRY(prepare_stem_u8(pl));
@@ -1659,22 +1681,22 @@ int ttnet_forward_u8(ttnet_plan *pl, int lane, const uint8_t *x_nhwc_dev, int64_
 }
 
 int ttnet_plan_set_input_norm(ttnet_plan *pl, const float *mean3, const float *std3) {
-  if (!pl || !mean3 || !std3 || pl->path == GatePath::VAlexnet) {
-    set_error("set_input_norm: null argument (or the vAlexnet variant, which has no uint8 path)");
+  if (!pl || !mean3 || !std3) {
+    set_error("set_input_norm: null argument");
     return TTNET_E_INVALID;
   }
-  for (int c = 0; c < 3; ++c) {
-    if (!(std3[c] > 0.f)) {
+  for (int c = 0; c < 3; ++c)
+    if (!(std3[c] > 0.f)) {                            // (refused whole: the plan keeps the constants it had)
       set_error("set_input_norm: std[%d] = %g", c, (double)std3[c]);
       return TTNET_E_INVALID;
     }
-    pl->in_mean[c] = mean3[c];
-    pl->in_std[c] = std3[c];
-  }
+  std::copy(mean3, mean3 + 3, pl->in_mean);
+  std::copy(std3, std3 + 3, pl->in_std);
   (void)hipSetDevice(pl->device);
+  TT_TRY(invalidate_graphs(pl));                       // as for a new tensor: what was captured ran with the old constants
   if (!pl->finalized) return TTNET_OK;                 // (finalize folds them into the uint8 stem's weights)
   TT_HIP(hipDeviceSynchronize());                      // no forward may be reading the buffers that are rewritten in place
-  return prepare_stem_u8(pl);
+  return pl->path == GatePath::VAlexnet ? prepare_va_stem_u8(pl) : prepare_stem_u8(pl);
 }
 
 int ttnet_forward_from_stem_bits(ttnet_plan *pl, const uint64_t *rows_dev, int64_t n, float *logits_dev,

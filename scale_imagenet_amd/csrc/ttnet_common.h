@@ -92,7 +92,8 @@ inline void table_entry(const BlockGeom &g, void *raw, int grp, uint32_t idx, vo
 
 // Byte sizes of a kernel's arguments, from its signature: KernelArgSizes<decltype(&kernel)>.  plan.hip re-points
 // arguments of captured graph nodes and must own a copy of every argument of those kernels; the files that define them
-// export their sizes through this (stem_kernel_arg_sizes, va_stem_kernel_arg_sizes, lin2_kernel_arg_sizes).
+// export their sizes through this (stem_kernel_arg_sizes, va_stem_kernel_arg_sizes, va_stem_u8_kernel_arg_sizes,
+// lin2_kernel_arg_sizes).
 template <typename F>
 struct KernelArgSizes;
 template <typename... A>
@@ -364,6 +365,13 @@ int launch_full_pool_split(const float *x, void *feat_frag, int n, int C, int H,
 int launch_va_stem(const float *x, const float *w, const float *bias, const float *scale, const float *shift,
                    uint64_t *rp, int n, hipStream_t s);
 int va_stem_kernel_arg_sizes(const int **sizes);      // va_stem_kernel's, as stem_kernel_arg_sizes
+// uint8 HWC input [n][32][32][3] (4-byte aligned): ToTensor + Normalize folded into the table that va_stem_u8_fold builds
+// on the host from the stem's weights [64][3][3][3], its bias and mean / std (va_stem_u8_table_elems() floats)
+int launch_va_stem_u8(const uint8_t *x, const float *tab, const float *scale, const float *shift, uint64_t *rp, int n,
+                      hipStream_t s);
+int va_stem_u8_kernel_arg_sizes(const int **sizes);   // va_stem_u8_kernel's, as stem_kernel_arg_sizes
+size_t va_stem_u8_table_elems();
+void va_stem_u8_fold(const float *w, const float *bias, const float *mean3, const float *std3, float *tab);
 int launch_va_block(const uint64_t *x_rp, const void *t1, const void *t2, const void *t3, uint64_t *y, int n, hipStream_t s);
 int launch_va_feat(const uint64_t *y, void *feat_frag, int n, hipStream_t s);
 int launch_va_frag_to_flat(const void *af, float *out, int n, hipStream_t s);

@@ -3,7 +3,7 @@
 Reproduces the reference's metric definitions -- cross-entropy loss, top-1 / top-5 running
 means weighted by batch size (utils/bar_show.py:110-148), the final ``Acc..`` line
 (main.py:284) -- around the forward.  The whole input pipeline is in scope: a batch may be a
-float tensor (``model(x)``), the decoder's uint8 crops (``model.forward_u8``), decoded images of
+float tensor (``model(x)``), uint8 HWC images of the model's input size (``model.forward_u8``), decoded images of
 mixed sizes (``RaggedU8`` -> ``preprocess.imgnet_eval_forward``) or compressed files
 (``RaggedJpeg`` -> ``jpeg.jpeg_eval_forward``); ``forward=`` overrides the choice.  TensorBoard
 and the terminal progress bar of the reference stay out of scope.
@@ -472,8 +472,8 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
     order of accumulation.
 
     A batch is ``(inputs, targets)``; ``inputs`` is moved with ``.to(device, non_blocking=True)`` on the lane's
-    stream and its type selects the forward: float tensor -> ``model(x)``; uint8 ``[n,224,224,3]`` ->
-    ``model.forward_u8``; ``RaggedU8`` -> ``preprocess.imgnet_eval_forward``; ``RaggedJpeg`` ->
+    stream and its type selects the forward: float tensor -> ``model(x)``; uint8 ``[n,H,W,3]`` at the model's input size
+    (224 x 224 crops; the 32 x 32 CIFAR bytes of ``cifar.device_batches`` for the vAlexnet model) -> ``model.forward_u8``; ``RaggedU8`` -> ``preprocess.imgnet_eval_forward``; ``RaggedJpeg`` ->
     ``jpeg.jpeg_eval_forward``.  ``forward(model, inputs, lane)`` replaces that choice.  After the loop the sticky
     error counts of the pipeline are checked (``check_range``, and ``check_ragged`` / ``check_jpeg`` when such
     batches were seen): a corrupt file or an overflow raises instead of returning metrics.

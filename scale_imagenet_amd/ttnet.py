@@ -330,8 +330,8 @@ class _TTNetBase(nn.Module):
         return out
 
     def forward_u8(self, x_u8: torch.Tensor, lane: int = 0) -> torch.Tensor:
-        """Forward from the decoder's uint8 HWC images ``[N,H,W,3]``: ToTensor + Normalize
-        (utils/preprocess.py:104-108) are applied inside the stem kernel."""
+        """Forward from uint8 HWC images ``[N,H,W,3]`` (the decoder's crops; the CIFAR bytes for the vAlexnet model):
+        ToTensor + Normalize (utils/preprocess.py:104-108, :82-87) are applied inside the stem kernel."""
         if self.training:
             raise RuntimeError("the HIP path implements eval-mode inference only: call model.eval()")
         h, w = self.spec.image_hw
@@ -384,7 +384,8 @@ class _TTNetBase(nn.Module):
         return out
 
     def set_input_norm(self, mean, std):
-        """Normalisation constants of ``forward_u8`` (default: the ImageNet ones)."""
+        """Normalisation constants of ``forward_u8`` (default: the ImageNet ones; the CIFAR ones, ``cifar.CIFAR_MEAN`` /
+        ``cifar.CIFAR_STD``, for the vAlexnet model)."""
         self.__dict__["_input_norm"] = (tuple(float(v) for v in mean), tuple(float(v) for v in std))
         for plan in self._plans.values():
             self._apply_input_norm(plan)
