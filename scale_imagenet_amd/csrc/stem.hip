@@ -45,8 +45,9 @@
 //
 // Bound: 16-bit MFMA (2.5 PFLOP/s dense) at 3 MFMA flops per algorithmic flop (3.6 with the slot / row
 // padding) at the clock the chip holds under this load, beside the HBM stream of the float32 input;
-// 29.5 MMAC/image.  The kernel is power-limited: all-zero input runs the same cycles at 1.93 instead of
-// 1.52 GHz.
+// 29.5 MMAC/image.  On 256 workgroups the kernel is power-limited: all-zero input runs the same cycles at 1.93 instead of
+// 1.52 GHz.  On 128 (plans with batches in flight) it is not: 2.3 GHz, 9,500 cycles per item against the 7,392 of the
+// matrix pipe; what fills the difference, and the hand-off and the producer priority chosen from it, are in DESIGN.md 4.
 
 #include <math.h>
 #include <string.h>
@@ -71,9 +72,10 @@ constexpr int LROWS = 64;                // rows a copy holds: the tile's 63 and
 constexpr int COPY_DW = LROWS * PITCH + 32;  // one copy of a plane; the +32 puts copy 1 thirty-two banks from copy 0
 constexpr int NPL = SPLIT_PLANES;       // fp16 planes per operand
 constexpr int PLANE_DW = 2 * COPY_DW;   // [copy 0: dword j = pixels (2j, 2j+1)][copy 1: dword j = copy 0's dword j+1]
-constexpr int TILE_DW = NPL * PLANE_DW; // dwords per tile buffer (60,928 B)
+constexpr int TILE_DW = NPL * PLANE_DW; // dwords per tile buffer (61,952 B)
 constexpr int KSTEPS = 11;              // 22 (c,kh) rows (21 + one repeated with zero weights), two per MFMA
 constexpr int NT = SR * 56 / 32;        // 14 N-tiles of 32 pixels
+constexpr int NSTAGE = 3;               // stage buffers of row-word pieces: written (item j), completed late (j-1), read (j-2)
 constexpr float X_PRESCALE = ACT_PRESCALE;
 
 // Diagnostic builds only (tools/ubench/stem_parts.hip): parts of the kernel switched off, in-kernel stamps.
@@ -89,7 +91,13 @@ constexpr float X_PRESCALE = ACT_PRESCALE;
 #define TT_STEM_PKCVT 0
 #endif
 #ifndef TT_STEM_PRIO
-#define TT_STEM_PRIO 2
+#define TT_STEM_PRIO 0            /* float32 input: > 0 raises the producer waves, < 0 the consumer waves.  The producers finish a tile
+                                     well inside a period (3,000 of 10,500 cycles early at priority 2), so at priority 2 they only took
+                                     vector issue from the MFMA waves: 0 takes 5 % off the kernel on 128 workgroups and 3 % on 256
+                                     (profiles/r05a_stem_half_chip.txt) */
+#endif
+#ifndef TT_STEM_PRIO_U8
+#define TT_STEM_PRIO_U8 2         /* uint8 input (two products per k-step, shorter periods): as it was measured */
 #endif
 constexpr int kStemSkip = TT_STEM_SKIP;   // 1 no global loads, 2 no split, 4 no MFMA, 8 no fragment reads, 16 no epilogue, 32 no row words, 64 no tile stores
 #ifdef TT_STEM_STAMP
@@ -98,11 +106,19 @@ constexpr int kStemSkip = TT_STEM_SKIP;   // 1 no global loads, 2 no split, 4 no
 #else
 #define TT_STEM_CLOCK() __builtin_amdgcn_s_memtime()                    /* shader cycles */
 #endif
-__device__ unsigned long long g_stem_stamps[256][2][16];
+constexpr int STAMP_SLOTS = 20, STAMP_ITEMS = 16;     // 3 + 14 items at batch 256 on 128 workgroups, and the end
+__device__ unsigned long long g_stem_stamps[256][2][STAMP_SLOTS];
 #define STEM_STAMP(role, j) \
-  do { if (lane == 0 && (wave == 0 || wave == CONS_WAVES) && (j) < 16) g_stem_stamps[blockIdx.x][role][j] = TT_STEM_CLOCK(); } while (0)
+  do { if (lane == 0 && (wave == 0 || wave == CONS_WAVES) && (j) < STAMP_SLOTS) g_stem_stamps[blockIdx.x][role][j] = TT_STEM_CLOCK(); } while (0)
+// Inside an item, consumer waves 0 (four units at MT = 2) and 4 (three, the same SIMD): k = 0 released from the barrier, 1 the
+// first fragment has landed (the first MFMA issues next), 2 the unit loop is done, 3 at the barrier.  (Reading the counter drains
+// the wave's LDS queue, so stamp 1 waits for the first three fragments, not one: it overstates by part of one LDS round trip.)
+__device__ unsigned long long g_stem_detail[256][2][STAMP_ITEMS][4];
+#define STEM_DETAIL(j, k) \
+  do { if (lane == 0 && (wave & 3) == 0 && wave < 8 && (j) < STAMP_ITEMS) g_stem_detail[blockIdx.x][wave >> 2][j][k] = TT_STEM_CLOCK(); } while (0)
 #else
 #define STEM_STAMP(role, j) do {} while (0)
+#define STEM_DETAIL(j, k) do {} while (0)
 #endif
 
 #ifndef TT_STEM_CONS
@@ -157,9 +173,9 @@ __global__ __launch_bounds__(STEM_THREADS) void stem_pc_kernel(const void *__res
   uint32_t *tiles = (uint32_t *)smem;                                              // [2][TILE_DW]
   static_assert(!CP || MT == 2, "the channel-word layout is built for p = 64");
   constexpr int CH = 32 * MT, UNITS = NT * MT;                                     // channels the kernel carries; (N-tile, M-tile) pairs of one item
-  uint32_t(*stage)[CH][NT + 2] = (uint32_t(*)[CH][NT + 2])(smem + 2 * TILE_DW * 4);   // [2][CH][NT+2]
+  uint32_t(*stage)[CH][NT + 2] = (uint32_t(*)[CH][NT + 2])(smem + 2 * TILE_DW * 4);   // [NSTAGE][CH][NT+2]
   // U8: norm_tab = [4] centres s_c (int32; the 4th unused), then the border corrections [16 classes][MT][2 halves][16 registers] float32
-  constexpr uint32_t CORR_OFF = 2 * TILE_DW * 4 + 2 * CH * (NT + 2) * 4;
+  constexpr uint32_t CORR_OFF = 2 * TILE_DW * 4 + NSTAGE * CH * (NT + 2) * 4;
   float *s_corr = (float *)(smem + CORR_OFF);
   int s_c[3] = {0, 0, 0};
   if constexpr (U8) {
@@ -179,7 +195,7 @@ __global__ __launch_bounds__(STEM_THREADS) void stem_pc_kernel(const void *__res
     const uint32_t cb = (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)init[0]);
     tiles[(threadIdx.x >> 2) * PLANE_DW + CONST_DW + (threadIdx.x & 3)] = threadIdx.x == 0 ? (cb | (cb << 16)) : 0u;
   }
-  for (int i = threadIdx.x; i < 2 * CH; i += STEM_THREADS) {
+  for (int i = threadIdx.x; i < NSTAGE * CH; i += STEM_THREADS) {
     stage[i / CH][i % CH][NT] = 0;
     stage[i / CH][i % CH][NT + 1] = 0;
   }
@@ -493,11 +509,22 @@ __global__ __launch_bounds__(STEM_THREADS) void stem_pc_kernel(const void *__res
   };
 
   // ---- pipeline --------------------------------------------------------------------------------
-  // Period j: consumers work on item j (tile buffer j&1); producers emit the row words of item
-  // j-1, split item j+1 (loaded during period j-1) into the other buffer and issue the loads of
-  // item j+2.  Each role runs its own loop with the same my_items + 2 barriers.
+  // Period j: consumers work on item j (tile buffer j&1); producers split item j+1 (loaded during
+  // period j-1) into the other buffer, issue the loads of item j+2 and emit the row words of item
+  // j-2.  Each role runs its own loop with the same my_items + 2 barriers: two before the loop, one
+  // at the end of every period, none anywhere else.
+  // Hand-off.  A consumer wave does not finish the transpose of its last unit before the barrier: it
+  // carries the sign word across it, and the five pieces ride in the MFMA gaps of the next item's first
+  // unit, as they do between the units of one item.  So the last pieces of item j-1 reach their stage
+  // buffer during period j, and the rows of an item are emitted two periods after it, not one.  Three
+  // stage buffers keep the three uses apart: in period j the consumers write stage[j % 3] (item j) and
+  // stage[(j-1) % 3] (the carried pieces), the producers read stage[(j-2) % 3], which was completed in
+  // period j-1 and is written next in period j+1; the barrier at the end of every period orders each
+  // buffer's write, late write and read.  Only a workgroup's last item, with no unit after it, still
+  // finishes its transpose in the open, before the last barrier.
+  constexpr int kPrio = U8 ? TT_STEM_PRIO_U8 : TT_STEM_PRIO;
   if (producer) {
-    if (TT_STEM_PRIO > 0) __builtin_amdgcn_s_setprio(TT_STEM_PRIO);
+    if constexpr (kPrio > 0) __builtin_amdgcn_s_setprio(kPrio);
     STEM_STAMP(1, 0);
     if (my_items > 0) {
       if constexpr (U8) u8_pass(std::false_type{}, 0, 0, tiles);
@@ -516,15 +543,16 @@ __global__ __launch_bounds__(STEM_THREADS) void stem_pc_kernel(const void *__res
         if constexpr (U8) u8_pass(std::true_type{}, j + 1, j + 2, tiles + ((j + 1) & 1) * TILE_DW);
         else f32_pass(std::true_type{}, j + 1, j + 2, tiles + ((j + 1) & 1) * TILE_DW);
       }
-      if (j > 0) emit_rows(j - 1, stage[(j - 1) & 1]);
+      if (j > 1) emit_rows(j - 2, stage[(j - 2) % NSTAGE]);
       STEM_STAMP(1, 3 + j);
       __syncthreads();
     }
-    if (my_items > 0) emit_rows(my_items - 1, stage[(my_items - 1) & 1]);
+    if (my_items > 1) emit_rows(my_items - 2, stage[(my_items - 2) % NSTAGE]);
+    if (my_items > 0) emit_rows(my_items - 1, stage[(my_items - 1) % NSTAGE]);
     STEM_STAMP(1, 3 + my_items);
     if (out_of_range || (ovf & 0xFFFFu) >= 0x7C00u || (ovf >> 16) >= 0x7C00u) *range_flag = 1u;
   } else {
-    if (TT_STEM_PRIO < 0) __builtin_amdgcn_s_setprio(-TT_STEM_PRIO);
+    if constexpr (kPrio < 0) __builtin_amdgcn_s_setprio(-kPrio);
     // this wave's weight fragments, [ks][plane][mtile][lane] x 16 bytes in global memory (L2)
     uint4 wreg[KSTEPS][NPL];
 #pragma unroll
@@ -538,11 +566,14 @@ __global__ __launch_bounds__(STEM_THREADS) void stem_pc_kernel(const void *__res
     // address of the constant block for the half-wave that holds the shift row (k-step 10, h = 1),
     // less that k-step's row offset, which read_frag adds as an immediate
     const uint32_t a_shift = (uint32_t)(CONST_DW * 4 - tile_row(20) * (PITCH * 4));
+    const int tlast = wave / MT + TSTEP * (nunits - 1);       // N-tile of the wave's last unit of an item
+    uint32_t pend = 0;                     // sign bits of the previous unit (of this item or of the one before), its transpose in progress
     for (int j = 0; j < my_items; ++j) {
       int n, oy0;
       item_of(j, n, oy0);
       const uint32_t buf = (uint32_t)(j & 1) * (TILE_DW * 4);
-      uint32_t (*st)[NT + 2] = stage[j & 1];
+      uint32_t (*st)[NT + 2] = stage[j % NSTAGE], (*stlast)[NT + 2] = stage[(j + NSTAGE - 1) % NSTAGE];
+      STEM_DETAIL(j, 0);
       // fragments are read two k-steps ahead, across unit boundaries
       unsigned long long q0[4] = {0, 0, 0, 0}, q1[4] = {0, 0, 0, 0};
       {
@@ -550,12 +581,13 @@ __global__ __launch_bounds__(STEM_THREADS) void stem_pc_kernel(const void *__res
         read_frag(a + hrow1, a + hrow15, a, std::integral_constant<int, 0>{}, q0);
         read_frag(a + hrow1, a + hrow15, a, std::integral_constant<int, 1>{}, q1);
       }
-      uint32_t pend = 0;                   // sign bits of the previous unit, its transpose in progress
 #pragma unroll 1
       for (int i = 0; i < nunits; ++i) {
         const uint32_t a = unit_addr(i) + buf, an = unit_addr(i + 1 < nunits ? i + 1 : i) + buf;
         const uint32_t a1 = a + hrow1, a15 = a + hrow15, a10 = h ? a_shift : a, an1 = an + hrow1, an15 = an + hrow15;
-        const int tprev = wave / MT + TSTEP * (i - 1);
+        // the previous unit: of this item, or (i = 0) the last one of the item before, carried across the barrier
+        const int tprev = i > 0 ? wave / MT + TSTEP * (i - 1) : tlast;
+        uint32_t (*stprev)[NT + 2] = i > 0 ? st : stlast;
         unsigned long long f[KSTEPS + 2][4];
 #pragma unroll
         for (int e = 0; e < (U8 ? 2 : 4); ++e) {
@@ -594,6 +626,11 @@ __global__ __launch_bounds__(STEM_THREADS) void stem_pc_kernel(const void *__res
             // the fragments of k-steps ks+1 and ks+2 (8 reads) may still be in flight
             if constexpr (!(kStemSkip & 8))
               asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(f[ks][0]), "+v"(f[ks][1]), "+v"(f[ks][2]), "+v"(f[ks][3]));
+#ifdef TT_STEM_STAMP
+            if constexpr (ks == 0) {
+              if (i == 0) STEM_DETAIL(j, 1);
+            }
+#endif
             const f16x8 x1 = frag(f[ks][0], f[ks][1]), x2 = frag(f[ks][2], f[ks][3]);
             if constexpr (kStemSkip & 4) {
               acc[0] += (float)x1[0] + (float)x2[1] + (float)w1[2] + (float)w2[3];
@@ -603,7 +640,7 @@ __global__ __launch_bounds__(STEM_THREADS) void stem_pc_kernel(const void *__res
               acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1, x1, acc, 0, 0, 0);
             }
           }
-          if constexpr (ks >= 1 && ks <= 5) epi_piece(std::integral_constant<int, ks - 1>{}, pend, tprev, st, i > 0);
+          if constexpr (ks >= 1 && ks <= 5) epi_piece(std::integral_constant<int, ks - 1>{}, pend, tprev, stprev, i > 0 || j > 0);
           __builtin_amdgcn_sched_barrier(0);     // reads stay two k-steps ahead of their MFMAs, no further
         });
 #pragma unroll
@@ -618,8 +655,10 @@ __global__ __launch_bounds__(STEM_THREADS) void stem_pc_kernel(const void *__res
         pend = sign_bits(acc);
         if constexpr (CP) channel_words(pend, wave / MT + TSTEP * i, n, oy0);
       }
-      // the last unit's transpose has no MFMAs to hide under
-      static_for<0, 5>([&](auto pc) { epi_piece(pc, pend, wave / MT + TSTEP * (nunits - 1), st, true); });
+      STEM_DETAIL(j, 2);
+      // only the transpose of the workgroup's very last unit has no MFMAs to hide under
+      if (j + 1 == my_items && nunits > 0) static_for<0, 5>([&](auto pc) { epi_piece(pc, pend, tlast, st, true); });
+      STEM_DETAIL(j, 3);
       STEM_STAMP(0, 3 + j);
       __syncthreads();
     }
@@ -806,11 +845,11 @@ int launch_stem(const void *x, bool x_is_u8, const uint32_t *norm_tab, const voi
     set_error("stem: the input must be %d-byte aligned", x_is_u8 ? 4 : 16);
     return TTNET_E_INVALID;
   }
-  const size_t lds = (size_t)2 * TILE_DW * 4 + (size_t)2 * 32 * MT * (NT + 2) * 4 + (x_is_u8 ? (size_t)16 * 32 * MT * 4 : 0);
+  const size_t lds = (size_t)2 * TILE_DW * 4 + (size_t)NSTAGE * 32 * MT * (NT + 2) * 4 + (x_is_u8 ? (size_t)16 * 32 * MT * 4 : 0);
   const int items = n * NBLK;
   // Persistent workgroups: one per CU when a forward has the chip to itself; HALF the CUs when the plan keeps several batches in
-  // flight.  The kernel is bound by the energy of its matrix instructions, not by per-CU throughput: on 128 CUs it holds a
-  // higher clock and takes 73 - 79 us instead of 57, and the other batch's kernels run on the other 128 meanwhile -- the forward
+  // flight.  On 256 CUs the kernel is power-limited (1.7 GHz); on 128 it holds 2.3 GHz and its time is cycles per item x 14 /
+  // clock ("on half the chip"): 64 us instead of 51, and the other batch's kernels run on the other 128 meanwhile -- the forward
   // with two batches in flight gains 5 - 7 % (profiles/r03_cache_policy.txt, same-box A/B; one batch at a time would lose 4 %; the
   // uint8 kernel, with two products, and the full variant gain nothing and keep 256: the caller decides).
   static const int grid_env = getenv("TTNET_STEM_GRID") ? atoi(getenv("TTNET_STEM_GRID")) : 0;        // (diagnostic override)
