@@ -252,6 +252,46 @@ def stem_pre64(x: np.ndarray, sd: Dict[str, np.ndarray]) -> np.ndarray:
     return out * s[None, :, None, None] + t[None, :, None, None]
 
 
+def stem_im2col(pooled: np.ndarray) -> np.ndarray:
+    """The 7x7 / stride 2 / pad 3 windows of pooled images [k,3,H,W] as rows [k * Ho * Wo, 147], k = (c, kh, kw)."""
+    xp = np.pad(pooled, ((0, 0), (0, 0), (3, 3), (3, 3)))
+    k, c, h, w = pooled.shape
+    ho, wo = (h + 6 - 7) // 2 + 1, (w + 6 - 7) // 2 + 1
+    sn, sc, sy, sx = xp.strides
+    win = np.lib.stride_tricks.as_strided(xp, (k, ho, wo, c, 7, 7), (sn, 2 * sy, 2 * sx, sc, sy, sx), writeable=False)
+    return win.reshape(k * ho * wo, c * 49)                                  # (a copy: the windows overlap)
+
+
+def stem_pre64_cond(x: np.ndarray, sd: Dict[str, np.ndarray], chunk: int = 16, cond: bool = True
+                    ) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    """(pre, E): ``stem_pre64`` by im2col and one BLAS product per ``chunk`` images, and the sum its rounding errors
+    are relative to,  E[n, ch, y, x] = sum_taps |w * scale| * |pooled x| + |shift|  (float64 both, [N,p,56,56]).
+    A split or an accumulation that keeps t significant bits of every term is off by at most ~2^-t E, whatever
+    cancels inside pre: a near-tie band that grows with the operands is a multiple of E (tests/test_stem_split_bound_cpu.py).
+    ``cond=False`` skips the second product and returns (pre, None)."""
+    x = x.astype(np.float64)
+    x = 0.25 * (x[:, :, 0::2, 0::2] + x[:, :, 0::2, 1::2] + x[:, :, 1::2, 0::2] + x[:, :, 1::2, 1::2])
+    w = sd["features.1.weight"].astype(np.float64)
+    p = w.shape[0]
+    s, t = fold_bn(sd, "features.2")
+    wt = np.ascontiguousarray(w.reshape(p, -1).T)                            # [147, p], k = (c, kh, kw)
+    wabs = np.ascontiguousarray(np.abs(w.reshape(p, -1) * s[:, None]).T)
+    n_ = x.shape[0]
+    ho, wo = (x.shape[2] + 6 - 7) // 2 + 1, (x.shape[3] + 6 - 7) // 2 + 1
+    pre = np.empty((n_, p, ho, wo))
+    E = np.empty((n_, p, ho, wo)) if cond else None
+    for i0 in range(0, n_, chunk):
+        cols = stem_im2col(x[i0:i0 + chunk])
+        k = cols.shape[0] // (ho * wo)
+        out = (cols @ wt) * s[None, :] + t[None, :]
+        pre[i0:i0 + k] = out.reshape(k, ho, wo, p).transpose(0, 3, 1, 2)
+        if cond:
+            np.abs(cols, out=cols)
+            out = cols @ wabs + np.abs(t)[None, :]
+            E[i0:i0 + k] = out.reshape(k, ho, wo, p).transpose(0, 3, 1, 2)
+    return pre, E
+
+
 # ---- packing helpers shared by the tests (layouts of include/ttnet.h) ------------------------
 
 def pack_rows(bits: np.ndarray) -> np.ndarray:
