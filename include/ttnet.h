@@ -567,6 +567,49 @@ int ttnet_minimise_covers_rounds(const uint32_t *on_dev, const uint32_t *dc_dev,
                                  uint32_t *cubes_dev, int64_t cube_cap, int32_t *counts_dev,
                                  void *work_dev, int64_t work_bytes, void *stream);
 
+/* Rule support: which cubes of a cover the data uses.  For each of n_funcs functions of n_bits inputs (1..16) it joins a
+ * cover with the lookup counts of the function's table and says what every cube carries.
+ *
+ * cubes_dev uint32 [n_funcs][cube_cap], counts_dev int32 [n_funcs]: the keys and counts of ttnet_minimise_covers, in that
+ * call's order (any list of keys will do; a cube holds pattern p iff p & mask == value).  Entries past counts[f] are never
+ * read.  A counts[f] above cube_cap cannot be refused without a host synchronisation: the caller, who knows the counts,
+ * checks it (scale_imagenet_amd.rules does); the kernel reads min(counts[f], cube_cap) cubes, a negative count as 0.
+ * keep_dev uint8 [n_funcs][cube_cap] or NULL: cube c of function f is KEPT iff keep[f][c] != 0; NULL keeps every cube.
+ * usage_dev int64 [n_usage_rows][2^n], usage_row_dev int32 [n_funcs]: function f weighs pattern p with
+ * u[p] = usage_dev[usage_row_dev[f]][p], patterns in the canonical order of ttnet_plan_get_table; several functions may
+ * share a row, as the output bits of a group do.
+ *
+ * Outputs, for function f over its kept cubes in their order (int64 [n_funcs][cube_cap]; a cube that is not kept and
+ * every entry from counts[f] on get 0 in all three):
+ *   hits[c]   the sum of u[p] over the patterns cube c holds;
+ *   first[c]  the sum of u[p] over the patterns for which c is the first kept cube that holds them (the decision-list
+ *             reading: a partition of the covered mass);
+ *   sole[c]   the sum of u[p] over the patterns that c holds and no other kept cube holds: the lookups whose output bit
+ *             changes if c alone is removed.
+ * totals_dev int64 [n_funcs][4] = {covered, lost, used_patterns, lost_patterns}: covered, the mass of the patterns held by
+ * at least one kept cube; lost, the mass of those held by a cube of the full list but by no kept cube; used_patterns, the
+ * patterns with u > 0; lost_patterns, the number of lost patterns whatever their u.  lost_bits_dev, uint32
+ * [n_funcs][max(1, 2^n / 32)] or NULL: the bitmap of the lost patterns in the format of ttnet_minimise_covers (unused
+ * high bits zero).  With keep_dev NULL nothing is lost: lost, lost_patterns and the bitmap are zero.
+ *
+ * A usage_row_dev[f] outside [0, n_usage_rows) reads nothing from usage_dev: every output of function f is zero (its
+ * hits / first / sole rows, its totals, its bitmap), and the number of such functions is left as an int64 in the first 8
+ * bytes of work_dev, which the call sets to zero before anything else; the rest of the workspace is scratch.
+ * work_dev / work_bytes: at least ttnet_cover_support_workspace(n_bits, n_funcs) bytes: 256 for that count, then 10 * 2^n
+ * bytes, rounded up to 256, for each of min(n_funcs, 1024) workgroups.
+ * A 256-byte memset and one launch on `stream`: no plan, no allocation, no host synchronisation, capturable in a graph.
+ * Integer adds only: the bytes do not depend on the launch geometry.  Every element of the six outputs is written, so the
+ * caller zeroes nothing.  TTNET_E_INVALID (nothing launched) for a NULL pointer other than keep_dev / lost_bits_dev, n_bits
+ * outside 1..16, n_funcs < 1, cube_cap outside 1..2^31-1, n_usage_rows < 0, a misaligned buffer (4 bytes for cubes,
+ * counts, rows and bitmap, 8 for the int64 buffers, 16 for the workspace) or a workspace that is too small;
+ * ttnet_cover_support_workspace returns TTNET_E_INVALID for n_bits or n_funcs outside those ranges. */
+int64_t ttnet_cover_support_workspace(int n_bits, int64_t n_funcs);
+int ttnet_cover_support(const uint32_t *cubes_dev, const int32_t *counts_dev, int64_t cube_cap, const uint8_t *keep_dev,
+                        const int64_t *usage_dev, const int32_t *usage_row_dev, int64_t n_usage_rows,
+                        int n_bits, int64_t n_funcs,
+                        int64_t *hits_dev, int64_t *first_dev, int64_t *sole_dev, int64_t *totals_dev,
+                        uint32_t *lost_bits_dev, void *work_dev, int64_t work_bytes, void *stream);
+
 /* Integer facts about the plan: "fcsize", "n_classes", "n_state_tensors", "max_batch",
  * "near_ties:<block_tt name>" (entries with |pre-activation| < 1e-5 found while building
  * that table), "table_bytes", "usage_bytes", "care_bytes", "care_blocks", "last_n:<lane>" (images of the

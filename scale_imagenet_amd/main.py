@@ -100,6 +100,27 @@ def check_care_flags(args):
         raise SystemExit(f"--care_from: {args.care_from} does not exist (write it with --table_usage)")
 
 
+def check_rule_flags(args):
+    if not args.rule_support:
+        for flag in ("rule_form", "rule_min_share"):
+            if getattr(args, flag) is not None:
+                raise SystemExit(f"--{flag} needs --rule_support")
+    elif not (args.table_usage or args.care_from):
+        raise SystemExit("--rule_support needs --table_usage or --care_from")
+    if args.rule_min_share is not None and not args.rule_min_share >= 0:
+        raise SystemExit("--rule_min_share must be at least 0")
+
+
+def write_rule_support(args, model, usage):
+    """--rule_support: the covers of every binarised block against ``usage``, pruned too with --rule_min_share."""
+    from . import report, rules
+    support = model.rule_support(usage, form=args.rule_form or "dnf", rounds=args.table_gates_rounds)
+    pruned = None
+    if args.rule_min_share is not None:
+        pruned = {name: rules.prune_by_share(block, usage[name], args.rule_min_share) for name, block in support.items()}
+    report.write_rule_support_csv(args.rule_support, support, pruned)
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(
         prog="python -m scale_imagenet_amd.main",
@@ -130,6 +151,16 @@ def build_parser() -> argparse.ArgumentParser:
     out.add_argument("--table_gates_rounds", type=int, default=0, metavar="R", choices=range(9),
                      help="reduce / expand rounds (0 .. 8) of the minimiser behind both columns of --table_gates; more rounds, "
                           "smaller covers, longer minimisation; 0: the covers it always gave")
+    out.add_argument("--rule_support", type=str, default=None, metavar="FILE",
+                     help="CSV, one row per binarised Block_TT: how the lookups of the table usage (this run's with --table_usage, "
+                          "else the file of --care_from) fall on the cubes of its filters' covers, minimised with the entries "
+                          "never read as don't-cares (--table_gates_rounds applies): cubes, literals, the share of lookups the "
+                          "top 1 %% / 10 %% of cubes decide, cubes without a lookup")
+    out.add_argument("--rule_form", choices=["dnf", "cnf"], default=None,
+                     help="the covers --rule_support measures: of the filters (dnf, the default) or of their complements (cnf)")
+    out.add_argument("--rule_min_share", type=float, default=None, metavar="S",
+                     help="also prune for --rule_support: drop every cube that holds less than the share S of its group's lookups, "
+                          "and report the cubes and literals kept, the lookups lost and the entries lost")
     add_care_flags(out)
     out.add_argument("--care_rows", type=str, default=None, metavar="FILE",
                      help="CSV index,covered,<one column per Block_TT>: every image's care-set misses (with --care_from)")
@@ -320,6 +351,8 @@ def run(args) -> int:
             report.write_gates_csv(args.table_gates, model.gate_counts(rounds=args.table_gates_rounds),
                                    model.gate_counts(usage, rounds=args.table_gates_rounds),
                                    {b.name: b.fan_in_bits for b in model.spec.block_tts()})
+    if rank == 0 and args.rule_support:
+        write_rule_support(args, model, usage if args.table_usage else report.load_table_usage(args.care_from))
     if extra.get("topk") is not None:
         names = report.read_class_names(args.classes) if args.classes else None
         pred = all_gather_predictions(part.predictions) if args.predictions else None
@@ -341,8 +374,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     check_topk(args, needed=bool(args.predictions))
     if args.table_coverage and not args.table_usage:
         raise SystemExit("--table_coverage needs --table_usage")
-    if args.table_gates_rounds and not args.table_gates:
-        raise SystemExit("--table_gates_rounds needs --table_gates")
+    if args.table_gates_rounds and not (args.table_gates or args.rule_support):
+        raise SystemExit("--table_gates_rounds needs --table_gates or --rule_support")
+    check_rule_flags(args)
     check_care_flags(args)
     views_args(args)
     return launch(args, argv, "scale_imagenet_amd.main", _check_paths, run)

@@ -18,6 +18,9 @@ Formats (fixed: tests and users' scripts read them):
                in any block) and its care-set misses per block (``evaluate.CareResult.rows``).
   care summary ``block,lookups,misses,images_with_misses`` per ``Block_TT`` and a last row ``total`` whose
                ``images_with_misses`` is the number of images that are not covered (``care_summary_rows``).
+  rule support ``block,inputs,form,functions,cubes,literals,top1pct_first_share,top10pct_first_share,unused_cubes`` per binarised
+               ``Block_TT`` (``rule_support_rows``), from ``model.rule_support``; with a pruning share also ``kept_cubes,
+               kept_literals,lost_share,lost_patterns``.
 Every file is written to a temporary name beside its own and then renamed, so a reader never sees half of one.
 """
 from __future__ import annotations
@@ -222,3 +225,44 @@ def gate_rows(full, seen, inputs) -> List[list]:
 def write_gates_csv(path: Optional[str], full, seen, inputs):
     with _replacing(path) as f:
         csv.writer(f, lineterminator="\n").writerows(gate_rows(full, seen, inputs))
+
+
+RULE_FIELDS = ["block", "inputs", "form", "functions", "cubes", "literals", "top1pct_first_share", "top10pct_first_share", "unused_cubes"]
+RULE_PRUNED_FIELDS = ["kept_cubes", "kept_literals", "lost_share", "lost_patterns"]
+
+
+def rule_support_rows(support, pruned=None) -> List[list]:
+    """The rows of the rule support file, header first; one row per block of ``support`` (``model.rule_support``):
+      functions             filters of the block, each with a cover of its own
+      cubes, literals       of all those covers (a constant filter has no cube, or the one cube without a literal)
+      top1pct_first_share   share of the covered lookups decided by the 1 % of the block's cubes with the largest ``first``
+                            (at least one cube): read as decision lists, so few rules settle that much of the data; empty for
+                            a block without a covered lookup
+      top10pct_first_share  the same for the top 10 %
+      unused_cubes          cubes with ``hits == 0``: only patterns that were never looked up justify them
+    and, with ``pruned`` (``{block: rules.prune_by_share(..)}``):
+      kept_cubes, kept_literals  what stays of the covers
+      lost_share            lookups that only dropped cubes hold / all lookups of the block's functions
+      lost_patterns         table entries that only dropped cubes hold, summed over the functions (looked up or not)"""
+    from . import minimise
+    rows = [RULE_FIELDS + (RULE_PRUNED_FIELDS if pruned is not None else [])]
+    for name, s in support.items():
+        first = np.sort(np.concatenate([np.asarray(a, dtype=np.int64) for a in s["first"]] + [np.zeros(0, dtype=np.int64)]))[::-1]
+        covered = int(first.sum())
+        shares = [repr(float(first[: max(1, len(first) // d)].sum()) / covered) if covered else "" for d in (100, 10)]
+        row = [name, int(s["n"]), s.get("form", "dnf"), len(s["cubes"]), int(sum(len(c) for c in s["cubes"])),
+               int(sum(minimise.literal_total(c) for c in s["cubes"])), shares[0], shares[1],
+               int(sum(int((np.asarray(h) == 0).sum()) for h in s["hits"]))]
+        if pruned is not None:
+            p = pruned[name]
+            kept = [np.asarray(c, dtype=np.uint32)[np.asarray(k, dtype=bool)] for c, k in zip(s["cubes"], p["keep"])]
+            lookups = int(np.asarray(s["row_total"], dtype=np.int64).sum())
+            row += [int(sum(len(c) for c in kept)), int(sum(minimise.literal_total(c) for c in kept)),
+                    repr(float(int(p["totals"][:, 1].sum())) / lookups) if lookups else "", int(p["totals"][:, 3].sum())]
+        rows.append(row)
+    return rows
+
+
+def write_rule_support_csv(path: Optional[str], support, pruned=None):
+    with _replacing(path) as f:
+        csv.writer(f, lineterminator="\n").writerows(rule_support_rows(support, pruned))

@@ -383,6 +383,29 @@ class _TTNetBase(nn.Module):
                                                   rounds)
         return out
 
+    def rule_support(self, usage, form: str = "dnf", rounds: int = 0, min_count: int = 1,
+                     dont_cares: bool = True) -> "OrderedDict[str, dict]":
+        """Which rules carry the network on the data of ``usage`` (``table_usage()``): per binarised ``Block_TT`` (the float
+        last block is skipped) the covers of its filters -- ``form`` "dnf", or "cnf" for the covers of the complements;
+        ``rounds`` / ``min_count`` as in ``gate_counts``; ``dont_cares`` False minimises the whole tables -- and what every
+        cube of them carries: ``{name: {cubes, hits, first, sole, totals, row_total, usage_row_of, n, ..}}``, the result of
+        ``scale_imagenet_amd.rules.cover_support`` with the covers beside it.  Block by block: tables -> covers -> support, all on
+        the plan's device, one block's usage there at a time.  To prune, pass ``rules.keep_by_support(block, ..)`` as ``keep`` to
+        ``rules.cover_support(block["cubes"], usage[name], block["usage_row_of"], block["n"], keep, lost_bits=True)``."""
+        from . import rules
+        device = torch.device("cuda", self._any_plan().device_index)
+        out: "OrderedDict[str, dict]" = OrderedDict()
+        for b in self.spec.block_tts():
+            if b.last:
+                continue
+            table = self.get_table(b.name)
+            u = np.asarray(usage[b.name], dtype=np.int64)
+            covers = rules.block_covers(table, u if dont_cares else None, b.fan_in_bits, form, rounds, min_count, device)
+            res = rules.cover_support(covers, u, np.repeat(np.arange(b.groups, dtype=np.int32), b.cout_g), b.fan_in_bits, device=device)
+            res.update(cubes=covers, form=form)
+            out[b.name] = res
+        return out
+
     def set_input_norm(self, mean, std):
         """Normalisation constants of ``forward_u8`` (default: the ImageNet ones; the CIFAR ones, ``cifar.CIFAR_MEAN`` /
         ``cifar.CIFAR_STD``, for the vAlexnet model)."""
