@@ -610,6 +610,53 @@ int ttnet_cover_support(const uint32_t *cubes_dev, const int32_t *counts_dev, in
                         int64_t *hits_dev, int64_t *first_dev, int64_t *sole_dev, int64_t *totals_dev,
                         uint32_t *lost_bits_dev, void *work_dev, int64_t work_bytes, void *stream);
 
+/* Certified L-infinity robustness of TTNET_VALEXNET on the device (csrc/certify.hip; DESIGN.md: certified robustness).
+ *
+ * Question: does image i keep the class classes_dev[i] when every input byte may move by up to eps?  x_nhwc_dev is what
+ * ttnet_forward_u8 takes: uint8 [n][32][32][3].  Every byte b may become any REAL value in [max(0, b - eps), min(255, b + eps)]
+ * (eps >= 0 in byte levels: 2.0 is 2/255); ToTensor and Normalize follow with the plan's constants
+ * (ttnet_plan_set_input_norm); the zero padding of the convolution stays zero in normalised space.  The answer is SOUND, not
+ * complete: "certified" is never wrong about the exact-arithmetic network, but a robust image may stay uncertified.
+ *
+ *   stage 0  Interval arithmetic through conv3x3 + bias (lo = sum w+ x_lo + w- x_hi + bias over the taps inside the image,
+ *            hi symmetrically), ReLU, eval BatchNorm (a negative scale swaps the bounds) and MaxPool(3) (max of the lows, max
+ *            of the highs), in float64.  Each bound is then widened outward by the per-channel slack
+ *              slack_c = 2^-40 ((|w_c|_1 X + |bias_c|) |scale_c| + |shift_c|),   X = max |normalised value| of the bytes 0..255,
+ *            computed once on the host: over a hundred times what the ~60 float64 roundings behind a bound can add up to
+ *            (2^-53 of operands of that size each), so the widened bounds hold for exact arithmetic whatever order and
+ *            form the sums are taken in.  lo_bit = (lo >= 0), hi_bit = (hi >= 0):
+ *            a stem bit is unknown where they differ; lo_bit <= hi_bit always.
+ *   stage 1  The block on three-valued bits, exact per lookup: an output bit can be 1 iff a table entry compatible with the
+ *            known inputs is 1 (likewise 0); paddings are known zeros; out4 carries the stem planes.  With the effective head
+ *            A = lin2 diag(bn_scale) lin1 (float64, [10][30976] as a matrix; how the library stores it is internal and
+ *            never crosses this interface), c0 = lin2 bn_shift + bias, and D = A_c - A_j:
+ *              lb_j = c0_c - c0_j + sum_f D_f ylo_f + sum_{f unknown} min(0, D_f),   lb_interval = min_{j != c} lb_j,
+ *            worst = the first j that attains it.
+ *   stage 2  For an image that stage 1 left open and that has 1 <= k <= enum_bits unknown stem bits: the minimum over all 2^k
+ *            completions of the unknown stem bits of min_{j != c} (logit_c - logit_j) (ties: the smaller j).  Still sound
+ *            (the unknown bits are free), and free of the independence loss of stage 1.  enum_bits 0 switches it off.
+ *
+ * rows_dev receives n records of 32 bytes (8-byte aligned):
+ *   { double lb_interval; double lb; int32 worst; int32 stage; int32 unknown_stem; int32 unknown_feat; }
+ * lb = the enumerated bound when stage 2 ran, else lb_interval; stage = 1 certified by the interval bound, 2 certified by
+ * enumeration, 0 not certified; certified means lb > min_margin.  The certificate speaks of the exact-arithmetic network;
+ * the logits of ttnet_forward_u8 lie within the 1e-5-scaled tolerance of it, so a caller who wants the device's own argmax
+ * certified passes min_margin = twice that tolerance.  A class outside 0..9 is NOT an error of the call (the classes live on
+ * the device and nothing is read back): that image gets stage 0, worst -1 and lb = lb_interval = -inf.
+ * planes_dev: NULL, or an 8-byte aligned buffer of n * (2 * 640 + 2 * 2816) uint64 that receives the stem planes lo, hi
+ * ([n][64][10], layout of stage "features.4") and the feature planes lo, hi ([n][256][11], layout of "features.5"), in that order.
+ *
+ * Float64 sums in a fixed order and integer work: the same input gives the same bytes.  Launches on `stream`, not captured in a
+ * graph by the plan; the lane's planes (55 KB per image of max_batch) are allocated by the first call on that lane, A, c0 and
+ * the slack by the first call after a (re)load, which synchronises; forwards and their workspaces are untouched, so a certify
+ * call and a forward on the same lane may overlap.  With profiling on, ttnet_plan_last_timings then reports the steps
+ * "certify.stem", "certify.block", "certify.margin", "certify.enum" of this call.  Errors: eps negative or not finite, enum_bits outside 0..12, min_margin
+ * NaN, a bad lane, n outside [1, max_batch], a NULL or misaligned pointer (4 bytes for images and classes, 8 for records and
+ * planes) TTNET_E_INVALID; any variant other than TTNET_VALEXNET TTNET_E_UNSUPPORTED (the certificate needs an affine head
+ * and truth tables of at most 8 inputs); before finalize TTNET_E_STATE. */
+int ttnet_certify_u8(ttnet_plan *plan, int lane, const uint8_t *x_nhwc_dev, int64_t n, const int32_t *classes_dev, double eps,
+                     int enum_bits, double min_margin, void *rows_dev, uint64_t *planes_dev, void *stream);
+
 /* Integer facts about the plan: "fcsize", "n_classes", "n_state_tensors", "max_batch",
  * "near_ties:<block_tt name>" (entries with |pre-activation| < 1e-5 found while building
  * that table), "table_bytes", "usage_bytes", "care_bytes", "care_blocks", "last_n:<lane>" (images of the

@@ -6,7 +6,8 @@ The reference feeds this model ``cifar_transform(False)`` (utils/preprocess.py:8
 dataset holds, bytes: ``read_cifar10`` transposes the files' planar CHW records to HWC once on the host,
 ``device_batches`` uploads the whole split once (30 MB for the test set) and hands out slices of it, and
 ``model.forward_u8`` normalises inside the stem kernel (include/ttnet.h: ttnet_forward_u8).  ``evaluate`` sends uint8
-tensors there by itself.
+tensors there by itself.  ``--certify EPS[,EPS...]`` then certifies the labels against perturbations of up to EPS byte levels
+over the same device-resident bytes (``scale_imagenet_amd.certify``) and prints the verified accuracy per eps.
 
 Both published layouts are read: ``cifar-10-batches-py`` (pickles ``test_batch`` / ``data_batch_1..5``, ``batches.meta``)
 and ``cifar-10-batches-bin`` (``*.bin`` records of 1 label byte + 3072 planar bytes, ``batches.meta.txt``).  The pickles go
@@ -200,7 +201,30 @@ def build_parser() -> argparse.ArgumentParser:
     out.add_argument("--per_class", type=str, default=None, metavar="FILE", help="CSV class,images,hits1,hits5,predicted,acc1,acc5")
     out.add_argument("--confusion", type=str, default=None, metavar="FILE",
                      help=".npy, int64 [10][10] indexed [target][top-1 class]")
+    cert = p.add_argument_group("certified L-infinity robustness of the labels (one more stdout line per eps, after `Acc..`)")
+    cert.add_argument("--certify", type=str, default=None, metavar="EPS[,EPS...]",
+                      help="certify every image's label against perturbations of up to EPS byte levels (2 is 2/255) and print "
+                           "`Verified.. eps=E certified/N pct (interval a, enumeration b; unknown stem bits median u max v)`: "
+                           "the verified accuracy.  Sound, not complete (scale_imagenet_amd.certify)")
+    cert.add_argument("--certify_enum", type=int, default=10, metavar="K",
+                      help="settle images with up to K unknown stem bits by enumeration (0..12, 0: interval bound only)")
+    cert.add_argument("--certify_min_margin", type=float, default=1e-6, metavar="M", help="certified means lower bound > M")
+    cert.add_argument("--certify_rows", type=str, default=None, metavar="FILE",
+                      help="CSV eps,index,class,stage,certified,lb,lb_interval,worst,unknown_stem,unknown_feat of every image")
     return p
+
+
+def certify_eps_list(text: Optional[str]) -> List[float]:
+    """The eps values of ``--certify``: comma-separated, finite, not negative."""
+    if not text:
+        return []
+    try:
+        eps = [float(t) for t in text.split(",")]
+    except ValueError:
+        raise SystemExit(f"--certify: {text!r} is not a comma-separated list of numbers") from None
+    if any(not (np.isfinite(e) and e >= 0) for e in eps):
+        raise SystemExit("--certify: every eps must be finite and >= 0")
+    return eps
 
 
 def _class_names(args) -> Optional[List[str]]:
@@ -236,7 +260,11 @@ def run(args) -> int:
     extra = {}
     if args.topk or args.predictions or args.per_class or args.confusion:
         extra = dict(topk=args.topk, per_class=bool(args.per_class or args.confusion), confusion=bool(args.confusion))
-    res = evaluate(model, device_batches(images, targets, args.eval_batch_size, device), device, inflight=max(1, args.inflight),
+    eps_list = certify_eps_list(args.certify)
+    batches = device_batches(images, targets, args.eval_batch_size, device)
+    if eps_list:
+        batches = list(batches)                                 # one upload: the certificate reads the bytes the evaluation read
+    res = evaluate(model, batches, device, inflight=max(1, args.inflight),
                    metrics="device", **extra)                   # prints `Acc.. top1 top5` (main.py:284)
     if extra:
         names = _class_names(args)
@@ -247,6 +275,13 @@ def run(args) -> int:
             report.write_per_class_csv(args.per_class, res.per_class, names)
         if args.confusion:
             report.write_confusion(args.confusion, res.confusion)
+    if eps_list:
+        from . import certify
+        sums = certify.certify_batches(model, batches, eps_list, args.certify_enum, args.certify_min_margin)
+        for s in sums:
+            print(certify.verified_line(s))
+        if args.certify_rows:
+            certify.write_rows_csv(args.certify_rows, sums, targets.tolist())
     return 0
 
 
@@ -256,6 +291,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     check_topk(args, needed=bool(args.predictions))
     if args.topk > N_CLASSES:
         raise SystemExit(f"--topk must be in [1, {N_CLASSES}]")
+    certify_eps_list(args.certify)
+    if not 0 <= args.certify_enum <= 12:
+        raise SystemExit("--certify_enum must be in [0, 12]")
+    if args.certify_rows and not args.certify:
+        raise SystemExit("--certify_rows needs --certify")
     return run(args)
 
 

@@ -1,0 +1,568 @@
+// Certified L-infinity robustness of TT_FHE_XSMALL_vAlexnet (include/ttnet.h: ttnet_certify_u8; DESIGN: certified robustness).
+//
+//   stage 0  certify_stem_kernel    interval arithmetic through conv3x3 + bias -> ReLU -> BatchNorm -> MaxPool(3) in float64,
+//                                   widened by the per-channel slack: two row-packed planes, lo_bit = (lo >= 0), hi_bit = (hi >= 0)
+//   stage 1  certify_dw_kernel,     the block on three-valued bits: an output bit can be 1 iff a table entry compatible with
+//            certify_c3_kernel      the known inputs is 1 -- the table word ANDed with one selector word per input
+//            certify_margin_kernel  lb_j = c0_c - c0_j + sum_f D_f ylo_f + sum_{f unknown} min(0, D_f), D = A_c - A_j
+//   stage 2  certify_enum_kernel    all 2^k completions of the k unknown stem bits; only the features whose windows hold one
+//                                   are re-evaluated, the others enter through a base sum
+//   certify_head_kernel, certify_t3_words_kernel: the effective head A = lin2 diag(bn_scale) lin1, c0, and the 256-entry
+//   tables of Block_conv3 as four 64-bit words per output bit; once per loaded state
+//
+// Everything is float64 and integer work in a fixed order: no float atomics, the same bytes on every run.
+
+#include <math.h>
+
+#include "ttnet_common.h"
+
+namespace ttnet {
+
+namespace {
+
+constexpr int kStemRows = 64 * 10, kFeatRows = 256 * 11, kFeat = 256 * 121, kClasses = 10, kInter = 100;
+constexpr int kMaxEnum = 12, kMaxEnt = kMaxEnum * 21;     // an unknown stem bit sits in the windows of at most 21 features
+
+// the entries of a 64-entry table that agree with the known inputs: `lo` holds the known values, `un` marks the unknown
+// inputs (bits 0..5).  M[p] = the indices whose bit p is 1.
+__device__ inline uint64_t selector(uint32_t lo, uint32_t un) {
+  constexpr uint64_t M[6] = {0xAAAAAAAAAAAAAAAAull, 0xCCCCCCCCCCCCCCCCull, 0xF0F0F0F0F0F0F0F0ull,
+                             0xFF00FF00FF00FF00ull, 0xFFFF0000FFFF0000ull, 0xFFFFFFFF00000000ull};
+  uint64_t S = ~0ull;
+#pragma unroll
+  for (int p = 0; p < 6; ++p) S &= ((un >> p) & 1u) ? ~0ull : (((lo >> p) & 1u) ? M[p] : ~M[p]);
+  return S;
+}
+
+struct Row {            // one record of ttnet_certify_u8, 32 bytes
+  double lb_interval, lb;
+  int32_t worst, stage, unknown_stem, unknown_feat;
+};
+static_assert(sizeof(Row) == 32, "record layout of include/ttnet.h");
+
+// A[j][f] = sum_i lin2[j][i] * s[i] * lin1[i][f] (i ascending; stored [f][j]), c0[j] = sum_i lin2[j][i] * t[i] + bias[j]
+__global__ __launch_bounds__(256) void certify_head_kernel(const float *__restrict__ lin1, const float *__restrict__ lin2,
+                                                           const float *__restrict__ bias, const double *__restrict__ bn,
+                                                           double *__restrict__ A, double *__restrict__ c0) {
+  __shared__ double m_s[kClasses][kInter];
+  for (int i = threadIdx.x; i < kClasses * kInter; i += blockDim.x) m_s[i / kInter][i % kInter] = (double)lin2[i] * bn[i % kInter];
+  __syncthreads();
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (blockIdx.x == 0 && threadIdx.x < kClasses) {
+    double acc = 0.0;
+    for (int i = 0; i < kInter; ++i) acc += (double)lin2[threadIdx.x * kInter + i] * bn[kInter + i];
+    c0[threadIdx.x] = acc + (double)bias[threadIdx.x];
+  }
+  if (f >= kFeat) return;
+  double acc[kClasses];
+#pragma unroll
+  for (int j = 0; j < kClasses; ++j) acc[j] = 0.0;
+  for (int i = 0; i < kInter; ++i) {
+    const double v = (double)lin1[(size_t)i * kFeat + f];
+#pragma unroll
+    for (int j = 0; j < kClasses; ++j) acc[j] += m_s[j][i] * v;
+  }
+#pragma unroll
+  for (int j = 0; j < kClasses; ++j) A[(size_t)f * kClasses + j] = acc[j];      // [feature][class]: what one feature adds is 80 contiguous bytes
+}
+
+// t3w[(g * 8 + o) * 4 + w] bit b = output o of entry 64 w + b of group g
+__global__ void certify_t3_words_kernel(const uint8_t *__restrict__ t3, uint64_t *__restrict__ t3w) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 8 * 8 * 4) return;
+  const int w = t & 3, o = (t >> 2) & 7, g = t >> 5;
+  uint64_t word = 0;
+  for (int b = 0; b < 64; ++b) word |= (uint64_t)((t3[g * 256 + 64 * w + b] >> o) & 1u) << b;
+  t3w[t] = word;
+}
+
+// stage 0: five workgroups per image, each two pooled rows: thread = (channel, pooled row) as va_stem_kernel.  The eight
+// image rows those need (image rows 3 p0 - 1 .. 3 p0 + 6, p0 = the first pooled row) live in LDS as the centre and the
+// radius of each normalised pixel's interval, with the zero column on the left (the padding is zero in normalised space:
+// centre 0, radius 0; the pooled outputs never touch the right or bottom padding).  13 KiB of LDS per workgroup.
+constexpr int kStemRowsPerWg = 2, kStemLdsRows = 3 * kStemRowsPerWg + 2;
+
+__global__ __launch_bounds__(64 * kStemRowsPerWg) void certify_stem_kernel(
+    const uint8_t *__restrict__ x, CertifyNorm nm, const float *__restrict__ w, const float *__restrict__ bias,
+    const double *__restrict__ bn, const double *__restrict__ slack, double eps, uint64_t *__restrict__ lo_rp,
+    uint64_t *__restrict__ hi_rp, int n) {
+  __shared__ double img_s[2][3][kStemLdsRows][34];
+  constexpr int kParts = 10 / kStemRowsPerWg;
+  const int img = blockIdx.x / kParts, p0 = (blockIdx.x % kParts) * kStemRowsPerWg;
+  if (img >= n) return;                                              // (whole workgroups: no barrier is left behind)
+  const int r0 = 3 * p0 - 1;                                         // image row of LDS row 0 (-1: the top padding)
+  for (int i = threadIdx.x; i < 3 * kStemLdsRows * 34; i += blockDim.x) {   // the zero column, and the zero row of the first part
+    const int r = (i / 34) % kStemLdsRows, q = i % 34;
+    if (q == 0 || q == 33 || r0 + r < 0) (&img_s[0][0][0][0])[i] = (&img_s[1][0][0][0])[i] = 0.0;
+  }
+  const uint32_t *src = (const uint32_t *)(x + (size_t)img * 3072);   // (4-byte aligned: checked by the plan; a row is 96 bytes)
+  for (int i = threadIdx.x; i < kStemLdsRows * 24; i += blockDim.x) {
+    const int lr = i / 24, ir = r0 + lr;                             // ir <= 3 * 8 - 1 + 7 = 30
+    if (ir < 0) continue;
+    const uint32_t v = src[ir * 24 + (i - lr * 24)];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int e = 4 * (i - lr * 24) + k, q = e / 3, c = e - 3 * q;
+      const double b = (double)((v >> (8 * k)) & 0xFFu);
+      // centre and radius of the interval: w+ x_lo + w- x_hi = w x_c - |w| x_r and w+ x_hi + w- x_lo = w x_c + |w| x_r,
+      // two multiply-adds per tap where the bounds themselves take four and a choice by the sign of w
+      const double xl = (fmax(0.0, b - eps) - nm.off[c]) * nm.a[c], xh = (fmin(255.0, b + eps) - nm.off[c]) * nm.a[c];
+      img_s[0][c][lr][q + 1] = 0.5 * (xl + xh);
+      img_s[1][c][lr][q + 1] = 0.5 * (xh - xl);
+    }
+  }
+  __syncthreads();
+  const int ch = threadIdx.x & 63, pl = threadIdx.x >> 6, py = p0 + pl;   // one wave per pooled row
+  double wr[27];
+#pragma unroll
+  for (int i = 0; i < 27; ++i) wr[i] = (double)w[ch * 27 + i];
+  const double b = (double)bias[ch], sc = bn[ch], sh = bn[64 + ch], sl = slack[ch];
+  uint64_t out_lo = 0, out_hi = 0;
+#pragma unroll 1
+  for (int px = 0; px < 10; ++px) {
+    // the nine convolution outputs of the pooled pixel, from its 5x5 patch: a patch row is read once (all 64 lanes of
+    // the wave read the same address: a broadcast) and feeds every output it belongs to; taps in (c, kh, kw) order
+    double mid[3][3], rad[3][3];
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 3; ++dx) mid[dy][dx] = rad[dy][dx] = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int r = 0; r < 5; ++r) {
+        double xc[5], xr[5];
+#pragma unroll
+        for (int q = 0; q < 5; ++q) {
+          xc[q] = img_s[0][c][3 * pl + r][3 * px + q];
+          xr[q] = img_s[1][c][3 * pl + r][3 * px + q];
+        }
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy) {
+          const int kh = r - dy;
+          if (kh < 0 || kh > 2) continue;
+#pragma unroll
+          for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+            for (int kw = 0; kw < 3; ++kw) {
+              const double wv = wr[(c * 3 + kh) * 3 + kw];
+              mid[dy][dx] = fma(wv, xc[dx + kw], mid[dy][dx]);
+              rad[dy][dx] = fma(fabs(wv), xr[dx + kw], rad[dy][dx]);
+            }
+        }
+      }
+    double best_lo = -INFINITY, best_hi = -INFINITY;
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 3; ++dx) {
+        const double lo = fmax(mid[dy][dx] - rad[dy][dx] + b, 0.0), hi = fmax(mid[dy][dx] + rad[dy][dx] + b, 0.0);   // ReLU
+        const double ylo = (sc >= 0.0 ? lo : hi) * sc + sh, yhi = (sc >= 0.0 ? hi : lo) * sc + sh;   // a negative scale swaps the bounds
+        best_lo = fmax(best_lo, ylo);                                // MaxPool2d(3): max of the lows, max of the highs
+        best_hi = fmax(best_hi, yhi);
+      }
+    out_lo |= (uint64_t)(best_lo - sl >= 0.0) << px;
+    out_hi |= (uint64_t)(best_hi + sl >= 0.0) << px;
+  }
+  lo_rp[((size_t)img * 64 + ch) * 10 + py] = out_lo;
+  hi_rp[((size_t)img * 64 + ch) * 10 + py] = out_hi | out_lo;        // (lo_bit <= hi_bit whatever the arithmetic did)
+}
+
+// stage 1, Block_conv1 / Block_conv2 / out4: thread = (image, channel, output row of the 11x11 plane), as va_dw_kernel.
+// ylo = the bits that are certainly 1, yhi = the bits that can be 1.
+__global__ void certify_dw_kernel(const uint64_t *__restrict__ slo, const uint64_t *__restrict__ shi, const uint32_t *__restrict__ t1,
+                                  const uint32_t *__restrict__ t2, uint64_t *__restrict__ ylo, uint64_t *__restrict__ yhi, int n) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)n * 64 * 11) return;
+  const int oy = t % 11, c = (t / 11) % 64, img = t / (11 * 64);
+  const uint64_t *pl = slo + ((size_t)img * 64 + c) * 10, *ph = shi + ((size_t)img * 64 + c) * 10;
+  uint64_t l[3], u[3];                                               // rows oy-1 .. oy+1, bit 0 = column -1; padding: known zeros
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int iy = oy - 1 + k;
+    const bool in = iy >= 0 && iy < 10;
+    l[k] = in ? pl[iy] << 1 : 0ull;
+    u[k] = in ? (pl[iy] ^ ph[iy]) << 1 : 0ull;
+  }
+  const size_t tb = (size_t)(c >> 4) * 2 * 16 + (c & 15);
+  const uint64_t T1 = t1[tb] | ((uint64_t)t1[tb + 16] << 32), T2 = t2[tb] | ((uint64_t)t2[tb + 16] << 32);
+  uint64_t r1l = 0, r1h = 0, r2l = 0, r2h = 0;
+  if (oy < 10) {      // conv1: 3x2 window, 11 output columns; bottom row 10 is zero padding
+    const bool known = ((u[0] | u[1] | u[2]) & 0xFFFull) == 0;       // the common case at small eps: plain lookups
+    for (int ox = 0; ox < 11; ++ox) {
+      const uint32_t idx = (uint32_t)((l[0] >> ox) & 3) | ((uint32_t)((l[1] >> ox) & 3) << 2) | ((uint32_t)((l[2] >> ox) & 3) << 4);
+      const uint32_t un = known ? 0u : (uint32_t)((u[0] >> ox) & 3) | ((uint32_t)((u[1] >> ox) & 3) << 2) | ((uint32_t)((u[2] >> ox) & 3) << 4);
+      if (un == 0) {
+        const uint64_t bit = (T1 >> idx) & 1ull;
+        r1l |= bit << ox;
+        r1h |= bit << ox;
+      } else {
+        const uint64_t S = selector(idx, un);
+        r1l |= (uint64_t)((~T1 & S) == 0) << ox;                     // no compatible entry is 0
+        r1h |= (uint64_t)((T1 & S) != 0) << ox;                      // some compatible entry is 1
+      }
+    }
+  }
+  {                   // conv2: 2x3 window, rows oy-1..oy, 10 output columns; right column 10 is zero padding
+    const bool known = ((u[0] | u[1]) & 0xFFFull) == 0;
+    for (int ox = 0; ox < 10; ++ox) {
+      const uint32_t idx = (uint32_t)((l[0] >> ox) & 7) | ((uint32_t)((l[1] >> ox) & 7) << 3);
+      const uint32_t un = known ? 0u : (uint32_t)((u[0] >> ox) & 7) | ((uint32_t)((u[1] >> ox) & 7) << 3);
+      if (un == 0) {
+        const uint64_t bit = (T2 >> idx) & 1ull;
+        r2l |= bit << ox;
+        r2h |= bit << ox;
+      } else {
+        const uint64_t S = selector(idx, un);
+        r2l |= (uint64_t)((~T2 & S) == 0) << ox;
+        r2h |= (uint64_t)((T2 & S) != 0) << ox;
+      }
+    }
+  }
+  const size_t o = (size_t)img * 256 * 11 + oy;
+  ylo[o + (size_t)c * 11] = r1l;
+  yhi[o + (size_t)c * 11] = r1h;
+  ylo[o + (size_t)(64 + c) * 11] = r2l;
+  yhi[o + (size_t)(64 + c) * 11] = r2h;
+  ylo[o + (size_t)(192 + c) * 11] = oy < 10 ? pl[oy] : 0ull;         // out4 = x, padded right / bottom
+  yhi[o + (size_t)(192 + c) * 11] = oy < 10 ? ph[oy] : 0ull;
+}
+
+// can0 / can1 of one output bit of a 256-entry table (four words): inputs 6 and 7 pick the words, inputs 0..5 the selector
+__device__ inline void lookup8(const uint64_t *T, uint32_t lo, uint32_t un, bool &can0, bool &can1) {
+  const uint64_t S = selector(lo, un);
+  can0 = can1 = false;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const bool ok = (((un >> 6) & 1u) || ((lo >> 6) & 1u) == (uint32_t)(w & 1)) && (((un >> 7) & 1u) || ((lo >> 7) & 1u) == (uint32_t)(w >> 1));
+    if (!ok) continue;
+    can1 = can1 || (T[w] & S) != 0;
+    can0 = can0 || (~T[w] & S) != 0;
+  }
+}
+
+// stage 1, Block_conv3: thread = (image, group of 8 channels, row), as va_c3_kernel
+__global__ void certify_c3_kernel(const uint64_t *__restrict__ slo, const uint64_t *__restrict__ shi, const uint8_t *__restrict__ t3,
+                                  const uint64_t *__restrict__ t3w, uint64_t *__restrict__ ylo, uint64_t *__restrict__ yhi, int n) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)n * 8 * 11) return;
+  const int oy = t % 11, g = (t / 11) % 8, img = t / 88;
+  uint64_t l[8], u[8], ol[8], oh[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const size_t r = ((size_t)img * 64 + 8 * g + k) * 10 + oy;
+    l[k] = oy < 10 ? slo[r] : 0ull;
+    u[k] = oy < 10 ? slo[r] ^ shi[r] : 0ull;
+    ol[k] = oh[k] = 0;
+  }
+  if (oy < 10)
+    for (int xx = 0; xx < 10; ++xx) {
+      uint32_t idx = 0, un = 0;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        idx |= (uint32_t)((l[k] >> xx) & 1ull) << k;
+        un |= (uint32_t)((u[k] >> xx) & 1ull) << k;
+      }
+      if (un == 0) {                                                 // plain lookup
+        const uint32_t v = t3[g * 256 + idx];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          ol[k] |= (uint64_t)((v >> k) & 1u) << xx;
+          oh[k] |= (uint64_t)((v >> k) & 1u) << xx;
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          bool can0, can1;
+          lookup8(t3w + (g * 8 + k) * 4, idx, un, can0, can1);
+          ol[k] |= (uint64_t)(!can0) << xx;
+          oh[k] |= (uint64_t)can1 << xx;
+        }
+      }
+    }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    ylo[((size_t)img * 256 + 128 + 8 * g + k) * 11 + oy] = ol[k];
+    yhi[((size_t)img * 256 + 128 + 8 * g + k) * 11 + oy] = oh[k];
+  }
+}
+
+// stage 1, margin: one workgroup per image.  Thread t owns the feature rows t, t + 256, ..; its partial sums meet in a
+// fixed tree, so the bytes do not depend on anything but the input.  The sum over the certain features is kept apart
+// (sums[img][j] = sum_f D_f ylo_f): stage 2 starts from it.
+__global__ __launch_bounds__(256) void certify_margin_kernel(const uint64_t *__restrict__ slo, const uint64_t *__restrict__ shi,
+                                                             const uint64_t *__restrict__ ylo, const uint64_t *__restrict__ yhi,
+                                                             const double *__restrict__ A, const double *__restrict__ c0,
+                                                             const int32_t *__restrict__ classes, double min_margin,
+                                                             Row *__restrict__ rows, double *__restrict__ sums, int n) {
+  __shared__ double red[2 * kClasses][256];                          // [j]: the certain features, [10 + j]: the unknown ones
+  __shared__ int cnt_s[2];
+  const int img = blockIdx.x, tid = threadIdx.x;
+  if (img >= n) return;
+  if (tid < 2) cnt_s[tid] = 0;
+  __syncthreads();
+  const int c = classes[img];
+  const bool valid = c >= 0 && c < kClasses;
+  int us = 0, uf = 0;
+  for (int r = tid; r < kStemRows; r += 256) us += __popcll(slo[(size_t)img * kStemRows + r] ^ shi[(size_t)img * kStemRows + r]);
+  double acc[2 * kClasses];
+#pragma unroll
+  for (int j = 0; j < 2 * kClasses; ++j) acc[j] = 0.0;
+  for (int r = tid; r < kFeatRows; r += 256) {
+    const uint64_t l = ylo[(size_t)img * kFeatRows + r], h = yhi[(size_t)img * kFeatRows + r];
+    uf += __popcll(l ^ h);
+    if (!valid) continue;
+    const int f0 = (r / 11) * 121 + (r % 11) * 11;
+    for (uint64_t m = h & 0x7FFull; m; m &= m - 1) {
+      const int bit = __builtin_ctzll(m);
+      const double *af = A + (size_t)(f0 + bit) * kClasses;          // the ten classes of a feature are contiguous
+      const bool one = (l >> bit) & 1ull;
+      const double ac = af[c];
+#pragma unroll
+      for (int j = 0; j < kClasses; ++j) {
+        const double d = ac - af[j];
+        acc[j] += one ? d : 0.0;
+        acc[kClasses + j] += one ? 0.0 : fmin(0.0, d);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 2 * kClasses; ++j) red[j][tid] = acc[j];
+  atomicAdd(&cnt_s[0], us);                                          // (integers: any order gives the same sum)
+  atomicAdd(&cnt_s[1], uf);
+  __syncthreads();
+  for (int s = 128; s >= 1; s >>= 1) {
+    if (tid < s)
+#pragma unroll
+      for (int j = 0; j < 2 * kClasses; ++j) red[j][tid] += red[j][tid + s];
+    __syncthreads();
+  }
+  if (tid < kClasses) sums[(size_t)img * kClasses + tid] = red[tid][0];
+  if (tid != 0) return;
+  Row out;
+  out.lb_interval = -INFINITY;
+  out.worst = -1;
+  if (valid) {
+    double best = INFINITY;
+    for (int j = 0; j < kClasses; ++j) {
+      if (j == c) continue;
+      const double lb = c0[c] - c0[j] + (red[j][0] + red[kClasses + j][0]);
+      if (lb < best) {
+        best = lb;
+        out.worst = j;
+      }
+    }
+    out.lb_interval = best;
+  }
+  out.lb = out.lb_interval;
+  out.stage = out.lb > min_margin ? 1 : 0;
+  out.unknown_stem = cnt_s[0];
+  out.unknown_feat = cnt_s[1];
+  rows[img] = out;
+}
+
+// stage 2: one workgroup per image that stage 1 left open with 1 <= k <= enum_bits unknown stem bits.  The unknown bits
+// (channel, row, column ascending) and the features they reach (per unknown bit: conv1, conv2, conv3, out4; the first
+// mention of a feature wins) are listed in that fixed order, so the sums below are taken in a fixed order too.
+__global__ __launch_bounds__(256) void certify_enum_kernel(const uint64_t *__restrict__ slo, const uint64_t *__restrict__ shi,
+                                                           const uint64_t *__restrict__ ylo, const uint32_t *__restrict__ t1,
+                                                           const uint32_t *__restrict__ t2, const uint64_t *__restrict__ t3w,
+                                                           const double *__restrict__ A, const double *__restrict__ c0,
+                                                           const int32_t *__restrict__ classes, int enum_bits, double min_margin,
+                                                           Row *__restrict__ rows, const double *__restrict__ sums, int n) {
+  __shared__ uint64_t s_lo[kStemRows], s_un[kStemRows];
+  __shared__ uint64_t e_T[kMaxEnt][4];
+  __shared__ double e_D[kMaxEnt][kClasses];
+  __shared__ uint16_t e_key[kMaxEnt], c_key[kMaxEnt];                // feature row * 16 + column: of the entries, of the candidates
+  __shared__ uint8_t c_new[kMaxEnt];
+  __shared__ uint8_t e_one[kMaxEnt], e_base[kMaxEnt], e_cnt[kMaxEnt], e_pos[kMaxEnt][8], e_unk[kMaxEnt][8];
+  __shared__ uint16_t u_pos[kMaxEnum];                               // unknown stem bit i: stem row * 16 + column
+  __shared__ int n_ent_s;
+  __shared__ double base_s[kClasses];
+  __shared__ double rv[256];
+  __shared__ int rj[256];
+  const int img = blockIdx.x, tid = threadIdx.x;
+  if (img >= n) return;
+  const int c = classes[img];
+  const int k = rows[img].unknown_stem;
+  if (rows[img].stage != 0 || k < 1 || k > enum_bits || k > kMaxEnum || c < 0 || c >= kClasses) return;   // (whole workgroups)
+  for (int r = tid; r < kStemRows; r += 256) {
+    const uint64_t l = slo[(size_t)img * kStemRows + r];
+    s_lo[r] = l;
+    s_un[r] = (l ^ shi[(size_t)img * kStemRows + r]) & 0x3FFull;
+  }
+  __syncthreads();
+  if (tid < 64) {                    // the unknown bits in order: lane = channel, a scan of the lanes' counts gives each its place
+    int cnt = 0;
+    for (int y = 0; y < 10; ++y) cnt += __popcll(s_un[tid * 10 + y]);
+    int incl = cnt;
+    for (int d = 1; d < 64; d <<= 1) {
+      const int v = __shfl_up(incl, d);
+      if (tid >= d) incl += v;
+    }
+    int at = incl - cnt;
+    for (int y = 0; y < 10; ++y)
+      for (uint64_t m = s_un[tid * 10 + y]; m; m &= m - 1, ++at)
+        if (at < kMaxEnum) u_pos[at] = (uint16_t)((tid * 10 + y) * 16 + __builtin_ctzll(m));
+  }
+  __syncthreads();
+  // candidate q = 21 i + t: feature t of those that unknown bit i reaches (0xFFFF: it falls outside the plane)
+  const int n_cand = 21 * k;                                         // <= kMaxEnt
+  uint32_t key = 0xFFFFu;
+  if (tid < n_cand) {
+    const int i = tid / 21, t = tid - 21 * i, r = u_pos[i] >> 4, x = u_pos[i] & 15, ch = r / 10, y = r - 10 * ch;
+    int row = -1, bit = 0;
+    if (t < 6) {                                                     // conv1: rows oy-1..oy+1, columns ox-1..ox; oy <= 9
+      const int oy = y - 1 + t / 2;
+      bit = x + t % 2;
+      if (oy >= 0 && oy <= 9) row = ch * 11 + oy;
+    } else if (t < 12) {                                             // conv2: rows oy-1..oy, columns ox-1..ox+1; ox <= 9
+      const int oy = y + (t - 6) / 3;
+      bit = x - 1 + (t - 6) % 3;
+      if (bit >= 0 && bit <= 9) row = (64 + ch) * 11 + oy;
+    } else if (t < 20) {                                             // conv3: the 8 outputs of the group
+      row = (128 + (ch & ~7) + (t - 12)) * 11 + y;
+      bit = x;
+    } else {                                                         // out4
+      row = (192 + ch) * 11 + y;
+      bit = x;
+    }
+    if (row >= 0) key = (uint32_t)(row * 16 + bit);
+    c_key[tid] = (uint16_t)key;
+  }
+  __syncthreads();
+  if (tid < n_cand) {
+    bool fresh = key != 0xFFFFu;
+    for (int q = 0; q < tid && fresh; ++q) fresh = c_key[q] != key;
+    c_new[tid] = fresh;
+  }
+  __syncthreads();
+  if (tid < n_cand) {
+    int at = 0;
+    for (int q = 0; q < tid; ++q) at += c_new[q];
+    if (c_new[tid]) e_key[at] = (uint16_t)key;
+    if (tid == n_cand - 1) n_ent_s = at + c_new[tid];
+  }
+  __syncthreads();
+  const int n_ent = n_ent_s;
+  // what each re-evaluated feature needs: its table, the known part of its index, where the unknown bits enter, its D
+  for (int e = tid; e < n_ent; e += 256) {
+    const int row = e_key[e] >> 4, bit = e_key[e] & 15, fc = row / 11, oy = row % 11, kind = fc >> 6, ch = fc & 63;
+    uint32_t base = 0;
+    int cnt = 0;
+    auto input = [&](int p, int sc, int iy, int ix) {               // window input p = stem bit (sc, iy, ix), or padding
+      if (iy < 0 || iy >= 10 || ix < 0 || ix >= 10) return;
+      const int r = sc * 10 + iy;
+      if ((s_un[r] >> ix) & 1ull) {
+        for (int i = 0; i < k; ++i)
+          if (u_pos[i] == r * 16 + ix) {
+            e_pos[e][cnt] = (uint8_t)p;
+            e_unk[e][cnt] = (uint8_t)i;
+            ++cnt;
+          }
+      } else if ((s_lo[r] >> ix) & 1ull) {
+        base |= 1u << p;
+      }
+    };
+    uint64_t T[4] = {0, 0, 0, 0};
+    const size_t tb = (size_t)(ch >> 4) * 2 * 16 + (ch & 15);
+    if (kind == 0) {
+      for (int p = 0; p < 6; ++p) input(p, ch, oy - 1 + p / 2, bit - 1 + p % 2);
+      T[0] = t1[tb] | ((uint64_t)t1[tb + 16] << 32);
+    } else if (kind == 1) {
+      for (int p = 0; p < 6; ++p) input(p, ch, oy - 1 + p / 3, bit - 1 + p % 3);
+      T[0] = t2[tb] | ((uint64_t)t2[tb + 16] << 32);
+    } else if (kind == 2) {
+      for (int p = 0; p < 8; ++p) input(p, (ch & ~7) + p, oy, bit);
+      for (int w = 0; w < 4; ++w) T[w] = t3w[ch * 4 + w];            // (ch = 8 group + output)
+    } else {
+      input(0, ch, oy, bit);
+      T[0] = 2ull;                                                   // the identity on one input
+    }
+    for (int w = 0; w < 4; ++w) e_T[e][w] = T[w];
+    e_base[e] = (uint8_t)base;
+    e_cnt[e] = (uint8_t)cnt;
+    e_one[e] = (uint8_t)((ylo[(size_t)img * kFeatRows + row] >> bit) & 1ull);
+    const double *af = A + (size_t)(fc * 121 + oy * 11 + bit) * kClasses;
+    const double ac = af[c];
+    for (int j = 0; j < kClasses; ++j) e_D[e][j] = ac - af[j];
+  }
+  __syncthreads();
+  // the base: stage 1's sum over the certain features, without those of them that are re-evaluated below
+  if (tid < kClasses) {
+    double sub = 0.0;
+    for (int e = 0; e < n_ent; ++e) sub += e_one[e] ? e_D[e][tid] : 0.0;
+    base_s[tid] = tid == c ? INFINITY : c0[c] - c0[tid] + (sums[(size_t)img * kClasses + tid] - sub);
+  }
+  __syncthreads();
+  double best = INFINITY;
+  int best_j = kClasses;
+  for (uint32_t a = tid; a < (1u << k); a += 256) {
+    double m[kClasses];
+#pragma unroll
+    for (int j = 0; j < kClasses; ++j) m[j] = base_s[j];
+    for (int e = 0; e < n_ent; ++e) {
+      uint32_t idx = e_base[e];
+      for (int q = 0; q < e_cnt[e]; ++q) idx |= ((a >> e_unk[e][q]) & 1u) << e_pos[e][q];
+      if ((e_T[e][idx >> 6] >> (idx & 63)) & 1ull)
+#pragma unroll
+        for (int j = 0; j < kClasses; ++j) m[j] += e_D[e][j];        // (e_D[e][c] = 0: m[c] stays +inf)
+    }
+#pragma unroll
+    for (int j = 0; j < kClasses; ++j)
+      if (m[j] < best || (m[j] == best && j < best_j)) {
+        best = m[j];
+        best_j = j;
+      }
+  }
+  rv[tid] = best;
+  rj[tid] = best_j;
+  __syncthreads();
+  for (int s = 128; s >= 1; s >>= 1) {                               // min of (value, class): the order does not matter
+    if (tid < s && (rv[tid + s] < rv[tid] || (rv[tid + s] == rv[tid] && rj[tid + s] < rj[tid]))) {
+      rv[tid] = rv[tid + s];
+      rj[tid] = rj[tid + s];
+    }
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  rows[img].lb = rv[0];
+  rows[img].worst = rj[0];
+  rows[img].stage = rv[0] > min_margin ? 2 : 0;
+}
+
+}  // namespace
+
+int launch_certify_head(const float *lin1, const float *lin2, const float *bias, const double *bn, const uint8_t *t3, double *A,
+                        double *c0, uint64_t *t3w, hipStream_t s) {
+  hipLaunchKernelGGL(certify_head_kernel, dim3((kFeat + 255) / 256), dim3(256), 0, s, lin1, lin2, bias, bn, A, c0);
+  hipLaunchKernelGGL(certify_t3_words_kernel, dim3(1), dim3(256), 0, s, t3, t3w);
+  TT_HIP(hipGetLastError());
+  return TTNET_OK;
+}
+
+int launch_certify(const CertifyArgs &a, int step, hipStream_t s) {
+  const int n = a.n;
+  Row *rows = (Row *)a.rows;
+  if (step == kCertifyStem) {
+    hipLaunchKernelGGL(certify_stem_kernel, dim3((unsigned)n * (10 / kStemRowsPerWg)), dim3(64 * kStemRowsPerWg), 0, s, a.x, a.norm, a.w, a.bias, a.stem_bn, a.slack, a.eps,
+                       a.stem_lo, a.stem_hi, n);
+  } else if (step == kCertifyBlock) {
+    size_t t = (size_t)n * 64 * 11;
+    hipLaunchKernelGGL(certify_dw_kernel, dim3((unsigned)((t + 127) / 128)), dim3(128), 0, s, a.stem_lo, a.stem_hi, a.t1, a.t2,
+                       a.feat_lo, a.feat_hi, n);
+    t = (size_t)n * 88;
+    hipLaunchKernelGGL(certify_c3_kernel, dim3((unsigned)((t + 127) / 128)), dim3(128), 0, s, a.stem_lo, a.stem_hi, a.t3, a.t3w,
+                       a.feat_lo, a.feat_hi, n);
+  } else if (step == kCertifyMargin) {
+    hipLaunchKernelGGL(certify_margin_kernel, dim3((unsigned)n), dim3(256), 0, s, a.stem_lo, a.stem_hi, a.feat_lo, a.feat_hi, a.A, a.c0,
+                       a.classes, a.min_margin, rows, a.sums, n);
+  } else {
+    hipLaunchKernelGGL(certify_enum_kernel, dim3((unsigned)n), dim3(256), 0, s, a.stem_lo, a.stem_hi, a.feat_lo, a.t1, a.t2, a.t3w,
+                       a.A, a.c0, a.classes, a.enum_bits, a.min_margin, rows, a.sums, n);
+  }
+  TT_HIP(hipGetLastError());
+  return TTNET_OK;
+}
+
+}  // namespace ttnet

@@ -115,6 +115,14 @@ struct ttnet_plan {
   float *va_scale = nullptr, *va_shift = nullptr;   // vAlexnet stem BatchNorm folded
   float *va_u8_tab = nullptr;       // vAlexnet, uint8 input: folded weights, border-class constants, centres (va_stem_u8_fold)
   size_t full_fix_cap = 0;          // full variant: list entries of Lane::full_fix
+  // vAlexnet, ttnet_certify_u8 (certify.hip): derived from the loaded state by the first call after a (re)load; dropped with
+  // every tensor, table or normalisation change (drop_certify)
+  struct Certify {
+    double *A = nullptr, *c0 = nullptr;       // effective head, stored [30976][10], and [10]
+    double *stem_bn = nullptr, *slack = nullptr;   // [2][64] folded features.2, [64] widening of the stem bounds
+    uint64_t *t3w = nullptr;                  // Block_conv3's table as 64-entry words
+    bool ready = false;
+  } cert;
   float *full_gel = nullptr;        // full variant: GELU tables of the fast kernels (launch_full_gelu_tables), shared by all lanes
 
   // stem
@@ -171,6 +179,7 @@ struct ttnet_plan {
     std::vector<uint16_t *> x_cp;
     std::vector<Block> blk;
     uint64_t *va_y = nullptr;       // vAlexnet: the concatenated block output [n][256][11] rows
+    uint64_t *cert_planes = nullptr;   // vAlexnet, ttnet_certify_u8: stem lo / hi [nb][64][10], feature lo / hi [nb][256][11], sums [nb][10]; first call
     float *last_float = nullptr;    // full variant: relu'd output of the last block before AvgPool2d
     uint32_t *full_fix = nullptr;   // full variant: [64] counters + the pixel lists of one grouped 1x1 block (gate_full.hip)
     float *part = nullptr;          // lin1's partial sums
@@ -235,6 +244,13 @@ void dev_free(ttnet_plan *pl, void *ptr) {
   auto it = std::find(pl->owned.begin(), pl->owned.end(), ptr);
   if (it != pl->owned.end()) pl->owned.erase(it);
   (void)hipFree(ptr);
+}
+
+// what ttnet_certify_u8 derived from the state goes with the state (the lanes' planes hold no state and stay)
+void drop_certify(ttnet_plan *pl) {
+  auto &c = pl->cert;
+  for (void *ptr : {(void *)c.A, (void *)c.c0, (void *)c.stem_bn, (void *)c.slack, (void *)c.t3w}) dev_free(pl, ptr);
+  c = ttnet_plan::Certify{};
 }
 
 void add_tensor(ttnet_plan *pl, const std::string &key, std::vector<int64_t> shape, int dtype, bool required) {
@@ -980,13 +996,13 @@ int check_range(ttnet_plan *pl) {
   return TTNET_OK;
 }
 
-int check_ready(ttnet_plan *pl, const void *in, int64_t n, const void *out) {
+int check_ready(ttnet_plan *pl, const void *in, int64_t n, const void *out, const char *who = "ttnet_forward") {
   if (!pl || !in || !out) {
     set_error("null argument");
     return TTNET_E_INVALID;
   }
   if (!pl->finalized) {
-    set_error("ttnet_forward before ttnet_plan_finalize");
+    set_error("%s before ttnet_plan_finalize", who);
     return TTNET_E_STATE;
   }
   if (n < 1 || n > pl->desc.max_batch) {
@@ -1340,6 +1356,59 @@ int forward_impl(ttnet_plan *pl, int lane, const void *x_dev, bool u8, int64_t n
   return TTNET_OK;
 }
 
+// ttnet_certify_u8: the effective head, the stem's BatchNorm in float64, the slack of the stem bounds and Block_conv3's
+// table as words, from the state the plan was finalized with.  Host synchronisations and allocations: first call only.
+int prepare_certify(ttnet_plan *pl, hipStream_t s) {
+  auto &c = pl->cert;
+  if (c.ready) return TTNET_OK;
+  drop_certify(pl);
+  std::vector<float> w, b;
+  std::vector<double> sc, sh, hs, ht;
+  TT_TRY(fetch(pl->tensors["features.0.weight"], w));
+  TT_TRY(fetch(pl->tensors["features.0.bias"], b));
+  TT_TRY(fold_bn(pl, "features.2", sc, sh));
+  TT_TRY(fold_bn(pl, pl->head + ".BN2", hs, ht));
+  // slack_c = 2^-40 ((|w_c|_1 X + |bias_c|) |scale_c| + |shift_c|), X = the largest |normalised value| of a byte (ttnet.h)
+  double X = 0.0;
+  for (int ch = 0; ch < 3; ++ch) {
+    const double a = 1.0 / (255.0 * (double)pl->in_std[ch]), off = 255.0 * (double)pl->in_mean[ch];
+    X = std::max(X, std::max(fabs((0.0 - off) * a), fabs((255.0 - off) * a)));
+  }
+  std::vector<double> slack(64), bn(sc), hbn(hs);
+  bn.insert(bn.end(), sh.begin(), sh.end());
+  hbn.insert(hbn.end(), ht.begin(), ht.end());
+  for (int ch = 0; ch < 64; ++ch) {
+    double l1 = 0.0;
+    for (int i = 0; i < 27; ++i) l1 += fabs((double)w[ch * 27 + i]);
+    slack[ch] = ldexp((l1 * X + fabs((double)b[ch])) * fabs(sc[ch]) + fabs(sh[ch]), -40);
+  }
+  double *hbn_dev = nullptr;                           // the head's folded BatchNorm: needed by the build alone
+  auto build = [&]() -> int {
+    TT_TRY(dev_alloc(pl, &c.A, (size_t)pl->n_classes * pl->fcsize, false));
+    TT_TRY(dev_alloc(pl, &c.c0, pl->n_classes, false));
+    TT_TRY(dev_alloc(pl, &c.stem_bn, 128, false));
+    TT_TRY(dev_alloc(pl, &c.slack, 64, false));
+    TT_TRY(dev_alloc(pl, &c.t3w, 8 * 8 * 4, false));
+    TT_TRY(dev_alloc(pl, &hbn_dev, hbn.size(), false));
+    TT_HIP(hipMemcpy(c.stem_bn, bn.data(), bn.size() * 8, hipMemcpyHostToDevice));
+    TT_HIP(hipMemcpy(c.slack, slack.data(), slack.size() * 8, hipMemcpyHostToDevice));
+    TT_HIP(hipMemcpy(hbn_dev, hbn.data(), hbn.size() * 8, hipMemcpyHostToDevice));
+    TT_TRY(launch_certify_head((const float *)pl->tensors[pl->head + ".lin1.weight"].dev, (const float *)pl->tensors[pl->head + ".lin2.weight"].dev,
+                               (const float *)pl->tensors[pl->head + ".lin2.bias"].dev, hbn_dev, (const uint8_t *)pl->blocks[0].c3.table, c.A,
+                               c.c0, c.t3w, s));
+    TT_HIP(hipStreamSynchronize(s));
+    return TTNET_OK;
+  };
+  const int st = build();
+  dev_free(pl, hbn_dev);                               // on every exit
+  if (st != TTNET_OK) {
+    drop_certify(pl);                                  // nothing half built stays
+    return st;
+  }
+  c.ready = true;
+  return TTNET_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1401,6 +1470,7 @@ int ttnet_plan_set_tensor(ttnet_plan *pl, const char *key, const void *ptr, cons
   TT_HIP(hipMemcpy(t.dev, ptr, t.bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
   t.set = true;
   pl->finalized = false;
+  drop_certify(pl);
   // new parameters for a Block_TT invalidate a table injected with ttnet_plan_set_table
   for (BlockTT *b : all_block_tts(pl))
     if (k.compare(0, b->g.name.size() + 1, b->g.name + ".") == 0) b->user_table = false;
@@ -1694,9 +1764,86 @@ int ttnet_plan_set_input_norm(ttnet_plan *pl, const float *mean3, const float *s
   std::copy(std3, std3 + 3, pl->in_std);
   (void)hipSetDevice(pl->device);
   TT_TRY(invalidate_graphs(pl));                       // as for a new tensor: what was captured ran with the old constants
+  if (pl->cert.ready) {
+    TT_HIP(hipDeviceSynchronize());
+    drop_certify(pl);                                  // (the slack of the stem bounds depends on the constants)
+  }
   if (!pl->finalized) return TTNET_OK;                 // (finalize folds them into the uint8 stem's weights)
   TT_HIP(hipDeviceSynchronize());                      // no forward may be reading the buffers that are rewritten in place
   return pl->path == GatePath::VAlexnet ? prepare_va_stem_u8(pl) : prepare_stem_u8(pl);
+}
+
+int ttnet_certify_u8(ttnet_plan *pl, int lane, const uint8_t *x_nhwc_dev, int64_t n, const int32_t *classes_dev, double eps,
+                     int enum_bits, double min_margin, void *rows_dev, uint64_t *planes_dev, void *stream) {
+  if (pl && pl->path != GatePath::VAlexnet) {
+    set_error("certify: only the vAlexnet variant is served: the certificate needs an affine head (no polynomial, no float last "
+              "block) and truth tables of at most 8 inputs");
+    return TTNET_E_UNSUPPORTED;
+  }
+  TT_TRY(check_ready(pl, x_nhwc_dev, n, rows_dev, "ttnet_certify_u8"));
+  if (!classes_dev) {
+    set_error("null argument");
+    return TTNET_E_INVALID;
+  }
+  if (!(eps >= 0.0) || !std::isfinite(eps) || enum_bits < 0 || enum_bits > 12 || std::isnan(min_margin)) {
+    set_error("certify: eps = %g (finite, >= 0), enum_bits = %d (0..12), min_margin = %g", eps, enum_bits, min_margin);
+    return TTNET_E_INVALID;
+  }
+  if (((uintptr_t)x_nhwc_dev & 3u) || ((uintptr_t)classes_dev & 3u) || ((uintptr_t)rows_dev & 7u) || ((uintptr_t)planes_dev & 7u)) {
+    set_error("certify: the images and classes must be 4-byte aligned, the records and planes 8-byte aligned");
+    return TTNET_E_INVALID;
+  }
+  if (lane < 0 || lane >= (int)pl->lanes.size()) {
+    set_error("certify: lane %d but the plan has %d (ttnet_plan_set_lanes)", lane, (int)pl->lanes.size());
+    return TTNET_E_INVALID;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  TT_HIP(hipSetDevice(pl->device));
+  TT_TRY(prepare_certify(pl, s));
+  ttnet_plan::Lane &L = pl->lanes[lane];
+  const size_t nb = (size_t)pl->desc.max_batch, stem_w = 64 * 10, feat_w = 256 * 11;
+  if (!L.cert_planes) TT_TRY(dev_alloc(pl, &L.cert_planes, nb * (2 * (stem_w + feat_w) + 10), false));
+  const MultiHead &mh = pl->blocks[0];
+  CertifyArgs a{};
+  a.n = (int)n;
+  a.x = x_nhwc_dev;
+  a.classes = classes_dev;
+  for (int c = 0; c < 3; ++c) {
+    a.norm.a[c] = 1.0 / (255.0 * (double)pl->in_std[c]);
+    a.norm.off[c] = 255.0 * (double)pl->in_mean[c];
+  }
+  a.eps = eps;
+  a.min_margin = min_margin;
+  a.enum_bits = enum_bits;
+  a.w = (const float *)pl->tensors["features.0.weight"].dev;
+  a.bias = (const float *)pl->tensors["features.0.bias"].dev;
+  a.stem_bn = pl->cert.stem_bn;
+  a.slack = pl->cert.slack;
+  a.t1 = (const uint32_t *)mh.c1.table;
+  a.t2 = (const uint32_t *)mh.c2.table;
+  a.t3 = (const uint8_t *)mh.c3.table;
+  a.t3w = pl->cert.t3w;
+  a.A = pl->cert.A;
+  a.c0 = pl->cert.c0;
+  a.stem_lo = L.cert_planes;
+  a.stem_hi = a.stem_lo + nb * stem_w;
+  a.feat_lo = a.stem_hi + nb * stem_w;
+  a.feat_hi = a.feat_lo + nb * feat_w;
+  a.sums = (double *)(a.feat_hi + nb * feat_w);
+  a.rows = rows_dev;
+  pl->timing_used = 0;                                // (with profiling on, ttnet_plan_last_timings then speaks of this call)
+  TT_TIMED(pl, "certify.stem", s, launch_certify(a, kCertifyStem, s));
+  TT_TIMED(pl, "certify.block", s, launch_certify(a, kCertifyBlock, s));
+  TT_TIMED(pl, "certify.margin", s, launch_certify(a, kCertifyMargin, s));
+  if (enum_bits > 0) TT_TIMED(pl, "certify.enum", s, launch_certify(a, kCertifyEnum, s));
+  if (planes_dev) {                                   // [stem lo][stem hi][feature lo][feature hi], each for n images
+    uint64_t *dst = planes_dev;
+    for (const auto &pw : {std::pair<const uint64_t *, size_t>{a.stem_lo, stem_w}, {a.stem_hi, stem_w}, {a.feat_lo, feat_w}, {a.feat_hi, feat_w}}) {
+      TT_HIP(hipMemcpyAsync(dst, pw.first, (size_t)n * pw.second * 8, hipMemcpyDeviceToDevice, s));
+      dst += (size_t)n * pw.second;
+    }
+  }
+  return TTNET_OK;
 }
 
 int ttnet_forward_from_stem_bits(ttnet_plan *pl, const uint64_t *rows_dev, int64_t n, float *logits_dev,
@@ -1803,6 +1950,7 @@ int ttnet_plan_set_table(ttnet_plan *pl, const char *name, const void *src_host,
   TT_HIP(hipSetDevice(pl->device));
   TT_TRY(invalidate_graphs(pl));
   TT_HIP(hipMemcpy(b->table, raw.data(), raw.size(), hipMemcpyHostToDevice));
+  drop_certify(pl);
   b->user_table = true;
   b->near_ties = -1;
   if (pl->path == GatePath::Fused)          // the kernels read images derived from the conv1 / conv2 / conv3 tables

@@ -375,6 +375,36 @@ void va_stem_u8_fold(const float *w, const float *bias, const float *mean3, cons
 int launch_va_block(const uint64_t *x_rp, const void *t1, const void *t2, const void *t3, uint64_t *y, int n, hipStream_t s);
 int launch_va_feat(const uint64_t *y, void *feat_frag, int n, hipStream_t s);
 int launch_va_frag_to_flat(const void *af, float *out, int n, hipStream_t s);
+// certified robustness of the vAlexnet variant (certify.hip; include/ttnet.h: ttnet_certify_u8)
+struct CertifyNorm {
+  double a[3], off[3];      // normalised value of a (real) byte level v of channel c: (v - off[c]) * a[c]
+};
+struct CertifyArgs {
+  int n;
+  const uint8_t *x;         // uint8 HWC [n][32][32][3], 4-byte aligned
+  const int32_t *classes;   // [n]
+  CertifyNorm norm;
+  double eps, min_margin;
+  int enum_bits;
+  const float *w, *bias;    // the stem's convolution
+  const double *stem_bn;    // [2][64]: folded scale, shift of features.2
+  const double *slack;      // [64]: outward widening of the stem bounds
+  const uint32_t *t1, *t2;  // tables of Block_conv1 / Block_conv2 (internal layout)
+  const uint8_t *t3;        // table of Block_conv3
+  const uint64_t *t3w;      // the same as [8 groups][8 outputs][4] words of 64 entries
+  const double *A, *c0;     // effective head, stored [30976 features][10 classes], and [10]
+  double *sums;             // [n][10]: sum_f D_f ylo_f of stage 1, from which stage 2 starts
+  uint64_t *stem_lo, *stem_hi;   // [n][64][10]
+  uint64_t *feat_lo, *feat_hi;   // [n][256][11]
+  void *rows;               // n records of 32 bytes
+};
+// A = lin2 diag(scale) lin1, c0 = lin2 shift + bias (head_bn = [2][100] folded scale, shift of BN2) and t3w from t3
+int launch_certify_head(const float *lin1, const float *lin2, const float *bias, const double *head_bn, const uint8_t *t3, double *A,
+                        double *c0, uint64_t *t3w, hipStream_t s);
+// one step of a call, in this order: the stem planes, the block's planes, the interval margin (writes the records), the
+// enumeration (updates them)
+constexpr int kCertifyStem = 0, kCertifyBlock = 1, kCertifyMargin = 2, kCertifyEnum = 3;
+int launch_certify(const CertifyArgs &a, int step, hipStream_t s);
 int launch_cp_to_rp(const uint16_t *cp, uint64_t *rp, int n, int C, int H, int W, hipStream_t s);
 int launch_rp_to_cp(const uint64_t *rp, uint16_t *cp, int n, int C, int H, int W, hipStream_t s);
 // feature planes (fragment order) -> float32 [n][(16g+k)*PP + pp] (reference Flatten order)

@@ -44,7 +44,7 @@ def read_class_names(path: str) -> List[str]:
 
 
 @contextlib.contextmanager
-def _replacing(path: Optional[str], mode: str = "w"):
+def replacing(path: Optional[str], mode: str = "w"):
     """A file that becomes ``path`` when the block ends well; ``path`` None: standard output."""
     if path is None:
         yield sys.stdout.buffer if "b" in mode else sys.stdout
@@ -79,7 +79,7 @@ def write_predictions_csv(path: Optional[str], paths: Sequence[str], targets: Op
     if covered is not None and len(covered) != len(paths):
         raise ValueError(f"{len(paths)} paths, {len(covered)} covered flags")
     k = pred.k
-    with _replacing(path) as f:
+    with replacing(path) as f:
         w = csv.writer(f, lineterminator="\n")
         w.writerow(["path", "target"] + [c for i in range(1, k + 1) for c in (f"class_{i}", f"logprob_{i}")] +
                    (["covered"] if covered is not None else []))
@@ -95,7 +95,7 @@ def write_predictions_csv(path: Optional[str], paths: Sequence[str], targets: Op
 def write_care_rows_csv(path: Optional[str], care):
     """``care``: ``evaluate.CareResult``."""
     rows, covered = np.asarray(care.rows), care.covered
-    with _replacing(path) as f:
+    with replacing(path) as f:
         w = csv.writer(f, lineterminator="\n")
         w.writerow(["index", "covered"] + list(care.blocks))
         for i in range(rows.shape[0]):
@@ -127,7 +127,7 @@ def care_summary_rows(care, lookups_per_image) -> List[list]:
 
 
 def write_care_summary_csv(path: Optional[str], care, lookups_per_image):
-    with _replacing(path) as f:
+    with replacing(path) as f:
         csv.writer(f, lineterminator="\n").writerows(care_summary_rows(care, lookups_per_image))
 
 
@@ -156,18 +156,18 @@ def per_class_rows(counts: np.ndarray, names: Optional[Sequence[str]] = None) ->
 
 
 def write_per_class_csv(path: Optional[str], counts: np.ndarray, names: Optional[Sequence[str]] = None):
-    with _replacing(path) as f:
+    with replacing(path) as f:
         csv.writer(f, lineterminator="\n").writerows(per_class_rows(counts, names))
 
 
 def write_confusion(path: str, confusion: np.ndarray):
-    with _replacing(path, "wb") as f:
+    with replacing(path, "wb") as f:
         np.save(f, np.ascontiguousarray(confusion, dtype=np.int64))
 
 
 def save_table_usage(path: str, usage) -> None:
     """``{Block_TT name: int64 [groups, 2^n]}`` -> a compressed ``.npz`` with one array per block name."""
-    with _replacing(path, "wb") as f:
+    with replacing(path, "wb") as f:
         np.savez_compressed(f, **{k: np.ascontiguousarray(v, dtype=np.int64) for k, v in usage.items()})
 
 
@@ -206,7 +206,7 @@ def coverage_rows(usage, tables=None) -> List[list]:
 
 
 def write_coverage_csv(path: Optional[str], usage, tables=None):
-    with _replacing(path) as f:
+    with replacing(path) as f:
         csv.writer(f, lineterminator="\n").writerows(coverage_rows(usage, tables))
 
 
@@ -223,7 +223,7 @@ def gate_rows(full, seen, inputs) -> List[list]:
 
 
 def write_gates_csv(path: Optional[str], full, seen, inputs):
-    with _replacing(path) as f:
+    with replacing(path) as f:
         csv.writer(f, lineterminator="\n").writerows(gate_rows(full, seen, inputs))
 
 
@@ -264,5 +264,5 @@ def rule_support_rows(support, pruned=None) -> List[list]:
 
 
 def write_rule_support_csv(path: Optional[str], support, pruned=None):
-    with _replacing(path) as f:
+    with replacing(path) as f:
         csv.writer(f, lineterminator="\n").writerows(rule_support_rows(support, pruned))

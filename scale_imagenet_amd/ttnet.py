@@ -348,6 +348,13 @@ class _TTNetBase(nn.Module):
                                              C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
         return out
 
+    def certify_u8(self, x_u8: torch.Tensor, classes, eps: float, enum_bits: int = 10, min_margin: float = 1e-6, lane: int = 0,
+                   return_planes: bool = False):
+        """Certified L-infinity robustness (vAlexnet only): does image i keep ``classes[i]`` when every byte of ``x_u8`` may
+        move by up to ``eps`` byte levels?  See ``scale_imagenet_amd.certify.certify_u8``."""
+        from . import certify
+        return certify.certify_u8(self, x_u8, classes, eps, enum_bits, min_margin, lane, return_planes)
+
     def export_truth_tables(self, block_name: str, out_dir: str, block: int = 0, sub_block: int = 0, filters=None,
                             max_expr_bits: int = 9, usage=None, minimiser: str = "sympy", rounds: int = 0,
                             min_count: int = 1):
