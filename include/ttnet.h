@@ -657,6 +657,75 @@ int ttnet_cover_support(const uint32_t *cubes_dev, const int32_t *counts_dev, in
 int ttnet_certify_u8(ttnet_plan *plan, int lane, const uint8_t *x_nhwc_dev, int64_t n, const int32_t *classes_dev, double eps,
                      int enum_bits, double min_margin, void *rows_dev, uint64_t *planes_dev, void *stream);
 
+/* Falsified L-infinity robustness of TTNET_VALEXNET on the device: a search for uint8 witnesses (csrc/attack.hip; DESIGN.md:
+ * falsified robustness).  ttnet_certify_u8 bounds the robust accuracy from below; an image is FALSIFIED when a concrete uint8
+ * image inside the integer box [max(0, b - e), min(255, b + e)] (e = eps_levels byte levels; the box lies inside the real box
+ * of the certificate at eps >= e) is held on which ttnet_forward_u8 does not give the class.  The forward itself checks a
+ * witness, so falsified is never wrong; the search decides nothing, an image it leaves open stays open.  The caller drives the
+ * rounds with the two entries below and ttnet_forward_u8:
+ *
+ *   round 0   forward of x0 (n images), then ttnet_attack_select_u8 with cand = x0, n_cand = 1, round = 0: initialises x_cur = x0,
+ *             the records, the runner-ups and the active flags.
+ *   round r   forward of x_cur on `lane` (n images; in round 1 the forward of x0 still stands), ttnet_attack_propose_u8 on that
+ *             lane, forwards of the 8 n candidates (any lane, chunks of at most max_batch) into one [8 n][10] float32 buffer,
+ *             ttnet_attack_select_u8 with n_cand = 8.
+ *
+ * The float32 fields of a record are those of the forwards that ran: the last bits of a logit depend on the number of images in
+ * a forward (lin1's split-K count; the same up to 256 images), so a caller who wants records that do not depend on the batch an
+ * image came in keeps every forward of a search at or below 256 images, as scale_imagenet_amd/attack.py does.
+ *
+ * ttnet_attack_propose_u8 reads the stage buffers of the forward last issued on `lane` ("features.4" stem bits, "features.5"
+ * feature bits), which must have been the forward of xcur_dev.  Per image with active_dev[i] != 0, class c = classes_dev[i] and
+ * runner-up j = worst_dev[i] (both in 0..9 and different; else the image counts as not active), with D_f = A[f][c] - A[f][j]
+ * (float64, A of ttnet_certify_u8):
+ *   gains      for every UNKNOWN stem bit s = (ch, py, px) -- the planes lo and hi of stem_planes_dev differ there; uint64
+ *              [2][n][64][10], lo then hi, the first two parts of ttnet_certify_u8's planes_dev --
+ *                g_s = sum D_f (y_f(bits with s flipped) - y_f(bits))
+ *              over the at most 21 features whose windows hold s (6 of conv1, 6 of conv2, 8 of conv3, 1 of out4), in that branch
+ *              order and raster order of the output position (output channel for conv3) inside a branch; every term is +D_f,
+ *              -D_f or nothing; the flipped lookup is the table read at index ^ mask; paddings are known zeros.  g_s = 0 for
+ *              every other bit.  gains_dev: NULL, or [n][6400] float64 that receives g ([64][10][10]; zeros for an image that is
+ *              not active).
+ *   push       wt_s = -g_s (bit_s == 0 ? +1 : -1) sign(bn_scale[ch]) (sign(0) = +1; the folded scale of the stem BatchNorm):
+ *              mode 0 for the unknown bits with g_s < 0 and zero elsewhere, mode 1 for every unknown bit.
+ *   score      score[y][x][k] = sum_s wt_s Wsum[ch_s][k][y - 3 py_s + 1][x - 3 px_s + 1] over the bits whose 5 x 5 field holds the
+ *              pixel (at most 2 x 2 pooled cells x 64 channels), ch ascending, then py, then px, each product and each sum
+ *              rounded on its own.  Wsum[ch][k][5][5] = the nine 3 x 3 stem kernels of (ch, k) shifted to the nine positions
+ *              (dy, dx ascending) of the MaxPool(3) window and summed, float64 from the float32 weights.  Row and column 31 lie
+ *              in no field and never change.
+ *   candidates cand_dev uint8 [n][8][32][32][3], index 4 mode + tau index, tau in {0, 1/8, 1/4, 1/2}: with M = max |score| of the
+ *              image and mode a byte is selected when score != 0 and |score| > tau M; a selected byte takes the upper end of the
+ *              box of x0_dev's byte when score > 0, the lower end when score < 0; every other byte keeps xcur_dev's.  An image
+ *              that is not active gets eight copies of its xcur_dev image.
+ *
+ * ttnet_attack_select_u8 takes logits_dev float32 [n * n_cand][10] (image-major, as cand_dev [n][n_cand][32][32][3]).  Per active
+ * image and candidate m = l[c] - max_{j != c} l[j] in float32 (runner-up: the first of equal maxima); a candidate with a NaN logit
+ * is skipped; the smallest m wins, ties go to the lowest index.  If it is below the image's best so far the candidate is copied
+ * to xcur_dev, worst_dev[i] becomes its runner-up and best, worst, round, changed (bytes of x_cur that differ from x0) and linf
+ * (largest |x_cur - x0|) are recorded; the image is falsified and active_dev[i] becomes 0 when m < -min_margin.  round = 0
+ * initialises first: x_cur = x0, worst -1, active = (class in 0..9), record { margin0 NaN, best +inf, the rest 0 }; margin0 is
+ * candidate 0's m; a falsified image then gets status 1 (wrong at x0), in later rounds 2.  A class outside 0..9 is NOT an error:
+ * that image gets margin0 = best = -inf, worst -1, status 0 and is never active.  tried counts the candidates compared.
+ * rows_dev holds n records of 32 bytes (8-byte aligned):
+ *   { float margin0; float best; int32 worst; int32 status; int32 round; int32 changed; int32 linf; int32 tried; }
+ * status: 0 open, 1 wrong at x0, 2 falsified by the search.  With min_margin at least the logit tolerance of ttnet_forward_u8 a
+ * falsified image is not robust for the exact-arithmetic network either, the one ttnet_certify_u8 speaks of.
+ *
+ * Both calls launch on `stream` and return; no read-back and no synchronisation, except that the first propose after a (re)load
+ * builds A and Wsum as ttnet_certify_u8 does (and synchronises once).  Fixed summation order, integer work and maxima: the same
+ * input gives the same bytes.  With profiling on, ttnet_plan_last_timings reports the step "attack.propose" / "attack.select" of
+ * the call.  Errors: eps_levels outside 0..64, n_cand outside 1..8, round < 0, min_margin NaN, a bad lane, n outside
+ * [1, max_batch], a NULL or misaligned pointer (4 bytes for images, logits, classes, worst_dev, active_dev and candidates, 8 for
+ * records, planes and gains; gains_dev alone may be NULL), xcur_dev equal to cand_dev or x0_dev in select TTNET_E_INVALID; any
+ * variant other than TTNET_VALEXNET TTNET_E_UNSUPPORTED; before finalize, or propose when the last forward on `lane` ran another
+ * n, TTNET_E_STATE.  Nothing is launched in an error case. */
+int ttnet_attack_propose_u8(ttnet_plan *plan, int lane, const uint8_t *x0_dev, const uint8_t *xcur_dev, int64_t n,
+                            const int32_t *classes_dev, const int32_t *worst_dev, const uint64_t *stem_planes_dev, int eps_levels,
+                            const int32_t *active_dev, uint8_t *cand_dev, double *gains_dev, void *stream);
+int ttnet_attack_select_u8(ttnet_plan *plan, const uint8_t *cand_dev, const float *logits_dev, int64_t n, int n_cand,
+                           const int32_t *classes_dev, double min_margin, const uint8_t *x0_dev, uint8_t *xcur_dev, void *rows_dev,
+                           int32_t *worst_dev, int32_t *active_dev, int round, void *stream);
+
 /* Integer facts about the plan: "fcsize", "n_classes", "n_state_tensors", "max_batch",
  * "near_ties:<block_tt name>" (entries with |pre-activation| < 1e-5 found while building
  * that table), "table_bytes", "usage_bytes", "care_bytes", "care_blocks", "last_n:<lane>" (images of the

@@ -7,7 +7,9 @@ dataset holds, bytes: ``read_cifar10`` transposes the files' planar CHW records 
 ``device_batches`` uploads the whole split once (30 MB for the test set) and hands out slices of it, and
 ``model.forward_u8`` normalises inside the stem kernel (include/ttnet.h: ttnet_forward_u8).  ``evaluate`` sends uint8
 tensors there by itself.  ``--certify EPS[,EPS...]`` then certifies the labels against perturbations of up to EPS byte levels
-over the same device-resident bytes (``scale_imagenet_amd.certify``) and prints the verified accuracy per eps.
+over the same device-resident bytes (``scale_imagenet_amd.certify``) and prints the verified accuracy per eps; with
+``--attack`` a search for uint8 counter-examples follows (``scale_imagenet_amd.attack``) and one ``Robust..`` line per eps
+brackets the robust accuracy from both sides.
 
 Both published layouts are read: ``cifar-10-batches-py`` (pickles ``test_batch`` / ``data_batch_1..5``, ``batches.meta``)
 and ``cifar-10-batches-bin`` (``*.bin`` records of 1 label byte + 3072 planar bytes, ``batches.meta.txt``).  The pickles go
@@ -211,6 +213,17 @@ def build_parser() -> argparse.ArgumentParser:
     cert.add_argument("--certify_min_margin", type=float, default=1e-6, metavar="M", help="certified means lower bound > M")
     cert.add_argument("--certify_rows", type=str, default=None, metavar="FILE",
                       help="CSV eps,index,class,stage,certified,lb,lb_interval,worst,unknown_stem,unknown_feat of every image")
+    att = p.add_argument_group("falsified robustness (with --certify: one more stdout line per eps, after its `Verified..`)")
+    att.add_argument("--attack", action="store_true",
+                     help="search the box of floor(EPS) byte levels for a uint8 image that loses the label and print `Robust.. eps=E "
+                          "certified a/N <= robust <= b/N (falsified f: wrong at x0 w, by search s; open o)`.  A search, not a "
+                          "decision: an open image stays open.  An EPS below 1 is skipped (scale_imagenet_amd.attack)")
+    att.add_argument("--attack_rounds", type=int, default=3, metavar="R", help="rounds of the search (0..8; 0: only the images wrong at x0)")
+    att.add_argument("--attack_rows", type=str, default=None, metavar="FILE",
+                     help="CSV eps,index,class,status,falsified,margin0,best,worst,round,changed,linf,tried of every image")
+    att.add_argument("--attack_witnesses", type=str, default=None, metavar="FILE",
+                     help=".npz: per searched eps `eps_<E>` uint8 [N][32][32][3], the image of the smallest margin found (a "
+                          "counter-example where the record says falsified), and `status_<E>`")
     return p
 
 
@@ -278,10 +291,35 @@ def run(args) -> int:
     if eps_list:
         from . import certify
         sums = certify.certify_batches(model, batches, eps_list, args.certify_enum, args.certify_min_margin)
+        searched = {}
+        if args.attack:                                         # the same min_margin for both sides of the bracket
+            from . import attack
+            todo = [e for e in eps_list if e >= 1]
+            found = attack.attack_batches(model, batches, todo, args.attack_rounds, args.certify_min_margin,
+                                          keep_witnesses=bool(args.attack_witnesses))
+            searched = dict(zip(todo, found))
         for s in sums:
             print(certify.verified_line(s))
+            if not args.attack:
+                continue
+            if s["eps"] not in searched:
+                print(f"Robust.. eps={s['eps']:g} not searched: the search moves whole byte levels and floor(eps) is 0")
+                continue
+            a = searched[s["eps"]]
+            note = "" if a["levels"] == s["eps"] else f" [searched at floor(eps) = {a['levels']} byte levels]"
+            print(attack.robust_line(s["eps"], s["rows"], a["rows"]) + note)
         if args.certify_rows:
             certify.write_rows_csv(args.certify_rows, sums, targets.tolist())
+        if args.attack_rows:
+            attack.write_rows_csv(args.attack_rows, list(searched.values()), targets.tolist())
+        if args.attack_witnesses:
+            from .report import replacing
+            arrays = {}
+            for e, a in searched.items():
+                arrays[f"eps_{e:g}"] = a["witnesses"]
+                arrays[f"status_{e:g}"] = a["rows"]["status"]
+            with replacing(args.attack_witnesses, "wb") as f:
+                np.savez(f, **arrays)
     return 0
 
 
@@ -296,6 +334,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         raise SystemExit("--certify_enum must be in [0, 12]")
     if args.certify_rows and not args.certify:
         raise SystemExit("--certify_rows needs --certify")
+    if args.attack and not args.certify:
+        raise SystemExit("--attack needs --certify EPS[,EPS...]")
+    if (args.attack_rows or args.attack_witnesses) and not args.attack:
+        raise SystemExit("--attack_rows and --attack_witnesses need --attack")
+    if not 0 <= args.attack_rounds <= 8:
+        raise SystemExit("--attack_rounds must be in [0, 8]")
+    if args.attack and any(e >= 65 for e in certify_eps_list(args.certify)):
+        raise SystemExit("--attack: eps must be below 65 byte levels")
     return run(args)
 
 

@@ -121,6 +121,7 @@ struct ttnet_plan {
     double *A = nullptr, *c0 = nullptr;       // effective head, stored [30976][10], and [10]
     double *stem_bn = nullptr, *slack = nullptr;   // [2][64] folded features.2, [64] widening of the stem bounds
     uint64_t *t3w = nullptr;                  // Block_conv3's table as 64-entry words
+    double *wsum = nullptr;                   // [64][3][5][5] summed stem kernels (attack.hip)
     bool ready = false;
   } cert;
   float *full_gel = nullptr;        // full variant: GELU tables of the fast kernels (launch_full_gelu_tables), shared by all lanes
@@ -249,7 +250,7 @@ void dev_free(ttnet_plan *pl, void *ptr) {
 // what ttnet_certify_u8 derived from the state goes with the state (the lanes' planes hold no state and stay)
 void drop_certify(ttnet_plan *pl) {
   auto &c = pl->cert;
-  for (void *ptr : {(void *)c.A, (void *)c.c0, (void *)c.stem_bn, (void *)c.slack, (void *)c.t3w}) dev_free(pl, ptr);
+  for (void *ptr : {(void *)c.A, (void *)c.c0, (void *)c.stem_bn, (void *)c.slack, (void *)c.t3w, (void *)c.wsum}) dev_free(pl, ptr);
   c = ttnet_plan::Certify{};
 }
 
@@ -1389,6 +1390,7 @@ int prepare_certify(ttnet_plan *pl, hipStream_t s) {
     TT_TRY(dev_alloc(pl, &c.stem_bn, 128, false));
     TT_TRY(dev_alloc(pl, &c.slack, 64, false));
     TT_TRY(dev_alloc(pl, &c.t3w, 8 * 8 * 4, false));
+    TT_TRY(dev_alloc(pl, &c.wsum, 64 * 3 * 25, false));
     TT_TRY(dev_alloc(pl, &hbn_dev, hbn.size(), false));
     TT_HIP(hipMemcpy(c.stem_bn, bn.data(), bn.size() * 8, hipMemcpyHostToDevice));
     TT_HIP(hipMemcpy(c.slack, slack.data(), slack.size() * 8, hipMemcpyHostToDevice));
@@ -1396,6 +1398,7 @@ int prepare_certify(ttnet_plan *pl, hipStream_t s) {
     TT_TRY(launch_certify_head((const float *)pl->tensors[pl->head + ".lin1.weight"].dev, (const float *)pl->tensors[pl->head + ".lin2.weight"].dev,
                                (const float *)pl->tensors[pl->head + ".lin2.bias"].dev, hbn_dev, (const uint8_t *)pl->blocks[0].c3.table, c.A,
                                c.c0, c.t3w, s));
+    TT_TRY(launch_attack_wsum((const float *)pl->tensors["features.0.weight"].dev, c.wsum, s));
     TT_HIP(hipStreamSynchronize(s));
     return TTNET_OK;
   };
@@ -1843,6 +1846,101 @@ int ttnet_certify_u8(ttnet_plan *pl, int lane, const uint8_t *x_nhwc_dev, int64_
       dst += (size_t)n * pw.second;
     }
   }
+  return TTNET_OK;
+}
+
+// what the two attack entries share: the variant, the plan's state and the batch size
+static int attack_ready(ttnet_plan *pl, const void *a, int64_t n, const void *b, const char *who) {
+  if (pl && pl->path != GatePath::VAlexnet) {
+    set_error("%s: only the vAlexnet variant is served: the search needs the certificate's stem planes, an affine head and truth "
+              "tables of at most 8 inputs", who);
+    return TTNET_E_UNSUPPORTED;
+  }
+  return check_ready(pl, a, n, b, who);
+}
+
+int ttnet_attack_propose_u8(ttnet_plan *pl, int lane, const uint8_t *x0_dev, const uint8_t *xcur_dev, int64_t n,
+                            const int32_t *classes_dev, const int32_t *worst_dev, const uint64_t *stem_planes_dev, int eps_levels,
+                            const int32_t *active_dev, uint8_t *cand_dev, double *gains_dev, void *stream) {
+  TT_TRY(attack_ready(pl, x0_dev, n, cand_dev, "ttnet_attack_propose_u8"));
+  if (!xcur_dev || !classes_dev || !worst_dev || !stem_planes_dev || !active_dev) {
+    set_error("null argument");
+    return TTNET_E_INVALID;
+  }
+  if (eps_levels < 0 || eps_levels > 64) {
+    set_error("attack_propose: eps_levels = %d (0..64)", eps_levels);
+    return TTNET_E_INVALID;
+  }
+  if ((((uintptr_t)x0_dev | (uintptr_t)xcur_dev | (uintptr_t)classes_dev | (uintptr_t)worst_dev | (uintptr_t)active_dev | (uintptr_t)cand_dev) & 3u) ||
+      (((uintptr_t)stem_planes_dev | (uintptr_t)gains_dev) & 7u)) {
+    set_error("attack_propose: the images, classes, runner-ups, flags and candidates must be 4-byte aligned, the planes and gains 8-byte aligned");
+    return TTNET_E_INVALID;
+  }
+  if (lane < 0 || lane >= (int)pl->lanes.size()) {
+    set_error("attack_propose: lane %d but the plan has %d (ttnet_plan_set_lanes)", lane, (int)pl->lanes.size());
+    return TTNET_E_INVALID;
+  }
+  ttnet_plan::Lane &L = pl->lanes[lane];
+  if (L.last_n != n) {
+    set_error("attack_propose: n=%lld but the last forward on lane %d ran %lld images", (long long)n, lane, (long long)L.last_n);
+    return TTNET_E_STATE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  TT_HIP(hipSetDevice(pl->device));
+  TT_TRY(prepare_certify(pl, s));
+  const MultiHead &mh = pl->blocks[0];
+  AttackProposeArgs a{};
+  a.n = (int)n;
+  a.levels = eps_levels;
+  a.x0 = x0_dev;
+  a.xcur = xcur_dev;
+  a.classes = classes_dev;
+  a.worst = worst_dev;
+  a.active = active_dev;
+  a.stem = L.x_rp[0];
+  a.feat = L.va_y;
+  a.plane_lo = stem_planes_dev;
+  a.plane_hi = stem_planes_dev + (size_t)n * 64 * 10;
+  a.t1 = (const uint32_t *)mh.c1.table;
+  a.t2 = (const uint32_t *)mh.c2.table;
+  a.t3w = pl->cert.t3w;
+  a.A = pl->cert.A;
+  a.bn_scale = pl->cert.stem_bn;
+  a.wsum = pl->cert.wsum;
+  a.cand = cand_dev;
+  a.gains = gains_dev;
+  pl->timing_used = 0;                                // (with profiling on, ttnet_plan_last_timings then speaks of this call)
+  TT_TIMED(pl, "attack.propose", s, launch_attack_propose(a, s));
+  return TTNET_OK;
+}
+
+int ttnet_attack_select_u8(ttnet_plan *pl, const uint8_t *cand_dev, const float *logits_dev, int64_t n, int n_cand,
+                           const int32_t *classes_dev, double min_margin, const uint8_t *x0_dev, uint8_t *xcur_dev, void *rows_dev,
+                           int32_t *worst_dev, int32_t *active_dev, int round, void *stream) {
+  TT_TRY(attack_ready(pl, cand_dev, n, logits_dev, "ttnet_attack_select_u8"));
+  if (!classes_dev || !x0_dev || !xcur_dev || !rows_dev || !worst_dev || !active_dev) {
+    set_error("null argument");
+    return TTNET_E_INVALID;
+  }
+  if (n_cand < 1 || n_cand > 8 || round < 0 || std::isnan(min_margin)) {
+    set_error("attack_select: n_cand = %d (1..8), round = %d (>= 0), min_margin = %g", n_cand, round, min_margin);
+    return TTNET_E_INVALID;
+  }
+  if ((((uintptr_t)cand_dev | (uintptr_t)logits_dev | (uintptr_t)classes_dev | (uintptr_t)x0_dev | (uintptr_t)xcur_dev | (uintptr_t)worst_dev |
+        (uintptr_t)active_dev) & 3u) || ((uintptr_t)rows_dev & 7u)) {
+    set_error("attack_select: the images, logits, classes, runner-ups and flags must be 4-byte aligned, the records 8-byte aligned");
+    return TTNET_E_INVALID;
+  }
+  if (xcur_dev == cand_dev || xcur_dev == x0_dev) {
+    set_error("attack_select: xcur_dev must be a buffer of its own");
+    return TTNET_E_INVALID;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  TT_HIP(hipSetDevice(pl->device));
+  pl->timing_used = 0;
+  TT_TIMED(pl, "attack.select", s,
+           launch_attack_select(cand_dev, logits_dev, (int)n, n_cand, classes_dev, (float)min_margin, x0_dev, xcur_dev, rows_dev, worst_dev,
+                                active_dev, round, s));
   return TTNET_OK;
 }
 

@@ -405,6 +405,26 @@ int launch_certify_head(const float *lin1, const float *lin2, const float *bias,
 // enumeration (updates them)
 constexpr int kCertifyStem = 0, kCertifyBlock = 1, kCertifyMargin = 2, kCertifyEnum = 3;
 int launch_certify(const CertifyArgs &a, int step, hipStream_t s);
+// falsified robustness of the vAlexnet variant (attack.hip; include/ttnet.h: ttnet_attack_propose_u8, ttnet_attack_select_u8)
+struct AttackProposeArgs {
+  int n, levels;
+  const uint8_t *x0, *xcur; // uint8 HWC [n][32][32][3]
+  const int32_t *classes, *worst, *active;   // [n]
+  const uint64_t *stem;     // [n][64][10]: the stem bits of the lane's last forward (stage "features.4")
+  const uint64_t *feat;     // [n][256][11]: its feature bits (stage "features.5")
+  const uint64_t *plane_lo, *plane_hi;       // [n][64][10]: the certificate's stem planes
+  const uint32_t *t1, *t2;  // tables of Block_conv1 / Block_conv2 (internal layout)
+  const uint64_t *t3w;      // Block_conv3's table as words (CertifyArgs)
+  const double *A;          // effective head [30976 features][10 classes]
+  const double *bn_scale;   // [64]: folded scale of features.2
+  const double *wsum;       // [64][3][5][5]
+  uint8_t *cand;            // [n][8][32][32][3]
+  double *gains;            // nullptr or [n][6400]
+};
+int launch_attack_wsum(const float *w, double *wsum, hipStream_t s);
+int launch_attack_propose(const AttackProposeArgs &a, hipStream_t s);
+int launch_attack_select(const uint8_t *cand, const float *logits, int n, int n_cand, const int32_t *classes, float min_margin,
+                         const uint8_t *x0, uint8_t *xcur, void *rows, int32_t *worst, int32_t *active, int round, hipStream_t s);
 int launch_cp_to_rp(const uint16_t *cp, uint64_t *rp, int n, int C, int H, int W, hipStream_t s);
 int launch_rp_to_cp(const uint64_t *rp, uint16_t *cp, int n, int C, int H, int W, hipStream_t s);
 // feature planes (fragment order) -> float32 [n][(16g+k)*PP + pp] (reference Flatten order)

@@ -355,6 +355,13 @@ class _TTNetBase(nn.Module):
         from . import certify
         return certify.certify_u8(self, x_u8, classes, eps, enum_bits, min_margin, lane, return_planes)
 
+    def attack_u8(self, x_u8: torch.Tensor, classes, eps: float, rounds: int = 3, min_margin: float = 0.0, lane: int = 0,
+                  planes=None):
+        """Falsified L-infinity robustness (vAlexnet only): a search for a uint8 image within ``floor(eps)`` byte levels of
+        image i on which ``forward_u8`` no longer gives ``classes[i]``.  See ``scale_imagenet_amd.attack.attack_u8``."""
+        from . import attack
+        return attack.attack_u8(self, x_u8, classes, eps, rounds, min_margin, lane, planes)
+
     def export_truth_tables(self, block_name: str, out_dir: str, block: int = 0, sub_block: int = 0, filters=None,
                             max_expr_bits: int = 9, usage=None, minimiser: str = "sympy", rounds: int = 0,
                             min_count: int = 1):
