@@ -16,7 +16,6 @@ the numpy float64 twin: the same sums in the same order, the same record.
 """
 from __future__ import annotations
 
-import csv
 import ctypes as C
 import math
 from typing import Callable, Iterable, List, Optional, Sequence, Tuple
@@ -25,6 +24,8 @@ import numpy as np
 
 from . import certify as CF
 from .cifar import CIFAR_MEAN, CIFAR_STD
+from .valexnet_block import FEAT_CH, N_REACH, POOL, SIDE, STEM_CH, f64, fold_bn, reached, table_words, window_indices  # noqa: F401
+from .valexnet_block import block_words as _words
 
 RECORD = np.dtype([("margin0", "<f4"), ("best", "<f4"), ("worst", "<i4"), ("status", "<i4"), ("round", "<i4"),
                    ("changed", "<i4"), ("linf", "<i4"), ("tried", "<i4")])     # the 32-byte record of ttnet_attack_select_u8
@@ -122,27 +123,13 @@ def attack_u8(model, x_u8, classes, eps: float, rounds: int = 3, min_margin: flo
     that size and no forward is larger, so an image's record and witness do not depend on the batch it came in.
     Asynchronous on the current stream; nothing is read back."""
     import torch
-    if getattr(model, "VARIANT", None) != "valexnet":
-        raise RuntimeError("attack_u8 serves TT_FHE_XSMALL_vAlexnet only: the search needs the certificate's stem planes, an "
-                           "affine head and truth tables of at most 8 inputs")
-    if model.training:
-        raise RuntimeError("the HIP path implements eval-mode inference only: call model.eval()")
-    if (not x_u8.is_cuda) or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or tuple(x_u8.shape[1:]) != (32, 32, 3):
-        raise RuntimeError(f"expected a uint8 HIP tensor [N,32,32,3], got {x_u8.dtype} {tuple(x_u8.shape)} on {x_u8.device}")
-    n = x_u8.shape[0]
-    classes = torch.as_tensor(classes)
-    if classes.dim() != 1 or classes.shape[0] != n or classes.dtype.is_floating_point or classes.dtype == torch.bool:
-        raise RuntimeError(f"expected {n} integer classes, got {classes.dtype} {tuple(classes.shape)}")
+    x0, classes = CF.checked_inputs(model, x_u8, classes, "attack_u8", "the search needs the certificate's stem planes,")
+    n, dev = x0.shape[0], x0.device
     levels = eps_levels(eps)
     if not 0 <= int(rounds) <= ROUNDS_MAX:
         raise ValueError(f"rounds must be in [0, {ROUNDS_MAX}], got {rounds}")
     if math.isnan(min_margin):
         raise ValueError("min_margin is NaN")
-    dev = x_u8.device
-    x0 = x_u8.contiguous()
-    if x0.data_ptr() % 4:
-        x0 = x0.clone()
-    classes = classes.to(device=dev, dtype=torch.int32).contiguous()
     if planes is not None:
         planes = tuple(torch.as_tensor(p).reshape(n, 64, 10).to(device=dev, dtype=torch.int64) for p in planes)
     rows = torch.empty((n, 8), dtype=torch.int32, device=dev)
@@ -252,10 +239,8 @@ def rows_csv_rows(summaries: Sequence[dict], classes: Sequence[int]) -> List[lis
 
 def write_rows_csv(path: Optional[str], summaries: Sequence[dict], classes: Sequence[int]):
     """The records of ``attack_batches`` as CSV (``path`` None: standard output); written to a temporary name and renamed."""
-    from .report import replacing
-    rows = rows_csv_rows(summaries, classes)
-    with replacing(path) as f:
-        csv.writer(f, lineterminator="\n").writerows(rows)
+    from .report import write_csv
+    write_csv(path, rows_csv_rows(summaries, classes))
 
 
 # ---- the numpy float64 twin ----------------------------------------------------------------------------------------------
@@ -264,7 +249,7 @@ def wsum_cpu(state) -> np.ndarray:
     """``Wsum[ch][k][5][5]``: the nine 3 x 3 stem kernels of channel ch, input channel k, shifted to the nine positions
     (dy, dx ascending) of the MaxPool(3) window and summed, float64 from the float32 weights.  Entry [r][q] weighs the pixel
     in row ``3 py - 1 + r``, column ``3 px - 1 + q`` of the 5 x 5 field of pooled cell (py, px)."""
-    w = CF._f64(state["features.0.weight"])
+    w = f64(state["features.0.weight"])
     out = np.zeros((64, 3, 5, 5))
     for dy in range(3):
         for dx in range(3):
@@ -276,35 +261,21 @@ def head_cpu(state) -> np.ndarray:
     """The effective head ``A = lin2 diag(bn_scale) lin1`` float64 ``[10, 30976]`` summed the way the device sums it (the
     hidden unit i ascending, every product and every sum rounded on its own), so that ``D_f`` has the device's bytes;
     ``certify.effective_head`` leaves the order to the BLAS and agrees to rounding."""
-    s, _ = CF.fold_bn(state, "features.7.BN2")
-    m = CF._f64(state["features.7.lin2.weight"]) * s[None, :]
-    lin1 = CF._f64(state["features.7.lin1.weight"])
+    s, _ = fold_bn(state, "features.7.BN2")
+    m = f64(state["features.7.lin2.weight"]) * s[None, :]
+    lin1 = f64(state["features.7.lin1.weight"])
     A = np.zeros((m.shape[0], lin1.shape[1]))
     for i in range(m.shape[1]):
         A = A + m[:, i, None] * lin1[i][None, :]
     return A
 
 
-def _words(tables):
-    return [CF.table_words(tables[b], 6 if i < 2 else 8) for i, b in enumerate(CF._BLOCKS)]
-
-
 def reached_features() -> np.ndarray:
     """int64 ``[21, 64, 10, 10]``: the flat index (``channel * 121 + oy * 11 + ox`` of the 256 x 11 x 11 features) of the
-    features whose windows hold stem bit (ch, py, px), in the order of the gain's sum; -1 where a window would lie outside
-    the plane."""
-    ch, py, px = np.meshgrid(np.arange(64), np.arange(10), np.arange(10), indexing="ij")
-    out = []
-    for doy in (-1, 0, 1):
-        for dox in (0, 1):
-            out.append(np.where((py + doy >= 0) & (py + doy <= 9), ch * 121 + (py + doy) * 11 + px + dox, -1))
-    for doy in (0, 1):
-        for dox in (-1, 0, 1):
-            out.append(np.where((px + dox >= 0) & (px + dox <= 9), (64 + ch) * 121 + (py + doy) * 11 + px + dox, -1))
-    for o in range(8):
-        out.append((128 + 8 * (ch // 8) + o) * 121 + py * 11 + px)
-    out.append((192 + ch) * 121 + py * 11 + px)
-    return np.stack(out)
+    features whose windows hold stem bit (ch, py, px), in the order of the gain's sum (``valexnet_block.reach``); -1 where a
+    window would lie outside the plane."""
+    valid, fc, oy, ox, _ = reached()
+    return np.where(valid != 0, (fc * SIDE + oy) * SIDE + ox, -1)
 
 
 def gains_cpu(A: np.ndarray, words, stem_bits: np.ndarray, feat_bits: np.ndarray, unknown: np.ndarray, classes, worst,
@@ -313,59 +284,40 @@ def gains_cpu(A: np.ndarray, words, stem_bits: np.ndarray, feat_bits: np.ndarray
     logit_j`` (c = ``classes[i]``, j = ``worst[i]``, through ``A`` ``[10, 30976]``) when s alone flips, zero elsewhere and
     for an image whose c or j is no class.  ``stem_bits`` ``[n, 64, 10, 10]``, ``feat_bits`` ``[n, 256, 11, 11]`` (what the
     forward produced: y before the flip), ``words = [table_words(conv1), (conv2), (conv3)]``.  The sum runs over the at most
-    21 features whose windows hold s -- conv1, conv2, conv3, out4, raster order inside a branch -- and every term is +D_f,
-    -D_f or nothing.  ``return_changed``: also bool ``[n, 21, 64, 10, 10]``, which of the 21 features change."""
+    21 features whose windows hold s, in the order of ``valexnet_block.reach``: the feature's table read at its index with
+    input p flipped, and every term is +D_f, -D_f or nothing.  ``return_changed``: also bool ``[n, 21, 64, 10, 10]``, which of
+    the 21 features change."""
     stem_bits = np.asarray(stem_bits).astype(np.int64)
     feat = np.asarray(feat_bits).astype(np.int64)
     n = stem_bits.shape[0]
     classes, worst = np.asarray(classes).astype(np.int64), np.asarray(worst).astype(np.int64)
     ok = (classes >= 0) & (classes < 10) & (worst >= 0) & (worst < 10)
     c, j = np.where(ok, classes, 0), np.where(ok, worst, 0)
-    D = (A[c] - A[j]).reshape(n, 256, 11, 11)
-    P = np.pad(stem_bits, ((0, 0), (0, 0), (1, 1), (1, 1)))                 # stem (y, x) at P[y + 1][x + 1]; paddings: known zeros
-    idx1 = sum(P[:, :, kh:kh + 10, kw:kw + 11] << (kh * 2 + kw) for kh in range(3) for kw in range(2))   # [n, 64, oy 10, ox 11]
-    idx2 = sum(P[:, :, kh:kh + 11, kw:kw + 10] << (kh * 3 + kw) for kh in range(2) for kw in range(3))   # [n, 64, oy 11, ox 10]
-    idx3 = sum(stem_bits[:, p::8] << p for p in range(8))                                                  # [n, 8, 10, 10]
+    D = (A[c] - A[j]).reshape(n, FEAT_CH, SIDE, SIDE)
+    idx = window_indices(stem_bits)                                        # [n, 64, 10, 11], [n, 64, 11, 10], [n, 8, 10, 10]
     T1, T2, T3 = words[0][:, 0, 0], words[1][:, 0, 0], words[2]              # [64], [64], [8, 8, 4]
-    py, px = np.meshgrid(np.arange(10), np.arange(10), indexing="ij")
-    ch = np.arange(64)[:, None, None]
-    g = np.zeros((n, 64, 10, 10))
-    changed = np.zeros((n, 21, 64, 10, 10), dtype=bool)
-    slot = 0
-
-    def add(d, Df):
-        nonlocal g, slot
-        g = g + np.where(d == 1, Df, np.where(d == -1, -Df, 0.0))
-        changed[:, slot] = d != 0
-        slot += 1
+    ch, py, px = np.meshgrid(np.arange(STEM_CH), np.arange(POOL), np.arange(POOL), indexing="ij")
+    g = np.zeros((n, STEM_CH, POOL, POOL))
+    changed = np.zeros((n, N_REACH, STEM_CH, POOL, POOL), dtype=bool)
 
     def bit(T, i):
         return ((T >> i.astype(np.uint64)) & np.uint64(1)).astype(np.int64)
-    for doy in (-1, 0, 1):                                                 # conv1: rows oy-1..oy+1, columns ox-1..ox; oy <= 9
-        for dox in (0, 1):
-            oy, ox = py + doy, px + dox
-            valid = (oy >= 0) & (oy <= 9)
-            oyc = np.clip(oy, 0, 9)
-            i = idx1[:, :, oyc, ox] ^ (1 << ((1 - doy) * 2 + (1 - dox)))
-            d = np.where(valid[None, None], bit(T1[None, :, None, None], i) - feat[:, :64][:, :, oyc, ox], 0)
-            add(d, D[:, :64][:, :, oyc, ox])
-    for doy in (0, 1):                                                     # conv2: rows oy-1..oy, columns ox-1..ox+1; ox <= 9
-        for dox in (-1, 0, 1):
-            oy, ox = py + doy, px + dox
-            valid = (ox >= 0) & (ox <= 9)
-            oxc = np.clip(ox, 0, 9)
-            i = idx2[:, :, oy, oxc] ^ (1 << ((1 - doy) * 3 + (1 - dox)))
-            d = np.where(valid[None, None], bit(T2[None, :, None, None], i) - feat[:, 64:128][:, :, oy, oxc], 0)
-            add(d, D[:, 64:128][:, :, oy, oxc])
-    grp = np.arange(64) // 8
-    i3 = idx3[:, grp] ^ (1 << (ch % 8))                                    # [n, 64, 10, 10]: the group's index with this channel flipped
-    for o in range(8):                                                     # conv3: the 8 outputs of the group at (py, px)
-        w = T3[grp, o][None, :, None, None, :]                             # [1, 64, 1, 1, 4]
-        word = np.take_along_axis(np.broadcast_to(w, i3.shape + (4,)), (i3 >> 6)[..., None], axis=-1)[..., 0]
-        fc = 128 + 8 * grp + o
-        d = bit(word, i3 & 63) - feat[:, fc][:, :, :10, :10]
-        add(d, D[:, fc][:, :, :10, :10])
-    add(1 - 2 * stem_bits, D[:, 192:][:, :, :10, :10])                     # out4 carries the bit itself
+    for t, (valid, fc, oy, ox, p) in enumerate(zip(*reached())):
+        valid = valid != 0
+        oy, ox = np.where(valid, oy, 0), np.where(valid, ox, 0)            # (a window outside the plane: any entry, masked below)
+        kind, old = int(fc[0, 0, 0]) // 64, feat[:, fc, oy, ox]
+        if kind < 2:                                                       # conv1 / conv2: the channel's 64-entry table
+            new = bit((T1, T2)[kind][ch], idx[kind][:, ch, oy, ox] ^ (1 << p))
+        elif kind == 2:                                                    # conv3: output fc of the group, four words
+            i3 = idx[2][:, ch // 8, py, px] ^ (1 << p)
+            w = np.broadcast_to(T3[(fc - 128) // 8, fc % 8], i3.shape + (4,))
+            new = bit(np.take_along_axis(w, (i3 >> 6)[..., None], axis=-1)[..., 0], i3 & 63)
+        else:                                                              # out4 carries the bit itself
+            new, old = 1 - stem_bits, stem_bits
+        d = np.where(valid, new - old, 0)
+        Df = D[:, fc, oy, ox]
+        g = g + np.where(d == 1, Df, np.where(d == -1, -Df, 0.0))
+        changed[:, t] = d != 0
     keep = np.asarray(unknown).astype(bool) & ok[:, None, None, None]
     g = np.where(keep, g, 0.0)
     return (g, changed & keep[:, None]) if return_changed else g
@@ -492,7 +444,7 @@ def attack_cpu(state, tables, x_u8, classes, eps: float, rounds: int = 3, min_ma
         lo, hi = planes if planes is not None else CF.stem_planes_cpu(state, x0, eps, mean, std)
         unknown = np.asarray(lo) != np.asarray(hi)
         A = head_cpu(state)
-        words, Wsum, scale = _words(tables), wsum_cpu(state), CF.fold_bn(state, "features.2")[0]
+        words, Wsum, scale = _words(tables), wsum_cpu(state), fold_bn(state, "features.2")[0]
     for r in range(1, int(rounds) + 1):
         if r > 1:
             stem, feat, _ = forward(xcur)

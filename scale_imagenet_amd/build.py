@@ -35,6 +35,7 @@ def build_lib(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, "ttnet_common.h"), os.path.join(HERE, "..", "include", "ttnet.h")]
     included = {"gate_full.hip": [os.path.join(CSRC, "erf_table.inc")]}
+    included.update({src: [os.path.join(CSRC, "va_block.h")] for src in ("gate_va.hip", "certify.hip", "attack.hip", "plan.hip")})
     jobs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

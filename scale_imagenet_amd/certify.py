@@ -13,23 +13,19 @@ three stages: the same slack, the same definitions, the same record.  It takes t
 """
 from __future__ import annotations
 
-import csv
 import ctypes as C
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from .cifar import CIFAR_MEAN, CIFAR_STD
+from .valexnet_block import (FEAT_ROWS, N_CLASSES, N_FEAT, N_REACH, PADS, STEM_ROWS, WINDOW_SIZE, block_windows,  # noqa: F401
+                             block_words, f64, fold_bn, reach, table_words, window_input, zpad)   # (some only re-exported)
 
 RECORD = np.dtype([("lb_interval", "<f8"), ("lb", "<f8"), ("worst", "<i4"), ("stage", "<i4"), ("unknown_stem", "<i4"),
                    ("unknown_feat", "<i4")])                # the 32-byte record of ttnet_certify_u8
 ENUM_BITS_MAX = 12
-BN_EPS = 1e-5
-N_CLASSES, N_FEAT = 10, 256 * 121
 ROWS_HEADER = ["index", "class", "stage", "certified", "lb", "lb_interval", "worst", "unknown_stem", "unknown_feat"]
-_BLOCKS = ("features.5.Block_conv1", "features.5.Block_conv2", "features.5.Block_conv3")
-# zero padding of (out1, out2, out3 / out4) as (left, right, top, bottom): spec.VAlexSpec.pads
-_PADS = ((0, 0, 0, 1), (0, 1, 0, 0), (0, 1, 0, 1))
 
 
 # ---- the device path ---------------------------------------------------------------------------------------------------
@@ -63,6 +59,26 @@ class CertifyResult:
         return {k: v.cpu().numpy().view(np.uint64) for k, v in (self.planes or {}).items()}
 
 
+def checked_inputs(model, x_u8, classes, who: str, needs: str):
+    """What ``certify_u8`` and ``attack_u8`` check first: the variant, eval mode, the image tensor and the classes.  Returns
+    the images contiguous and 4-byte aligned and the classes as an int32 tensor on their device."""
+    import torch
+    if getattr(model, "VARIANT", None) != "valexnet":
+        raise RuntimeError(f"{who} serves TT_FHE_XSMALL_vAlexnet only: {needs} an affine head and truth tables of at most 8 inputs")
+    if model.training:
+        raise RuntimeError("the HIP path implements eval-mode inference only: call model.eval()")
+    if (not x_u8.is_cuda) or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or tuple(x_u8.shape[1:]) != (32, 32, 3):
+        raise RuntimeError(f"expected a uint8 HIP tensor [N,32,32,3], got {x_u8.dtype} {tuple(x_u8.shape)} on {x_u8.device}")
+    n = x_u8.shape[0]
+    classes = torch.as_tensor(classes)
+    if classes.dim() != 1 or classes.shape[0] != n or classes.dtype.is_floating_point or classes.dtype == torch.bool:
+        raise RuntimeError(f"expected {n} integer classes, got {classes.dtype} {tuple(classes.shape)}")
+    x_u8 = x_u8.contiguous()
+    if x_u8.data_ptr() % 4:
+        x_u8 = x_u8.clone()
+    return x_u8, classes.to(device=x_u8.device, dtype=torch.int32).contiguous()
+
+
 def certify_u8(model, x_u8, classes, eps: float, enum_bits: int = 10, min_margin: float = 1e-6, lane: int = 0,
                return_planes: bool = False) -> CertifyResult:
     """Certify that image i of ``x_u8`` (uint8 HIP tensor ``[N, 32, 32, 3]``, what ``forward_u8`` takes) keeps the class
@@ -72,35 +88,22 @@ def certify_u8(model, x_u8, classes, eps: float, enum_bits: int = 10, min_margin
     import torch
 
     from . import _lib
-    if getattr(model, "VARIANT", None) != "valexnet":
-        raise RuntimeError("certify_u8 serves TT_FHE_XSMALL_vAlexnet only: the certificate needs an affine head and truth "
-                           "tables of at most 8 inputs")
-    if model.training:
-        raise RuntimeError("the HIP path implements eval-mode inference only: call model.eval()")
-    if (not x_u8.is_cuda) or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or tuple(x_u8.shape[1:]) != (32, 32, 3):
-        raise RuntimeError(f"expected a uint8 HIP tensor [N,32,32,3], got {x_u8.dtype} {tuple(x_u8.shape)} on {x_u8.device}")
+    x_u8, classes = checked_inputs(model, x_u8, classes, "certify_u8", "the certificate needs")
     n = x_u8.shape[0]
-    classes = torch.as_tensor(classes)
-    if classes.dim() != 1 or classes.shape[0] != n or classes.dtype.is_floating_point or classes.dtype == torch.bool:
-        raise RuntimeError(f"expected {n} integer classes, got {classes.dtype} {tuple(classes.shape)}")
     if not (np.isfinite(eps) and eps >= 0):
         raise ValueError(f"eps must be finite and >= 0, got {eps}")
     if not 0 <= int(enum_bits) <= ENUM_BITS_MAX:
         raise ValueError(f"enum_bits must be in [0, {ENUM_BITS_MAX}], got {enum_bits}")
-    x_u8 = x_u8.contiguous()
-    if x_u8.data_ptr() % 4:
-        x_u8 = x_u8.clone()
-    classes = classes.to(device=x_u8.device, dtype=torch.int32).contiguous()
     plan = model._plan_for(x_u8.device, n)
     rows = torch.empty((n, 4), dtype=torch.float64, device=x_u8.device)
-    words = torch.empty(n * 2 * (640 + 2816) if return_planes else 0, dtype=torch.int64, device=x_u8.device)
+    words = torch.empty(n * 2 * (STEM_ROWS + FEAT_ROWS) if return_planes else 0, dtype=torch.int64, device=x_u8.device)
     stream = torch.cuda.current_stream(x_u8.device).cuda_stream
     _lib.check(plan.lib.ttnet_certify_u8(plan.handle, int(lane), C.c_void_p(x_u8.data_ptr()), n, C.c_void_p(classes.data_ptr()),
                                          float(eps), int(enum_bits), float(min_margin), C.c_void_p(rows.data_ptr()),
                                          C.c_void_p(words.data_ptr() if return_planes else None), C.c_void_p(stream)))
     planes = None
     if return_planes:
-        a, b = n * 640, n * 2816
+        a, b = n * STEM_ROWS, n * FEAT_ROWS
         planes = {"stem_lo": words[:a].view(n, 64, 10), "stem_hi": words[a:2 * a].view(n, 64, 10),
                   "feat_lo": words[2 * a:2 * a + b].view(n, 256, 11), "feat_hi": words[2 * a + b:].view(n, 256, 11)}
     return CertifyResult(rows, planes)
@@ -156,23 +159,11 @@ def rows_csv_rows(summaries: Sequence[dict], classes: Sequence[int]) -> List[lis
 
 def write_rows_csv(path: Optional[str], summaries: Sequence[dict], classes: Sequence[int]):
     """The records of ``certify_batches`` as CSV (``path`` None: standard output); written to a temporary name and renamed."""
-    from .report import replacing
-    rows = rows_csv_rows(summaries, classes)
-    with replacing(path) as f:
-        csv.writer(f, lineterminator="\n").writerows(rows)
+    from .report import write_csv
+    write_csv(path, rows_csv_rows(summaries, classes))
 
 
 # ---- the numpy float64 twin ----------------------------------------------------------------------------------------------
-
-def _f64(a) -> np.ndarray:
-    return np.asarray(a, dtype=np.float64)
-
-
-def fold_bn(state, prefix: str) -> Tuple[np.ndarray, np.ndarray]:
-    """Eval-mode BatchNorm as ``y = x * scale + shift`` in float64."""
-    scale = _f64(state[f"{prefix}.weight"]) / np.sqrt(_f64(state[f"{prefix}.running_var"]) + BN_EPS)
-    return scale, _f64(state[f"{prefix}.bias"]) - _f64(state[f"{prefix}.running_mean"]) * scale
-
 
 def _norm(mean, std) -> Tuple[np.ndarray, np.ndarray]:
     """(a, off): the normalised value of byte level v of channel c is (v - off[c]) * a[c]; the constants are float32, as the
@@ -186,8 +177,8 @@ def stem_slack(state, mean=CIFAR_MEAN, std=CIFAR_STD) -> np.ndarray:
     a, off = _norm(mean, std)
     X = max(np.abs((0.0 - off) * a).max(), np.abs((255.0 - off) * a).max())
     scale, shift = fold_bn(state, "features.2")
-    l1 = np.abs(_f64(state["features.0.weight"])).reshape(64, -1).sum(axis=1)
-    return np.ldexp((l1 * X + np.abs(_f64(state["features.0.bias"]))) * np.abs(scale) + np.abs(shift), -40)
+    l1 = np.abs(f64(state["features.0.weight"])).reshape(64, -1).sum(axis=1)
+    return np.ldexp((l1 * X + np.abs(f64(state["features.0.bias"]))) * np.abs(scale) + np.abs(shift), -40)
 
 
 def stem_bounds_cpu(state, x_u8: np.ndarray, eps: float, mean=CIFAR_MEAN, std=CIFAR_STD) -> Tuple[np.ndarray, np.ndarray]:
@@ -198,9 +189,9 @@ def stem_bounds_cpu(state, x_u8: np.ndarray, eps: float, mean=CIFAR_MEAN, std=CI
     b = np.asarray(x_u8).astype(np.float64).transpose(0, 3, 1, 2)                      # [n, 3, 32, 32]
     x_lo = (np.maximum(0.0, b - eps) - off[None, :, None, None]) * a[None, :, None, None]
     x_hi = (np.minimum(255.0, b + eps) - off[None, :, None, None]) * a[None, :, None, None]
-    w = _f64(state["features.0.weight"])
+    w = f64(state["features.0.weight"])
     wp, wn = torch.from_numpy(np.maximum(w, 0.0)), torch.from_numpy(np.minimum(w, 0.0))
-    bias = torch.from_numpy(_f64(state["features.0.bias"]))
+    bias = torch.from_numpy(f64(state["features.0.bias"]))
     tl, th = torch.from_numpy(np.ascontiguousarray(x_lo)), torch.from_numpy(np.ascontiguousarray(x_hi))
     lo = F.relu(F.conv2d(tl, wp, bias, 1, 1) + F.conv2d(th, wn, None, 1, 1))          # zero padding: zero in normalised space
     hi = F.relu(F.conv2d(th, wp, bias, 1, 1) + F.conv2d(tl, wn, None, 1, 1))
@@ -224,22 +215,6 @@ _IDX_MASK = np.array([0xAAAAAAAAAAAAAAAA, 0xCCCCCCCCCCCCCCCC, 0xF0F0F0F0F0F0F0F0
 _ALL = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
-def table_words(table: np.ndarray, n: int) -> np.ndarray:
-    """A truth table in the canonical order (``[G, 2^n, cout]`` bits, index = inputs MSB first) as uint64 words
-    ``[G, cout, max(1, 2^n / 64)]`` indexed by the window itself: bit ``i % 64`` of word ``i / 64``, input p in bit p of i."""
-    table = np.asarray(table)
-    g, size, cout = table.shape
-    assert size == 1 << n
-    i = np.arange(size)
-    canon = np.zeros(size, dtype=np.int64)
-    for p in range(n):
-        canon |= ((i >> p) & 1) << (n - 1 - p)
-    bits = table[:, canon, :].astype(np.uint64).transpose(0, 2, 1)                     # [G, cout, 2^n], window order
-    nw = max(1, size // 64)
-    bits = bits.reshape(g, cout, nw, -1)
-    return (bits << np.arange(bits.shape[-1], dtype=np.uint64)).sum(axis=-1, dtype=np.uint64)
-
-
 def lookup3(words: np.ndarray, lo: np.ndarray, hi: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
     """Three-valued lookup by selector words.  ``words`` ``[..., W]`` (W = 1 for n <= 6, 4 for n = 8), ``lo`` / ``hi``
     ``[..., n]`` bits (unknown where they differ).  Returns ``(ylo, yhi)``: certainly 1, possibly 1."""
@@ -260,40 +235,23 @@ def lookup3(words: np.ndarray, lo: np.ndarray, hi: np.ndarray) -> Tuple[np.ndarr
     return (~can0).astype(np.uint8), can1.astype(np.uint8)
 
 
-def _windows(bits: np.ndarray, kh: int, kw: int, pad: int) -> np.ndarray:
-    """[n, C, H, W] -> [n, C, Ho, Wo, kh * kw] (input p = kh index * kw + kw index), zero padding."""
-    x = np.pad(bits, ((0, 0), (0, 0), (pad, pad), (pad, pad)))
-    ho, wo = x.shape[2] - kh + 1, x.shape[3] - kw + 1
-    return np.stack([x[:, :, a:a + ho, b:b + wo] for a in range(kh) for b in range(kw)], axis=-1)
-
-
-def _zpad(x: np.ndarray, p) -> np.ndarray:
-    l, r, t, b = p
-    return np.pad(x, ((0, 0), (0, 0), (t, b), (l, r)))
-
-
 def block_planes_cpu(tables, lo_bit: np.ndarray, hi_bit: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
     """Stage 1, the block: ``(ylo, yhi)`` uint8 ``[n, 256, 11, 11]`` from the stem planes; paddings are known zeros."""
-    n = lo_bit.shape[0]
-    outs = []
-    for name, (kh, kw, pad) in zip(_BLOCKS[:2], ((3, 2, 1), (2, 3, 1))):
-        w = table_words(tables[name], 6)[:, 0, :]                                      # [64, 1]
-        outs.append(lookup3(w[None, :, None, None, :], _windows(lo_bit, kh, kw, pad), _windows(hi_bit, kh, kw, pad)))
-    w3 = table_words(tables[_BLOCKS[2]], 8)                                            # [8, 8, 4]
-    gl = lo_bit.reshape(n, 8, 8, 10, 10).transpose(0, 1, 3, 4, 2)[:, :, None]          # [n, g, 1, y, x, 8 inputs]
-    gh = hi_bit.reshape(n, 8, 8, 10, 10).transpose(0, 1, 3, 4, 2)[:, :, None]
-    l3, h3 = lookup3(w3[None, :, :, None, None, :], gl, gh)                            # [n, g, o, y, x]
-    outs.append((l3.reshape(n, 64, 10, 10), h3.reshape(n, 64, 10, 10)))
+    w1, w2, w3 = block_words(tables)                                                   # [64, 1, 1], [64, 1, 1], [8, 8, 4]
+    wl, wh = block_windows(lo_bit), block_windows(hi_bit)
+    outs = [lookup3(w[None, :, 0, None, None, :], wl[k], wh[k]) for k, w in enumerate((w1, w2))]
+    l3, h3 = lookup3(w3[None, :, :, None, None, :], wl[2][:, :, None], wh[2][:, :, None])   # [n, g, o, y, x]
+    outs.append((l3.reshape(lo_bit.shape), h3.reshape(lo_bit.shape)))
     outs.append((lo_bit, hi_bit))
-    pads = (_PADS[0], _PADS[1], _PADS[2], _PADS[2])
-    return tuple(np.concatenate([_zpad(o[k], p) for o, p in zip(outs, pads)], axis=1) for k in (0, 1))
+    pads = (PADS[0], PADS[1], PADS[2], PADS[2])
+    return tuple(np.concatenate([zpad(o[k], p) for o, p in zip(outs, pads)], axis=1) for k in (0, 1))
 
 
 def effective_head(state) -> Tuple[np.ndarray, np.ndarray]:
     """``A = lin2 diag(bn_scale) lin1`` float64 ``[10, 30976]`` and ``c0 = lin2 bn_shift + bias``."""
     s, t = fold_bn(state, "features.7.BN2")
-    l2 = _f64(state["features.7.lin2.weight"])
-    return (l2 * s[None, :]) @ _f64(state["features.7.lin1.weight"]), l2 @ t + _f64(state["features.7.lin2.bias"])
+    l2 = f64(state["features.7.lin2.weight"])
+    return (l2 * s[None, :]) @ f64(state["features.7.lin1.weight"]), l2 @ t + f64(state["features.7.lin2.bias"])
 
 
 def margins_cpu(A, c0, ylo: np.ndarray, yhi: np.ndarray, c: int) -> np.ndarray:
@@ -310,23 +268,14 @@ def _affected(lo_bit: np.ndarray, hi_bit: np.ndarray):
     ``(channel of the 256, oy, ox, [(input p, stem channel, y, x)])``; inputs that fall into the padding are left out."""
     unk = [tuple(int(v) for v in u) for u in np.argwhere(lo_bit != hi_bit)]
     seen, feats = set(), []
-
-    def add(fc, oy, ox, inputs):
-        if (fc, oy, ox) in seen:
-            return
-        seen.add((fc, oy, ox))
-        feats.append((fc, oy, ox, [(p, c, y, x) for p, c, y, x in inputs if 0 <= y < 10 and 0 <= x < 10]))
     for ch, y, x in unk:
-        for oy in range(max(y - 1, 0), min(y + 1, 9) + 1):
-            for ox in (x, x + 1):
-                add(ch, oy, ox, [(p, ch, oy - 1 + p // 2, ox - 1 + p % 2) for p in range(6)])
-        for oy in (y, y + 1):
-            for ox in range(max(x - 1, 0), min(x + 1, 9) + 1):
-                add(64 + ch, oy, ox, [(p, ch, oy - 1 + p // 3, ox - 1 + p % 3) for p in range(6)])
-        g = ch // 8
-        for o in range(8):
-            add(128 + 8 * g + o, y, x, [(p, 8 * g + p, y, x) for p in range(8)])
-        add(192 + ch, y, x, [(0, ch, y, x)])
+        for t in range(N_REACH):
+            valid, fc, oy, ox, _ = reach(ch, y, x, t)
+            if not valid or (fc, oy, ox) in seen:
+                continue
+            seen.add((fc, oy, ox))
+            inputs = [(p, window_input(fc // 64, fc % 64, oy, ox, p)) for p in range(WINDOW_SIZE[fc // 64])]
+            feats.append((fc, oy, ox, [(p, *s) for p, s in inputs if s is not None]))
     return unk, feats
 
 
@@ -394,7 +343,7 @@ def certify_cpu(state, tables, x_u8, classes, eps: float, enum_bits: int = 10, m
     lo_bit, hi_bit = np.asarray(lo_bit, dtype=np.uint8), np.asarray(hi_bit, dtype=np.uint8)
     ylo, yhi = block_planes_cpu(tables, lo_bit, hi_bit)
     A, c0 = effective_head(state)
-    words = [table_words(tables[_BLOCKS[0]], 6), table_words(tables[_BLOCKS[1]], 6), table_words(tables[_BLOCKS[2]], 8)]
+    words = block_words(tables)
     rows = np.zeros(n, dtype=RECORD)
     bounds = np.full((n, N_CLASSES), np.inf)
     rows["unknown_stem"] = (lo_bit != hi_bit).reshape(n, -1).sum(axis=1)

@@ -15,12 +15,15 @@
 #include <math.h>
 
 #include "ttnet_common.h"
+#include "va_block.h"
 
 namespace ttnet {
 
+using namespace va;
+
 namespace {
 
-constexpr int kStemRows = 64 * 10, kStemBits = 64 * 100, kFeatRows = 256 * 11, kClasses = 10, kImg = 32 * 32 * 3, kCand = 8;
+constexpr int kCand = 8;
 
 struct Row {            // one record of ttnet_attack_select_u8, 32 bytes
   float margin0, best;
@@ -31,7 +34,7 @@ static_assert(sizeof(Row) == 32, "record layout of include/ttnet.h");
 // Wsum[ch][k][r][q] = sum over the pooling positions (dy, dx ascending) of w[ch][k][r - dy][q - dx]
 __global__ void attack_wsum_kernel(const float *__restrict__ w, double *__restrict__ wsum) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= 64 * 3 * 25) return;
+  if (t >= kWsum) return;
   const int q = t % 5, r = (t / 5) % 5, ck = t / 25;
   double acc = 0.0;
   for (int dy = 0; dy < 3; ++dy)
@@ -51,7 +54,7 @@ __device__ inline void cells_of(int v, int cell[2], int off[2]) {
 #pragma unroll
   for (int a = 0; a < 2; ++a) {
     off[a] = v - 3 * cell[a] + 1;
-    if (cell[a] < 0 || cell[a] > 9 || off[a] < 0 || off[a] > 4) off[a] = -1;
+    if (cell[a] < 0 || cell[a] >= kPool || off[a] < 0 || off[a] > 4) off[a] = -1;
   }
 }
 
@@ -89,34 +92,35 @@ __global__ __launch_bounds__(256) void attack_propose_kernel(
   __syncthreads();
   // ---- flip gains: thread = stem row (channel, pooled row) ------------------------------------------------------------------
   const uint64_t *fy = feat + (size_t)img * kFeatRows;
-  auto row1 = [&](int ch, int y) -> uint32_t {                       // a stem row with bit 0 = column -1; paddings are known zeros
-    return (y >= 0 && y < 10) ? (uint32_t)s_bit[ch * 10 + y] << 1 : 0u;
+  auto row1 = [&](int ch, int y) {                                   // a stem row of the forward, shifted
+    return shifted_row(y, [&](int iy) { return (uint32_t)s_bit[ch * kPool + iy]; });
   };
-  auto D = [&](int f) -> double { return A[(size_t)f * kClasses + c] - A[(size_t)f * kClasses + j]; };
   for (int r = tid; r < kStemRows; r += 256) {
-    const int ch = r / 10, py = r - 10 * ch;
-    const size_t tb = (size_t)(ch >> 4) * 2 * 16 + (ch & 15);
-    const uint64_t T1 = t1[tb] | ((uint64_t)t1[tb + 16] << 32), T2 = t2[tb] | ((uint64_t)t2[tb + 16] << 32);
+    const int ch = r / kPool, py = r - kPool * ch;
+    const uint64_t T1 = table_word(t1, ch), T2 = table_word(t2, ch);
     const double sgn = bn_scale[ch] >= 0.0 ? 1.0 : -1.0;
     uint32_t neg = 0;
-    for (int px = 0; px < 10; ++px) {
+    for (int px = 0; px < kPool; ++px) {
       double g = 0.0;
       if ((s_un[r] >> px) & 1u) {
-        auto term = [&](int f, int ynew, int yold) {                 // +D_f, -D_f or nothing
+        // The 21 features of va_block.h's reach(), in its order, written out as three nests: one loop over reach(ch, py, px, t)
+        // gives the same sums but a propose step 17 % slower (profiles/va_block_refactor.txt).
+        auto term = [&](int fc, int oy, int ox, int ynew, int yold) {  // +D_f, -D_f or nothing
           if (ynew != yold) {
-            const double d = D(f);
+            const size_t f = (size_t)(fc * kPlane + oy * kSide + ox) * kClasses;
+            const double d = A[f + c] - A[f + j];
             g += ynew > yold ? d : -d;
           }
         };
+        auto old = [&](int fc, int oy, int ox) { return (int)((fy[fc * kSide + oy] >> ox) & 1ull); };
         for (int doy = -1; doy <= 1; ++doy) {                        // conv1: rows oy-1..oy+1, columns ox-1..ox; oy <= 9
           const int oy = py + doy;
-          if (oy < 0 || oy > 9) continue;
+          if (oy < 0 || oy >= kPool) continue;
           const uint32_t l0 = row1(ch, oy - 1), l1 = row1(ch, oy), l2 = row1(ch, oy + 1);
           for (int dox = 0; dox <= 1; ++dox) {
             const int ox = px + dox;
-            const uint32_t idx = ((l0 >> ox) & 3u) | (((l1 >> ox) & 3u) << 2) | (((l2 >> ox) & 3u) << 4);
-            const uint32_t fl = idx ^ (1u << ((1 - doy) * 2 + (1 - dox)));
-            term(ch * 121 + oy * 11 + ox, (int)((T1 >> fl) & 1ull), (int)((fy[ch * 11 + oy] >> ox) & 1ull));
+            const uint32_t fl = conv1_index(l0, l1, l2, ox) ^ (1u << ((1 - doy) * 2 + (1 - dox)));
+            term(ch, oy, ox, (int)((T1 >> fl) & 1ull), old(ch, oy, ox));
           }
         }
         for (int doy = 0; doy <= 1; ++doy) {                         // conv2: rows oy-1..oy, columns ox-1..ox+1; ox <= 9
@@ -124,30 +128,27 @@ __global__ __launch_bounds__(256) void attack_propose_kernel(
           const uint32_t l0 = row1(ch, oy - 1), l1 = row1(ch, oy);
           for (int dox = -1; dox <= 1; ++dox) {
             const int ox = px + dox;
-            if (ox < 0 || ox > 9) continue;
-            const uint32_t idx = ((l0 >> ox) & 7u) | (((l1 >> ox) & 7u) << 3);
-            const uint32_t fl = idx ^ (1u << ((1 - doy) * 3 + (1 - dox)));
-            term((64 + ch) * 121 + oy * 11 + ox, (int)((T2 >> fl) & 1ull), (int)((fy[(64 + ch) * 11 + oy] >> ox) & 1ull));
+            if (ox < 0 || ox >= kPool) continue;
+            const uint32_t fl = conv2_index(l0, l1, ox) ^ (1u << ((1 - doy) * 3 + (1 - dox)));
+            term(64 + ch, oy, ox, (int)((T2 >> fl) & 1ull), old(64 + ch, oy, ox));
           }
         }
-        const int g8 = ch >> 3;
-        uint32_t idx = 0;
+        uint32_t grp[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) idx |= ((uint32_t)(s_bit[(8 * g8 + k) * 10 + py] >> px) & 1u) << k;
-        const uint32_t fl = idx ^ (1u << (ch & 7));
+        for (int k = 0; k < 8; ++k) grp[k] = s_bit[((ch & ~7) + k) * kPool + py];
+        const uint32_t fl = conv3_index(grp, px) ^ (1u << (ch & 7));
         for (int o = 0; o < 8; ++o) {                                // conv3: the 8 outputs of the group
-          const int fc = 128 + 8 * g8 + o;
-          term(fc * 121 + py * 11 + px, (int)((t3w[(g8 * 8 + o) * 4 + (fl >> 6)] >> (fl & 63u)) & 1ull),
-               (int)((fy[fc * 11 + py] >> px) & 1ull));
+          const int fc = 128 + (ch & ~7) + o;
+          term(fc, py, px, (int)((t3w[(fc - 128) * 4 + (fl >> 6)] >> (fl & 63u)) & 1ull), old(fc, py, px));
         }
         const int bit = (s_bit[r] >> px) & 1;
-        term((192 + ch) * 121 + py * 11 + px, 1 - bit, bit);         // out4 carries the bit itself
-        s_wt[r * 10 + px] = -g * (bit == 0 ? 1.0 : -1.0) * sgn;
+        term(192 + ch, py, px, 1 - bit, bit);                        // out4 carries the bit itself
+        s_wt[r * kPool + px] = -g * (bit == 0 ? 1.0 : -1.0) * sgn;
         neg |= (uint32_t)(g < 0.0) << px;
       } else {
-        s_wt[r * 10 + px] = 0.0;
+        s_wt[r * kPool + px] = 0.0;
       }
-      if (gains) gains[(size_t)img * kStemBits + r * 10 + px] = g;
+      if (gains) gains[(size_t)img * kStemBits + r * kPool + px] = g;
     }
     s_neg[r] = (uint16_t)neg;
   }
@@ -165,15 +166,15 @@ __global__ __launch_bounds__(256) void attack_propose_kernel(
     for (int m = 0; m < 2; ++m)
 #pragma unroll
       for (int k = 0; k < 3; ++k) sc[i][m][k] = 0.0;
-    for (int ch = 0; ch < 64; ++ch)                                  // ch ascending, then py, then px
+    for (int ch = 0; ch < kStemCh; ++ch)                             // ch ascending, then py, then px
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
           if (oy[a] < 0 || ox[b] < 0) continue;
-          const double w1 = s_wt[ch * 100 + cy[a] * 10 + cx[b]];
+          const double w1 = s_wt[(ch * kPool + cy[a]) * kPool + cx[b]];
           if (w1 == 0.0) continue;                                   // (a zero term changes no sum: the sums are never -0)
-          const double w0 = ((s_neg[ch * 10 + cy[a]] >> cx[b]) & 1u) ? w1 : 0.0;
+          const double w0 = ((s_neg[ch * kPool + cy[a]] >> cx[b]) & 1u) ? w1 : 0.0;
           const double *W = wsum + (size_t)ch * 75 + oy[a] * 5 + ox[b];
 #pragma unroll
           for (int k = 0; k < 3; ++k) {
@@ -330,7 +331,7 @@ __global__ __launch_bounds__(256) void attack_select_kernel(const uint8_t *__res
 }  // namespace
 
 int launch_attack_wsum(const float *w, double *wsum, hipStream_t s) {
-  hipLaunchKernelGGL(attack_wsum_kernel, dim3((64 * 3 * 25 + 255) / 256), dim3(256), 0, s, w, wsum);
+  hipLaunchKernelGGL(attack_wsum_kernel, dim3((kWsum + 255) / 256), dim3(256), 0, s, w, wsum);
   TT_HIP(hipGetLastError());
   return TTNET_OK;
 }

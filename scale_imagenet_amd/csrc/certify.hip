@@ -15,13 +15,15 @@
 #include <math.h>
 
 #include "ttnet_common.h"
+#include "va_block.h"
 
 namespace ttnet {
 
+using namespace va;
+
 namespace {
 
-constexpr int kStemRows = 64 * 10, kFeatRows = 256 * 11, kFeat = 256 * 121, kClasses = 10, kInter = 100;
-constexpr int kMaxEnum = 12, kMaxEnt = kMaxEnum * 21;     // an unknown stem bit sits in the windows of at most 21 features
+constexpr int kInter = 100, kMaxEnum = 12, kMaxEnt = kMaxEnum * kReach;
 
 // the entries of a 64-entry table that agree with the known inputs: `lo` holds the known values, `un` marks the unknown
 // inputs (bits 0..5).  M[p] = the indices whose bit p is 1.
@@ -87,7 +89,7 @@ __global__ __launch_bounds__(64 * kStemRowsPerWg) void certify_stem_kernel(
     const double *__restrict__ bn, const double *__restrict__ slack, double eps, uint64_t *__restrict__ lo_rp,
     uint64_t *__restrict__ hi_rp, int n) {
   __shared__ double img_s[2][3][kStemLdsRows][34];
-  constexpr int kParts = 10 / kStemRowsPerWg;
+  constexpr int kParts = kPool / kStemRowsPerWg;
   const int img = blockIdx.x / kParts, p0 = (blockIdx.x % kParts) * kStemRowsPerWg;
   if (img >= n) return;                                              // (whole workgroups: no barrier is left behind)
   const int r0 = 3 * p0 - 1;                                         // image row of LDS row 0 (-1: the top padding)
@@ -95,7 +97,7 @@ __global__ __launch_bounds__(64 * kStemRowsPerWg) void certify_stem_kernel(
     const int r = (i / 34) % kStemLdsRows, q = i % 34;
     if (q == 0 || q == 33 || r0 + r < 0) (&img_s[0][0][0][0])[i] = (&img_s[1][0][0][0])[i] = 0.0;
   }
-  const uint32_t *src = (const uint32_t *)(x + (size_t)img * 3072);   // (4-byte aligned: checked by the plan; a row is 96 bytes)
+  const uint32_t *src = (const uint32_t *)(x + (size_t)img * kImg);   // (4-byte aligned: checked by the plan; a row is 96 bytes)
   for (int i = threadIdx.x; i < kStemLdsRows * 24; i += blockDim.x) {
     const int lr = i / 24, ir = r0 + lr;                             // ir <= 3 * 8 - 1 + 7 = 30
     if (ir < 0) continue;
@@ -121,7 +123,7 @@ __global__ __launch_bounds__(64 * kStemRowsPerWg) void certify_stem_kernel(
 #pragma unroll 1
   for (int px = 0; px < 10; ++px) {
     // the nine convolution outputs of the pooled pixel, from its 5x5 patch: a patch row is read once (all 64 lanes of
-    // the wave read the same address: a broadcast) and feeds every output it belongs to; taps in (c, kh, kw) order
+    // the wave read the same address: a broadcast) and feeds every output it belongs to; the tap order of va_stem_patch
     double mid[3][3], rad[3][3];
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy)
@@ -164,8 +166,8 @@ __global__ __launch_bounds__(64 * kStemRowsPerWg) void certify_stem_kernel(
     out_lo |= (uint64_t)(best_lo - sl >= 0.0) << px;
     out_hi |= (uint64_t)(best_hi + sl >= 0.0) << px;
   }
-  lo_rp[((size_t)img * 64 + ch) * 10 + py] = out_lo;
-  hi_rp[((size_t)img * 64 + ch) * 10 + py] = out_hi | out_lo;        // (lo_bit <= hi_bit whatever the arithmetic did)
+  lo_rp[((size_t)img * kStemCh + ch) * kPool + py] = out_lo;
+  hi_rp[((size_t)img * kStemCh + ch) * kPool + py] = out_hi | out_lo;   // (lo_bit <= hi_bit whatever the arithmetic did)
 }
 
 // stage 1, Block_conv1 / Block_conv2 / out4: thread = (image, channel, output row of the 11x11 plane), as va_dw_kernel.
@@ -173,25 +175,21 @@ __global__ __launch_bounds__(64 * kStemRowsPerWg) void certify_stem_kernel(
 __global__ void certify_dw_kernel(const uint64_t *__restrict__ slo, const uint64_t *__restrict__ shi, const uint32_t *__restrict__ t1,
                                   const uint32_t *__restrict__ t2, uint64_t *__restrict__ ylo, uint64_t *__restrict__ yhi, int n) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (size_t)n * 64 * 11) return;
-  const int oy = t % 11, c = (t / 11) % 64, img = t / (11 * 64);
-  const uint64_t *pl = slo + ((size_t)img * 64 + c) * 10, *ph = shi + ((size_t)img * 64 + c) * 10;
-  uint64_t l[3], u[3];                                               // rows oy-1 .. oy+1, bit 0 = column -1; padding: known zeros
+  if (t >= (size_t)n * kStemCh * kSide) return;
+  const int oy = t % kSide, c = (t / kSide) % kStemCh, img = t / (kSide * kStemCh);
+  const uint64_t *pl = slo + ((size_t)img * kStemCh + c) * kPool, *ph = shi + ((size_t)img * kStemCh + c) * kPool;
+  uint64_t l[3], u[3];                                               // rows oy-1 .. oy+1: the values, the unknown bits
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    const int iy = oy - 1 + k;
-    const bool in = iy >= 0 && iy < 10;
-    l[k] = in ? pl[iy] << 1 : 0ull;
-    u[k] = in ? (pl[iy] ^ ph[iy]) << 1 : 0ull;
+    l[k] = shifted_row(oy - 1 + k, [&](int iy) { return pl[iy]; });
+    u[k] = l[k] ^ shifted_row(oy - 1 + k, [&](int iy) { return ph[iy]; });
   }
-  const size_t tb = (size_t)(c >> 4) * 2 * 16 + (c & 15);
-  const uint64_t T1 = t1[tb] | ((uint64_t)t1[tb + 16] << 32), T2 = t2[tb] | ((uint64_t)t2[tb + 16] << 32);
+  const uint64_t T1 = table_word(t1, c), T2 = table_word(t2, c);
   uint64_t r1l = 0, r1h = 0, r2l = 0, r2h = 0;
-  if (oy < 10) {      // conv1: 3x2 window, 11 output columns; bottom row 10 is zero padding
+  if (oy < kPool) {   // conv1: 3x2 window, 11 output columns; bottom row 10 is zero padding
     const bool known = ((u[0] | u[1] | u[2]) & 0xFFFull) == 0;       // the common case at small eps: plain lookups
-    for (int ox = 0; ox < 11; ++ox) {
-      const uint32_t idx = (uint32_t)((l[0] >> ox) & 3) | ((uint32_t)((l[1] >> ox) & 3) << 2) | ((uint32_t)((l[2] >> ox) & 3) << 4);
-      const uint32_t un = known ? 0u : (uint32_t)((u[0] >> ox) & 3) | ((uint32_t)((u[1] >> ox) & 3) << 2) | ((uint32_t)((u[2] >> ox) & 3) << 4);
+    for (int ox = 0; ox < kSide; ++ox) {
+      const uint32_t idx = conv1_index(l[0], l[1], l[2], ox), un = known ? 0u : conv1_index(u[0], u[1], u[2], ox);
       if (un == 0) {
         const uint64_t bit = (T1 >> idx) & 1ull;
         r1l |= bit << ox;
@@ -205,9 +203,8 @@ __global__ void certify_dw_kernel(const uint64_t *__restrict__ slo, const uint64
   }
   {                   // conv2: 2x3 window, rows oy-1..oy, 10 output columns; right column 10 is zero padding
     const bool known = ((u[0] | u[1]) & 0xFFFull) == 0;
-    for (int ox = 0; ox < 10; ++ox) {
-      const uint32_t idx = (uint32_t)((l[0] >> ox) & 7) | ((uint32_t)((l[1] >> ox) & 7) << 3);
-      const uint32_t un = known ? 0u : (uint32_t)((u[0] >> ox) & 7) | ((uint32_t)((u[1] >> ox) & 7) << 3);
+    for (int ox = 0; ox < kPool; ++ox) {
+      const uint32_t idx = conv2_index(l[0], l[1], ox), un = known ? 0u : conv2_index(u[0], u[1], ox);
       if (un == 0) {
         const uint64_t bit = (T2 >> idx) & 1ull;
         r2l |= bit << ox;
@@ -219,13 +216,13 @@ __global__ void certify_dw_kernel(const uint64_t *__restrict__ slo, const uint64
       }
     }
   }
-  const size_t o = (size_t)img * 256 * 11 + oy;
-  ylo[o + (size_t)c * 11] = r1l;
-  yhi[o + (size_t)c * 11] = r1h;
-  ylo[o + (size_t)(64 + c) * 11] = r2l;
-  yhi[o + (size_t)(64 + c) * 11] = r2h;
-  ylo[o + (size_t)(192 + c) * 11] = oy < 10 ? pl[oy] : 0ull;         // out4 = x, padded right / bottom
-  yhi[o + (size_t)(192 + c) * 11] = oy < 10 ? ph[oy] : 0ull;
+  const size_t o = (size_t)img * kFeatRows + oy;
+  ylo[o + (size_t)c * kSide] = r1l;
+  yhi[o + (size_t)c * kSide] = r1h;
+  ylo[o + (size_t)(64 + c) * kSide] = r2l;
+  yhi[o + (size_t)(64 + c) * kSide] = r2h;
+  ylo[o + (size_t)(192 + c) * kSide] = oy < kPool ? pl[oy] : 0ull;   // out4 = x, padded right / bottom
+  yhi[o + (size_t)(192 + c) * kSide] = oy < kPool ? ph[oy] : 0ull;
 }
 
 // can0 / can1 of one output bit of a 256-entry table (four words): inputs 6 and 7 pick the words, inputs 0..5 the selector
@@ -245,19 +242,19 @@ __device__ inline void lookup8(const uint64_t *T, uint32_t lo, uint32_t un, bool
 __global__ void certify_c3_kernel(const uint64_t *__restrict__ slo, const uint64_t *__restrict__ shi, const uint8_t *__restrict__ t3,
                                   const uint64_t *__restrict__ t3w, uint64_t *__restrict__ ylo, uint64_t *__restrict__ yhi, int n) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (size_t)n * 8 * 11) return;
-  const int oy = t % 11, g = (t / 11) % 8, img = t / 88;
+  if (t >= (size_t)n * 8 * kSide) return;
+  const int oy = t % kSide, g = (t / kSide) % 8, img = t / (8 * kSide);
   uint64_t l[8], u[8], ol[8], oh[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    const size_t r = ((size_t)img * 64 + 8 * g + k) * 10 + oy;
-    l[k] = oy < 10 ? slo[r] : 0ull;
-    u[k] = oy < 10 ? slo[r] ^ shi[r] : 0ull;
+    const size_t r = ((size_t)img * kStemCh + 8 * g + k) * kPool + oy;
+    l[k] = oy < kPool ? slo[r] : 0ull;
+    u[k] = oy < kPool ? slo[r] ^ shi[r] : 0ull;
     ol[k] = oh[k] = 0;
   }
-  if (oy < 10)
-    for (int xx = 0; xx < 10; ++xx) {
-      uint32_t idx = 0, un = 0;
+  if (oy < kPool)
+    for (int xx = 0; xx < kPool; ++xx) {
+      uint32_t idx = 0, un = 0;                                      // conv3_index of l and of u in one pass (two calls: 83 more instructions)
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         idx |= (uint32_t)((l[k] >> xx) & 1ull) << k;
@@ -282,8 +279,8 @@ __global__ void certify_c3_kernel(const uint64_t *__restrict__ slo, const uint64
     }
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    ylo[((size_t)img * 256 + 128 + 8 * g + k) * 11 + oy] = ol[k];
-    yhi[((size_t)img * 256 + 128 + 8 * g + k) * 11 + oy] = oh[k];
+    ylo[((size_t)img * kFeatCh + 128 + 8 * g + k) * kSide + oy] = ol[k];
+    yhi[((size_t)img * kFeatCh + 128 + 8 * g + k) * kSide + oy] = oh[k];
   }
 }
 
@@ -312,7 +309,7 @@ __global__ __launch_bounds__(256) void certify_margin_kernel(const uint64_t *__r
     const uint64_t l = ylo[(size_t)img * kFeatRows + r], h = yhi[(size_t)img * kFeatRows + r];
     uf += __popcll(l ^ h);
     if (!valid) continue;
-    const int f0 = (r / 11) * 121 + (r % 11) * 11;
+    const int f0 = (r / kSide) * kPlane + (r % kSide) * kSide;
     for (uint64_t m = h & 0x7FFull; m; m &= m - 1) {
       const int bit = __builtin_ctzll(m);
       const double *af = A + (size_t)(f0 + bit) * kClasses;          // the ten classes of a feature are contiguous
@@ -392,42 +389,27 @@ __global__ __launch_bounds__(256) void certify_enum_kernel(const uint64_t *__res
     s_un[r] = (l ^ shi[(size_t)img * kStemRows + r]) & 0x3FFull;
   }
   __syncthreads();
-  if (tid < 64) {                    // the unknown bits in order: lane = channel, a scan of the lanes' counts gives each its place
+  if (tid < kStemCh) {               // the unknown bits in order: lane = channel, a scan of the lanes' counts gives each its place
     int cnt = 0;
-    for (int y = 0; y < 10; ++y) cnt += __popcll(s_un[tid * 10 + y]);
+    for (int y = 0; y < kPool; ++y) cnt += __popcll(s_un[tid * kPool + y]);
     int incl = cnt;
     for (int d = 1; d < 64; d <<= 1) {
       const int v = __shfl_up(incl, d);
       if (tid >= d) incl += v;
     }
     int at = incl - cnt;
-    for (int y = 0; y < 10; ++y)
-      for (uint64_t m = s_un[tid * 10 + y]; m; m &= m - 1, ++at)
-        if (at < kMaxEnum) u_pos[at] = (uint16_t)((tid * 10 + y) * 16 + __builtin_ctzll(m));
+    for (int y = 0; y < kPool; ++y)
+      for (uint64_t m = s_un[tid * kPool + y]; m; m &= m - 1, ++at)
+        if (at < kMaxEnum) u_pos[at] = (uint16_t)((tid * kPool + y) * 16 + __builtin_ctzll(m));
   }
   __syncthreads();
   // candidate q = 21 i + t: feature t of those that unknown bit i reaches (0xFFFF: it falls outside the plane)
-  const int n_cand = 21 * k;                                         // <= kMaxEnt
+  const int n_cand = kReach * k;                                     // <= kMaxEnt
   uint32_t key = 0xFFFFu;
   if (tid < n_cand) {
-    const int i = tid / 21, t = tid - 21 * i, r = u_pos[i] >> 4, x = u_pos[i] & 15, ch = r / 10, y = r - 10 * ch;
-    int row = -1, bit = 0;
-    if (t < 6) {                                                     // conv1: rows oy-1..oy+1, columns ox-1..ox; oy <= 9
-      const int oy = y - 1 + t / 2;
-      bit = x + t % 2;
-      if (oy >= 0 && oy <= 9) row = ch * 11 + oy;
-    } else if (t < 12) {                                             // conv2: rows oy-1..oy, columns ox-1..ox+1; ox <= 9
-      const int oy = y + (t - 6) / 3;
-      bit = x - 1 + (t - 6) % 3;
-      if (bit >= 0 && bit <= 9) row = (64 + ch) * 11 + oy;
-    } else if (t < 20) {                                             // conv3: the 8 outputs of the group
-      row = (128 + (ch & ~7) + (t - 12)) * 11 + y;
-      bit = x;
-    } else {                                                         // out4
-      row = (192 + ch) * 11 + y;
-      bit = x;
-    }
-    if (row >= 0) key = (uint32_t)(row * 16 + bit);
+    const int i = tid / kReach, t = tid - kReach * i, r = u_pos[i] >> 4, x = u_pos[i] & 15, ch = r / kPool, y = r - kPool * ch;
+    const Reach f = reach(ch, y, x, t);
+    if (f.valid) key = (uint32_t)(f.row() * 16 + f.ox);
     c_key[tid] = (uint16_t)key;
   }
   __syncthreads();
@@ -447,43 +429,37 @@ __global__ __launch_bounds__(256) void certify_enum_kernel(const uint64_t *__res
   const int n_ent = n_ent_s;
   // what each re-evaluated feature needs: its table, the known part of its index, where the unknown bits enter, its D
   for (int e = tid; e < n_ent; e += 256) {
-    const int row = e_key[e] >> 4, bit = e_key[e] & 15, fc = row / 11, oy = row % 11, kind = fc >> 6, ch = fc & 63;
+    const int row = e_key[e] >> 4, bit = e_key[e] & 15, fc = row / kSide, oy = row % kSide, kind = fc >> 6, ch = fc & 63;
     uint32_t base = 0;
     int cnt = 0;
-    auto input = [&](int p, int sc, int iy, int ix) {               // window input p = stem bit (sc, iy, ix), or padding
-      if (iy < 0 || iy >= 10 || ix < 0 || ix >= 10) return;
-      const int r = sc * 10 + iy;
-      if ((s_un[r] >> ix) & 1ull) {
+    for (int p = 0; p < window_size(kind); ++p) {                    // window input p: an unknown bit, a known one, or padding
+      const StemBit s = window_input(kind, ch, oy, bit, p);
+      if (!s.in) continue;
+      const int r = s.ch * kPool + s.y;
+      if ((s_un[r] >> s.x) & 1ull) {
         for (int i = 0; i < k; ++i)
-          if (u_pos[i] == r * 16 + ix) {
+          if (u_pos[i] == r * 16 + s.x) {
             e_pos[e][cnt] = (uint8_t)p;
             e_unk[e][cnt] = (uint8_t)i;
             ++cnt;
           }
-      } else if ((s_lo[r] >> ix) & 1ull) {
+      } else if ((s_lo[r] >> s.x) & 1ull) {
         base |= 1u << p;
       }
-    };
+    }
     uint64_t T[4] = {0, 0, 0, 0};
-    const size_t tb = (size_t)(ch >> 4) * 2 * 16 + (ch & 15);
-    if (kind == 0) {
-      for (int p = 0; p < 6; ++p) input(p, ch, oy - 1 + p / 2, bit - 1 + p % 2);
-      T[0] = t1[tb] | ((uint64_t)t1[tb + 16] << 32);
-    } else if (kind == 1) {
-      for (int p = 0; p < 6; ++p) input(p, ch, oy - 1 + p / 3, bit - 1 + p % 3);
-      T[0] = t2[tb] | ((uint64_t)t2[tb + 16] << 32);
+    if (kind < 2) {
+      T[0] = table_word(kind == 0 ? t1 : t2, ch);
     } else if (kind == 2) {
-      for (int p = 0; p < 8; ++p) input(p, (ch & ~7) + p, oy, bit);
       for (int w = 0; w < 4; ++w) T[w] = t3w[ch * 4 + w];            // (ch = 8 group + output)
     } else {
-      input(0, ch, oy, bit);
-      T[0] = 2ull;                                                   // the identity on one input
+      T[0] = 2ull;                                                   // out4: the identity on one input
     }
     for (int w = 0; w < 4; ++w) e_T[e][w] = T[w];
     e_base[e] = (uint8_t)base;
     e_cnt[e] = (uint8_t)cnt;
     e_one[e] = (uint8_t)((ylo[(size_t)img * kFeatRows + row] >> bit) & 1ull);
-    const double *af = A + (size_t)(fc * 121 + oy * 11 + bit) * kClasses;
+    const double *af = A + (size_t)(fc * kPlane + oy * kSide + bit) * kClasses;
     const double ac = af[c];
     for (int j = 0; j < kClasses; ++j) e_D[e][j] = ac - af[j];
   }
@@ -545,13 +521,13 @@ int launch_certify(const CertifyArgs &a, int step, hipStream_t s) {
   const int n = a.n;
   Row *rows = (Row *)a.rows;
   if (step == kCertifyStem) {
-    hipLaunchKernelGGL(certify_stem_kernel, dim3((unsigned)n * (10 / kStemRowsPerWg)), dim3(64 * kStemRowsPerWg), 0, s, a.x, a.norm, a.w, a.bias, a.stem_bn, a.slack, a.eps,
+    hipLaunchKernelGGL(certify_stem_kernel, dim3((unsigned)n * (kPool / kStemRowsPerWg)), dim3(64 * kStemRowsPerWg), 0, s, a.x, a.norm, a.w, a.bias, a.stem_bn, a.slack, a.eps,
                        a.stem_lo, a.stem_hi, n);
   } else if (step == kCertifyBlock) {
-    size_t t = (size_t)n * 64 * 11;
+    size_t t = (size_t)n * kStemCh * kSide;
     hipLaunchKernelGGL(certify_dw_kernel, dim3((unsigned)((t + 127) / 128)), dim3(128), 0, s, a.stem_lo, a.stem_hi, a.t1, a.t2,
                        a.feat_lo, a.feat_hi, n);
-    t = (size_t)n * 88;
+    t = (size_t)n * 8 * kSide;
     hipLaunchKernelGGL(certify_c3_kernel, dim3((unsigned)((t + 127) / 128)), dim3(128), 0, s, a.stem_lo, a.stem_hi, a.t3, a.t3w,
                        a.feat_lo, a.feat_hi, n);
   } else if (step == kCertifyMargin) {

@@ -13,10 +13,40 @@
 #include <math.h>
 
 #include "ttnet_common.h"
+#include "va_block.h"
 
 namespace ttnet {
 
+using namespace va;
+
 namespace {
+
+// The nine convolution outputs (without the constant) of pooled pixel (py, px): its 5x5x3 patch of the padded image is read
+// once, the taps are accumulated in (c, kh, kw) order with fmaf.  Both float stems run this loop.
+__device__ __forceinline__ void va_stem_patch(const float (&img_s)[3][34][34], const float (&wr)[27], int py, int px,
+                                              float (&acc)[3][3]) {
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) acc[dy][dx] = 0.f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float patch[5][5];
+#pragma unroll
+    for (int r = 0; r < 5; ++r)
+#pragma unroll
+      for (int q = 0; q < 5; ++q) patch[r][q] = img_s[c][3 * py + r][3 * px + q];
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+      for (int kw = 0; kw < 3; ++kw)
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+          for (int dx = 0; dx < 3; ++dx)
+            acc[dy][dx] = fmaf(patch[dy + kh][dx + kw], wr[(c * 3 + kh) * 3 + kw], acc[dy][dx]);
+  }
+}
 
 // stem: one workgroup per image, thread = (channel, pooled row); the zero-padded image lives in LDS
 // (all 64 channel lanes of a wave read the same address: a broadcast), the 27 weights of the
@@ -42,27 +72,7 @@ __global__ __launch_bounds__(640) void va_stem_kernel(const float *__restrict__ 
   uint64_t out = 0;
   for (int px = 0; px < 10; ++px) {
     float acc[3][3];
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-      for (int dx = 0; dx < 3; ++dx) acc[dy][dx] = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float patch[5][5];
-#pragma unroll
-      for (int r = 0; r < 5; ++r)
-#pragma unroll
-        for (int q = 0; q < 5; ++q) patch[r][q] = img_s[c][3 * py + r][3 * px + q];
-#pragma unroll
-      for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw)
-#pragma unroll
-          for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx)
-              acc[dy][dx] = fmaf(patch[dy + kh][dx + kw], wr[(c * 3 + kh) * 3 + kw], acc[dy][dx]);
-    }
+    va_stem_patch(img_s, wr, py, px, acc);
     float best = -INFINITY;
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy)
@@ -70,7 +80,7 @@ __global__ __launch_bounds__(640) void va_stem_kernel(const float *__restrict__ 
       for (int dx = 0; dx < 3; ++dx) best = fmaxf(best, fmaf(fmaxf(acc[dy][dx] + b, 0.f), sc, sh));   // ReLU, eval BatchNorm, MaxPool2d(3)
     out |= (uint64_t)(best >= 0.f) << px;
   }
-  if (img < n) rp[((size_t)img * 64 + ch) * 10 + py] = out;
+  if (img < n) rp[((size_t)img * kStemCh + ch) * kPool + py] = out;
 }
 
 // stem from the dataset's bytes: uint8 [n][32][32][3] (HWC) in, the same bits out.  ToTensor + Normalize are folded in
@@ -115,27 +125,7 @@ __global__ __launch_bounds__(640) void va_stem_u8_kernel(const uint8_t *__restri
   for (int j = 0; j < 5; ++j) {
     const int px = 5 * half + j;
     float acc[3][3];
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-      for (int dx = 0; dx < 3; ++dx) acc[dy][dx] = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float patch[5][5];
-#pragma unroll
-      for (int r = 0; r < 5; ++r)
-#pragma unroll
-        for (int q = 0; q < 5; ++q) patch[r][q] = img_s[c][3 * py + r][3 * px + q];
-#pragma unroll
-      for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw)
-#pragma unroll
-          for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx)
-              acc[dy][dx] = fmaf(patch[dy + kh][dx + kw], wr[(c * 3 + kh) * 3 + kw], acc[dy][dx]);
-    }
+    va_stem_patch(img_s, wr, py, px, acc);
     float best = -INFINITY;
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy)
@@ -148,7 +138,7 @@ __global__ __launch_bounds__(640) void va_stem_u8_kernel(const uint8_t *__restri
     out |= (uint32_t)(best >= 0.f) << px;
   }
   out |= (uint32_t)__shfl_xor((int)out, 32);                         // columns 0..4 and 5..9 of the row word
-  if (half == 0) rp[((size_t)img * 64 + ch) * 10 + py] = out;
+  if (half == 0) rp[((size_t)img * kStemCh + ch) * kPool + py] = out;
 }
 
 // Block_conv1 / Block_conv2 / out4: thread = (image, channel, output row of the 11x11 plane).
@@ -156,55 +146,45 @@ __global__ __launch_bounds__(640) void va_stem_u8_kernel(const uint8_t *__restri
 __global__ void va_dw_kernel(const uint64_t *__restrict__ x_rp, const uint32_t *__restrict__ t1,
                              const uint32_t *__restrict__ t2, uint64_t *__restrict__ y, int n) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (size_t)n * 64 * 11) return;
-  const int oy = t % 11, c = (t / 11) % 64, img = t / (11 * 64);
-  const uint64_t *pl = x_rp + ((size_t)img * 64 + c) * 10;
-  auto row = [&](int iy) -> uint64_t { return (iy >= 0 && iy < 10) ? pl[iy] << 1 : 0ull; };   // bit 0 = column -1
-  const size_t tb = (size_t)(c >> 4) * 2 * 16 + (c & 15);
-  const uint64_t T1 = t1[tb] | ((uint64_t)t1[tb + 16] << 32), T2 = t2[tb] | ((uint64_t)t2[tb + 16] << 32);
+  if (t >= (size_t)n * kStemCh * kSide) return;
+  const int oy = t % kSide, c = (t / kSide) % kStemCh, img = t / (kSide * kStemCh);
+  const uint64_t *pl = x_rp + ((size_t)img * kStemCh + c) * kPool;
+  auto row = [&](int iy) { return shifted_row(iy, [&](int r) { return pl[r]; }); };
+  const uint64_t T1 = table_word(t1, c), T2 = table_word(t2, c);
   uint64_t r1 = 0, r2 = 0;
-  if (oy < 10) {      // conv1: 3x2 window, rows oy-1..oy+1, 11 output columns; bottom row 10 is zero padding
+  if (oy < kPool) {   // conv1: 3x2 window, rows oy-1..oy+1, 11 output columns; bottom row 10 is zero padding
     const uint64_t a = row(oy - 1), b = row(oy), d = row(oy + 1);
-    for (int ox = 0; ox < 11; ++ox) {
-      const uint32_t idx = (uint32_t)((a >> ox) & 3) | ((uint32_t)((b >> ox) & 3) << 2) | ((uint32_t)((d >> ox) & 3) << 4);
-      r1 |= ((T1 >> idx) & 1ull) << ox;
-    }
+    for (int ox = 0; ox < kSide; ++ox) r1 |= ((T1 >> conv1_index(a, b, d, ox)) & 1ull) << ox;
   }
   {                   // conv2: 2x3 window, rows oy-1..oy, 10 output columns; right column 10 is zero padding
     const uint64_t a = row(oy - 1), b = row(oy);
-    for (int ox = 0; ox < 10; ++ox) {
-      const uint32_t idx = (uint32_t)((a >> ox) & 7) | ((uint32_t)((b >> ox) & 7) << 3);
-      r2 |= ((T2 >> idx) & 1ull) << ox;
-    }
+    for (int ox = 0; ox < kPool; ++ox) r2 |= ((T2 >> conv2_index(a, b, ox)) & 1ull) << ox;
   }
-  y[((size_t)img * 256 + c) * 11 + oy] = r1;
-  y[((size_t)img * 256 + 64 + c) * 11 + oy] = r2;
-  y[((size_t)img * 256 + 192 + c) * 11 + oy] = oy < 10 ? pl[oy] : 0ull;       // out4 = x, padded right / bottom
+  y[((size_t)img * kFeatCh + c) * kSide + oy] = r1;
+  y[((size_t)img * kFeatCh + 64 + c) * kSide + oy] = r2;
+  y[((size_t)img * kFeatCh + 192 + c) * kSide + oy] = oy < kPool ? pl[oy] : 0ull;   // out4 = x, padded right / bottom
 }
 
 // Block_conv3: thread = (image, group of 8 channels, row); table uint8 [8][256]
 __global__ void va_c3_kernel(const uint64_t *__restrict__ x_rp, const uint8_t *__restrict__ t3, uint64_t *__restrict__ y,
                              int n) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (size_t)n * 8 * 11) return;
-  const int oy = t % 11, g = (t / 11) % 8, img = t / 88;
+  if (t >= (size_t)n * 8 * kSide) return;
+  const int oy = t % kSide, g = (t / kSide) % 8, img = t / (8 * kSide);
   uint64_t rows[8], out[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    rows[k] = oy < 10 ? x_rp[((size_t)img * 64 + 8 * g + k) * 10 + oy] : 0ull;
+    rows[k] = oy < kPool ? x_rp[((size_t)img * kStemCh + 8 * g + k) * kPool + oy] : 0ull;
     out[k] = 0;
   }
-  if (oy < 10)
-    for (int xx = 0; xx < 10; ++xx) {
-      uint32_t idx = 0;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) idx |= (uint32_t)((rows[k] >> xx) & 1ull) << k;
-      const uint32_t v = t3[g * 256 + idx];
+  if (oy < kPool)
+    for (int xx = 0; xx < kPool; ++xx) {
+      const uint32_t v = t3[g * 256 + conv3_index(rows, xx)];
 #pragma unroll
       for (int k = 0; k < 8; ++k) out[k] |= (uint64_t)((v >> k) & 1u) << xx;
     }
 #pragma unroll
-  for (int k = 0; k < 8; ++k) y[((size_t)img * 256 + 128 + 8 * g + k) * 11 + oy] = out[k];
+  for (int k = 0; k < 8; ++k) y[((size_t)img * kFeatCh + 128 + 8 * g + k) * kSide + oy] = out[k];
 }
 
 // Flatten (C-major over [256][11][11]) into lin1's fragment-ordered operand.  The features are
@@ -212,7 +192,7 @@ __global__ void va_c3_kernel(const uint64_t *__restrict__ x_rp, const uint8_t *_
 // (plane 1 stays zero from allocation).  Thread = (image, k-step): its 16 features are two aligned
 // 16-byte runs of plane 0 (lane halves k < 8 and k >= 8 of the fragment).
 __global__ void va_feat_kernel(const uint64_t *__restrict__ y, uint16_t *__restrict__ feat_frag, int n) {
-  constexpr int KS = 256 * 121 / 16;
+  constexpr int KS = kFeat / 16;
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (size_t)n * KS) return;
   const int ks = t % KS, img = t / KS;
@@ -221,8 +201,8 @@ __global__ void va_feat_kernel(const uint64_t *__restrict__ y, uint16_t *__restr
   uint32_t half[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
 #pragma unroll
   for (int kk = 0; kk < 16; ++kk) {
-    const int f = 16 * ks + kk, ch = f / 121, rem = f - 121 * ch, oy = rem / 11, ox = rem - 11 * oy;
-    const uint32_t bit = (uint32_t)(y[((size_t)img * 256 + ch) * 11 + oy] >> ox) & 1u;
+    const int f = 16 * ks + kk, ch = f / kPlane, rem = f - kPlane * ch, oy = rem / kSide, ox = rem - kSide * oy;
+    const uint32_t bit = (uint32_t)(y[((size_t)img * kFeatCh + ch) * kSide + oy] >> ox) & 1u;
     half[kk >> 3][(kk & 7) >> 1] |= (bit ? ONE : 0u) << (16 * (kk & 1));
   }
   uint4 *dst = (uint4 *)feat_frag + ((((size_t)(img >> 5) * KS + ks) * SPLIT_PLANES + 0) * 64 + (img & 31));
@@ -232,7 +212,7 @@ __global__ void va_feat_kernel(const uint64_t *__restrict__ y, uint16_t *__restr
 
 __global__ void va_frag_to_flat_kernel(const uint16_t *__restrict__ af, float *__restrict__ out, int n) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  constexpr int K = 256 * 121, KS = K / 16;
+  constexpr int K = kFeat, KS = K / 16;
   if (t >= (size_t)n * K) return;
   const int f = t % K, img = t / K;
   out[t] = load_feature(af, img, KS, f >> 4, f & 15);
@@ -298,24 +278,24 @@ int va_stem_u8_kernel_arg_sizes(const int **sizes) {
 }
 
 int launch_va_block(const uint64_t *x_rp,const void *t1, const void *t2, const void *t3, uint64_t *y, int n, hipStream_t s) {
-  size_t t = (size_t)n * 64 * 11;
+  size_t t = (size_t)n * kStemCh * kSide;
   hipLaunchKernelGGL(va_dw_kernel, dim3((unsigned)((t + 127) / 128)), dim3(128), 0, s, x_rp, (const uint32_t *)t1,
                      (const uint32_t *)t2, y, n);
-  t = (size_t)n * 88;
+  t = (size_t)n * 8 * kSide;
   hipLaunchKernelGGL(va_c3_kernel, dim3((unsigned)((t + 127) / 128)), dim3(128), 0, s, x_rp, (const uint8_t *)t3, y, n);
   TT_HIP(hipGetLastError());
   return TTNET_OK;
 }
 
 int launch_va_feat(const uint64_t *y, void *feat_frag, int n, hipStream_t s) {
-  const size_t t = (size_t)n * (256 * 121 / 16);
+  const size_t t = (size_t)n * (kFeat / 16);
   hipLaunchKernelGGL(va_feat_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, y, (uint16_t *)feat_frag, n);
   TT_HIP(hipGetLastError());
   return TTNET_OK;
 }
 
 int launch_va_frag_to_flat(const void *af, float *out, int n, hipStream_t s) {
-  const size_t t = (size_t)n * 256 * 121;
+  const size_t t = (size_t)n * kFeat;
   hipLaunchKernelGGL(va_frag_to_flat_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, (const uint16_t *)af, out, n);
   TT_HIP(hipGetLastError());
   return TTNET_OK;

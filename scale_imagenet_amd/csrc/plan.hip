@@ -21,6 +21,7 @@
 #include <unordered_map>
 
 #include "ttnet_common.h"
+#include "va_block.h"
 
 namespace ttnet {
 
@@ -322,7 +323,7 @@ int build_geometry_valexnet(ttnet_plan *pl) {
   }
   pl->path = GatePath::VAlexnet;
   pl->p = 64;
-  pl->n_classes = 10; pl->inter = 100; pl->fcsize = 256 * 11 * 11;
+  pl->n_classes = va::kClasses; pl->inter = 100; pl->fcsize = va::kFeat;
   pl->head = "features.7";
   const float mean[3] = {0.4914f, 0.4822f, 0.4465f}, std[3] = {0.2023f, 0.1994f, 0.2010f};   // cifar_transform, utils/preprocess.py:82-87
   std::copy(mean, mean + 3, pl->in_mean);
@@ -503,8 +504,8 @@ int alloc_workspace(ttnet_plan *pl, ttnet_plan::Lane &L) {
   L.x_cp.assign(pl->blocks.size(), nullptr);
   L.blk.assign(pl->blocks.size(), {});
   if (path == GatePath::VAlexnet) {
-    TT_TRY(dev_alloc(pl, &L.x_rp[0], (size_t)nb * 64 * 10, true, ws));
-    TT_TRY(dev_alloc(pl, &L.va_y, (size_t)nb * 256 * 11, true, ws));
+    TT_TRY(dev_alloc(pl, &L.x_rp[0], (size_t)nb * va::kStemRows, true, ws));
+    TT_TRY(dev_alloc(pl, &L.va_y, (size_t)nb * va::kFeatRows, true, ws));
   } else {
     for (size_t i = 0; i < pl->blocks.size(); ++i) {
       const MultiHead &mh = pl->blocks[i];
@@ -1390,7 +1391,7 @@ int prepare_certify(ttnet_plan *pl, hipStream_t s) {
     TT_TRY(dev_alloc(pl, &c.stem_bn, 128, false));
     TT_TRY(dev_alloc(pl, &c.slack, 64, false));
     TT_TRY(dev_alloc(pl, &c.t3w, 8 * 8 * 4, false));
-    TT_TRY(dev_alloc(pl, &c.wsum, 64 * 3 * 25, false));
+    TT_TRY(dev_alloc(pl, &c.wsum, va::kWsum, false));
     TT_TRY(dev_alloc(pl, &hbn_dev, hbn.size(), false));
     TT_HIP(hipMemcpy(c.stem_bn, bn.data(), bn.size() * 8, hipMemcpyHostToDevice));
     TT_HIP(hipMemcpy(c.slack, slack.data(), slack.size() * 8, hipMemcpyHostToDevice));
@@ -1804,8 +1805,8 @@ int ttnet_certify_u8(ttnet_plan *pl, int lane, const uint8_t *x_nhwc_dev, int64_
   TT_HIP(hipSetDevice(pl->device));
   TT_TRY(prepare_certify(pl, s));
   ttnet_plan::Lane &L = pl->lanes[lane];
-  const size_t nb = (size_t)pl->desc.max_batch, stem_w = 64 * 10, feat_w = 256 * 11;
-  if (!L.cert_planes) TT_TRY(dev_alloc(pl, &L.cert_planes, nb * (2 * (stem_w + feat_w) + 10), false));
+  const size_t nb = (size_t)pl->desc.max_batch, stem_w = va::kStemRows, feat_w = va::kFeatRows;
+  if (!L.cert_planes) TT_TRY(dev_alloc(pl, &L.cert_planes, nb * (2 * (stem_w + feat_w) + va::kClasses), false));
   const MultiHead &mh = pl->blocks[0];
   CertifyArgs a{};
   a.n = (int)n;
@@ -1900,7 +1901,7 @@ int ttnet_attack_propose_u8(ttnet_plan *pl, int lane, const uint8_t *x0_dev, con
   a.stem = L.x_rp[0];
   a.feat = L.va_y;
   a.plane_lo = stem_planes_dev;
-  a.plane_hi = stem_planes_dev + (size_t)n * 64 * 10;
+  a.plane_hi = stem_planes_dev + (size_t)n * va::kStemRows;
   a.t1 = (const uint32_t *)mh.c1.table;
   a.t2 = (const uint32_t *)mh.c2.table;
   a.t3w = pl->cert.t3w;
@@ -1993,8 +1994,8 @@ int ttnet_read_stage(ttnet_plan *pl, const char *stage, int64_t n, void *dst, si
     return copy_out(tmp.p, bytes);
   }
   if (path == GatePath::VAlexnet) {
-    if (st == "features.4") return copy_out(L.x_rp[0], (size_t)n * 64 * 10 * 8);
-    if (st == "features.5") return copy_out(L.va_y, (size_t)n * 256 * 11 * 8);
+    if (st == "features.4") return copy_out(L.x_rp[0], (size_t)n * va::kStemRows * 8);
+    if (st == "features.5") return copy_out(L.va_y, (size_t)n * va::kFeatRows * 8);
     set_error("unknown stage %s", stage);
     return TTNET_E_INVALID;
   }

@@ -62,6 +62,12 @@ def replacing(path: Optional[str], mode: str = "w"):
         raise
 
 
+def write_csv(path: Optional[str], rows):
+    """``rows`` (header first) as CSV (``path`` None: standard output); written to a temporary name and renamed."""
+    with replacing(path) as f:
+        csv.writer(f, lineterminator="\n").writerows(rows)
+
+
 def _name(index: int, names: Optional[Sequence[str]]) -> str:
     if names is None or index < 0:
         return str(int(index))
@@ -127,8 +133,7 @@ def care_summary_rows(care, lookups_per_image) -> List[list]:
 
 
 def write_care_summary_csv(path: Optional[str], care, lookups_per_image):
-    with replacing(path) as f:
-        csv.writer(f, lineterminator="\n").writerows(care_summary_rows(care, lookups_per_image))
+    write_csv(path, care_summary_rows(care, lookups_per_image))
 
 
 def read_predictions_csv(path: str) -> Tuple[List[str], List[str], List[List[str]], np.ndarray]:
@@ -156,8 +161,7 @@ def per_class_rows(counts: np.ndarray, names: Optional[Sequence[str]] = None) ->
 
 
 def write_per_class_csv(path: Optional[str], counts: np.ndarray, names: Optional[Sequence[str]] = None):
-    with replacing(path) as f:
-        csv.writer(f, lineterminator="\n").writerows(per_class_rows(counts, names))
+    write_csv(path, per_class_rows(counts, names))
 
 
 def write_confusion(path: str, confusion: np.ndarray):
@@ -206,8 +210,7 @@ def coverage_rows(usage, tables=None) -> List[list]:
 
 
 def write_coverage_csv(path: Optional[str], usage, tables=None):
-    with replacing(path) as f:
-        csv.writer(f, lineterminator="\n").writerows(coverage_rows(usage, tables))
+    write_csv(path, coverage_rows(usage, tables))
 
 
 GATE_FIELDS = ["constant", "dnf_cubes", "dnf_literals", "cnf_cubes", "cnf_literals"]
@@ -223,8 +226,7 @@ def gate_rows(full, seen, inputs) -> List[list]:
 
 
 def write_gates_csv(path: Optional[str], full, seen, inputs):
-    with replacing(path) as f:
-        csv.writer(f, lineterminator="\n").writerows(gate_rows(full, seen, inputs))
+    write_csv(path, gate_rows(full, seen, inputs))
 
 
 RULE_FIELDS = ["block", "inputs", "form", "functions", "cubes", "literals", "top1pct_first_share", "top10pct_first_share", "unused_cubes"]
@@ -264,5 +266,4 @@ def rule_support_rows(support, pruned=None) -> List[list]:
 
 
 def write_rule_support_csv(path: Optional[str], support, pruned=None):
-    with replacing(path) as f:
-        csv.writer(f, lineterminator="\n").writerows(rule_support_rows(support, pruned))
+    write_csv(path, rule_support_rows(support, pruned))

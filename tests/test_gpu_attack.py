@@ -133,6 +133,30 @@ def test_propose_equals_the_twin(models, dev, norm, eps):
           f"{int(unknown.sum())} unknown stem bits, {int((active == 0).sum())} images falsified after round 1")
 
 
+def test_propose_gains_at_hand_placed_unknown_bits(models, dev):
+    """Unknown bits placed on the corners, the edges and one interior cell of channels 0, 7, 8 and 63 -- where a wrong border
+    or conv3 group boundary in the reach of a stem bit shows -- and nowhere else."""
+    model = models["cifar"]
+    _, st = spec_and_state("valexnet")
+    n = 3
+    x = images(dev, n)
+    bits, feats, logits = device_forward(model, dev)(U.images_np(n))    # lane 0 now holds the forward of x
+    cls = logits.argmax(axis=1)
+    worst = U.runner_up(logits, cls)
+    unknown = np.zeros((n, 64, 10, 10), dtype=bool)
+    for ch in (0, 7, 8, 63):
+        for y, xx in [(0, 0), (0, 9), (9, 0), (9, 9), (0, 5), (9, 5), (5, 0), (5, 9), (5, 5)]:
+            unknown[:, ch, y, xx] = True
+    # lo, hi: the forward's own bits, the marked ones 0 in lo and 1 in hi (unknown = where the planes differ)
+    planes = torch.from_numpy(np.stack([OB.pack_rows(bits & ~unknown), OB.pack_rows(bits | unknown)]).view(np.int64)).to(dev)
+    as_i32 = lambda a: torch.from_numpy(np.asarray(a).astype(np.int32)).to(dev)     # noqa: E731
+    _, gains = AT.propose_u8(model, x, x.clone(), as_i32(cls), as_i32(worst), planes, 1, as_i32(np.ones(n)), 0, return_gains=True)
+    got = gains.cpu().numpy()
+    want = AT.gains_cpu(AT.head_cpu(st), AT._words(tables(model)), bits, feats, unknown, cls, worst)
+    assert got.shape == (n, 64, 10, 10) and got.tobytes() == want.tobytes(), int((got != want).sum())
+    assert (got[~unknown] == 0).all() and (got[unknown] != 0).any()
+
+
 # ---- 2. select equals the twin -------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("n_cand", [1, 8])
