@@ -738,6 +738,29 @@ int ttnet_attack_select_u8(ttnet_plan *plan, const uint8_t *cand_dev, const floa
  * first launch at the batch size of the forward last issued on the lane used last). */
 int ttnet_plan_query(ttnet_plan *plan, const char *what, int64_t *out);
 
+/* How the launchers cut a batch into slices, rounds, runs and chunks (csrc/partition.h), read out by name.  Stateless:
+ * no plan, no device, no HIP call; it answers on a machine without a GPU.  `what` names a quantity, `args` are its n_args
+ * integer arguments, and the values are written to out[0 .. return value).  Keys, arguments -> values:
+ *   "slices_for" (n, units, target) -> slices          "slice" (sl, n, slices) -> n0, n1
+ *   "fused.const" () -> threads, table buffer bytes, round bytes, workgroups at most      "fused.round" (HO) -> images per round
+ *   "fused.launch" (C, HO, n) -> grid, slices, R, placement (0 plain, 1 quad, 2 pairs of 8)    "fused.owner" (b, C, n) -> strand, slice
+ *   "two_launch.const" () -> depthwise, conv3, convf workgroup targets
+ *   "two_launch.stage1" (C, n) -> grid, depthwise units, their slices, conv3 units, their slices    "two_launch.pf" (C, n) -> units, slices
+ *   "flat.xs_branches" (C, Ho), "flat.xs_pf" (C, Ho), "flat.xs_last" (C, Ho, Wo), "flat.va_dw" (), "flat.va_c3" (), "flat.va_feat" ()
+ *       -> tasks per image, threads per workgroup
+ *   "full.const" () -> depthwise rows per chunk, its grid cap, the grid of its list pass, 1x1 wave tasks per chunk, its grid cap,
+ *       the grid cap of its list pass, listed pixels per wave task, the share of the main pass's tasks that pass is sized for
+ *   "full.row_bundle" (H, W) -> rows per wave task, wave tasks per image      "full.dw" (n, C, ho) -> chunks, chunks at most
+ *   "full.pw" (n, groups, H, W) -> wave tasks, chunks, chunks at most, chunks of the list pass
+ *   "full.fix" (n, groups, H, W, listed) -> wave tasks of a group's list, chunks      "full.fix_entries" (groups, H, W) -> list entries per image
+ *   "stem.const" () -> items per image, stage buffers, workgroups on the whole chip, on half of it
+ *   "stem.workgroups" (lanes, u8, full variant) -> workgroups asked for       "stem.grid" (n, G) -> workgroups launched
+ *   "stem.run" (bid, n, G) -> first item, items                               "stem.continues" (first item, j) -> 0 / 1
+ * Returns the number of values written.  An unknown key, a wrong n_args, out_cap below the key's value count, n < 1, C not a
+ * multiple of 8 (16 for "two_launch.stage1") or any argument outside its range: TTNET_E_INVALID with the reason in
+ * ttnet_last_error(), and nothing is written. */
+int ttnet_launch_partition(const char *what, const int64_t *args, int n_args, int64_t *out, int out_cap);
+
 /* Device time of the kernels of the last forward, measured with HIP events on the stream
  * the kernels were launched on (enable with ttnet_plan_set_profiling).  names/ms are
  * arrays of capacity `cap`; returns the number of entries.  Synchronises. */

@@ -104,6 +104,7 @@ SYMBOLS: List[Tuple[str, object, list]] = [
     ("ttnet_attack_propose_u8", C.c_int, [_P, C.c_int, _P, _P, C.c_int64, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
     ("ttnet_attack_select_u8", C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, C.c_double, _P, _P, _P, _P, _P, C.c_int, _P]),
     ("ttnet_plan_query", C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
+    ("ttnet_launch_partition", C.c_int, [C.c_char_p, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64), C.c_int]),
     ("ttnet_plan_set_profiling", C.c_int, [_P, C.c_int]),
     ("ttnet_plan_last_timings", C.c_int, [_P, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
     ("ttnet_plan_destroy", None, [_P]),
@@ -140,3 +141,10 @@ def check(status: int) -> int:
     if status < 0:
         raise TTNetError(status, load().ttnet_last_error().decode("utf-8", "replace"))
     return status
+
+
+def launch_partition(what: str, *args: int) -> Tuple[int, ...]:
+    """ttnet_launch_partition: the launch arithmetic of csrc/partition.h by name (no plan, no device)."""
+    a = (C.c_int64 * max(1, len(args)))(*args)
+    out = (C.c_int64 * 8)()
+    return tuple(out[:check(load().ttnet_launch_partition(what.encode(), a, len(args), out, len(out)))])

@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libttnet.so")
-SOURCES = ["plan.hip", "comm.hip", "lut_build.hip", "stem.hip", "gate.hip", "gate_fused.hip", "gate_xs.hip", "gate_full.hip", "gate_va.hip", "head.hip", "preproc.hip", "jpeg.hip", "metrics.hip", "usage.hip", "minimise.hip", "rules.hip", "certify.hip", "attack.hip"]
+SOURCES = ["plan.hip", "partition.hip", "comm.hip", "lut_build.hip", "stem.hip", "gate.hip", "gate_fused.hip", "gate_xs.hip", "gate_full.hip", "gate_va.hip", "head.hip", "preproc.hip", "jpeg.hip", "metrics.hip", "usage.hip", "minimise.hip", "rules.hip", "certify.hip", "attack.hip"]
 # gate_full.hip: the same flag keeps the float32 GELU of the fast kernels out of v_pk_* with shuffling moves.
 # stem.hip: without -fno-slp-vectorize the producers' pooling adds become v_pk_add_f32 behind shuffling moves, which
 # beside the consumers' MFMAs cost 82 us per launch instead of 65 (tools/ubench/stem_parts.hip)
@@ -36,6 +36,8 @@ def build_lib(force: bool = False, verbose: bool = True) -> str:
     headers = [os.path.join(CSRC, "ttnet_common.h"), os.path.join(HERE, "..", "include", "ttnet.h")]
     included = {"gate_full.hip": [os.path.join(CSRC, "erf_table.inc")]}
     included.update({src: [os.path.join(CSRC, "va_block.h")] for src in ("gate_va.hip", "certify.hip", "attack.hip", "plan.hip")})
+    for src in ("partition.hip", "plan.hip", "stem.hip", "gate.hip", "gate_fused.hip", "gate_xs.hip", "gate_full.hip", "gate_va.hip"):
+        included[src] = included.get(src, []) + [os.path.join(CSRC, "partition.h"), os.path.join(CSRC, "va_block.h")]      # (partition.h includes va_block.h)
     jobs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

@@ -22,6 +22,7 @@
 #include <stdlib.h>
 #include <type_traits>
 
+#include "partition.h"
 #include "ttnet_common.h"
 
 namespace ttnet {
@@ -93,56 +94,6 @@ __device__ inline void dw_row(const uint32_t (&lo)[KH], const uint32_t (&hi)[KH]
 // Each lane accumulates its own output row (bit x = column x); the 16 lanes of a channel
 // group then transpose their 16x16 bit blocks in registers (4 butterfly stages, both
 // halves at once) so that lane j holds the channel words of columns j and 16+j.
-template <int P, bool HIGH_HALF>
-__device__ inline void dw_pair(const uint32_t (&d)[4][3], const uint32_t *tab32_bytes, uint32_t c4, uint32_t &acc) {
-  // shift of the pair base column P: 2P bits; funnel over dwords (j, j+1)
-  constexpr int SH = 2 * P, J = SH / 32, R = SH % 32;
-  uint32_t idx2;
-  {
-    const uint32_t a0 = R ? __builtin_amdgcn_alignbit(d[0][J + 1], d[0][J], R) : d[0][J];
-    const uint32_t a1 = R ? __builtin_amdgcn_alignbit(d[1][J + 1], d[1][J], R) : d[1][J];
-    const uint32_t a2 = R ? __builtin_amdgcn_alignbit(d[2][J + 1], d[2][J], R) : d[2][J];
-    const uint32_t a3 = R ? __builtin_amdgcn_alignbit(d[3][J + 1], d[3][J], R) : d[3][J];
-    idx2 = (a0 & 0x000F000Fu) | (a1 & 0x00F000F0u) | (a2 & 0x0F000F00u) | (a3 & 0xF000F000u);
-  }
-  const uint8_t *tb = (const uint8_t *)tab32_bytes;
-  // striped table: dword (idx>>5) of channel c at byte ((idx>>5)*16 + c)*4
-  const uint32_t w_lo = *(const uint32_t *)(tb + (((idx2 & 0xFFE0u) << 1) | c4));
-  acc |= ((w_lo >> (idx2 & 31u)) & 1u) << P;
-  if constexpr (HIGH_HALF) {
-    const uint32_t w_hi = *(const uint32_t *)(tb + (((idx2 >> 15) & 0x1FFC0u) | c4));
-    acc |= ((w_hi >> ((idx2 >> 16) & 31u)) & 1u) << (P + 8);
-  }
-}
-
-// rows: the lane's four input rows (bit x = column x); returns the channel words of columns
-// (lane&15) [low half] and 16 + (lane&15) [high half] of this lane's output row.
-template <int WO>
-__device__ inline uint32_t dw_row_4x4s2(const uint64_t (&rows)[4], const uint32_t *tab32, const DwLaneConst &k) {
-  uint32_t d[4][3];
-#pragma unroll
-  for (int kh = 0; kh < 4; ++kh) {
-    // padded row (2 zero columns on the left) shifted left by 4*kh: up to 60 + 2 + 12 = 74 bits
-    const uint32_t lo = (uint32_t)rows[kh], hi = (uint32_t)(rows[kh] >> 32);
-    const int sh = 2 + 4 * kh;
-    d[kh][0] = lo << sh;
-    d[kh][1] = __builtin_amdgcn_alignbit(hi, lo, 32 - sh);
-    d[kh][2] = hi >> (32 - sh);
-  }
-  uint32_t acc = 0;
-  static_for<0, 8>([&](auto p) { dw_pair<decltype(p)::value, (WO > 8)>(d, tab32, k.c4, acc); });
-  if constexpr (WO > 16) static_for<16, 24>([&](auto p) { dw_pair<decltype(p)::value, (WO > 24)>(d, tab32, k.c4, acc); });
-  // 16x16 bit transpose across the 16 lanes of the channel group, both halves at once
-  constexpr int S[4] = {8, 4, 2, 1};
-  static_for<0, 4>([&](auto i) {
-    constexpr int I = decltype(i)::value;
-    const uint32_t partner = (uint32_t)__builtin_amdgcn_ds_swizzle((int)acc, 0x1F | (S[I] << 10));
-    const uint32_t moved = __builtin_amdgcn_alignbit(partner, partner, k.rot[I]);
-    acc = moved ^ ((moved ^ acc) & k.keep[I]);
-  });
-  return acc;
-}
-
 // Both depthwise branches at once.  Block_conv1 and Block_conv2 read the same input windows, so
 // the window index (the expensive part: four funnel shifts and four masked merges per column pair)
 // is formed once and looked up in both tables.  The LDS table set of such a unit is striped as
@@ -219,9 +170,9 @@ __global__ __launch_bounds__(kGateThreads) void gate_stage1_kernel(GateBlockArgs
   if ((int)blockIdx.x < dw_blocks) {
     const int unit = blockIdx.x % n_dw;
     const int sl = blockIdx.x / n_dw;                   // batch slices of (almost) equal size
-    const int n0 = (int)((long long)sl * a.n / slices_dw);
+    const int n0 = part::slice_begin(sl, a.n, slices_dw);
     if (n0 >= a.n) return;
-    const int n1 = (int)((long long)(sl + 1) * a.n / slices_dw);
+    const int n1 = part::slice_begin(sl + 1, a.n, slices_dw);
     if constexpr (KH == 4 && KW == 4 && STRIDE == 2 && PAD == 2 && WO <= 32) {
       // unit = (group q, half h): 8 channels, BOTH branches (see dw_pair2)
       const int q = unit >> 1, half = unit & 1;
@@ -329,9 +280,9 @@ __global__ __launch_bounds__(kGateThreads) void gate_stage1_kernel(GateBlockArgs
     const int b = blockIdx.x - dw_blocks;
     const int q = b % Q;
     const int sl = b / Q;
-    const int n0 = (int)((long long)sl * a.n / slices_pw);
+    const int n0 = part::slice_begin(sl, a.n, slices_pw);
     if (n0 >= a.n) return;
-    const int n1 = (int)((long long)(sl + 1) * a.n / slices_pw);
+    const int n1 = part::slice_begin(sl + 1, a.n, slices_pw);
     stage_lds_async(lds, (const uint8_t *)(a.t_c3 + (size_t)q * 65536), kTableLds);
     wait_lds_stage();
     const uint16_t *tab = (const uint16_t *)lds;
@@ -414,9 +365,9 @@ __global__ __launch_bounds__(kGateThreads) void gate_pf_kernel(GateBlockArgs a, 
   constexpr int LPR = WO <= 16 ? 16 : (WO <= 32 ? 32 : 64), RPW = 64 / LPR, chunks = (HO + RPW - 1) / RPW;
   const int j = blockIdx.x;              // output word; groups 2j, 2j+1
   const int Q = a.C / 16, Cout = CG * (a.C / 4), Qout = Cout / 16;
-  const int n0 = (int)((long long)blockIdx.y * a.n / slices);
+  const int n0 = part::slice_begin(blockIdx.y, a.n, slices);
   if (n0 >= a.n) return;
-  const int n1 = (int)((long long)(blockIdx.y + 1) * a.n / slices);
+  const int n1 = part::slice_begin(blockIdx.y + 1, a.n, slices);
   stage_lds_async(lds, t_cf + (size_t)(2 * j) * 65536, kTableLds);
   const int wq = j >> 1, sh = 8 * (j & 1);
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = kGateThreads / 64;
@@ -614,47 +565,29 @@ __global__ void rp_to_cp_kernel(const uint64_t *rp, uint16_t *cp, int n, int C, 
   }
 }
 
-// batch slices per table set so that `units` table sets spread over at most `target` workgroups
-int slices_for(int n, int units, int target) { return std::max(1, std::min(n, target / std::max(1, units))); }
-constexpr int kDwTarget = 208, kPwTarget = 48;       // stage 1: workgroups of the depthwise / conv3 units (launch_stage1_t)
-
-template <typename K>
-int allow_big_lds(K kernel, size_t bytes) {
-  return ensure_dynamic_lds((const void *)kernel, bytes);
-}
-
 template <int H, int HO, int STRIDE = 2>
 int launch_stage1_t(const GateBlockArgs &a, hipStream_t s) {
   // 1 workgroup per CU (128 KiB of tables in LDS), and every workgroup pays ~2 us of table
-  // staging: the whole launch is one round of the chip, 208 depthwise + 48 conv3 workgroups
-  // (measured best split at B = 256; a second round of conv3 blocks cost 3-5 us per launch).
-  const int n_dw = (a.C / 16) * 2, n_pw = a.C / 16;
-  const int sl_dw = slices_for(a.n, n_dw, kDwTarget), sl_pw = slices_for(a.n, n_pw, kPwTarget);
-  const int dw_blocks = n_dw * sl_dw, pw_blocks = n_pw * sl_pw;
+  // staging: the whole launch is one round of the chip (partition.h: kDwTarget, kPwTarget)
+  const part::Stage1Grid g = part::stage1_grid(a.C, a.n);
   auto k = gate_stage1_kernel<4, 4, STRIDE, 2, H, HO>;
-  TT_TRY(allow_big_lds(k, kTableLds));
-  hipLaunchKernelGGL(k, dim3(dw_blocks + pw_blocks), dim3(kGateThreads), kTableLds, s, a, n_dw, dw_blocks, sl_dw, sl_pw);
+  TT_TRY(ensure_dynamic_lds((const void *)k, kTableLds));
+  hipLaunchKernelGGL(k, dim3(g.blocks()), dim3(kGateThreads), kTableLds, s, a, g.n_dw, g.dw_blocks(), g.sl_dw, g.sl_pw);
   TT_HIP(hipGetLastError());
   return TTNET_OK;
 }
 
 template <int HO, int CG = 8>
 int launch_pf_t(const GateBlockArgs &a, const uint8_t *t_cf, uint16_t *out_cp, uint64_t *out_rp, hipStream_t s) {
-  const int units = a.C / 8;
-  const int slices = slices_for(a.n, units, 256);
+  const int units = part::pf_units(a.C), slices = part::pf_slices(a.C, a.n);
   auto k = gate_pf_kernel<HO, CG>;
-  TT_TRY(allow_big_lds(k, kTableLds));
+  TT_TRY(ensure_dynamic_lds((const void *)k, kTableLds));
   hipLaunchKernelGGL(k, dim3(units, slices), dim3(kGateThreads), kTableLds, s, a, t_cf, out_cp, out_rp, slices);
   TT_HIP(hipGetLastError());
   return TTNET_OK;
 }
 
 }  // namespace
-
-int gate_stage1_grid(int C, int n) {
-  const int n_dw = (C / 16) * 2, n_pw = C / 16;
-  return n_dw * slices_for(n, n_dw, kDwTarget) + n_pw * slices_for(n, n_pw, kPwTarget);
-}
 
 int launch_gate_stage1(const GateBlockArgs &a, hipStream_t s) {
   if (a.C % 16 || a.H != a.W || a.Ho != a.Wo || a.kh1 != 4 || a.kw1 != 4 || a.kh2 != 4 || a.kw2 != 4 ||

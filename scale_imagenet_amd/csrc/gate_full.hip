@@ -18,6 +18,7 @@
 
 #include <cstdlib>
 
+#include "partition.h"
 #include "ttnet_common.h"
 
 namespace ttnet {
@@ -142,18 +143,9 @@ __global__ __launch_bounds__(256) void full_dw_tab_kernel(FullDwArgs a) {
 // block, relu'd float32.
 constexpr int kPwCin = 30, kPwMid = 240, kPwMT = kPwMid / 16;     // MT: tiles of 16 hidden units
 
-// A wave task covers as many whole image rows as fit its 64 lanes (one row of 56 pixels, two of 29,
-// four of 16, seven of 9): lane = (row r of the bundle, column x).  (One row per wave left 55-85 % of
+// A wave task covers as many whole image rows as fit its 64 lanes (partition.h).  (One row per wave left 55-85 % of
 // the lanes idle in the later blocks.)
-struct RowBundle {
-  int W, rpw, bundles;                 // row width; rows per bundle, bundles per image
-  __host__ __device__ RowBundle(int H, int W_) : W(W_), rpw(64 / W_), bundles((H + rpw - 1) / rpw) {}
-  struct Pixel { int r, x; };          // row inside the bundle, column
-  __device__ Pixel pixel(int p) const {        // pixel p = 0 .. 63 of a bundle (r >= rpw: beyond it)
-    const int r = p / W;
-    return {r, p - r * W};
-  }
-};
+using part::RowBundle;
 
 // One ballot per pixel tile of 16: bits 16 q .. 16 q + 15 = member q of a channel quartet over the tile's pixels.
 // Lane (q = lg, bundle row ln) gets the row word of its channel: the W bits of row ln out of the 64 pixels.
@@ -199,9 +191,10 @@ __global__ __launch_bounds__(512) void full_pw_mfma_kernel(FullPwArgs a) {
   erf_table_to_lds(erf_tab);
   constexpr int CIN = kPwCin, MT = kPwMT, KS1 = L::KS1;
   constexpr int NTT = FIX ? 1 : 4;                       // pixel tiles of 16 per task (FIX: one, so that a short list still spreads over the chip)
+  static_assert(part::kFullFixPixels == 16 && part::kFullFixShare == 4, "a FIX task is one tile of 16 listed pixels, a quarter of a row task");
   if constexpr (FIX) {                                   // nothing listed for this workgroup: skip the weight staging too
     const uint32_t capq = (uint32_t)a.n * (uint32_t)a.H * (uint32_t)a.W, cnt = min(a.fix_count[blockIdx.x], capq);
-    if (blockIdx.y * (blockDim.x >> 6) >= (cnt + 15u) / 16u) return;
+    if (blockIdx.y * (blockDim.x >> 6) >= part::full_fix_tasks(cnt)) return;
   }
   double *w1f = (double *)(lds_raw + L::w1f), *w2f = (double *)(lds_raw + L::w2f);
   double *s1 = (double *)(lds_raw + L::s1), *t1 = (double *)(lds_raw + L::t1);
@@ -226,7 +219,7 @@ __global__ __launch_bounds__(512) void full_pw_mfma_kernel(FullPwArgs a) {
   const RowBundle rb(a.H, a.W);
   const uint32_t cap = (uint32_t)a.n * (uint32_t)a.H * (uint32_t)a.W;
   const uint32_t listed = FIX ? min(a.fix_count[g], cap) : 0u;
-  const int tasks = FIX ? (int)((listed + 15u) / 16u) : a.n * rb.bundles;
+  const int tasks = FIX ? (int)part::full_fix_tasks(listed) : a.n * rb.bundles;
   for (int t = blockIdx.y * nwaves + wave; t < tasks; t += gridDim.y * nwaves) {
     int n, y0, y, x;
     bool live;
@@ -976,28 +969,26 @@ float full_tau_scale() {
 
 template <int KH, int KW>
 int launch_full_dw_window(const FullDwArgs &a, hipStream_t s) {
-  const int rows = a.n * a.ho;
-  const int chunks = std::max(1, std::min((rows + 255) / 256, std::max(1, 1024 / a.C)));
-  if (full_exact_only() || !(a.fix_list && a.fix_count && a.fix_cap))
-    return launch_kernel(full_dw_tab_kernel<KH, KW>, dim3(a.C, chunks), dim3(256), 0, s, a);
+  const int chunks = part::full_dw_chunks(a.n, a.C, a.ho);
+  const dim3 grid(a.C, chunks), block(part::kFullDwRows);
+  if (full_exact_only() || !(a.fix_list && a.fix_count && a.fix_cap)) return launch_kernel(full_dw_tab_kernel<KH, KW>, grid, block, 0, s, a);
   TT_HIP(hipMemsetAsync(a.fix_count, 0, sizeof(uint32_t), s));
-  TT_TRY(launch_kernel(full_dw_fast_kernel<KH, KW>, dim3(a.C, chunks), dim3(256), 0, s, a));
-  return launch_kernel(full_dw_fix_kernel, dim3(1024), dim3(256), 0, s, a);
+  TT_TRY(launch_kernel(full_dw_fast_kernel<KH, KW>, grid, block, 0, s, a));
+  return launch_kernel(full_dw_fix_kernel, dim3(part::kFullDwFixGrid), dim3(256), 0, s, a);
 }
 
 template <int OT>
 int launch_full_pw_tiles(const FullPwArgs &a, hipStream_t s) {
-  const int tasks = a.n * RowBundle(a.H, a.W).bundles;
-  const int chunks = std::max(1, std::min((tasks + 7) / 8, std::max(1, 512 / a.groups)));
+  const int tasks = part::full_pw_tasks(a.n, a.H, a.W);
+  const dim3 grid(a.groups, part::full_pw_chunks(tasks, a.groups)), block(64 * part::kFullPwWaves);
   const bool fast = !full_exact_only() && (a.out_float || (a.fix_list && a.fix_count)) && a.groups <= 62;
-  if (!fast) return launch_kernel(full_pw_mfma_kernel<OT, false>, dim3(a.groups, chunks), dim3(512), MfmaLds<OT>::bytes, s, a);
+  if (!fast) return launch_kernel(full_pw_mfma_kernel<OT, false>, grid, block, MfmaLds<OT>::bytes, s, a);
   if (!a.out_float) TT_HIP(hipMemsetAsync(a.fix_count, 0, 62 * sizeof(uint32_t), s));
-  TT_TRY(launch_kernel(full_pw_fast_kernel<OT>, dim3(a.groups, chunks), dim3(512), FastLds<OT>::bytes, s, a));
+  TT_TRY(launch_kernel(full_pw_fast_kernel<OT>, grid, block, FastLds<OT>::bytes, s, a));
   if (a.out_float) return TTNET_OK;
   // the listed pixels in float64, 16 per wave task: one workgroup per CU (its float64 fragments fill the LDS);
   // workgroups without listed pixels leave at once
-  const int xchunks = std::max(1, std::min((tasks / 4 + 7) / 8, std::max(1, 256 / a.groups)));
-  return launch_kernel(full_pw_mfma_kernel<OT, true>, dim3(a.groups, xchunks), dim3(512), MfmaLds<OT>::bytes, s, a);
+  return launch_kernel(full_pw_mfma_kernel<OT, true>, dim3(a.groups, part::full_fix_xchunks(tasks, a.groups)), block, MfmaLds<OT>::bytes, s, a);
 }
 
 }  // namespace

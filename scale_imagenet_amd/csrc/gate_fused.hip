@@ -39,6 +39,7 @@
 
 #include <type_traits>
 
+#include "partition.h"
 #include "ttnet_common.h"
 
 namespace ttnet {
@@ -52,20 +53,13 @@ namespace {
 #endif
 constexpr int kSkip = TT_FUSED_SKIP;
 
-constexpr int kFT = 1024;              // threads per workgroup: 16 waves, 4 per SIMD
-constexpr int kFBuf = 65536;           // one table buffer
-constexpr int kFMaxScratch = 160 * 1024 - 2 * kFBuf;
+// partition.h: threads per workgroup, bytes of a table buffer, images per round; also the batch slices and the slice bounds
+using part::kFT;
+using part::kFBuf;
+using part::fused_round;
 
 template <int W>
 using row_t = std::conditional_t<(W > 32), uint64_t, std::conditional_t<(W > 16), uint32_t, uint16_t>>;
-
-// images per round of a workgroup: one depthwise (channel, output row) task per thread, the branch dwords
-// of a round in the LDS left over by the two table buffers
-template <int HO>
-constexpr int fused_round() {
-  constexpr int RG = (HO + 3) / 4, a = kFT / (16 * RG), b = kFMaxScratch / (HO * HO * 4);
-  return a < b ? (a < 32 ? a : 32) : (b < 32 ? b : 32);
-}
 
 struct FusedArgs {
   int n, C, slices, off34, R;
@@ -205,6 +199,10 @@ __global__ __launch_bounds__(kFT) void gate_block_kernel(FusedArgs a) {
   if (lds_addr(lds) & (kFBuf - 1)) __builtin_trap();   // (never: a kernel without static LDS has its dynamic array at 0)
 
   // ---- which strand, which images (placement: see the file header) ----------------------------
+  // The one restatement left of partition.h: these lines are part::fused_owner(blockIdx.x, strands, a.slices).  Called
+  // as a function it compiles to the same instruction count with the two scalar tests at kernel entry inverted, and
+  // that state did not pass the alternated timing rule (profiles/partition_refactor.txt, section 2), so the kernel keeps
+  // its own lines and its listing is the parent's.  Whoever changes one changes the other.
   const int strands = a.C / 8, P = strands / 2;
   int st, sl;
   {
@@ -221,7 +219,7 @@ __global__ __launch_bounds__(kFT) void gate_block_kernel(FusedArgs a) {
       sl = b / strands;
     }
   }
-  const int n0 = (int)((long long)sl * a.n / a.slices), n1 = (int)((long long)(sl + 1) * a.n / a.slices);
+  const int n0 = part::slice_begin(sl, a.n, a.slices), n1 = part::slice_begin(sl + 1, a.n, a.slices);
   if (n0 >= n1) return;
   const int q = st >> 1, half = st & 1;
   const int tid0 = threadIdx.x, lane = tid0 & 63;
@@ -241,7 +239,7 @@ __global__ __launch_bounds__(kFT) void gate_block_kernel(FusedArgs a) {
   const uint8_t *const src_cf0 = LAST ? nullptr : a.t_cf + (size_t)(2 * st) * kFBuf, *const src_cf1 = LAST ? nullptr : src_cf0 + kFBuf;
 
   // ---- register-resident inputs of the phases (loaded one phase ahead) -------------------------
-  constexpr int RMAX = fused_round<HO>();                  // images per round (host: launch_block_t)
+  constexpr int RMAX = fused_round(HO);                    // images per round (host: launch_block_t)
   constexpr int TA = (RMAX * HP + kFT / 16 - 1) / (kFT / 16);   // phase-A tasks (image, row pair) per 16-lane group
   static_assert(RMAX * RG * 16 <= kFT, "one depthwise task per thread");
   TI ra[TA][2];
@@ -544,9 +542,7 @@ int launch_block_t(const FusedBlockArgs &f, hipStream_t s) {
   auto k = gate_block_kernel<H, HO, LAST>;
   constexpr int PIX = HO * HO;
   const int strands = f.C / 8;
-  int R = fused_round<HO>();
-  const int slices = fused_block_slices(f.C, f.n);
-  R = std::max(1, std::min(R, (f.n + slices - 1) / slices));
+  const int slices = part::fused_block_slices(f.C, f.n), R = part::fused_launch_round(HO, f.n, slices);
   const size_t lds = (size_t)2 * kFBuf + (size_t)R * PIX * 4;
   TT_TRY(ensure_dynamic_lds((const void *)k, kMaxLds));
   FusedArgs a{};
@@ -560,14 +556,6 @@ int launch_block_t(const FusedBlockArgs &f, hipStream_t s) {
 }  // namespace
 
 int row_bytes(int W) { return W > 32 ? 8 : (W > 16 ? 4 : 2); }
-
-// batch slices per strand: the grid of a block is (C / 8) * slices workgroups (launch_block_t; "gate_grid:<i>" of ttnet_plan_query)
-int fused_block_slices(int C, int n) {
-  const int strands = C / 8;
-  int slices = std::max(1, std::min(n, 256 / strands));
-  if (strands == 8 && slices > 1 && (slices & 1)) slices -= 1;       // (the pair placement wants an even count)
-  return slices;
-}
 
 bool fused_block_supported(int C, int H, int Ho, int stride, int pad, int kh, int kw) {
   if (stride != 2 || pad != 2 || kh != 4 || kw != 4 || C % 16) return false;

@@ -12,6 +12,7 @@
 
 #include <math.h>
 
+#include "partition.h"
 #include "ttnet_common.h"
 #include "va_block.h"
 
@@ -146,8 +147,8 @@ __global__ __launch_bounds__(640) void va_stem_u8_kernel(const uint8_t *__restri
 __global__ void va_dw_kernel(const uint64_t *__restrict__ x_rp, const uint32_t *__restrict__ t1,
                              const uint32_t *__restrict__ t2, uint64_t *__restrict__ y, int n) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (size_t)n * kStemCh * kSide) return;
-  const int oy = t % kSide, c = (t / kSide) % kStemCh, img = t / (kSide * kStemCh);
+  if (t >= (size_t)n * part::kVaDwTasks) return;
+  const int oy = t % kSide, c = (t / kSide) % kStemCh, img = t / part::kVaDwTasks;
   const uint64_t *pl = x_rp + ((size_t)img * kStemCh + c) * kPool;
   auto row = [&](int iy) { return shifted_row(iy, [&](int r) { return pl[r]; }); };
   const uint64_t T1 = table_word(t1, c), T2 = table_word(t2, c);
@@ -169,8 +170,8 @@ __global__ void va_dw_kernel(const uint64_t *__restrict__ x_rp, const uint32_t *
 __global__ void va_c3_kernel(const uint64_t *__restrict__ x_rp, const uint8_t *__restrict__ t3, uint64_t *__restrict__ y,
                              int n) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (size_t)n * 8 * kSide) return;
-  const int oy = t % kSide, g = (t / kSide) % 8, img = t / (8 * kSide);
+  if (t >= (size_t)n * part::kVaC3Tasks) return;
+  const int oy = t % kSide, g = (t / kSide) % part::kVaC3Groups, img = t / part::kVaC3Tasks;
   uint64_t rows[8], out[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
@@ -192,7 +193,7 @@ __global__ void va_c3_kernel(const uint64_t *__restrict__ x_rp, const uint8_t *_
 // (plane 1 stays zero from allocation).  Thread = (image, k-step): its 16 features are two aligned
 // 16-byte runs of plane 0 (lane halves k < 8 and k >= 8 of the fragment).
 __global__ void va_feat_kernel(const uint64_t *__restrict__ y, uint16_t *__restrict__ feat_frag, int n) {
-  constexpr int KS = kFeat / 16;
+  constexpr int KS = part::kVaFeatTasks;
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (size_t)n * KS) return;
   const int ks = t % KS, img = t / KS;
@@ -278,18 +279,17 @@ int va_stem_u8_kernel_arg_sizes(const int **sizes) {
 }
 
 int launch_va_block(const uint64_t *x_rp,const void *t1, const void *t2, const void *t3, uint64_t *y, int n, hipStream_t s) {
-  size_t t = (size_t)n * kStemCh * kSide;
-  hipLaunchKernelGGL(va_dw_kernel, dim3((unsigned)((t + 127) / 128)), dim3(128), 0, s, x_rp, (const uint32_t *)t1,
+  constexpr part::FlatGrid dw = part::va_dw_grid(), c3 = part::va_c3_grid();
+  hipLaunchKernelGGL(va_dw_kernel, dim3(dw.workgroups(n)), dim3(dw.threads), 0, s, x_rp, (const uint32_t *)t1,
                      (const uint32_t *)t2, y, n);
-  t = (size_t)n * 8 * kSide;
-  hipLaunchKernelGGL(va_c3_kernel, dim3((unsigned)((t + 127) / 128)), dim3(128), 0, s, x_rp, (const uint8_t *)t3, y, n);
+  hipLaunchKernelGGL(va_c3_kernel, dim3(c3.workgroups(n)), dim3(c3.threads), 0, s, x_rp, (const uint8_t *)t3, y, n);
   TT_HIP(hipGetLastError());
   return TTNET_OK;
 }
 
 int launch_va_feat(const uint64_t *y, void *feat_frag, int n, hipStream_t s) {
-  const size_t t = (size_t)n * (kFeat / 16);
-  hipLaunchKernelGGL(va_feat_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s, y, (uint16_t *)feat_frag, n);
+  constexpr part::FlatGrid g = part::va_feat_grid();
+  hipLaunchKernelGGL(va_feat_kernel, dim3(g.workgroups(n)), dim3(g.threads), 0, s, y, (uint16_t *)feat_frag, n);
   TT_HIP(hipGetLastError());
   return TTNET_OK;
 }

@@ -10,6 +10,7 @@
 // instead of one lookup per pixel.  Stride-2 windows and the 2x2 majority are evaluated at every
 // bit position on the un-decimated rows and the even positions are then squeezed together.
 
+#include "partition.h"
 #include "ttnet_common.h"
 
 namespace ttnet {
@@ -156,8 +157,8 @@ int launch_xs_branches(const GateBlockArgs &a, const void *t_c3, uint64_t *const
     set_error("xs_branches: unsupported geometry");
     return TTNET_E_UNSUPPORTED;
   }
-  const size_t t = (size_t)a.n * (a.C / 4) * a.Ho;
-  hipLaunchKernelGGL(xs_branches_kernel, dim3((unsigned)((t + 127) / 128)), dim3(128), 0, s, a, (const uint32_t *)a.t_dw1,
+  const part::FlatGrid g = part::xs_branches_grid(a.C, a.Ho);
+  hipLaunchKernelGGL(xs_branches_kernel, dim3(g.workgroups(a.n)), dim3(g.threads), 0, s, a, (const uint32_t *)a.t_dw1,
                      (const uint32_t *)a.t_dw2, (const uint8_t *)t_c3, o[0], o[1], o[2], o[3]);
   TT_HIP(hipGetLastError());
   return TTNET_OK;
@@ -169,8 +170,8 @@ int launch_xs_pf(int n, int C, int Ho, int Wo, int cout_g, uint64_t *const o[4],
     set_error("xs_pf: cout_g=%d", cout_g);
     return TTNET_E_UNSUPPORTED;
   }
-  const size_t t = (size_t)n * C * Ho;
-  hipLaunchKernelGGL(xs_pf_kernel, dim3((unsigned)((t + 127) / 128)), dim3(128), 0, s, n, C, Ho, Wo, cout_g, o[0], o[1], o[2],
+  const part::FlatGrid g = part::xs_pf_grid(C, Ho);
+  hipLaunchKernelGGL(xs_pf_kernel, dim3(g.workgroups(n)), dim3(g.threads), 0, s, n, C, Ho, Wo, cout_g, o[0], o[1], o[2],
                      o[3], (const uint8_t *)t_cf, out_rp);
   TT_HIP(hipGetLastError());
   return TTNET_OK;
@@ -182,8 +183,8 @@ int launch_xs_last(int n, int C, int Ho, int Wo, int cout_g, uint64_t *const o[4
     set_error("xs_last: cout_g=%d", cout_g);
     return TTNET_E_UNSUPPORTED;
   }
-  const size_t t = (size_t)n * C * (Ho / 2) * (Wo / 2);
-  hipLaunchKernelGGL(xs_last_kernel, dim3((unsigned)((t + 127) / 128)), dim3(128), 0, s, n, C, Ho, Wo, cout_g, o[0], o[1], o[2],
+  const part::FlatGrid g = part::xs_last_grid(C, Ho, Wo);
+  hipLaunchKernelGGL(xs_last_kernel, dim3(g.workgroups(n)), dim3(g.threads), 0, s, n, C, Ho, Wo, cout_g, o[0], o[1], o[2],
                      o[3], t_last, (uint16_t *)feat_frag, range_flag);
   TT_HIP(hipGetLastError());
   return TTNET_OK;

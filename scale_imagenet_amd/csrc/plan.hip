@@ -20,6 +20,7 @@
 #include <mutex>
 #include <unordered_map>
 
+#include "partition.h"
 #include "ttnet_common.h"
 #include "va_block.h"
 
@@ -533,8 +534,8 @@ int alloc_workspace(ttnet_plan *pl, ttnet_plan::Lane &L) {
       TT_TRY(dev_alloc(pl, &L.last_float, (size_t)nb * lb.cf.g.out_planes * lb.Ho * lb.Wo, true, ws));
       size_t cap = 0;                                  // pixels x groups of the largest binarised 1x1 block
       for (const MultiHead &mh : pl->blocks) {
-        cap = std::max(cap, (size_t)mh.c3.g.groups * mh.H * mh.W);
-        if (!mh.last) cap = std::max(cap, (size_t)mh.cf.g.groups * mh.Ho * mh.Wo);
+        cap = std::max(cap, part::full_fix_entries(mh.c3.g.groups, mh.H, mh.W));
+        if (!mh.last) cap = std::max(cap, part::full_fix_entries(mh.cf.g.groups, mh.Ho, mh.Wo));
       }
       pl->full_fix_cap = cap * (size_t)nb;
       TT_TRY(dev_alloc(pl, &L.full_fix, 64 + pl->full_fix_cap, true, ws));
@@ -1166,7 +1167,7 @@ int forward_eager(ttnet_plan *pl, ttnet_plan::Lane &L, const void *x_dev, bool u
     TT_TIMED(pl, "stem", s,
              launch_stem(x_dev, u8, pl->norm_tab, u8 ? pl->stem_wt_u8 : pl->stem_wt, u8 ? pl->stem_init_u8 : pl->stem_init, L.x_rp[0],
                          pl->path == GatePath::TwoLaunch ? L.x_cp[0] : nullptr, (int)n, pl->p, pl->range_dev, s,
-                         (pl->lanes.size() >= 2 && !u8 && pl->path != GatePath::Full) ? 128 : 256));      // (stem.hip: half the CUs for float32 input with batches in flight)
+                         part::stem_workgroups((int)pl->lanes.size(), u8, pl->path == GatePath::Full)));      // (half the CUs for float32 input with batches in flight)
   }
   return run_from_blocks(pl, L, (int)n, logits_dev, s);
 }
@@ -2117,7 +2118,7 @@ int ttnet_plan_query(ttnet_plan *pl, const char *what, int64_t *out) {
       return TTNET_E_INVALID;
     }
     const int C = pl->blocks[(size_t)i].C;
-    *out = pl->path == GatePath::Fused ? (int64_t)(C / 8) * fused_block_slices(C, n) : (int64_t)gate_stage1_grid(C, n);
+    *out = pl->path == GatePath::Fused ? (int64_t)(C / 8) * part::fused_block_slices(C, n) : (int64_t)part::stage1_grid(C, n).blocks();
   }
   else if (w == "full_listed_pw" || w == "full_listed_dw") {      // full variant: (pixel, group) pairs / outputs sent to float64 so far (lane used last)
     uint32_t v[2] = {0, 0};

@@ -61,6 +61,7 @@
 #include <cmath>
 #include <vector>
 
+#include "partition.h"
 #include "ttnet_common.h"
 
 namespace ttnet {
@@ -70,8 +71,8 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int SR = 8;                   // output rows per item
-constexpr int NBLK = 56 / SR;           // row blocks (items) per image
+constexpr int SR = part::kStemItemRows;  // output rows per item
+using part::NBLK;                       // row blocks (items) per image
 constexpr int TR = 2 * SR + 5;          // pooled rows in the tile
 constexpr int PITCH = 60;               // dwords per tile row: 120 fp16 = pooled columns -4 .. 115
 constexpr int LROWS = 64;                // rows a copy holds: the tile's 63 and a spare one (a producer wave owns 16)
@@ -81,7 +82,7 @@ constexpr int PLANE_DW = 2 * COPY_DW;   // [copy 0: dword j = pixels (2j, 2j+1)]
 constexpr int TILE_DW = NPL * PLANE_DW; // dwords per tile buffer (61,952 B)
 constexpr int KSTEPS = 11;              // 22 (c,kh) rows (21 + one repeated with zero weights), two per MFMA
 constexpr int NT = SR * 56 / 32;        // 14 N-tiles of 32 pixels
-constexpr int NSTAGE = 3;               // stage buffers of row-word pieces: written (item j), completed late (j-1), read (j-2)
+using part::NSTAGE;                     // stage buffers of row-word pieces: written (item j), completed late (j-1), read (j-2)
 constexpr float X_PRESCALE = ACT_PRESCALE;
 
 // Diagnostic builds only (tools/ubench/stem_parts.hip): parts of the kernel switched off, in-kernel stamps.
@@ -212,16 +213,15 @@ __global__ __launch_bounds__(STEM_THREADS) void stem_pc_kernel(const void *__res
   // previous tile inside LDS instead of being loaded, pooled and split again (16 of 21 rows to load:
   // no byte of the input is read twice, and a quarter less producer work).
   const int G = gridDim.x, bid = blockIdx.x;
-  const long long total_items = (long long)n_images * NBLK;
-  const int first_item = (int)(bid * total_items / G);
-  const int my_items = (int)((bid + 1) * total_items / G) - first_item;
+  const int first_item = part::stem_first_item(bid, n_images, G);
+  const int my_items = part::stem_my_items(bid, n_images, G);
   auto item_of = [&](int j, int &n, int &oy0) {
     const int it = first_item + j;
     n = it / NBLK;
     oy0 = (it % NBLK) * SR;
   };
   // item j continues the image of item j-1 of this workgroup
-  auto continues = [&](int j) -> bool { return j > 0 && (first_item + j) % NBLK != 0; };
+  auto continues = [&](int j) -> bool { return part::stem_continues(first_item, j); };
 
   // ---- producer side -----------------------------------------------------------------------
   // Tile column t = pooled image column t - 4.  Lane l < 60 makes dword l of a row = pooled pixels
@@ -852,14 +852,13 @@ int launch_stem(const void *x, bool x_is_u8, const uint32_t *norm_tab, const voi
     return TTNET_E_INVALID;
   }
   const size_t lds = (size_t)2 * TILE_DW * 4 + (size_t)NSTAGE * 32 * MT * (NT + 2) * 4 + (x_is_u8 ? (size_t)16 * 32 * MT * 4 : 0);
-  const int items = n * NBLK;
   // Persistent workgroups: one per CU when a forward has the chip to itself; HALF the CUs when the plan keeps several batches in
   // flight.  On 256 CUs the kernel is power-limited (1.7 GHz); on 128 it holds 2.3 GHz and its time is cycles per item x 14 /
   // clock ("on half the chip"): 64 us instead of 51, and the other batch's kernels run on the other 128 meanwhile -- the forward
   // with two batches in flight gains 5 - 7 % (profiles/r03_cache_policy.txt, same-box A/B; one batch at a time would lose 4 %; the
   // uint8 kernel, with two products, and the full variant gain nothing and keep 256: the caller decides).
   static const int grid_env = getenv("TTNET_STEM_GRID") ? atoi(getenv("TTNET_STEM_GRID")) : 0;        // (diagnostic override)
-  const int grid = std::min(items, std::max(1, grid_env > 0 ? grid_env : (workgroups > 0 ? workgroups : 256)));
+  const int grid = part::stem_grid(n, grid_env > 0 ? grid_env : (workgroups > 0 ? workgroups : part::kStemGrid));
   auto launch = [&](auto kernel) -> int {
     TT_TRY(ensure_dynamic_lds((const void *)kernel, lds));
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(STEM_THREADS), lds, s, x, (const uint4 *)wfrag, init, rp, cp, p, n, norm_tab,

@@ -285,8 +285,8 @@ struct GateBlockArgs {
   uint16_t *o1, *o2, *o3, *o4;    // [n][C/16][Ho][Wo]
 };
 // stage 1: Block_conv1, Block_conv2 (depthwise units) and Block_conv3 + both majority pools
+// (its workgroups: partition.h, stage1_grid)
 int launch_gate_stage1(const GateBlockArgs &a, hipStream_t s);
-int gate_stage1_grid(int C, int n);       // its workgroups: depthwise units + conv3 units, each times its batch slices
 // stage 2: convf of a non-last block: 4 branch tensors -> words [n][Cout/16][Ho][Wo] and rows
 // [n][Cout][Ho], Cout = cf_bits * (4C/16)
 int launch_gate_pf(const GateBlockArgs &a, const uint8_t *t_cf, uint16_t *out_cp, uint64_t *out_rp, hipStream_t s);
@@ -307,7 +307,6 @@ struct FusedBlockArgs {
 };
 bool fused_block_supported(int C, int H, int Ho, int stride, int pad, int kh, int kw);
 int row_bytes(int W);
-int fused_block_slices(int C, int n);      // batch slices per strand of launch_gate_block's grid
 int launch_gate_block(const FusedBlockArgs &f, hipStream_t s);
 int launch_fused_images(const void *t_dw1, const void *t_dw2, const void *t_c3, int C, void *img_dw, void *img_c3, hipStream_t s);
 int launch_branch_rows(const uint32_t *idx, uint64_t *rows, int n, int C, int Ho, int branch, hipStream_t s);

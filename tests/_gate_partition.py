@@ -1,45 +1,44 @@
-"""The batch partition of the gate kernels, restated in plain Python (test infrastructure).
+"""Which batch sizes and which images the gate sweeps run (test infrastructure).
 
-Which image a workgroup handles, in how many rounds and with which table buffer is decided by a few integer
-formulas in scale_imagenet_amd/csrc/gate_fused.hip and gate.hip.  They are restated here so that the batch sizes
-of tests/test_gpu_gate_batches.py are DERIVED from the launch arithmetic (first two-round batch, a last round of
-one image, unequal slices, ...) and tests/test_gate_batch_sizes_cpu.py can assert, without a GPU, that the chosen
-sizes reach every one of those cases.
+Which image a workgroup handles, in how many rounds and with which table buffer is decided by a few integer formulas
+in scale_imagenet_amd/csrc/partition.h, which the launchers and kernels of gate_fused.hip, gate.hip, gate_xs.hip,
+gate_va.hip, gate_full.hip and plan.hip call.  This file reads them from the library itself, through the stateless
+``ttnet_launch_partition`` (it answers without a GPU), so that the batch sizes of tests/test_gpu_gate_batches.py are
+DERIVED from the launch arithmetic (first two-round batch, a last round of one image, unequal slices, ...) and
+tests/test_gate_batch_sizes_cpu.py can assert, without a GPU, that the chosen sizes reach every one of those cases.
+What stays here is test design: the geometries, the sizes that are always run, how sizes and constant images are picked
+from the partition, and the order of a sweep.
 
-Drift.  A restatement can fall behind the kernels if their constants change.  Part of it is guarded on the GPU
-side: the sweep asserts that ``ttnet_plan_query("gate_grid:<block>")`` equals ``fused_grid`` / ``stage1_grid`` below
-for every batch size it runs.  On the fused path that query calls fused_block_slices(), the function launch_block_t
-itself calls, so ``fused_slices`` is pinned to the launcher.  On the two-launch path it calls gate_stage1_grid(),
-which sits beside launch_stage1_t in gate.hip and shares its slices_for() and its kDwTarget / kPwTarget, but is a
-second statement of the sum inside the library, not the value the launcher passes to the launch: the guard pins the
-two constants and slices_for(), not the launcher's own line.  NOT guarded at all, and so free to drift unnoticed:
-``PF_TARGET`` (a literal 256 in launch_pf_t), the round length R of ``fused_round`` (inside the kernel; only the
-static_assert ``RMAX * RG * 16 <= kFT`` of gate_block_kernel bounds it), the placement branches of ``fused_owner``
-and the tasks per image of the flat grids (``xs_kernels``, ``VA_KERNELS``).  If one of those changes in the
-kernels, the bit comparison still holds for every size that is run, but a size may stop reaching the case it was
-derived for; whoever changes them updates this file, and tests/test_gate_batch_sizes_cpu.py then says whether the
-sizes still reach every case.
-
-The full variant (gate_full.hip, the last section below) is not pinned to its launchers by any plan query:
-``gate_grid:`` serves gate paths 0 and 1 only.  Its grids are ``chunks = min(ceil(work / per chunk), cap / units)`` with
-the literals 256 rows per chunk and 1024 workgroups (launch_full_dw_window), 8 wave tasks per chunk and 512 workgroups
-(launch_full_pw_tiles), 256 / groups chunks for the float64 pass over the list and 16 listed pixels per wave task of
-that pass (full_pw_mfma_kernel<OT, true>), and the list capacity of plan.hip (``full_fix_cap``).  All of them are
-restated here by hand: whoever changes one of them in gate_full.hip or plan.hip updates that section, and
-tests/test_gate_batch_sizes_cpu.py then says whether ``full_sizes`` and the forced-list cases of
-tests/test_gpu_full_fallback.py still reach every branch.
+Drift.  None of the arithmetic is restated here: a launcher that changes a target, a cap, a round length or the
+placement changes what these functions return, and tests/test_gate_batch_sizes_cpu.py then says whether the sizes
+still reach every case.  On the GPU the sweep still asserts that ``ttnet_plan_query("gate_grid:<block>")`` equals
+``fused_grid`` / ``stage1_grid`` for every batch size it runs.  One restatement is left inside the library:
+gate_block_kernel keeps the three placement branches of ``fused_owner`` as its own lines beside partition.h's
+fused_owner(), which is what this file reads (called as a function the kernel compiled differently and did not pass the
+timing rule of profiles/partition_refactor.txt); the comment in the kernel says so.  ``fusable`` remains a restatement
+(of fused_block_supported, plan.hip's choice of path, which is no launch partition).
 """
 from __future__ import annotations
 
+import os
+from functools import lru_cache
 from math import gcd
 from typing import List, NamedTuple, Tuple
 
-# gate_fused.hip: kFT, kFBuf, kFMaxScratch
-FT = 1024
-FBUF = 65536
-MAX_SCRATCH = 160 * 1024 - 2 * FBUF
-# gate.hip: launch_stage1_t (kDwTarget, kPwTarget) and launch_pf_t
-DW_TARGET, PW_TARGET, PF_TARGET = 208, 48, 256
+from scale_imagenet_amd import _lib
+
+
+@lru_cache(maxsize=None)
+def part(what: str, *args: int) -> Tuple[int, ...]:
+    """ttnet_launch_partition(what, args): the values csrc/partition.h gives, from the library itself."""
+    if not os.path.exists(_lib.LIB_PATH):
+        from scale_imagenet_amd.build import build_lib
+        build_lib(verbose=False)
+    return _lib.launch_partition(what, *args)
+
+
+FT, FBUF, MAX_SCRATCH, _ = part("fused.const")
+DW_TARGET, PW_TARGET, PF_TARGET = part("two_launch.const")
 
 
 class Block(NamedTuple):
@@ -61,60 +60,42 @@ def fusable(blocks: List[Block]) -> bool:
 
 
 # ---- gate_fused.hip ---------------------------------------------------------------------------------------------
+# (HO of a launch whose round length does not matter: any fused output size)
+_ANY_HO = 5
+
 
 def fused_round(HO: int) -> int:
-    """fused_round<HO>(): images per round of a workgroup (8, 16, 32, 32 for HO = 29, 15, 8, 5)."""
-    RG = (HO + 3) // 4
-    a, b = FT // (16 * RG), MAX_SCRATCH // (HO * HO * 4)
-    return min(a, b, 32)
+    """fused_round(HO): images per round of a workgroup (8, 16, 32, 32 for HO = 29, 15, 8, 5)."""
+    return part("fused.round", HO)[0]
 
 
 def fused_slices(n: int, C: int) -> int:
     """fused_block_slices(): batch slices per strand; even when there are 8 strands (the pair placement)."""
-    strands = C // 8
-    slices = max(1, min(n, 256 // strands))
-    if strands == 8 and slices > 1 and slices & 1:
-        slices -= 1
-    return slices
+    return part("fused.launch", C, _ANY_HO, n)[1]
 
 
 def fused_R(n: int, C: int, HO: int) -> int:
-    """launch_block_t: R = min(fused_round<HO>(), ceil(n / slices))."""
-    slices = fused_slices(n, C)
-    return max(1, min(fused_round(HO), (n + slices - 1) // slices))
+    """launch_block_t: the images per round of a launch, fused_launch_round()."""
+    return part("fused.launch", C, HO, n)[2]
 
 
 def fused_grid(n: int, C: int) -> int:
-    return (C // 8) * fused_slices(n, C)
+    return part("fused.launch", C, _ANY_HO, n)[0]
 
 
 def placement_branch(n: int, C: int) -> str:
-    """gate_block_kernel, "which strand, which images": the branch that maps blockIdx.x to (strand, slice)."""
-    P = C // 8 // 2
-    if P >= 8 and P % 8 == 0:
-        return "pairs8"
-    if P == 4 and fused_slices(n, C) % 2 == 0:
-        return "quad"
-    return "plain"
+    """fused_placement(): the branch of fused_owner() that maps blockIdx.x to (strand, slice)."""
+    return ("plain", "quad", "pairs8")[part("fused.launch", C, _ANY_HO, n)[3]]
 
 
 def fused_owner(b: int, n: int, C: int) -> Tuple[int, int]:
-    """(strand, slice) of workgroup b, as gate_block_kernel computes st and sl."""
-    strands, slices = C // 8, fused_slices(n, C)
-    P = strands // 2
-    x, k = b & 7, b >> 3
-    if P >= 8 and P % 8 == 0:
-        m = P // 8
-        pair, kk = x + 8 * (k % m), k // m
-        return 2 * pair + (kk & 1), kk >> 1
-    if P == 4 and slices % 2 == 0:
-        return 2 * (x >> 1) + (k & 1), (x & 1) * (slices // 2) + (k >> 1)
-    return b % strands, b // strands
+    """(strand, slice) of workgroup b, as gate_block_kernel gets st and sl."""
+    return part("fused.owner", b, C, n)
 
 
 def slice_bounds(sl: int, n: int, slices: int) -> Tuple[int, int]:
-    """n0, n1 of a batch slice (gate_block_kernel; the same formula in gate_stage1_kernel and gate_pf_kernel)."""
-    return sl * n // slices, (sl + 1) * n // slices
+    """n0, n1 of a batch slice (gate_block_kernel, gate_stage1_kernel and gate_pf_kernel: slice_begin())."""
+    return part("slice", sl, n, slices)
 
 
 def fused_rounds(n: int, C: int, HO: int) -> List[Tuple[int, List[int]]]:
@@ -142,22 +123,22 @@ def fused_locate(image: int, n: int, C: int, HO: int) -> str:
 
 def slices_for(n: int, units: int, target: int) -> int:
     """slices_for(): batch slices per table set so that ``units`` sets spread over at most ``target`` workgroups."""
-    return max(1, min(n, target // max(1, units)))
+    return part("slices_for", n, units, target)[0]
 
 
 def stage1_slices(n: int, C: int) -> Tuple[int, int]:
     """launch_stage1_t: slices of the depthwise units (2 per 16 channels) and of the conv3 units (1 per 16)."""
-    return slices_for(n, (C // 16) * 2, DW_TARGET), slices_for(n, C // 16, PW_TARGET)
+    _, _, sl_dw, _, sl_pw = part("two_launch.stage1", C, n)
+    return sl_dw, sl_pw
 
 
 def stage1_grid(n: int, C: int) -> int:
-    sl_dw, sl_pw = stage1_slices(n, C)
-    return (C // 16) * 2 * sl_dw + (C // 16) * sl_pw
+    return part("two_launch.stage1", C, n)[0]
 
 
 def pf_slices(n: int, C: int) -> int:
     """launch_pf_t: grid (C / 8, slices)."""
-    return slices_for(n, C // 8, PF_TARGET)
+    return part("two_launch.pf", C, n)[1]
 
 
 def slice_sizes(n: int, slices: int) -> List[int]:
@@ -208,17 +189,16 @@ class FlatKernel(NamedTuple):
 
 
 def xs_kernels(blocks: List[Block]) -> List[FlatKernel]:
-    """launch_xs_branches: n * (C / 4) * Ho tasks; launch_xs_pf: n * C * Ho; launch_xs_last: n * C * (Ho / 2) * (Wo / 2);
-    128 threads each."""
+    """launch_xs_branches and, per block, launch_xs_pf or (last block) launch_xs_last."""
     out = []
     for i, b in enumerate(blocks):
-        out.append(FlatKernel(f"xs_branches[{i}]", (b.C // 4) * b.HO, 128))
-        out.append(FlatKernel("xs_last", b.C * (b.HO // 2) ** 2, 128) if b.last else FlatKernel(f"xs_pf[{i}]", b.C * b.HO, 128))
+        out.append(FlatKernel(f"xs_branches[{i}]", *part("flat.xs_branches", b.C, b.HO)))
+        out.append(FlatKernel("xs_last", *part("flat.xs_last", b.C, b.HO, b.HO)) if b.last else FlatKernel(f"xs_pf[{i}]", *part("flat.xs_pf", b.C, b.HO)))
     return out
 
 
-# launch_va_block: va_dw n * 64 * 11 and va_c3 n * 88 tasks on 128 threads; launch_va_feat: n * 256 * 121 / 16 on 256
-VA_KERNELS = [FlatKernel("va_dw", 64 * 11, 128), FlatKernel("va_c3", 88, 128), FlatKernel("va_feat", 256 * 121 // 16, 256)]
+# launch_va_block (va_dw, va_c3) and launch_va_feat
+VA_KERNELS = [FlatKernel(k, *part("flat." + k)) for k in ("va_dw", "va_c3", "va_feat")]
 
 
 def flat_period(k: FlatKernel) -> int:
@@ -307,9 +287,8 @@ def flat_edge_images(kernels: List[FlatKernel], sizes: List[int]) -> List[int]:
 
 # ---- gate_full.hip: grid-stride loops over rows (depthwise) and over wave tasks (grouped 1x1) ---------------------
 
-FULL_DW_ROWS, FULL_DW_GRID = 256, 1024        # launch_full_dw_window: threads (= output rows) per chunk, workgroups at most
-FULL_PW_WAVES, FULL_PW_GRID = 8, 512          # launch_full_pw_tiles: wave tasks per chunk (512 threads), workgroups at most
-FULL_FIX_GRID, FULL_FIX_PIXELS = 256, 16      # the float64 pass over the list: workgroups at most, listed pixels per wave task
+# launch_full_dw_window: threads (= output rows) per chunk; launch_full_pw_tiles: wave tasks per chunk (512 threads)
+FULL_DW_ROWS, _, _, FULL_PW_WAVES, _, _, _, _ = part("full.const")
 
 
 def _ceil(a: int, b: int) -> int:
@@ -318,7 +297,7 @@ def _ceil(a: int, b: int) -> int:
 
 def full_dw_chunks(n: int, C: int, ho: int) -> int:
     """launch_full_dw_window: grid (C, chunks), one thread per (image, output row)."""
-    return max(1, min(_ceil(n * ho, FULL_DW_ROWS), max(1, FULL_DW_GRID // C)))
+    return part("full.dw", n, C, ho)[0]
 
 
 def full_dw_sweeps(n: int, C: int, ho: int) -> int:
@@ -327,13 +306,12 @@ def full_dw_sweeps(n: int, C: int, ho: int) -> int:
 
 def row_bundle(H: int, W: int) -> Tuple[int, int]:
     """RowBundle: (rows per 64-lane wave task, tasks per image)."""
-    rpw = 64 // W
-    return rpw, _ceil(H, rpw)
+    return part("full.row_bundle", H, W)
 
 
 def full_pw_chunks(n: int, groups: int, H: int, W: int) -> int:
     """launch_full_pw_tiles: grid (groups, chunks), 8 waves per workgroup, one task per wave and sweep."""
-    return max(1, min(_ceil(n * row_bundle(H, W)[1], FULL_PW_WAVES), max(1, FULL_PW_GRID // groups)))
+    return part("full.pw", n, groups, H, W)[1]
 
 
 def full_pw_sweeps(n: int, groups: int, H: int, W: int) -> int:
@@ -342,14 +320,13 @@ def full_pw_sweeps(n: int, groups: int, H: int, W: int) -> int:
 
 def full_fix_xchunks(n: int, groups: int, H: int, W: int) -> int:
     """launch_full_pw_tiles: the y extent of full_pw_mfma_kernel<OT, true>'s grid."""
-    tasks = n * row_bundle(H, W)[1]
-    return max(1, min((tasks // 4 + 7) // 8, max(1, FULL_FIX_GRID // groups)))
+    return part("full.pw", n, groups, H, W)[3]
 
 
 def full_fix_sweeps(n: int, groups: int, H: int, W: int, listed: int) -> int:
     """Sweeps of the float64 pass of one group that has ``listed`` pixels on its list (at most all n * H * W)."""
-    tasks = _ceil(min(listed, n * H * W), FULL_FIX_PIXELS)
-    return _ceil(tasks, FULL_PW_WAVES * full_fix_xchunks(n, groups, H, W))
+    tasks, xchunks = part("full.fix", n, groups, H, W, listed)
+    return _ceil(tasks, FULL_PW_WAVES * xchunks)
 
 
 class FullKernel(NamedTuple):
@@ -378,11 +355,11 @@ def full_kernels(spec) -> List[FullKernel]:
         H, W = b.in_hw
         for c in (b.conv1, b.conv2):
             ho, wo = c.out_hw(H, W)
-            out.append(FullKernel(f"{b.name} {c.name.rsplit('_', 1)[1]}", i, "dw", ho, FULL_DW_ROWS, max(1, FULL_DW_GRID // b.in_planes),
+            out.append(FullKernel(f"{b.name} {c.name.rsplit('_', 1)[1]}", i, "dw", ho, FULL_DW_ROWS, part("full.dw", 1, b.in_planes, ho)[1],
                                   b.in_planes * ho * wo, b.in_planes, (ho, wo)))
         for c, (h, w) in ((b.conv3, (H, W)), (b.convf, b.out_hw)):
             out.append(FullKernel(f"{b.name} {c.name.rsplit('_', 1)[1]}", i, "pw", row_bundle(h, w)[1], FULL_PW_WAVES,
-                                  max(1, FULL_PW_GRID // c.groups), 0 if c.last else c.groups * h * w, c.groups, (h, w)))
+                                  part("full.pw", 1, c.groups, h, w)[2], 0 if c.last else part("full.fix_entries", c.groups, h, w)[0], c.groups, (h, w)))
     for k in out:                                     # the two statements of each grid agree
         for n in (1, 7, 40, 200):
             if k.kind == "dw":

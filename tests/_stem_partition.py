@@ -1,25 +1,29 @@
-"""The item partition of the stem kernel, restated in plain Python (test infrastructure).
+"""Which batch sizes and which images the stem sweeps run (test infrastructure).
 
 scale_imagenet_amd/csrc/stem.hip cuts a batch into items (one image x 8 output rows, seven per image) and gives every
-persistent workgroup a run of consecutive items:  grid = min(7n, G),  first_item = bid * 7n / grid,  my_items up to the
-next workgroup's first item.  G is 256, or 128 for float32 input on a plan with two or more lanes (plan.hip); the uint8
-kernel always gets 256.  What depends on the run: the tile double buffer (item j in buffer j & 1), the NSTAGE = 3 stage
-ring whose rows are emitted two periods late, the sign word carried across the item barrier, and ``continues(j)``, which
-picks the halo copy inside LDS (the item continues the image of the one before) or a whole-tile load (first item of a
-run, or of an image).
+persistent workgroup a run of consecutive items.  The arithmetic -- the grid, a workgroup's first item and item count,
+whether an item continues the image of the one before -- stands once, in csrc/partition.h, which the launcher, the
+kernel and plan.hip call; this file reads it from the library through the stateless ``ttnet_launch_partition`` (it
+answers without a GPU).  G is 256, or 128 for float32 input on a plan with two or more lanes; the uint8 kernel always
+gets 256.  What depends on the run: the tile double buffer (item j in buffer j & 1), the NSTAGE = 3 stage ring whose rows
+are emitted two periods late, the sign word carried across the item barrier, and ``continues(j)``, which picks the halo
+copy inside LDS (the item continues the image of the one before) or a whole-tile load (first item of a run, or of an
+image).
 
-The sizes of tests/test_gpu_stem_batches.py are chosen with these formulas, and tests/test_stem_batch_sizes_cpu.py
-asserts without a GPU that they reach every case.  No plan query reports the stem's grid: if NBLK, the grid rule or
-``continues`` change in stem.hip / plan.hip, whoever changes them updates this file.
+The sizes of tests/test_gpu_stem_batches.py are chosen with these functions, and tests/test_stem_batch_sizes_cpu.py
+asserts without a GPU that they reach every case.  Nothing of the partition is restated here: if NBLK, the grid rule or
+``continues`` change in the library, the CPU test says whether SIZES still reaches every case.
 """
 from __future__ import annotations
 
 from typing import List, NamedTuple
 
-NBLK = 7                      # stem.hip: row blocks (items) per image
-NSTAGE = 3                    # stem.hip: stage buffers of row-word pieces
-GRIDS = (128, 256)            # float32 input: two or more lanes, one lane
-GRID_U8 = 256
+from _gate_partition import part
+
+NBLK, NSTAGE, _, _ = part("stem.const")     # row blocks (items) per image; stage buffers of row-word pieces
+# workgroups asked for (lanes, uint8 input, full variant).  float32 input: two or more lanes, one lane
+GRIDS = (part("stem.workgroups", 2, 0, 0)[0], part("stem.workgroups", 1, 0, 0)[0])
+GRID_U8 = part("stem.workgroups", 2, 1, 0)[0]
 # the batch sizes of the sweep (tests/test_stem_batch_sizes_cpu.py: what each one is there for)
 #   n     runs on G = 128   runs on G = 256
 #   1     1                 1                  7 workgroups
@@ -33,20 +37,20 @@ N_MAX = 150
 
 
 def grid(n: int, G: int) -> int:
-    return min(NBLK * n, G)
+    return part("stem.grid", n, G)[0]
 
 
 def first_item(bid: int, n: int, G: int) -> int:
-    return bid * (NBLK * n) // grid(n, G)
+    return part("stem.run", bid, n, G)[0]
 
 
 def my_items(bid: int, n: int, G: int) -> int:
-    return first_item(bid + 1, n, G) - first_item(bid, n, G)
+    return part("stem.run", bid, n, G)[1]
 
 
 def continues(bid: int, j: int, n: int, G: int) -> bool:
     """Item j of the workgroup continues the image of its item j - 1 (halo copy); otherwise a whole tile is loaded."""
-    return j > 0 and (first_item(bid, n, G) + j) % NBLK != 0
+    return bool(part("stem.continues", first_item(bid, n, G), j)[0])
 
 
 class Run(NamedTuple):

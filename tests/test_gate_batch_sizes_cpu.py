@@ -1,8 +1,8 @@
 """The batch sizes of tests/test_gpu_gate_batches.py reach what they are meant to reach (no GPU needed).
 
 The GPU sweep compares bits; whether a given batch size makes a workgroup walk a second round, flip its table buffer at
-both parities or end on a round of one image follows from integer arithmetic alone (tests/_gate_partition.py, a
-restatement of the launchers).  This file asserts it for every geometry and every block of the sweep, so that the sweep
+both parities or end on a round of one image follows from integer arithmetic alone (tests/_gate_partition.py, which reads
+the launchers' own arithmetic, csrc/partition.h, from the library).  This file asserts it for every geometry and every block of the sweep, so that the sweep
 cannot quietly cover nothing.
 """
 import numpy as np

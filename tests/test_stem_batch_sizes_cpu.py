@@ -1,8 +1,8 @@
 """The batch sizes of tests/test_gpu_stem_batches.py reach what they are meant to reach (no GPU needed).
 
 The GPU sweep compares bits; how long a workgroup's run of items is, whether it starts in the middle of an image and
-whether an image boundary falls inside it follow from integer arithmetic alone (tests/_stem_partition.py, a restatement
-of stem.hip's item partition).  This file asserts that the size list reaches every case on both grids, so that the sweep
+whether an image boundary falls inside it follow from integer arithmetic alone (tests/_stem_partition.py, which reads
+stem.hip's item partition, csrc/partition.h, from the library).  This file asserts that the size list reaches every case on both grids, so that the sweep
 cannot quietly cover nothing.
 """
 import pytest
