@@ -657,6 +657,54 @@ int ttnet_cover_support(const uint32_t *cubes_dev, const int32_t *counts_dev, in
 int ttnet_certify_u8(ttnet_plan *plan, int lane, const uint8_t *x_nhwc_dev, int64_t n, const int32_t *classes_dev, double eps,
                      int enum_bits, double min_margin, void *rows_dev, uint64_t *planes_dev, void *stream);
 
+/* The same certificate for a box given per byte: byte k of image i may take any REAL value in [lo, hi], lo and hi being byte k of
+ * lo_nhwc_dev and hi_nhwc_dev (uint8 [n][32][32][3] each, 4-byte aligned).  Where lo > hi the byte counts as the degenerate
+ * box [lo, lo] (nothing is read back to refuse it; the Python wrappers refuse it).  Stage 0 takes the centre and the radius of
+ * every pixel's interval from the two images where ttnet_certify_u8 takes them from b -+ eps: the same kernel, slack and
+ * float64 order, so lo = max(0, b - e), hi = min(255, b + e) for an integer e gives the bytes of ttnet_certify_u8 at eps = e.
+ * Stages 1 and 2, the records, planes_dev, the lane's buffers, the profiling steps and the errors are ttnet_certify_u8's
+ * (without eps; hi_nhwc_dev NULL or misaligned is TTNET_E_INVALID). */
+int ttnet_certify_box_u8(ttnet_plan *plan, int lane, const uint8_t *lo_nhwc_dev, const uint8_t *hi_nhwc_dev, int64_t n,
+                         const int32_t *classes_dev, int enum_bits, double min_margin, void *rows_dev, uint64_t *planes_dev,
+                         void *stream);
+
+/* Certified PATCH robustness of TTNET_VALEXNET: every position of a patch_h x patch_w patch (1..8 each) in one call (DESIGN.md:
+ * certified patch robustness).  Positions (y0, x0) = (a * stride, b * stride) with y0 + patch_h <= 32 and x0 + patch_w <= 32, row-major:
+ * P = Py * Px, Py = (32 - patch_h) / stride + 1, Px likewise (stride 1..32).  The box of position p: the bytes of the patch's
+ * pixels (all three channels) lie in [max(0, b - amp), min(255, b + amp)], amp an integer in 1..255 (255: any value); every
+ * other byte is exact.  The record of (image, position) is what ttnet_certify_box_u8 gives for that box: the same three-valued
+ * planes, the same integers, and lb equal as a real number -- computed incrementally:
+ *   per image, once ("patch.base"): stages 0 and 1 on the degenerate box (a clean bit within the slack of zero stays unknown),
+ *     which leave the clean planes and, per class j, S_j = sum_f D_f ylo_f and U_j = sum_{f unknown} min(0, D_f) in
+ *     ttnet_certify_u8's order;
+ *   per (image, position), one workgroup ("patch.sweep"): stage 0 for the pooled cells whose 5 x 5 pixel field (rows 3 py - 1 ..
+ *     3 py + 3, likewise columns) meets the patch, at most 4 x 4 cells x 64 channels, by the code stage 0 runs; stage 1's lookups
+ *     for the features those cells reach; for each such feature whose three-valued value differs from the clean one, the
+ *     differences dS_j = D_f (ylo_f - clean ylo_f) and dU_j = min(0, D_f) (unknown_f - clean unknown_f).  Summation order:
+ *     thread t of 256 adds the differences of the features t, t + 256, .. of each branch's rectangle of reached features (conv1,
+ *     conv2, conv3, out4; within a rectangle the channel runs fastest, then the column, then the row), the 64 lanes of a wave
+ *     are added by a butterfly (distance 32, 16, .., 1), the four waves in order; then
+ *       lb_j = c0_c - c0_j + ((S_j + dS_j) + (U_j + dU_j)),   worst = the first j that attains the minimum;
+ *     a position that is open with 1 <= k <= enum_bits unknown stem bits goes through stage 2 in its workgroup (the code of
+ *     ttnet_certify_u8's stage 2, started from S_j + dS_j).
+ * Row and column 31 lie in no field: a position that touches only them has the clean planes and sums.
+ *
+ * map_dev receives [n][P] records of 16 bytes (8-byte aligned): { double lb; int32 worst; uint16 stage; uint16 unknown_stem; },
+ * lb, worst, stage (0, 1, 2) and unknown_stem as in ttnet_certify_u8's record.  rows_dev receives n records of 32 bytes:
+ *   { double lb_min; int32 pos_min; int32 worst; int32 certified; int32 interval; int32 enumeration; int32 positions; }
+ * lb_min = the smallest lb over the positions, pos_min the first position that attains it, worst that position's; interval and
+ * enumeration count the positions of stage 1 and 2, certified is their sum, positions = P.  An image is patch-certified when
+ * certified == positions; only stride 1 makes that a statement about every placement.  A class outside 0..9: stage 0, worst -1
+ * and lb = -inf at every position, not an error.
+ *
+ * Float64 in a fixed order, no float atomics, nothing read back; the same bytes on every run and whatever else the batch holds.
+ * n * P workgroups are cut into launches (csrc/partition.h).  The lane's planes are ttnet_certify_u8's; 112 more bytes per image
+ * of max_batch are allocated by the first call on a lane.  Errors: those of ttnet_certify_u8 (without eps), and patch_h, patch_w,
+ * stride or amp outside their ranges or map_dev NULL or misaligned TTNET_E_INVALID. */
+int ttnet_certify_patch_u8(ttnet_plan *plan, int lane, const uint8_t *x_nhwc_dev, int64_t n, const int32_t *classes_dev, int patch_h,
+                           int patch_w, int stride, int amp, int enum_bits, double min_margin, void *rows_dev, void *map_dev,
+                           void *stream);
+
 /* Falsified L-infinity robustness of TTNET_VALEXNET on the device: a search for uint8 witnesses (csrc/attack.hip; DESIGN.md:
  * falsified robustness).  ttnet_certify_u8 bounds the robust accuracy from below; an image is FALSIFIED when a concrete uint8
  * image inside the integer box [max(0, b - e), min(255, b + e)] (e = eps_levels byte levels; the box lies inside the real box
@@ -756,6 +804,8 @@ int ttnet_plan_query(ttnet_plan *plan, const char *what, int64_t *out);
  *   "stem.const" () -> items per image, stage buffers, workgroups on the whole chip, on half of it
  *   "stem.workgroups" (lanes, u8, full variant) -> workgroups asked for       "stem.grid" (n, G) -> workgroups launched
  *   "stem.run" (bid, n, G) -> first item, items                               "stem.continues" (first item, j) -> 0 / 1
+ *   "patch.sweep" (n, patch_h, patch_w, stride) -> positions down, across, launches of ttnet_certify_patch_u8's sweep, workgroups
+ *       of the first launch, of the last, at most
  * Returns the number of values written.  An unknown key, a wrong n_args, out_cap below the key's value count, n < 1, C not a
  * multiple of 8 (16 for "two_launch.stage1") or any argument outside its range: TTNET_E_INVALID with the reason in
  * ttnet_last_error(), and nothing is written. */

@@ -34,9 +34,9 @@ def build_lib(force: bool = False, verbose: bool = True) -> str:
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, "ttnet_common.h"), os.path.join(HERE, "..", "include", "ttnet.h")]
-    included = {"gate_full.hip": [os.path.join(CSRC, "erf_table.inc")]}
+    included = {"gate_full.hip": [os.path.join(CSRC, "erf_table.inc")], "certify.hip": [os.path.join(CSRC, "certify_stem_cell.inc")]}
     included.update({src: [os.path.join(CSRC, "va_block.h")] for src in ("gate_va.hip", "certify.hip", "attack.hip", "plan.hip")})
-    for src in ("partition.hip", "plan.hip", "stem.hip", "gate.hip", "gate_fused.hip", "gate_xs.hip", "gate_full.hip", "gate_va.hip"):
+    for src in ("partition.hip", "plan.hip", "certify.hip", "stem.hip", "gate.hip", "gate_fused.hip", "gate_xs.hip", "gate_full.hip", "gate_va.hip"):
         included[src] = included.get(src, []) + [os.path.join(CSRC, "partition.h"), os.path.join(CSRC, "va_block.h")]      # (partition.h includes va_block.h)
     jobs = []
     for src in SOURCES:

@@ -213,6 +213,18 @@ def build_parser() -> argparse.ArgumentParser:
     cert.add_argument("--certify_min_margin", type=float, default=1e-6, metavar="M", help="certified means lower bound > M")
     cert.add_argument("--certify_rows", type=str, default=None, metavar="FILE",
                       help="CSV eps,index,class,stage,certified,lb,lb_interval,worst,unknown_stem,unknown_feat of every image")
+    pat = p.add_argument_group("certified patch robustness of the labels (one more stdout line per patch size, after every line above)")
+    pat.add_argument("--certify_patch", type=str, default=None, metavar="HxW[,HxW...]",
+                     help="certify every image's label against a patch of H x W pixels (1..8 each) at every position and print "
+                          "`Patch.. size=HxW amp=A stride=S certified/N pct (positions p/P certified: interval a, enumeration b; "
+                          "unknown stem bits median u max v)`; --certify_enum and --certify_min_margin apply")
+    pat.add_argument("--patch_stride", type=int, default=1, metavar="S",
+                     help="positions every S pixels (1..32); above 1 the line says `sampled`: only stride 1 covers every placement")
+    pat.add_argument("--patch_amp", type=int, default=255, metavar="A", help="the patch's bytes move by up to A levels (1..255; 255: any value)")
+    pat.add_argument("--patch_map", type=str, default=None, metavar="FILE",
+                     help=".npz: per size lb_HxW, stage_HxW, worst_HxW, unknown_stem_HxW, each [N][Py][Px]")
+    pat.add_argument("--patch_rows", type=str, default=None, metavar="FILE",
+                     help="CSV size,amp,stride,index,class,patch_certified,certified,positions,interval,enumeration,lb_min,pos_min,worst")
     att = p.add_argument_group("falsified robustness (with --certify: one more stdout line per eps, after its `Verified..`)")
     att.add_argument("--attack", action="store_true",
                      help="search the box of floor(EPS) byte levels for a uint8 image that loses the label and print `Robust.. eps=E "
@@ -238,6 +250,19 @@ def certify_eps_list(text: Optional[str]) -> List[float]:
     if any(not (np.isfinite(e) and e >= 0) for e in eps):
         raise SystemExit("--certify: every eps must be finite and >= 0")
     return eps
+
+
+def certify_patch_list(text: Optional[str]) -> List[tuple]:
+    """The sizes of ``--certify_patch``: comma-separated ``HxW``, each side 1..8."""
+    if not text:
+        return []
+    try:
+        sizes = [tuple(int(v) for v in t.split("x")) for t in text.split(",")]
+    except ValueError:
+        raise SystemExit(f"--certify_patch: {text!r} is not a comma-separated list of HxW") from None
+    if any(len(p) != 2 or not all(1 <= v <= 8 for v in p) for p in sizes):
+        raise SystemExit("--certify_patch: every size is HxW with H and W in 1..8")
+    return sizes
 
 
 def _class_names(args) -> Optional[List[str]]:
@@ -275,7 +300,8 @@ def run(args) -> int:
         extra = dict(topk=args.topk, per_class=bool(args.per_class or args.confusion), confusion=bool(args.confusion))
     eps_list = certify_eps_list(args.certify)
     batches = device_batches(images, targets, args.eval_batch_size, device)
-    if eps_list:
+    patches = certify_patch_list(args.certify_patch)
+    if eps_list or patches:
         batches = list(batches)                                 # one upload: the certificate reads the bytes the evaluation read
     res = evaluate(model, batches, device, inflight=max(1, args.inflight),
                    metrics="device", **extra)                   # prints `Acc.. top1 top5` (main.py:284)
@@ -320,6 +346,16 @@ def run(args) -> int:
                 arrays[f"status_{e:g}"] = a["rows"]["status"]
             with replacing(args.attack_witnesses, "wb") as f:
                 np.savez(f, **arrays)
+    if patches:
+        from . import certify
+        psums = certify.certify_patch_batches(model, batches, patches, args.patch_stride, args.patch_amp, args.certify_enum,
+                                              args.certify_min_margin)
+        for s in psums:
+            print(certify.patch_line(s))
+        if args.patch_rows:
+            certify.write_patch_rows_csv(args.patch_rows, psums, targets.tolist())
+        if args.patch_map:
+            certify.write_patch_map_npz(args.patch_map, psums)
     return 0
 
 
@@ -336,6 +372,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         raise SystemExit("--certify_rows needs --certify")
     if args.attack and not args.certify:
         raise SystemExit("--attack needs --certify EPS[,EPS...]")
+    certify_patch_list(args.certify_patch)
+    if not 1 <= args.patch_stride <= 32:
+        raise SystemExit("--patch_stride must be in [1, 32]")
+    if not 1 <= args.patch_amp <= 255:
+        raise SystemExit("--patch_amp must be in [1, 255]")
+    if (args.patch_map or args.patch_rows) and not args.certify_patch:
+        raise SystemExit("--patch_map and --patch_rows need --certify_patch HxW[,HxW...]")
     if (args.attack_rows or args.attack_witnesses) and not args.attack:
         raise SystemExit("--attack_rows and --attack_witnesses need --attack")
     if not 0 <= args.attack_rounds <= 8:

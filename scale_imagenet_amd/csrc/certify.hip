@@ -10,10 +10,18 @@
 //   certify_head_kernel, certify_t3_words_kernel: the effective head A = lin2 diag(bn_scale) lin1, c0, and the 256-entry
 //   tables of Block_conv3 as four 64-bit words per output bit; once per loaded state
 //
+//   ttnet_certify_box_u8 is the same with stage 0's intervals taken from two images (a loader parameter of certify_stem_kernel).
+//   ttnet_certify_patch_u8: all positions of a patch.  Per image the clean planes and sums (the stages above on the degenerate
+//   box), then certify_patch_kernel, one workgroup per (image, position): the stem bounds of the <= 4 x 4 pooled cells whose
+//   field meets the patch (certify_stem_cell.inc, the body stage 0 runs), the features those cells reach, lb_j = clean sums + the changed
+//   features' differences, stage 2 in the workgroup (enumerate_completions, the body of certify_enum_kernel), and
+//   certify_patch_rows_kernel, which folds an image's positions into its record.
+//
 // Everything is float64 and integer work in a fixed order: no float atomics, the same bytes on every run.
 
 #include <math.h>
 
+#include "partition.h"
 #include "ttnet_common.h"
 #include "va_block.h"
 
@@ -78,16 +86,27 @@ __global__ void certify_t3_words_kernel(const uint8_t *__restrict__ t3, uint64_t
   t3w[t] = word;
 }
 
+// centre and radius of the normalised interval of a byte of channel c that may take any value in [bl, bh]:
+// w+ x_lo + w- x_hi = w x_c - |w| x_r and w+ x_hi + w- x_lo = w x_c + |w| x_r, two multiply-adds per tap where the bounds
+// themselves take four and a choice by the sign of w
+__device__ inline void pixel_interval(double bl, double bh, const CertifyNorm &nm, int c, double &centre, double &radius) {
+  const double xl = (bl - nm.off[c]) * nm.a[c], xh = (bh - nm.off[c]) * nm.a[c];
+  centre = 0.5 * (xl + xh);
+  radius = 0.5 * (xh - xl);
+}
+
+
 // stage 0: five workgroups per image, each two pooled rows: thread = (channel, pooled row) as va_stem_kernel.  The eight
 // image rows those need (image rows 3 p0 - 1 .. 3 p0 + 6, p0 = the first pooled row) live in LDS as the centre and the
 // radius of each normalised pixel's interval, with the zero column on the left (the padding is zero in normalised space:
 // centre 0, radius 0; the pooled outputs never touch the right or bottom padding).  13 KiB of LDS per workgroup.
+// The loader takes the interval of byte b from eps (xhi == nullptr) or from the two images (the box [b, max(b, xhi's byte)]).
 constexpr int kStemRowsPerWg = 2, kStemLdsRows = 3 * kStemRowsPerWg + 2;
 
 __global__ __launch_bounds__(64 * kStemRowsPerWg) void certify_stem_kernel(
-    const uint8_t *__restrict__ x, CertifyNorm nm, const float *__restrict__ w, const float *__restrict__ bias,
-    const double *__restrict__ bn, const double *__restrict__ slack, double eps, uint64_t *__restrict__ lo_rp,
-    uint64_t *__restrict__ hi_rp, int n) {
+    const uint8_t *__restrict__ x, const uint8_t *__restrict__ xhi, CertifyNorm nm, const float *__restrict__ w,
+    const float *__restrict__ bias, const double *__restrict__ bn, const double *__restrict__ slack, double eps,
+    uint64_t *__restrict__ lo_rp, uint64_t *__restrict__ hi_rp, int n) {
   __shared__ double img_s[2][3][kStemLdsRows][34];
   constexpr int kParts = kPool / kStemRowsPerWg;
   const int img = blockIdx.x / kParts, p0 = (blockIdx.x % kParts) * kStemRowsPerWg;
@@ -98,19 +117,17 @@ __global__ __launch_bounds__(64 * kStemRowsPerWg) void certify_stem_kernel(
     if (q == 0 || q == 33 || r0 + r < 0) (&img_s[0][0][0][0])[i] = (&img_s[1][0][0][0])[i] = 0.0;
   }
   const uint32_t *src = (const uint32_t *)(x + (size_t)img * kImg);   // (4-byte aligned: checked by the plan; a row is 96 bytes)
+  const uint32_t *srch = xhi ? (const uint32_t *)(xhi + (size_t)img * kImg) : nullptr;
   for (int i = threadIdx.x; i < kStemLdsRows * 24; i += blockDim.x) {
     const int lr = i / 24, ir = r0 + lr;                             // ir <= 3 * 8 - 1 + 7 = 30
     if (ir < 0) continue;
-    const uint32_t v = src[ir * 24 + (i - lr * 24)];
+    const uint32_t v = src[ir * 24 + (i - lr * 24)], vh = srch ? srch[ir * 24 + (i - lr * 24)] : 0u;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int e = 4 * (i - lr * 24) + k, q = e / 3, c = e - 3 * q;
       const double b = (double)((v >> (8 * k)) & 0xFFu);
-      // centre and radius of the interval: w+ x_lo + w- x_hi = w x_c - |w| x_r and w+ x_hi + w- x_lo = w x_c + |w| x_r,
-      // two multiply-adds per tap where the bounds themselves take four and a choice by the sign of w
-      const double xl = (fmax(0.0, b - eps) - nm.off[c]) * nm.a[c], xh = (fmin(255.0, b + eps) - nm.off[c]) * nm.a[c];
-      img_s[0][c][lr][q + 1] = 0.5 * (xl + xh);
-      img_s[1][c][lr][q + 1] = 0.5 * (xh - xl);
+      const double bl = srch ? b : fmax(0.0, b - eps), bh = srch ? fmax(b, (double)((vh >> (8 * k)) & 0xFFu)) : fmin(255.0, b + eps);
+      pixel_interval(bl, bh, nm, c, img_s[0][c][lr][q + 1], img_s[1][c][lr][q + 1]);
     }
   }
   __syncthreads();
@@ -122,52 +139,14 @@ __global__ __launch_bounds__(64 * kStemRowsPerWg) void certify_stem_kernel(
   uint64_t out_lo = 0, out_hi = 0;
 #pragma unroll 1
   for (int px = 0; px < 10; ++px) {
-    // the nine convolution outputs of the pooled pixel, from its 5x5 patch: a patch row is read once (all 64 lanes of
-    // the wave read the same address: a broadcast) and feeds every output it belongs to; the tap order of va_stem_patch
-    double mid[3][3], rad[3][3];
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-      for (int dx = 0; dx < 3; ++dx) mid[dy][dx] = rad[dy][dx] = 0.0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-      for (int r = 0; r < 5; ++r) {
-        double xc[5], xr[5];
-#pragma unroll
-        for (int q = 0; q < 5; ++q) {
-          xc[q] = img_s[0][c][3 * pl + r][3 * px + q];
-          xr[q] = img_s[1][c][3 * pl + r][3 * px + q];
-        }
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy) {
-          const int kh = r - dy;
-          if (kh < 0 || kh > 2) continue;
-#pragma unroll
-          for (int dx = 0; dx < 3; ++dx)
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-              const double wv = wr[(c * 3 + kh) * 3 + kw];
-              mid[dy][dx] = fma(wv, xc[dx + kw], mid[dy][dx]);
-              rad[dy][dx] = fma(fabs(wv), xr[dx + kw], rad[dy][dx]);
-            }
-        }
-      }
-    double best_lo = -INFINITY, best_hi = -INFINITY;
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-      for (int dx = 0; dx < 3; ++dx) {
-        const double lo = fmax(mid[dy][dx] - rad[dy][dx] + b, 0.0), hi = fmax(mid[dy][dx] + rad[dy][dx] + b, 0.0);   // ReLU
-        const double ylo = (sc >= 0.0 ? lo : hi) * sc + sh, yhi = (sc >= 0.0 ? hi : lo) * sc + sh;   // a negative scale swaps the bounds
-        best_lo = fmax(best_lo, ylo);                                // MaxPool2d(3): max of the lows, max of the highs
-        best_hi = fmax(best_hi, yhi);
-      }
-    out_lo |= (uint64_t)(best_lo - sl >= 0.0) << px;
-    out_hi |= (uint64_t)(best_hi + sl >= 0.0) << px;
+#define STEM_AT(k, c, r, q) img_s[k][c][3 * pl + (r)][3 * px + (q)]
+#include "certify_stem_cell.inc"
+#undef STEM_AT
+    out_lo |= (uint64_t)lo_bit << px;
+    out_hi |= (uint64_t)hi_bit << px;
   }
   lo_rp[((size_t)img * kStemCh + ch) * kPool + py] = out_lo;
-  hi_rp[((size_t)img * kStemCh + ch) * kPool + py] = out_hi | out_lo;   // (lo_bit <= hi_bit whatever the arithmetic did)
+  hi_rp[((size_t)img * kStemCh + ch) * kPool + py] = out_hi;
 }
 
 // stage 1, Block_conv1 / Block_conv2 / out4: thread = (image, channel, output row of the 11x11 plane), as va_dw_kernel.
@@ -291,7 +270,8 @@ __global__ __launch_bounds__(256) void certify_margin_kernel(const uint64_t *__r
                                                              const uint64_t *__restrict__ ylo, const uint64_t *__restrict__ yhi,
                                                              const double *__restrict__ A, const double *__restrict__ c0,
                                                              const int32_t *__restrict__ classes, double min_margin,
-                                                             Row *__restrict__ rows, double *__restrict__ sums, int n) {
+                                                             Row *__restrict__ rows, double *__restrict__ sums,
+                                                             double *__restrict__ sums_un, int n) {
   __shared__ double red[2 * kClasses][256];                          // [j]: the certain features, [10 + j]: the unknown ones
   __shared__ int cnt_s[2];
   const int img = blockIdx.x, tid = threadIdx.x;
@@ -335,6 +315,7 @@ __global__ __launch_bounds__(256) void certify_margin_kernel(const uint64_t *__r
     __syncthreads();
   }
   if (tid < kClasses) sums[(size_t)img * kClasses + tid] = red[tid][0];
+  if (sums_un && tid < kClasses) sums_un[(size_t)img * kClasses + tid] = red[kClasses + tid][0];
   if (tid != 0) return;
   Row out;
   out.lb_interval = -INFINITY;
@@ -358,16 +339,46 @@ __global__ __launch_bounds__(256) void certify_margin_kernel(const uint64_t *__r
   rows[img] = out;
 }
 
-// stage 2: one workgroup per image that stage 1 left open with 1 <= k <= enum_bits unknown stem bits.  The unknown bits
-// (channel, row, column ascending) and the features they reach (per unknown bit: conv1, conv2, conv3, out4; the first
-// mention of a feature wins) are listed in that fixed order, so the sums below are taken in a fixed order too.
-__global__ __launch_bounds__(256) void certify_enum_kernel(const uint64_t *__restrict__ slo, const uint64_t *__restrict__ shi,
-                                                           const uint64_t *__restrict__ ylo, const uint32_t *__restrict__ t1,
-                                                           const uint32_t *__restrict__ t2, const uint64_t *__restrict__ t3w,
-                                                           const double *__restrict__ A, const double *__restrict__ c0,
-                                                           const int32_t *__restrict__ classes, int enum_bits, double min_margin,
-                                                           Row *__restrict__ rows, const double *__restrict__ sums, int n) {
-  __shared__ uint64_t s_lo[kStemRows], s_un[kStemRows];
+// One feature on three-valued stem planes held as (values, unknown bits) words [640]: what certify_dw_kernel and
+// certify_c3_kernel give that feature, by the generic window (window_input).  The caller keeps (oy, ox) inside the plane
+// that the branch computes (conv1: oy < 10; conv2: ox < 10; conv3 / out4: both < 10).
+__device__ inline void feature3(const uint64_t *s_lo, const uint64_t *s_un, int kind, int ch, int oy, int ox, const uint32_t *__restrict__ t1,
+                                const uint32_t *__restrict__ t2, const uint64_t *__restrict__ t3w, bool &lo, bool &hi) {
+  uint32_t idx = 0, un = 0;
+  for (int p = 0; p < window_size(kind); ++p) {
+    const StemBit s = window_input(kind, ch, oy, ox, p);
+    if (!s.in) continue;
+    const int r = s.ch * kPool + s.y;
+    idx |= (uint32_t)((s_lo[r] >> s.x) & 1ull) << p;
+    un |= (uint32_t)((s_un[r] >> s.x) & 1ull) << p;
+  }
+  idx &= ~un;
+  if (kind < 2) {
+    const uint64_t T = table_word(kind == 0 ? t1 : t2, ch), S = selector(idx, un);
+    lo = (~T & S) == 0;
+    hi = (T & S) != 0;
+  } else if (kind == 2) {
+    bool can0, can1;
+    lookup8(t3w + ch * 4, idx, un, can0, can1);                      // (ch = 8 group + output)
+    lo = !can0;
+    hi = can1;
+  } else {
+    lo = idx & 1u;
+    hi = (idx | un) & 1u;
+  }
+}
+
+// stage 2 for one set of stem planes, by a whole workgroup of 256 threads (every thread calls it, under a condition that is
+// uniform over the workgroup): s_lo / s_un = the values and the unknown bits [640] in LDS, written and barriered by the caller;
+// k = the number of unknown bits (1 .. kMaxEnum); ylo_bit(feature row, column) = stage 1's lower plane; sums10 = stage 1's
+// sum over the certain features.  The unknown bits (channel, row, column ascending) and the features they reach (per unknown
+// bit: conv1, conv2, conv3, out4; the first mention of a feature wins) are listed in that fixed order, so the sums below are
+// taken in a fixed order too.  Every thread returns the bound and its class.
+template <class YLo>
+__device__ inline void enumerate_completions(const uint64_t *s_lo, const uint64_t *s_un, int k, int c, YLo ylo_bit, const double *sums10,
+                                             const uint32_t *__restrict__ t1, const uint32_t *__restrict__ t2,
+                                             const uint64_t *__restrict__ t3w, const double *__restrict__ A,
+                                             const double *__restrict__ c0, double &lb, int &worst) {
   __shared__ uint64_t e_T[kMaxEnt][4];
   __shared__ double e_D[kMaxEnt][kClasses];
   __shared__ uint16_t e_key[kMaxEnt], c_key[kMaxEnt];                // feature row * 16 + column: of the entries, of the candidates
@@ -378,17 +389,7 @@ __global__ __launch_bounds__(256) void certify_enum_kernel(const uint64_t *__res
   __shared__ double base_s[kClasses];
   __shared__ double rv[256];
   __shared__ int rj[256];
-  const int img = blockIdx.x, tid = threadIdx.x;
-  if (img >= n) return;
-  const int c = classes[img];
-  const int k = rows[img].unknown_stem;
-  if (rows[img].stage != 0 || k < 1 || k > enum_bits || k > kMaxEnum || c < 0 || c >= kClasses) return;   // (whole workgroups)
-  for (int r = tid; r < kStemRows; r += 256) {
-    const uint64_t l = slo[(size_t)img * kStemRows + r];
-    s_lo[r] = l;
-    s_un[r] = (l ^ shi[(size_t)img * kStemRows + r]) & 0x3FFull;
-  }
-  __syncthreads();
+  const int tid = threadIdx.x;
   if (tid < kStemCh) {               // the unknown bits in order: lane = channel, a scan of the lanes' counts gives each its place
     int cnt = 0;
     for (int y = 0; y < kPool; ++y) cnt += __popcll(s_un[tid * kPool + y]);
@@ -458,7 +459,7 @@ __global__ __launch_bounds__(256) void certify_enum_kernel(const uint64_t *__res
     for (int w = 0; w < 4; ++w) e_T[e][w] = T[w];
     e_base[e] = (uint8_t)base;
     e_cnt[e] = (uint8_t)cnt;
-    e_one[e] = (uint8_t)((ylo[(size_t)img * kFeatRows + row] >> bit) & 1ull);
+    e_one[e] = (uint8_t)ylo_bit(row, bit);
     const double *af = A + (size_t)(fc * kPlane + oy * kSide + bit) * kClasses;
     const double ac = af[c];
     for (int j = 0; j < kClasses; ++j) e_D[e][j] = ac - af[j];
@@ -468,7 +469,7 @@ __global__ __launch_bounds__(256) void certify_enum_kernel(const uint64_t *__res
   if (tid < kClasses) {
     double sub = 0.0;
     for (int e = 0; e < n_ent; ++e) sub += e_one[e] ? e_D[e][tid] : 0.0;
-    base_s[tid] = tid == c ? INFINITY : c0[c] - c0[tid] + (sums[(size_t)img * kClasses + tid] - sub);
+    base_s[tid] = tid == c ? INFINITY : c0[c] - c0[tid] + (sums10[tid] - sub);
   }
   __syncthreads();
   double best = INFINITY;
@@ -501,10 +502,261 @@ __global__ __launch_bounds__(256) void certify_enum_kernel(const uint64_t *__res
     }
     __syncthreads();
   }
+  lb = rv[0];
+  worst = rj[0];
+}
+
+// stage 2: one workgroup per image that stage 1 left open with 1 <= k <= enum_bits unknown stem bits
+__global__ __launch_bounds__(256) void certify_enum_kernel(const uint64_t *__restrict__ slo, const uint64_t *__restrict__ shi,
+                                                           const uint64_t *__restrict__ ylo, const uint32_t *__restrict__ t1,
+                                                           const uint32_t *__restrict__ t2, const uint64_t *__restrict__ t3w,
+                                                           const double *__restrict__ A, const double *__restrict__ c0,
+                                                           const int32_t *__restrict__ classes, int enum_bits, double min_margin,
+                                                           Row *__restrict__ rows, const double *__restrict__ sums, int n) {
+  __shared__ uint64_t s_lo[kStemRows], s_un[kStemRows];
+  const int img = blockIdx.x, tid = threadIdx.x;
+  if (img >= n) return;
+  const int c = classes[img];
+  const int k = rows[img].unknown_stem;
+  if (rows[img].stage != 0 || k < 1 || k > enum_bits || k > kMaxEnum || c < 0 || c >= kClasses) return;   // (whole workgroups)
+  for (int r = tid; r < kStemRows; r += 256) {
+    const uint64_t l = slo[(size_t)img * kStemRows + r];
+    s_lo[r] = l;
+    s_un[r] = (l ^ shi[(size_t)img * kStemRows + r]) & 0x3FFull;
+  }
+  __syncthreads();
+  double lb;
+  int worst;
+  enumerate_completions(s_lo, s_un, k, c, [&](int row, int bit) { return (ylo[(size_t)img * kFeatRows + row] >> bit) & 1ull; },
+                        sums + (size_t)img * kClasses, t1, t2, t3w, A, c0, lb, worst);
   if (tid != 0) return;
-  rows[img].lb = rv[0];
-  rows[img].worst = rj[0];
-  rows[img].stage = rv[0] > min_margin ? 2 : 0;
+  rows[img].lb = lb;
+  rows[img].worst = worst;
+  rows[img].stage = lb > min_margin ? 2 : 0;
+}
+
+// ---- all positions of a patch (include/ttnet.h: ttnet_certify_patch_u8) -------------------------------------------------------
+struct MapRec {         // one (image, position) record, 16 bytes
+  double lb;
+  int32_t worst;
+  uint16_t stage, unknown_stem;
+};
+struct PatchRow {       // one image's record, 32 bytes
+  double lb_min;
+  int32_t pos_min, worst, certified, interval, enumeration, positions;
+};
+static_assert(sizeof(MapRec) == 16 && sizeof(PatchRow) == 32, "record layouts of include/ttnet.h");
+
+struct PatchGeom {
+  int h, w, stride, amp, py, px;
+};
+
+// the features of branch `kind` that the cells rows x cols reach: a rectangle of its plane (inside what the branch computes)
+struct FeatRect {
+  int r0, nr, c0, nc;
+};
+__device__ inline FeatRect reached_rect(int kind, FieldSpan rows, FieldSpan cols) {
+  int r0 = rows.first, r1 = rows.last(), q0 = cols.first, q1 = cols.last();
+  if (kind == 0) {                   // conv1: window rows oy - 1 .. oy + 1, columns ox - 1 .. ox; 10 x 11 outputs
+    r0 = r0 > 0 ? r0 - 1 : 0;
+    r1 = r1 + 1 < kPool ? r1 + 1 : kPool - 1;
+    q1 = q1 + 1;                     // <= 10
+  } else if (kind == 1) {            // conv2: window rows oy - 1 .. oy, columns ox - 1 .. ox + 1; 11 x 10 outputs
+    r1 = r1 + 1;                     // <= 10
+    q0 = q0 > 0 ? q0 - 1 : 0;
+    q1 = q1 + 1 < kPool ? q1 + 1 : kPool - 1;
+  }
+  return {r0, r1 - r0 + 1, q0, q1 - q0 + 1};
+}
+
+// One workgroup per (image, position); task = first_task + blockIdx.x = image * P + position.
+//   1. the clean planes of the image into LDS; the pixels of the fields that meet the patch as centres and radii (those of
+//      the patch from [max(0, b - amp), min(255, b + amp)], the others exact): at most 14 x 14 x 3
+//   2. thread (channel, cell row) recomputes that row's cells (certify_stem_cell.inc) and rewrites its word of the planes
+//   3. every feature of the four rectangles those cells reach is looked up on the new planes; where it differs from the clean
+//      feature planes, its contribution changes: thread t sums the differences of the features t, t + 256, .. of a branch
+//      (branches in order), the 64 lanes of a wave meet by shuffles (xor 32, 16, .., 1), the four waves are added in order
+//   4. lb_j = c0_c - c0_j + ((clean certain sum_j + its change) + (clean unknown sum_j + its change)); stage 2 in the workgroup
+__global__ __launch_bounds__(256, 2) void certify_patch_kernel(
+    const uint8_t *__restrict__ x, CertifyNorm nm, const float *__restrict__ w, const float *__restrict__ bias,
+    const double *__restrict__ bn, const double *__restrict__ slack, const uint64_t *__restrict__ slo, const uint64_t *__restrict__ shi,
+    const uint64_t *__restrict__ ylo, const uint64_t *__restrict__ yhi, const uint32_t *__restrict__ t1, const uint32_t *__restrict__ t2,
+    const uint64_t *__restrict__ t3w, const double *__restrict__ A, const double *__restrict__ c0, const int32_t *__restrict__ classes,
+    const double *__restrict__ sums, const double *__restrict__ sums_un, const Row *__restrict__ clean_rows, PatchGeom g, int enum_bits,
+    double min_margin, MapRec *__restrict__ map, long long first_task, long long n_tasks) {
+  __shared__ uint64_t s_lo[kStemRows], s_un[kStemRows];
+  __shared__ double win[2][3][kFieldPixels][kFieldPixels];
+  __shared__ double part[4][2 * kClasses];
+  __shared__ double pos_sums[kClasses];
+  __shared__ double lb_s;
+  __shared__ int dk_s, worst_s, stage_s;
+  const long long task = first_task + blockIdx.x;
+  if (task >= n_tasks) return;                                       // (whole workgroups)
+  const int P = g.py * g.px, img = (int)(task / P), pos = (int)(task - (long long)img * P), tid = threadIdx.x;
+  const int y0 = (pos / g.px) * g.stride, x0 = (pos % g.px) * g.stride;
+  const FieldSpan fr = field_span(y0, g.h), fq = field_span(x0, g.w);
+  const bool touched = fr.count > 0 && fq.count > 0;
+  const int c = classes[img];
+  const bool valid = c >= 0 && c < kClasses;
+  for (int r = tid; r < kStemRows; r += 256) {
+    const uint64_t l = slo[(size_t)img * kStemRows + r];
+    s_lo[r] = l;
+    s_un[r] = (l ^ shi[(size_t)img * kStemRows + r]) & 0x3FFull;
+  }
+  if (tid == 0) dk_s = 0;
+  const int wr_n = 3 * fr.count + 2, wq_n = 3 * fq.count + 2;        // <= kFieldPixels
+  if (touched)
+    for (int i = tid; i < 3 * wr_n * wq_n; i += 256) {
+      const int ch = i % 3, lq = (i / 3) % wq_n, lr = i / (3 * wq_n), ir = 3 * fr.first - 1 + lr, iq = 3 * fq.first - 1 + lq;   // ir, iq <= 30
+      double centre = 0.0, radius = 0.0;                             // the top / left padding: zero in normalised space
+      if (ir >= 0 && iq >= 0) {
+        const int b = x[(size_t)img * kImg + (ir * 32 + iq) * 3 + ch];
+        const bool in = ir >= y0 && ir < y0 + g.h && iq >= x0 && iq < x0 + g.w;
+        const int bl = in ? (b - g.amp > 0 ? b - g.amp : 0) : b, bh = in ? (b + g.amp < 255 ? b + g.amp : 255) : b;
+        pixel_interval((double)bl, (double)bh, nm, ch, centre, radius);
+      }
+      win[0][ch][lr][lq] = centre;
+      win[1][ch][lr][lq] = radius;
+    }
+  __syncthreads();
+  if (touched && tid < 64 * fr.count) {
+    const int ch = tid & 63, cy = tid >> 6, r = ch * kPool + fr.first + cy;   // one wave per row of cells
+    double wr[27];
+#pragma unroll
+    for (int i = 0; i < 27; ++i) wr[i] = (double)w[ch * 27 + i];
+    const double b = (double)bias[ch], sc = bn[ch], sh = bn[64 + ch], sl = slack[ch];
+    uint64_t lo_w = s_lo[r], un_w = s_un[r];
+    const int before = __popcll(un_w);
+#pragma unroll 1
+    for (int cx = 0; cx < fq.count; ++cx) {
+      // (the included text declares its own loop variables c and r, which shadow the class c and the plane row r inside it:
+      // STEM_AT's arguments are the text's, and both outer names mean what they meant again after it)
+#define STEM_AT(k, c, r, q) win[k][c][3 * cy + (r)][3 * cx + (q)]
+#include "certify_stem_cell.inc"
+#undef STEM_AT
+      const int px = fq.first + cx;
+      lo_w = (lo_w & ~(1ull << px)) | ((uint64_t)lo_bit << px);
+      un_w = (un_w & ~(1ull << px)) | ((uint64_t)(lo_bit != hi_bit) << px);
+    }
+    s_lo[r] = lo_w;
+    s_un[r] = un_w;
+    const int dk = __popcll(un_w) - before;
+    if (dk) atomicAdd(&dk_s, dk);                                    // (integers: any order gives the same sum)
+  }
+  __syncthreads();
+  double acc[2 * kClasses];                                          // [j]: the certain part, [10 + j]: the unknown part
+#pragma unroll
+  for (int j = 0; j < 2 * kClasses; ++j) acc[j] = 0.0;
+  if (touched && valid)
+    for (int kind = 0; kind < 4; ++kind) {
+      const FeatRect rc = reached_rect(kind, fr, fq);
+      for (int e = tid; e < 64 * rc.nr * rc.nc; e += 256) {
+        const int ch = e & 63, cell = e >> 6, oy = rc.r0 + cell / rc.nc, ox = rc.c0 + cell % rc.nc, fc = 64 * kind + ch;
+        bool lo, hi;
+        feature3(s_lo, s_un, kind, ch, oy, ox, t1, t2, t3w, lo, hi);
+        const size_t row = (size_t)img * kFeatRows + fc * kSide + oy;
+        const bool clo = (ylo[row] >> ox) & 1ull, chi = (yhi[row] >> ox) & 1ull;
+        if (lo == clo && hi == chi) continue;
+        const double *af = A + (size_t)(fc * kPlane + oy * kSide + ox) * kClasses;
+        const double ac = af[c];
+#pragma unroll
+        for (int j = 0; j < kClasses; ++j) {
+          const double d = ac - af[j], m = fmin(0.0, d);
+          acc[j] += (lo ? d : 0.0) - (clo ? d : 0.0);
+          acc[kClasses + j] += ((hi && !lo) ? m : 0.0) - ((chi && !clo) ? m : 0.0);
+        }
+      }
+    }
+#pragma unroll
+  for (int j = 0; j < 2 * kClasses; ++j) {
+    double v = acc[j];
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    if ((tid & 63) == 0) part[tid >> 6][j] = v;
+  }
+  __syncthreads();
+  const int k = clean_rows[img].unknown_stem + dk_s;
+  if (tid == 0) {
+    double best = valid ? INFINITY : -INFINITY;
+    int best_j = -1;
+    for (int j = 0; j < kClasses && valid; ++j) {
+      const double cert = sums[(size_t)img * kClasses + j] + (((part[0][j] + part[1][j]) + part[2][j]) + part[3][j]);
+      const double unk = sums_un[(size_t)img * kClasses + j] + (((part[0][kClasses + j] + part[1][kClasses + j]) + part[2][kClasses + j]) + part[3][kClasses + j]);
+      pos_sums[j] = cert;
+      if (j == c) continue;
+      const double lb = c0[c] - c0[j] + (cert + unk);
+      if (lb < best) {
+        best = lb;
+        best_j = j;
+      }
+    }
+    lb_s = best;
+    worst_s = best_j;
+    stage_s = (valid && best > min_margin) ? 1 : 0;
+  }
+  __syncthreads();
+  double lb = lb_s;
+  int worst = worst_s, stage = stage_s;
+  if (valid && stage == 0 && k >= 1 && k <= enum_bits && k <= kMaxEnum) {   // (uniform over the workgroup)
+    enumerate_completions(s_lo, s_un, k, c,
+                          [&](int row, int bit) {
+                            const int fc = row / kSide;
+                            bool lo, hi;
+                            feature3(s_lo, s_un, fc >> 6, fc & 63, row % kSide, bit, t1, t2, t3w, lo, hi);
+                            return lo;
+                          },
+                          pos_sums, t1, t2, t3w, A, c0, lb, worst);
+    stage = lb > min_margin ? 2 : 0;
+  }
+  if (tid != 0) return;
+  MapRec out;
+  out.lb = lb;
+  out.worst = worst;
+  out.stage = (uint16_t)stage;
+  out.unknown_stem = (uint16_t)k;                                    // <= 6400
+  map[task] = out;
+}
+
+// an image's positions into its record: one workgroup per image; the smallest lb, ties to the first position
+__global__ __launch_bounds__(256) void certify_patch_rows_kernel(const MapRec *__restrict__ map, PatchRow *__restrict__ rows, int P, int n) {
+  __shared__ double rv[256];
+  __shared__ int rp[256], cnt_s[2];
+  const int img = blockIdx.x, tid = threadIdx.x;
+  if (img >= n) return;
+  if (tid < 2) cnt_s[tid] = 0;
+  __syncthreads();
+  double best = INFINITY;
+  int best_p = P, n1 = 0, n2 = 0;
+  for (int p = tid; p < P; p += 256) {
+    const MapRec m = map[(size_t)img * P + p];
+    n1 += m.stage == 1;
+    n2 += m.stage == 2;
+    if (m.lb < best || (m.lb == best && p < best_p) || best_p == P) {
+      best = m.lb;
+      best_p = p;
+    }
+  }
+  rv[tid] = best;
+  rp[tid] = best_p;
+  if (n1) atomicAdd(&cnt_s[0], n1);
+  if (n2) atomicAdd(&cnt_s[1], n2);
+  __syncthreads();
+  for (int s = 128; s >= 1; s >>= 1) {                               // min of (value, position): the order does not matter
+    if (tid < s && rp[tid + s] < P && (rp[tid] == P || rv[tid + s] < rv[tid] || (rv[tid + s] == rv[tid] && rp[tid + s] < rp[tid]))) {
+      rv[tid] = rv[tid + s];
+      rp[tid] = rp[tid + s];
+    }
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  PatchRow out;
+  out.lb_min = rv[0];
+  out.pos_min = rp[0];
+  out.worst = map[(size_t)img * P + rp[0]].worst;
+  out.interval = cnt_s[0];
+  out.enumeration = cnt_s[1];
+  out.certified = cnt_s[0] + cnt_s[1];
+  out.positions = P;
+  rows[img] = out;
 }
 
 }  // namespace
@@ -521,7 +773,7 @@ int launch_certify(const CertifyArgs &a, int step, hipStream_t s) {
   const int n = a.n;
   Row *rows = (Row *)a.rows;
   if (step == kCertifyStem) {
-    hipLaunchKernelGGL(certify_stem_kernel, dim3((unsigned)n * (kPool / kStemRowsPerWg)), dim3(64 * kStemRowsPerWg), 0, s, a.x, a.norm, a.w, a.bias, a.stem_bn, a.slack, a.eps,
+    hipLaunchKernelGGL(certify_stem_kernel, dim3((unsigned)n * (kPool / kStemRowsPerWg)), dim3(64 * kStemRowsPerWg), 0, s, a.x, a.x_hi, a.norm, a.w, a.bias, a.stem_bn, a.slack, a.eps,
                        a.stem_lo, a.stem_hi, n);
   } else if (step == kCertifyBlock) {
     size_t t = (size_t)n * kStemCh * kSide;
@@ -532,11 +784,30 @@ int launch_certify(const CertifyArgs &a, int step, hipStream_t s) {
                        a.feat_lo, a.feat_hi, n);
   } else if (step == kCertifyMargin) {
     hipLaunchKernelGGL(certify_margin_kernel, dim3((unsigned)n), dim3(256), 0, s, a.stem_lo, a.stem_hi, a.feat_lo, a.feat_hi, a.A, a.c0,
-                       a.classes, a.min_margin, rows, a.sums, n);
+                       a.classes, a.min_margin, rows, a.sums, a.sums_un, n);
   } else {
     hipLaunchKernelGGL(certify_enum_kernel, dim3((unsigned)n), dim3(256), 0, s, a.stem_lo, a.stem_hi, a.feat_lo, a.t1, a.t2, a.t3w,
                        a.A, a.c0, a.classes, a.enum_bits, a.min_margin, rows, a.sums, n);
   }
+  TT_HIP(hipGetLastError());
+  return TTNET_OK;
+}
+
+int launch_certify_patch(const PatchArgs &p, int step, hipStream_t s) {
+  const CertifyArgs &a = p.clean;
+  if (step == kPatchBase) {
+    TT_TRY(launch_certify(a, kCertifyStem, s));
+    TT_TRY(launch_certify(a, kCertifyBlock, s));
+    return launch_certify(a, kCertifyMargin, s);
+  }
+  const PatchGeom g{p.patch_h, p.patch_w, p.stride, p.amp, p.py, p.px};
+  const long long tasks = (long long)a.n * p.py * p.px;
+  for (long long l = 0; l < part::patch_launches(tasks); ++l)
+    hipLaunchKernelGGL(certify_patch_kernel, dim3((unsigned)part::patch_launch_size(tasks, l)), dim3(256), 0, s, a.x, a.norm, a.w, a.bias,
+                       a.stem_bn, a.slack, a.stem_lo, a.stem_hi, a.feat_lo, a.feat_hi, a.t1, a.t2, a.t3w, a.A, a.c0, a.classes, a.sums,
+                       a.sums_un, (const Row *)a.rows, g, a.enum_bits, a.min_margin, (MapRec *)p.map, l * part::kPatchGrid, tasks);
+  hipLaunchKernelGGL(certify_patch_rows_kernel, dim3((unsigned)a.n), dim3(256), 0, s, (const MapRec *)p.map, (PatchRow *)p.rows,
+                     p.py * p.px, a.n);
   TT_HIP(hipGetLastError());
   return TTNET_OK;
 }

@@ -109,6 +109,17 @@ TT_PART_FN FlatGrid va_dw_grid() { return {kVaDwTasks, 128}; }
 TT_PART_FN FlatGrid va_c3_grid() { return {kVaC3Tasks, 128}; }
 TT_PART_FN FlatGrid va_feat_grid() { return {kVaFeatTasks, 256}; }
 
+// ---- patch sweep (certify.hip): one workgroup per (image, position), cut into launches of at most kPatchGrid workgroups -------
+// n * P has no bound that the interface states (max_batch is the caller's), so the sweep is cut whatever n is.  2,048 is four
+// rounds of two workgroups on each of 256 CUs: large enough that the tail of a launch is a small share of it, small enough that
+// the tests' 3 x 1,024 positions take the cut (two launches), not only batches no test can afford.
+constexpr int kPatchGrid = 2048;
+TT_PART_FN int patch_positions(int patch, int stride) { return (32 - patch) / stride + 1; }       // along one side of the image
+TT_PART_FN long long patch_launches(long long tasks) { return (tasks + kPatchGrid - 1) / kPatchGrid; }
+TT_PART_FN int patch_launch_size(long long tasks, long long launch) {      // workgroups of launch 0 .. patch_launches - 1
+  return (int)((tasks - launch * kPatchGrid) < kPatchGrid ? (tasks - launch * kPatchGrid) : kPatchGrid);
+}
+
 // ---- full variant (gate_full.hip): grid-stride loops, grid (channels or groups, chunks) ---------------------------------
 constexpr int kFullDwRows = 256, kFullDwGrid = 1024;      // depthwise: threads (= output rows) per chunk, workgroups at most
 constexpr int kFullDwFixGrid = 1024;                      // its float64 pass over the list: workgroups

@@ -182,6 +182,7 @@ struct ttnet_plan {
     std::vector<uint16_t *> x_cp;
     std::vector<Block> blk;
     uint64_t *va_y = nullptr;       // vAlexnet: the concatenated block output [n][256][11] rows
+    double *patch_base = nullptr;      // vAlexnet, ttnet_certify_patch_u8: the clean pass's records [nb][4] and unknown sums [nb][10]; first call
     uint64_t *cert_planes = nullptr;   // vAlexnet, ttnet_certify_u8: stem lo / hi [nb][64][10], feature lo / hi [nb][256][11], sums [nb][10]; first call
     float *last_float = nullptr;    // full variant: relu'd output of the last block before AvgPool2d
     uint32_t *full_fix = nullptr;   // full variant: [64] counters + the pixel lists of one grouped 1x1 block (gate_full.hip)
@@ -1778,23 +1779,35 @@ int ttnet_plan_set_input_norm(ttnet_plan *pl, const float *mean3, const float *s
   return pl->path == GatePath::VAlexnet ? prepare_va_stem_u8(pl) : prepare_stem_u8(pl);
 }
 
-int ttnet_certify_u8(ttnet_plan *pl, int lane, const uint8_t *x_nhwc_dev, int64_t n, const int32_t *classes_dev, double eps,
-                     int enum_bits, double min_margin, void *rows_dev, uint64_t *planes_dev, void *stream) {
+// what the three certificate entries share: the variant, the plan's state, the arguments they all take, A / c0 / slack, the
+// lane's planes; then the argument block of the stages, with the box [x, x_hi] or x +- eps
+static int certify_begin(ttnet_plan *pl, int lane, const uint8_t *x_nhwc_dev, const uint8_t *x_hi_dev, int64_t n, const int32_t *classes_dev,
+                         double eps, int enum_bits, double min_margin, void *rows_dev, const void *second_out, bool needs_second,
+                         const char *bad_args, const char *who, hipStream_t s, CertifyArgs &a) {
   if (pl && pl->path != GatePath::VAlexnet) {
     set_error("certify: only the vAlexnet variant is served: the certificate needs an affine head (no polynomial, no float last "
               "block) and truth tables of at most 8 inputs");
     return TTNET_E_UNSUPPORTED;
   }
-  TT_TRY(check_ready(pl, x_nhwc_dev, n, rows_dev, "ttnet_certify_u8"));
-  if (!classes_dev) {
+  TT_TRY(check_ready(pl, x_nhwc_dev, n, rows_dev, who));
+  if (!classes_dev || (needs_second && !(x_hi_dev ? (const void *)x_hi_dev : second_out))) {   // (box: the second image; patch: the map)
     set_error("null argument");
     return TTNET_E_INVALID;
   }
-  if (!(eps >= 0.0) || !std::isfinite(eps) || enum_bits < 0 || enum_bits > 12 || std::isnan(min_margin)) {
-    set_error("certify: eps = %g (finite, >= 0), enum_bits = %d (0..12), min_margin = %g", eps, enum_bits, min_margin);
+  if (bad_args) {                                      // what only one entry takes, judged by it and reported in this order
+    set_error("%s", bad_args);
     return TTNET_E_INVALID;
   }
-  if (((uintptr_t)x_nhwc_dev & 3u) || ((uintptr_t)classes_dev & 3u) || ((uintptr_t)rows_dev & 7u) || ((uintptr_t)planes_dev & 7u)) {
+  if (!(eps >= 0.0) || !std::isfinite(eps)) {
+    set_error("certify: eps = %g (finite, >= 0)", eps);
+    return TTNET_E_INVALID;
+  }
+  if (enum_bits < 0 || enum_bits > 12 || std::isnan(min_margin)) {
+    set_error("certify: enum_bits = %d (0..12), min_margin = %g", enum_bits, min_margin);
+    return TTNET_E_INVALID;
+  }
+  if (((uintptr_t)x_nhwc_dev & 3u) || ((uintptr_t)x_hi_dev & 3u) || ((uintptr_t)classes_dev & 3u) || ((uintptr_t)rows_dev & 7u) ||
+      ((uintptr_t)second_out & 7u)) {
     set_error("certify: the images and classes must be 4-byte aligned, the records and planes 8-byte aligned");
     return TTNET_E_INVALID;
   }
@@ -1802,16 +1815,16 @@ int ttnet_certify_u8(ttnet_plan *pl, int lane, const uint8_t *x_nhwc_dev, int64_
     set_error("certify: lane %d but the plan has %d (ttnet_plan_set_lanes)", lane, (int)pl->lanes.size());
     return TTNET_E_INVALID;
   }
-  hipStream_t s = (hipStream_t)stream;
   TT_HIP(hipSetDevice(pl->device));
   TT_TRY(prepare_certify(pl, s));
   ttnet_plan::Lane &L = pl->lanes[lane];
   const size_t nb = (size_t)pl->desc.max_batch, stem_w = va::kStemRows, feat_w = va::kFeatRows;
   if (!L.cert_planes) TT_TRY(dev_alloc(pl, &L.cert_planes, nb * (2 * (stem_w + feat_w) + va::kClasses), false));
   const MultiHead &mh = pl->blocks[0];
-  CertifyArgs a{};
+  a = CertifyArgs{};
   a.n = (int)n;
   a.x = x_nhwc_dev;
+  a.x_hi = x_hi_dev;
   a.classes = classes_dev;
   for (int c = 0; c < 3; ++c) {
     a.norm.a[c] = 1.0 / (255.0 * (double)pl->in_std[c]);
@@ -1836,18 +1849,68 @@ int ttnet_certify_u8(ttnet_plan *pl, int lane, const uint8_t *x_nhwc_dev, int64_
   a.feat_hi = a.feat_lo + nb * feat_w;
   a.sums = (double *)(a.feat_hi + nb * feat_w);
   a.rows = rows_dev;
+  return TTNET_OK;
+}
+
+// the four stages on `s`, then the planes [stem lo][stem hi][feature lo][feature hi], each for n images
+static int certify_run(ttnet_plan *pl, const CertifyArgs &a, uint64_t *planes_dev, hipStream_t s) {
   pl->timing_used = 0;                                // (with profiling on, ttnet_plan_last_timings then speaks of this call)
   TT_TIMED(pl, "certify.stem", s, launch_certify(a, kCertifyStem, s));
   TT_TIMED(pl, "certify.block", s, launch_certify(a, kCertifyBlock, s));
   TT_TIMED(pl, "certify.margin", s, launch_certify(a, kCertifyMargin, s));
-  if (enum_bits > 0) TT_TIMED(pl, "certify.enum", s, launch_certify(a, kCertifyEnum, s));
-  if (planes_dev) {                                   // [stem lo][stem hi][feature lo][feature hi], each for n images
+  if (a.enum_bits > 0) TT_TIMED(pl, "certify.enum", s, launch_certify(a, kCertifyEnum, s));
+  if (planes_dev) {
     uint64_t *dst = planes_dev;
+    const size_t stem_w = va::kStemRows, feat_w = va::kFeatRows;
     for (const auto &pw : {std::pair<const uint64_t *, size_t>{a.stem_lo, stem_w}, {a.stem_hi, stem_w}, {a.feat_lo, feat_w}, {a.feat_hi, feat_w}}) {
-      TT_HIP(hipMemcpyAsync(dst, pw.first, (size_t)n * pw.second * 8, hipMemcpyDeviceToDevice, s));
-      dst += (size_t)n * pw.second;
+      TT_HIP(hipMemcpyAsync(dst, pw.first, (size_t)a.n * pw.second * 8, hipMemcpyDeviceToDevice, s));
+      dst += (size_t)a.n * pw.second;
     }
   }
+  return TTNET_OK;
+}
+
+int ttnet_certify_u8(ttnet_plan *pl, int lane, const uint8_t *x_nhwc_dev, int64_t n, const int32_t *classes_dev, double eps,
+                     int enum_bits, double min_margin, void *rows_dev, uint64_t *planes_dev, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  CertifyArgs a;
+  TT_TRY(certify_begin(pl, lane, x_nhwc_dev, nullptr, n, classes_dev, eps, enum_bits, min_margin, rows_dev, planes_dev, false, nullptr, "ttnet_certify_u8", s, a));
+  return certify_run(pl, a, planes_dev, s);
+}
+
+int ttnet_certify_box_u8(ttnet_plan *pl, int lane, const uint8_t *lo_nhwc_dev, const uint8_t *hi_nhwc_dev, int64_t n,
+                         const int32_t *classes_dev, int enum_bits, double min_margin, void *rows_dev, uint64_t *planes_dev, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  CertifyArgs a;
+  TT_TRY(certify_begin(pl, lane, lo_nhwc_dev, hi_nhwc_dev, n, classes_dev, 0.0, enum_bits, min_margin, rows_dev, planes_dev, true, nullptr, "ttnet_certify_box_u8", s, a));
+  return certify_run(pl, a, planes_dev, s);
+}
+
+int ttnet_certify_patch_u8(ttnet_plan *pl, int lane, const uint8_t *x_nhwc_dev, int64_t n, const int32_t *classes_dev, int patch_h,
+                           int patch_w, int stride, int amp, int enum_bits, double min_margin, void *rows_dev, void *map_dev, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  PatchArgs p{};
+  char bad[160] = "";                                 // (the variant and the plan's state are judged first, as everywhere)
+  if (patch_h < 1 || patch_h > va::kPatchMax || patch_w < 1 || patch_w > va::kPatchMax || stride < 1 || stride > 32 || amp < 1 || amp > 255)
+    snprintf(bad, sizeof bad, "certify_patch: patch %d x %d (1..8 each), stride %d (1..32), amp %d (1..255)", patch_h, patch_w, stride, amp);
+  TT_TRY(certify_begin(pl, lane, x_nhwc_dev, nullptr, n, classes_dev, 0.0, enum_bits, min_margin, rows_dev, map_dev, true, bad[0] ? bad : nullptr,
+                       "ttnet_certify_patch_u8", s, p.clean));
+  ttnet_plan::Lane &L = pl->lanes[lane];
+  // per image of max_batch: the clean pass's record (4 doubles) and the unknown part of its sums (10)
+  if (!L.patch_base) TT_TRY(dev_alloc(pl, &L.patch_base, (size_t)pl->desc.max_batch * (4 + va::kClasses), false));
+  p.clean.rows = L.patch_base;
+  p.clean.sums_un = L.patch_base + (size_t)pl->desc.max_batch * 4;
+  p.patch_h = patch_h;
+  p.patch_w = patch_w;
+  p.stride = stride;
+  p.amp = amp;
+  p.py = part::patch_positions(patch_h, stride);
+  p.px = part::patch_positions(patch_w, stride);
+  p.map = map_dev;
+  p.rows = rows_dev;
+  pl->timing_used = 0;
+  TT_TIMED(pl, "patch.base", s, launch_certify_patch(p, kPatchBase, s));
+  TT_TIMED(pl, "patch.sweep", s, launch_certify_patch(p, kPatchSweep, s));
   return TTNET_OK;
 }
 

@@ -381,6 +381,7 @@ struct CertifyNorm {
 struct CertifyArgs {
   int n;
   const uint8_t *x;         // uint8 HWC [n][32][32][3], 4-byte aligned
+  const uint8_t *x_hi;      // nullptr: byte b moves in [max(0, b - eps), min(255, b + eps)]; else the box [x, max(x, x_hi)] per byte (eps unused)
   const int32_t *classes;   // [n]
   CertifyNorm norm;
   double eps, min_margin;
@@ -393,6 +394,7 @@ struct CertifyArgs {
   const uint64_t *t3w;      // the same as [8 groups][8 outputs][4] words of 64 entries
   const double *A, *c0;     // effective head, stored [30976 features][10 classes], and [10]
   double *sums;             // [n][10]: sum_f D_f ylo_f of stage 1, from which stage 2 starts
+  double *sums_un;          // nullptr, or [n][10]: sum_{f unknown} min(0, D_f) of stage 1 (the patch sweep starts from both)
   uint64_t *stem_lo, *stem_hi;   // [n][64][10]
   uint64_t *feat_lo, *feat_hi;   // [n][256][11]
   void *rows;               // n records of 32 bytes
@@ -404,6 +406,17 @@ int launch_certify_head(const float *lin1, const float *lin2, const float *bias,
 // enumeration (updates them)
 constexpr int kCertifyStem = 0, kCertifyBlock = 1, kCertifyMargin = 2, kCertifyEnum = 3;
 int launch_certify(const CertifyArgs &a, int step, hipStream_t s);
+// all positions of a patch (include/ttnet.h: ttnet_certify_patch_u8).  `clean` describes the per-image pass on the degenerate
+// box (x_hi = nullptr, eps = 0, sums_un set, rows = n scratch records of 32 bytes); the sweep reads what it left.
+struct PatchArgs {
+  CertifyArgs clean;
+  int patch_h, patch_w, stride, amp;
+  int py, px;               // positions down and across
+  void *map;                // [n][py * px] records of 16 bytes
+  void *rows;               // n records of 32 bytes
+};
+constexpr int kPatchBase = 0, kPatchSweep = 1;
+int launch_certify_patch(const PatchArgs &a, int step, hipStream_t s);
 // falsified robustness of the vAlexnet variant (attack.hip; include/ttnet.h: ttnet_attack_propose_u8, ttnet_attack_select_u8)
 struct AttackProposeArgs {
   int n, levels;

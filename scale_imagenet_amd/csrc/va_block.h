@@ -78,4 +78,16 @@ __host__ __device__ inline StemBit window_input(int kind, int ch, int oy, int ox
   return {y >= 0 && y < kPool && x >= 0 && x < kPool, kind == 2 ? (ch & ~7) + p : ch, y, x};
 }
 
+// The pooled cells whose 5 x 5 pixel field (pixel rows 3 py - 1 .. 3 py + 3; likewise columns) meets the pixel rows
+// [y0, y0 + h): cells first .. first + count - 1.  At most 4 for h <= 8; none for a patch in row 31 alone, which lies in no field.
+struct FieldSpan {
+  int first, count;
+  __host__ __device__ int last() const { return first + count - 1; }
+};
+__host__ __device__ inline FieldSpan field_span(int y0, int h) {
+  const int first = y0 < 3 ? 0 : (y0 - 1) / 3, last = (y0 + h) / 3 < kPool - 1 ? (y0 + h) / 3 : kPool - 1;
+  return {first, last >= first ? last - first + 1 : 0};
+}
+constexpr int kPatchMax = 8, kFieldCells = 4, kFieldPixels = 3 * kFieldCells + 2;   // patch side at most; cells, pixel rows a span holds at most
+
 }  // namespace ttnet::va

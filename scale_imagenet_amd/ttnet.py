@@ -355,6 +355,21 @@ class _TTNetBase(nn.Module):
         from . import certify
         return certify.certify_u8(self, x_u8, classes, eps, enum_bits, min_margin, lane, return_planes)
 
+    def certify_box_u8(self, lo_u8: torch.Tensor, hi_u8: torch.Tensor, classes, enum_bits: int = 10, min_margin: float = 1e-6,
+                       lane: int = 0, return_planes: bool = False):
+        """The certificate for a box given per byte (vAlexnet only): byte k of image i may take any real value in
+        ``[lo_u8, hi_u8]``.  See ``scale_imagenet_amd.certify.certify_box_u8``."""
+        from . import certify
+        return certify.certify_box_u8(self, lo_u8, hi_u8, classes, enum_bits, min_margin, lane, return_planes)
+
+    def certify_patch_u8(self, x_u8: torch.Tensor, classes, patch=(1, 1), stride: int = 1, amp: int = 255, enum_bits: int = 10,
+                         min_margin: float = 1e-6, lane: int = 0):
+        """Certified patch robustness (vAlexnet only): does image i keep ``classes[i]`` when a patch of ``patch = (h, w)`` pixels
+        anywhere in it moves by up to ``amp`` byte levels (255: any value)?  One record per position and one per image.  See
+        ``scale_imagenet_amd.certify.certify_patch_u8``."""
+        from . import certify
+        return certify.certify_patch_u8(self, x_u8, classes, patch, stride, amp, enum_bits, min_margin, lane)
+
     def attack_u8(self, x_u8: torch.Tensor, classes, eps: float, rounds: int = 3, min_margin: float = 0.0, lane: int = 0,
                   planes=None):
         """Falsified L-infinity robustness (vAlexnet only): a search for a uint8 image within ``floor(eps)`` byte levels of

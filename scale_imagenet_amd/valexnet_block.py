@@ -96,6 +96,21 @@ def window_input(kind: int, ch: int, oy: int, ox: int, p: int):
     return (ch // 8 * 8 + p if kind == 2 else ch, y, x) if 0 <= y < POOL and 0 <= x < POOL else None
 
 
+PATCH_MAX = 8                                            # a patch side at most
+
+
+def field_span(y0: int, h: int) -> Tuple[int, int]:
+    """``(first, count)``: the pooled cells whose 5 x 5 pixel field (pixel rows ``3 py - 1 .. 3 py + 3``; likewise columns)
+    meets the pixel rows ``[y0, y0 + h)``.  At most 4 for h <= 8; none for row 31 alone, which lies in no field."""
+    first, last = (0 if y0 < 3 else (y0 - 1) // 3), min((y0 + h) // 3, POOL - 1)
+    return first, max(0, last - first + 1)
+
+
+def patch_positions(patch: int, stride: int) -> int:
+    """Positions of a patch along one side of the 32-pixel image."""
+    return (32 - patch) // stride + 1
+
+
 @lru_cache(maxsize=None)
 def reached():
     """``reach`` for every stem bit: five int64 arrays ``[21, 64, 10, 10]`` (valid, fc, oy, ox, p), read-only."""
