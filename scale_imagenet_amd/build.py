@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libttnet.so")
-SOURCES = ["plan.hip", "partition.hip", "comm.hip", "lut_build.hip", "stem.hip", "gate.hip", "gate_fused.hip", "gate_xs.hip", "gate_full.hip", "gate_va.hip", "head.hip", "preproc.hip", "jpeg.hip", "metrics.hip", "usage.hip", "minimise.hip", "rules.hip", "certify.hip", "attack.hip"]
+SOURCES = ["plan.hip", "plan_tables.hip", "plan_certify.hip", "partition.hip", "comm.hip", "lut_build.hip", "stem.hip", "gate.hip", "gate_fused.hip", "gate_xs.hip", "gate_full.hip", "gate_va.hip", "head.hip", "preproc.hip", "jpeg.hip", "metrics.hip", "usage.hip", "minimise.hip", "rules.hip", "certify.hip", "attack.hip"]
 # gate_full.hip: the same flag keeps the float32 GELU of the fast kernels out of v_pk_* with shuffling moves.
 # stem.hip: without -fno-slp-vectorize the producers' pooling adds become v_pk_add_f32 behind shuffling moves, which
 # beside the consumers' MFMAs cost 82 us per launch instead of 65 (tools/ubench/stem_parts.hip)
@@ -35,8 +35,11 @@ def build_lib(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, "ttnet_common.h"), os.path.join(HERE, "..", "include", "ttnet.h")]
     included = {"gate_full.hip": [os.path.join(CSRC, "erf_table.inc")], "certify.hip": [os.path.join(CSRC, "certify_stem_cell.inc")]}
-    included.update({src: [os.path.join(CSRC, "va_block.h")] for src in ("gate_va.hip", "certify.hip", "attack.hip", "plan.hip")})
-    for src in ("partition.hip", "plan.hip", "certify.hip", "stem.hip", "gate.hip", "gate_fused.hip", "gate_xs.hip", "gate_full.hip", "gate_va.hip"):
+    for src in ("gate_va.hip", "certify.hip", "attack.hip"):
+        included[src] = included.get(src, []) + [os.path.join(CSRC, "va_block.h")]
+    for src in ("plan.hip", "plan_tables.hip", "plan_certify.hip"):
+        included[src] = [os.path.join(CSRC, "plan.h")]      # (plan.h includes partition.h)
+    for src in ("partition.hip", "plan.hip", "plan_tables.hip", "plan_certify.hip", "certify.hip", "stem.hip", "gate.hip", "gate_fused.hip", "gate_xs.hip", "gate_full.hip", "gate_va.hip"):
         included[src] = included.get(src, []) + [os.path.join(CSRC, "partition.h"), os.path.join(CSRC, "va_block.h")]      # (partition.h includes va_block.h)
     jobs = []
     for src in SOURCES:

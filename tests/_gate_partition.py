@@ -2,7 +2,7 @@
 
 Which image a workgroup handles, in how many rounds and with which table buffer is decided by a few integer formulas
 in scale_imagenet_amd/csrc/partition.h, which the launchers and kernels of gate_fused.hip, gate.hip, gate_xs.hip,
-gate_va.hip, gate_full.hip and plan.hip call.  This file reads them from the library itself, through the stateless
+gate_va.hip, gate_full.hip and the plan's host code (plan.hip, plan_certify.hip) call.  This file reads them from the library itself, through the stateless
 ``ttnet_launch_partition`` (it answers without a GPU), so that the batch sizes of tests/test_gpu_gate_batches.py are
 DERIVED from the launch arithmetic (first two-round batch, a last round of one image, unequal slices, ...) and
 tests/test_gate_batch_sizes_cpu.py can assert, without a GPU, that the chosen sizes reach every one of those cases.
