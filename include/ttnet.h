@@ -705,6 +705,63 @@ int ttnet_certify_patch_u8(ttnet_plan *plan, int lane, const uint8_t *x_nhwc_dev
                            int patch_w, int stride, int amp, int enum_bits, double min_margin, void *rows_dev, void *map_dev,
                            void *stream);
 
+/* Falsified PATCH robustness of TTNET_VALEXNET: for every position of ttnet_certify_patch_u8 (the same positions, stride and amp) a
+ * search for a concrete uint8 fill of the patch, each byte inside [max(0, b - amp), min(255, b + amp)] of its clean byte b, on
+ * which the image loses its class (csrc/attack.hip; DESIGN.md: falsified patch robustness).  The entry PREDICTS; a witness is a
+ * witness only once ttnet_forward_u8 has judged it (ttnet_patch_paste_u8 builds the image, ttnet_attack_select_u8 with round = 0
+ * and n_cand = 1 takes the margin), as for the L-infinity search.
+ *   per image, once ("patch.base"): the clean pass of ttnet_certify_patch_u8;
+ *   per (image, position), one workgroup of 256 threads ("patch.attack"), cut into launches as the sweep is (csrc/partition.h).
+ * Predicted margin m_pred of a fill: with the fill pasted into the image, the lb_interval that ttnet_certify_box_u8 gives for the
+ * degenerate box lo = hi = that image -- the same real number, computed as the sweep computes its bound: the pooled cells whose
+ * field meets the patch again at radius 0 by stage 0's code, the features they reach, the differences dS_j, dU_j against the
+ * clean feature planes in the sweep's summation order, lb_j = c0_c - c0_j + ((S_j + dS_j) + (U_j + dU_j)), worst = the first j
+ * that attains the minimum.  A recomputed cell within the stem slack of zero is unknown and m_pred is then a lower bound of the
+ * exact-arithmetic margin; otherwise it IS that margin.
+ * Movable bits: the stem bits that the box of the position leaves unknown (what the sweep's stage 0 computes), fixed over the
+ * rounds.  State: the current fill (initially the clean bytes), its stem planes, its m_cur and runner-up j_cur.  One round
+ * (rounds in 1..4):
+ *   gains, pushes  g_s for every movable bit on the current planes (a bit within the slack counts as 0) with D_f = A[f][c] -
+ *                  A[f][j_cur], and wt_s for modes 0 and 1: the terms, their order and the flipped lookup of
+ *                  ttnet_attack_propose_u8, the unflipped value read from the table too.
+ *   scores         through Wsum in ttnet_attack_propose_u8's order (ch, then py, then px), for the bytes of the patch only; every
+ *                  other byte scores 0 and never moves; M = max |score| over the patch, per mode.
+ *   candidates     eight, index 4 mode + tau index.  tau in {0, 1/8, 1/4}: a byte with score != 0 and |score| > tau M takes the upper
+ *                  (score > 0) or lower end of its box, every other byte keeps the current fill's value.  The two slots of tau =
+ *                  1/2 (3 and 7) hold another proposal: the sign corner of mode 1 (upper end where the score is positive, lower end
+ *                  where negative, the current byte where zero) with the bytes i for which H(position, round, 11 + slot, i) is set
+ *                  at the opposite end; H = bit 16 of v after v = position * 0x9E3779B1 + (8 round + 11 + slot) * 0x85EBCA6B + i *
+ *                  0xC2B2AE35, v ^= v >> 15, v *= 0x2C1B3C6D, v ^= v >> 12, v *= 0x297A2D39, v ^= v >> 15 in 32 bits; i = the byte's
+ *                  index in the fill record.  In round 1 of a 1 x 1 patch the eight candidates are its eight corners instead:
+ *                  candidate k gives channel ch the upper end if bit ch of k is set, else the lower end.
+ *   selection      every candidate gets its m_pred (a candidate byte-equal to an earlier one of the round is not evaluated: it
+ *                  cannot win); the smallest wins, ties go to the lowest index; it replaces the state only if strictly below m_cur.
+ * The search stops after a round that leaves m_cur < -min_margin.  No search -- round 0, fill = the clean bytes, m_pred = the
+ * clean value -- where the class is outside 0..9 (m_pred -inf, worst -1, unknown 0; not an error), where the clean m_pred is
+ * already below -min_margin, and where the position has no movable bit (a position that touches only row or column 31 included).
+ *
+ * map_dev receives [n][P] records of 16 bytes (8-byte aligned): { double m_pred; int32 worst; uint16 round; uint16 unknown; },
+ * round = the round that produced the kept fill, unknown = the cells of the kept fill's recomputed span that are within the slack
+ * (round 0: of the clean planes); unknown == 0 means m_pred is exact.  fills_dev receives uint8 [n][P][192] (4-byte aligned): the
+ * first 3 patch_h patch_w bytes hold the patch row-major (y, x, channel), the rest are zero.
+ *
+ * Float64 in a fixed order, no float atomics, nothing read back: the same bytes on every run, lane and batch composition.  A and
+ * Wsum are built by the first call after a (re)load, as ttnet_attack_propose_u8 does; the lane's buffers are the sweep's,
+ * allocated by the first call on a lane.  Errors: those of ttnet_certify_patch_u8 (without enum_bits and rows_dev), and rounds
+ * outside 1..4 or fills_dev NULL or misaligned TTNET_E_INVALID; any other variant TTNET_E_UNSUPPORTED.  Nothing is launched in an
+ * error case. */
+int ttnet_attack_patch_u8(ttnet_plan *plan, int lane, const uint8_t *x_nhwc_dev, int64_t n, const int32_t *classes_dev,
+                          int patch_h, int patch_w, int stride, int amp, int rounds, double min_margin,
+                          void *map_dev, uint8_t *fills_dev, void *stream);
+
+/* Witnesses as images: out_nhwc_dev[k] (uint8 [m][32][32][3]) = image tasks_dev[k] / P of x_nhwc_dev ([n][32][32][3]) with the fill of
+ * task tasks_dev[k] = image * P + position (fills_dev: [n][P][192] as ttnet_attack_patch_u8 writes it) pasted at its position; a task
+ * outside [0, n P) leaves out[k] all zero.  One launch on `stream` ("patch.paste").  Errors: patch_h, patch_w or stride outside
+ * their ranges, m < 1, n outside [1, max_batch], a NULL or misaligned pointer (4 bytes for images and fills, 8 for tasks)
+ * TTNET_E_INVALID; any other variant TTNET_E_UNSUPPORTED; before finalize TTNET_E_STATE. */
+int ttnet_patch_paste_u8(ttnet_plan *plan, const uint8_t *x_nhwc_dev, int64_t n, int patch_h, int patch_w, int stride,
+                         const uint8_t *fills_dev, const int64_t *tasks_dev, int64_t m, uint8_t *out_nhwc_dev, void *stream);
+
 /* Falsified L-infinity robustness of TTNET_VALEXNET on the device: a search for uint8 witnesses (csrc/attack.hip; DESIGN.md:
  * falsified robustness).  ttnet_certify_u8 bounds the robust accuracy from below; an image is FALSIFIED when a concrete uint8
  * image inside the integer box [max(0, b - e), min(255, b + e)] (e = eps_levels byte levels; the box lies inside the real box
@@ -805,7 +862,7 @@ int ttnet_plan_query(ttnet_plan *plan, const char *what, int64_t *out);
  *   "stem.workgroups" (lanes, u8, full variant) -> workgroups asked for       "stem.grid" (n, G) -> workgroups launched
  *   "stem.run" (bid, n, G) -> first item, items                               "stem.continues" (first item, j) -> 0 / 1
  *   "patch.sweep" (n, patch_h, patch_w, stride) -> positions down, across, launches of ttnet_certify_patch_u8's sweep, workgroups
- *       of the first launch, of the last, at most
+ *       of the first launch, of the last, at most      "patch.attack" (the same) -> the same for ttnet_attack_patch_u8's search
  * Returns the number of values written.  An unknown key, a wrong n_args, out_cap below the key's value count, n < 1, C not a
  * multiple of 8 (16 for "two_launch.stage1") or any argument outside its range: TTNET_E_INVALID with the reason in
  * ttnet_last_error(), and nothing is written. */

@@ -103,6 +103,8 @@ SYMBOLS: List[Tuple[str, object, list]] = [
     ("ttnet_certify_u8", C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_double, C.c_int, C.c_double, _P, _P, _P]),
     ("ttnet_certify_box_u8", C.c_int, [_P, C.c_int, _P, _P, C.c_int64, _P, C.c_int, C.c_double, _P, _P, _P]),
     ("ttnet_certify_patch_u8", C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, _P]),
+    ("ttnet_attack_patch_u8", C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, _P]),
+    ("ttnet_patch_paste_u8", C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int64, _P, _P]),
     ("ttnet_attack_propose_u8", C.c_int, [_P, C.c_int, _P, _P, C.c_int64, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
     ("ttnet_attack_select_u8", C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, C.c_double, _P, _P, _P, _P, _P, C.c_int, _P]),
     ("ttnet_plan_query", C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),

@@ -24,7 +24,7 @@ import numpy as np
 
 from . import certify as CF
 from .cifar import CIFAR_MEAN, CIFAR_STD
-from .valexnet_block import FEAT_CH, N_REACH, POOL, SIDE, STEM_CH, f64, fold_bn, reached, table_words, window_indices  # noqa: F401
+from .valexnet_block import FEAT_CH, N_REACH, POOL, SIDE, STEM_CH, f64, fold_bn, reach, reached, table_words, window_indices  # noqa: F401
 from .valexnet_block import block_words as _words
 
 RECORD = np.dtype([("margin0", "<f4"), ("best", "<f4"), ("worst", "<i4"), ("status", "<i4"), ("round", "<i4"),
@@ -453,3 +453,609 @@ def attack_cpu(state, tables, x_u8, classes, eps: float, rounds: int = 3, min_ma
         _, _, logits = forward(cand.reshape(-1, 32, 32, 3))
         select_cpu(cand, logits, N_CAND, classes, min_margin, x0, xcur, rows, worst, active, r)
     return rows, xcur
+
+
+# ---- patches: the falsifying side of certify.certify_patch_u8 (include/ttnet.h: ttnet_attack_patch_u8) ------------------------------
+
+PATCH_RECORD = np.dtype([("m_pred", "<f8"), ("worst", "<i4"), ("round", "<u2"), ("unknown", "<u2")])   # 16 bytes: the entry's map
+PATCH_MAP = np.dtype([("m_pred", "<f8"), ("worst", "<i4"), ("round", "<u2"), ("unknown", "<u2"), ("status", "<i4"), ("margin", "<f4")])
+PATCH_ROW = np.dtype([("positions", "<i4"), ("falsified", "<i4"), ("predicted", "<i4"), ("pos_first", "<i4"), ("status", "<i4")])
+FILL_BYTES = 3 * CF.PATCH_MAX * CF.PATCH_MAX             # a fill record: the patch row-major (y, x, channel), zeros behind it
+PATCH_ROUNDS_MAX = 4
+PREDICTED = 3                                            # a position's status: the search predicts a witness that no forward judged
+CONFIRM = ("all", "best", "none")
+
+
+def check_patch_attack(patch, stride, amp, rounds, min_margin, confirm="all"):
+    """``(h, w, stride, amp, Py, Px, rounds)`` of a patch search, or ValueError."""
+    h, w, stride, amp, py, px = CF.check_patch(patch, stride, amp)
+    if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)) or not 1 <= rounds <= PATCH_ROUNDS_MAX:
+        raise ValueError(f"rounds must be an integer in [1, {PATCH_ROUNDS_MAX}], got {rounds!r}")
+    if math.isnan(min_margin):
+        raise ValueError("min_margin is NaN")
+    if confirm not in CONFIRM:
+        raise ValueError(f"confirm must be one of {CONFIRM}, got {confirm!r}")
+    return h, w, stride, amp, py, px, int(rounds)
+
+
+def paste_cpu(x_u8: np.ndarray, patch, stride: int, fills: np.ndarray, tasks) -> np.ndarray:
+    """What ``ttnet_patch_paste_u8`` writes: image ``tasks[k] // P`` of ``x_u8`` with fill ``tasks[k]`` of ``fills``
+    (``[n, P, 192]``) pasted at position ``tasks[k] % P``; all zero for a task outside ``[0, n P)``."""
+    h, w, stride, _, py, px = CF.check_patch(patch, stride, 1)
+    x_u8, tasks = np.asarray(x_u8), np.asarray(tasks).astype(np.int64).reshape(-1)
+    P, n = py * px, x_u8.shape[0]
+    flat = np.asarray(fills).reshape(n * P, FILL_BYTES)
+    out = np.zeros((tasks.size, 32, 32, 3), np.uint8)
+    for k, t in enumerate(tasks):
+        if 0 <= t < n * P:
+            y0, x0 = (t % P) // px * stride, (t % P) % px * stride
+            out[k] = x_u8[t // P]
+            out[k, y0:y0 + h, x0:x0 + w] = flat[t, :3 * h * w].reshape(h, w, 3)
+    return out
+
+
+class PatchAttackResult:
+    """What ``attack_patch_u8`` (or the twin) found.  ``map``: structured ``[n, Py, Px]`` of dtype ``PATCH_MAP`` -- ``m_pred``,
+    ``worst``, ``round``, ``unknown`` as the entry wrote them, ``status`` (0 open, 2 falsified: a forward judged the witness,
+    3 predicted but not forwarded) and ``margin`` (the confirmed float32 margin, NaN where no forward ran); ``rows``: ``PATCH_ROW``
+    per image -- ``positions``, ``falsified``, ``predicted`` (positions of status 2 or 3), ``pos_first`` (the first falsified
+    position, -1: none) and ``status`` (0 open, 1 wrong at x0, 2 falsified at some position); ``fills`` uint8 ``[n, P, 192]``
+    (numpy, or the device tensor); ``near`` (the twin only): bool ``[n, P]``, positions where the best and the second-best distinct prediction
+    of some round lay within the summation tolerance ``1e-9 sum|A|`` of each other."""
+
+    def __init__(self, x0, patch, stride, amp, map_, rows, fills, near=None):
+        self.x0, self.patch, self.stride, self.amp = x0, tuple(patch), int(stride), int(amp)
+        self.map, self.rows, self.fills, self.near = map_, rows, fills, near
+
+    def __len__(self):
+        return self.rows.shape[0]
+
+    def fills_numpy(self) -> np.ndarray:
+        return self.fills if isinstance(self.fills, np.ndarray) else self.fills.cpu().numpy()
+
+    def witness(self, i: int, p: int) -> np.ndarray:
+        """Image i with the kept fill of position p pasted: uint8 numpy ``[32, 32, 3]``."""
+        P = self.map.shape[1] * self.map.shape[2]
+        if not (0 <= i < len(self) and 0 <= p < P):
+            raise IndexError(f"image {i}, position {p} of {len(self)} x {P}")
+        x = self.x0[i:i + 1]
+        x = x if isinstance(x, np.ndarray) else x.cpu().numpy()
+        f = self.fills[i:i + 1]
+        f = f if isinstance(f, np.ndarray) else f.cpu().numpy()
+        return paste_cpu(x, self.patch, self.stride, f, [p])[0]
+
+
+def patch_rows_from_map(maps: np.ndarray, wrong: np.ndarray) -> np.ndarray:
+    """The image records (``PATCH_ROW``) of position records ``[n, Py, Px]``; ``wrong``: bool ``[n]``, wrong at x0."""
+    n = maps.shape[0]
+    flat = maps.reshape(n, -1)
+    rows = np.zeros(n, dtype=PATCH_ROW)
+    rows["positions"] = flat.shape[1]
+    fals = flat["status"] == FALSIFIED
+    rows["falsified"] = fals.sum(axis=1)
+    rows["predicted"] = (fals | (flat["status"] == PREDICTED)).sum(axis=1)
+    rows["pos_first"] = np.where(fals.any(axis=1), fals.argmax(axis=1), -1)
+    rows["status"] = np.where(np.asarray(wrong).astype(bool), WRONG, np.where(fals.any(axis=1), FALSIFIED, OPEN))
+    return rows
+
+
+def confirm_tasks(rec: np.ndarray, confirm: str, confirm_slack: float) -> np.ndarray:
+    """The tasks (``image * P + position``) whose witness goes through the forward, from the entry's records ``[n, P]``: the kept
+    fill differs from the clean bytes (``round > 0``: a kept candidate lowered the prediction, so it is no copy) and ``m_pred <
+    confirm_slack``; ``"best"``: of those only each image's position of smallest ``m_pred`` (the first one)."""
+    n, P = rec.shape
+    want = (rec["round"] > 0) & (rec["m_pred"] < confirm_slack)
+    if confirm == "none":
+        want[:] = False
+    elif confirm == "best":
+        best = rec["m_pred"].argmin(axis=1)
+        only = np.zeros_like(want)
+        only[np.arange(n), best] = True
+        want &= only
+    return np.flatnonzero(want.reshape(-1))
+
+
+HASH_SLOTS, HASH_STREAM = (3, 7), 11                     # the candidates of tau = 1/2 give their slots away; slot k hashes stream 11 + k
+
+
+def hash_corner(pos, rnd: int, slot: int, byte) -> np.ndarray:
+    """bool per byte ``byte`` of the patch at position ``pos``, round ``rnd`` and stream ``slot``: bit 16 of a 32-bit integer
+    mix, the same on the device (csrc/attack.hip: hash_corner)."""
+    m = np.uint64(0xFFFFFFFF)
+    v = (np.asarray(pos).astype(np.uint64) * np.uint64(0x9E3779B1) + np.uint64((rnd * 8 + slot) * 0x85EBCA6B)
+         + np.asarray(byte).astype(np.uint64) * np.uint64(0xC2B2AE35)) & m
+    v ^= v >> np.uint64(15)
+    v = (v * np.uint64(0x2C1B3C6D)) & m
+    v ^= v >> np.uint64(12)
+    v = (v * np.uint64(0x297A2D39)) & m
+    v ^= v >> np.uint64(15)
+    return ((v >> np.uint64(16)) & np.uint64(1)).astype(bool)
+
+
+def _cells_of(v: np.ndarray):
+    """The two cells whose 5-wide field may hold row / column v (ascending), v's offset in each, and whether it does."""
+    hi = (v + 1) // 3
+    cells = np.stack([hi - 1, hi], axis=-1)
+    offs = v[..., None] - 3 * cells + 1
+    valid = (cells >= 0) & (cells <= 9) & (offs >= 0) & (offs <= 4)
+    return np.clip(cells, 0, 9), np.clip(offs, 0, 4), valid
+
+
+def _reached_rect(kind: int, r0, rn, q0, qn):
+    """``reached_rect`` of csrc/certify_lookup.h on arrays: first row, rows, first column, columns of branch ``kind``."""
+    r1, q1 = r0 + rn - 1, q0 + qn - 1
+    if kind == 0:
+        r0, r1, q1 = np.maximum(r0 - 1, 0), np.minimum(r1 + 1, POOL - 1), q1 + 1
+    elif kind == 1:
+        r1, q0, q1 = r1 + 1, np.maximum(q0 - 1, 0), np.minimum(q1 + 1, POOL - 1)
+    return r0, r1 - r0 + 1, q0, q1 - q0 + 1
+
+
+class _PatchTwin:
+    """What the patch twin derives once per call: the head in the device's bytes, the tables as words, the summed kernels."""
+
+    def __init__(self, state, tables, mean, std):
+        self.state, self.tables, self.mean, self.std = state, tables, mean, std
+        self.A = head_cpu(state)                                           # [10, F]: D_f in the device's bytes
+        self.c0 = CF.effective_head(state)[1]
+        self.words = _words(tables)
+        self.T = (self.words[0][:, 0, 0], self.words[1][:, 0, 0], self.words[2].reshape(64, 4))
+        self.Wsum = wsum_cpu(state)
+        self.scale = fold_bn(state, "features.2")[0]
+        self.slack = CF.stem_slack(state, mean, std)[None, :, None, None]
+        self.a, self.off = CF._norm(mean, std)
+        self.tol = 1e-9 * float(np.abs(self.A).sum())
+
+    # gains of the listed stem bits (pi: the plane of `pad` each lives in; pad: int64 [B, 64, 12, 12], the definite bits with the
+    # zero padding around them), in gains_cpu's order and bytes
+    def gains(self, pad, pi, ch, y, x, c, j):
+        def bit(T, i):
+            return ((T >> i.astype(np.uint64)) & np.uint64(1)).astype(np.int64)
+        g = np.zeros(pi.size)
+        for t in range(N_REACH):
+            valid, fc, oy, ox, p = reach(ch, y, x, t)
+            valid = np.broadcast_to(np.asarray(valid, dtype=bool), pi.shape)
+            oy, ox = np.where(valid, oy, 0), np.where(valid, ox, 0)
+            kind = 0 if t < 6 else 1 if t < 12 else 2 if t < 20 else 3
+            if kind < 2:
+                kw = (2, 3)[kind]
+                idx = sum(pad[pi, ch, oy + q // kw, ox + q % kw] << q for q in range(6))
+                new, old = bit(self.T[kind][ch], idx ^ (1 << p)), bit(self.T[kind][ch], idx)
+            elif kind == 2:
+                idx = sum(pad[pi, ch // 8 * 8 + q, y + 1, x + 1] << q for q in range(8))
+                i3 = idx ^ (1 << p)
+                new, old = bit(self.T[2][fc - 128, i3 >> 6], i3 & 63), bit(self.T[2][fc - 128, idx >> 6], idx & 63)
+            else:
+                old = pad[pi, ch, y + 1, x + 1]
+                new = 1 - old
+            d = np.where(valid, new - old, 0)
+            f = (fc * SIDE + oy) * SIDE + ox
+            Df = self.A[c, f] - self.A[j, f]
+            g = g + np.where(d == 1, Df, np.where(d == -1, -Df, 0.0))
+        return g
+
+    # scores of the patch bytes [2, B, h, w, 3] from dense pushes wt[m] [B, 64, 10, 10], in scores_cpu's order and bytes
+    def scores(self, wt, y0, x0, h, w):
+        B = y0.size
+        cy, oy, vy = _cells_of(y0[:, None] + np.arange(h)[None, :])        # [B, h, 2]
+        cx, ox, vx = _cells_of(x0[:, None] + np.arange(w)[None, :])
+        out = np.zeros((2, B, h, w, 3))
+        b = np.arange(B)[:, None, None]
+        live = np.flatnonzero((wt[1] != 0).reshape(B, STEM_CH, -1).any(axis=(0, 2)))
+        for ch in live:                                                    # (a channel without a push adds zeros only)
+            for a_ in range(2):
+                for b_ in range(2):
+                    v = vy[:, :, a_][:, :, None] & vx[:, :, b_][:, None, :]
+                    W = np.where(v[..., None], self.Wsum[ch][:, oy[:, :, a_][:, :, None], ox[:, :, b_][:, None, :]].transpose(1, 2, 3, 0), 0.0)
+                    for m in range(2):
+                        G = wt[m][b, ch, cy[:, :, a_][:, :, None], cx[:, :, b_][:, None, :]]
+                        out[m] += G[..., None] * W
+        return out
+
+
+def _patch_image_cpu(tw: _PatchTwin, x: np.ndarray, c: int, h, w, stride, amp, rounds, min_margin, chunk: int = 128):
+    """The search of every position of one image: ``(records [P] PATCH_RECORD, fills [P, 192], near [P])``."""
+    org = CF.patch_origins((h, w), stride)
+    P = len(org)
+    y0, x0 = org[:, 0].astype(np.int64), org[:, 1].astype(np.int64)
+    rec = np.zeros(P, dtype=PATCH_RECORD)
+    near = np.zeros(P, dtype=bool)
+    clean_fill = np.stack([x[a:a + h, b:b + w] for a, b in org])            # [P, h, w, 3]
+    fills = np.zeros((P, FILL_BYTES), np.uint8)
+    fills[:, :3 * h * w] = clean_fill.reshape(P, -1)
+    if not 0 <= c < 10:
+        rec["m_pred"], rec["worst"] = -np.inf, -1
+        return rec, fills, near
+    st, tables = tw.state, tw.tables
+    clean_lo, clean_hi = (v[0] for v in CF.stem_planes_cpu(st, x[None], 0.0, tw.mean, tw.std))
+    ylo_c, yhi_c = (v[0].reshape(-1).astype(np.int64) for v in CF.block_planes_cpu(tables, clean_lo[None], clean_hi[None]))
+    unk_c = (ylo_c != yhi_c).astype(np.int64)
+    D = tw.A[c][None, :] - tw.A
+    Dm = np.minimum(D, 0.0)
+    S, U = D @ ylo_c.astype(np.float64), Dm @ unk_c.astype(np.float64)
+    lb0 = tw.c0[c] - tw.c0 + (S + U)
+    lb0[c] = np.inf
+    m_clean, j_clean = float(lb0.min()), int(lb0.argmin())
+    rec["m_pred"], rec["worst"] = m_clean, j_clean
+    spans = np.array([(*CF.field_span(int(a), h), *CF.field_span(int(b), w)) for a, b in org]).reshape(P, 4)   # first row, rows, first column, columns
+    in_span = np.zeros((P, POOL, POOL), dtype=bool)
+    for p, (r0, rn, q0, qn) in enumerate(spans):
+        in_span[p, r0:r0 + rn, q0:q0 + qn] = rn > 0 and qn > 0
+    blo, bhi = CF._patch_stem_planes(st, x, clean_lo, clean_hi, h, w, stride, amp, tw.mean, tw.std)
+    movable = (blo != bhi) & in_span[:, None]                                # [P, 64, 10, 10]
+    del blo, bhi
+    rec["unknown"] = ((clean_lo != clean_hi)[None] & in_span[:, None]).reshape(P, -1).sum(axis=1)   # round 0: the clean cells of the span
+    active = movable.reshape(P, -1).any(axis=1) & (not m_clean < -min_margin)
+    cur_lo = np.broadcast_to(clean_lo, (P,) + clean_lo.shape).copy()
+    cur_un = np.broadcast_to((clean_lo != clean_hi).astype(np.uint8), (P,) + clean_lo.shape).copy()
+    fill = clean_fill.copy()
+    m_cur, j_cur = np.full(P, m_clean), np.full(P, j_clean)
+    b0 = clean_fill.astype(np.int64)
+    up, dn = np.minimum(255, b0 + amp).astype(np.uint8), np.maximum(0, b0 - amp).astype(np.uint8)
+    bpad = np.zeros((33, 33, 3))                                             # row / column 0: the padding
+    bpad[1:, 1:] = x.astype(np.float64)
+    for r in range(1, rounds + 1):
+        corners = h == 1 and w == 1 and r == 1
+        for a0 in range(0, P, chunk):
+            sel = a0 + np.flatnonzero(active[a0:a0 + chunk])
+            if not sel.size:
+                continue
+            B = sel.size
+            # ---- the eight candidates -----------------------------------------------------------------------------------------------
+            cand = np.empty((B, N_CAND, h, w, 3), np.uint8)
+            if corners:
+                for k in range(N_CAND):
+                    for ch in range(3):
+                        cand[:, k, 0, 0, ch] = (up if (k >> ch) & 1 else dn)[sel, 0, 0, ch]
+            else:
+                bits = (cur_lo[sel] & (1 - cur_un[sel])).astype(np.int64)
+                pad = np.pad(bits, ((0, 0), (0, 0), (1, 1), (1, 1)))
+                pi, ch, yy, xx = np.nonzero(movable[sel])
+                g = tw.gains(pad, pi, ch, yy, xx, c, j_cur[sel][pi])
+                sgn = np.where(bits[pi, ch, yy, xx] == 0, 1.0, -1.0) * np.where(tw.scale[ch] >= 0, 1.0, -1.0)
+                wt1 = -g * sgn
+                wt = np.zeros((2, B, STEM_CH, POOL, POOL))
+                wt[1][pi, ch, yy, xx] = wt1
+                wt[0][pi, ch, yy, xx] = np.where(g < 0, wt1, 0.0)
+                sc = tw.scores(wt, y0[sel], x0[sel], h, w)
+                # the six score slots are candidates_cpu's: the scores masked to the patch, every other byte scores 0 and keeps x_cur
+                full = np.zeros((B, 2, 32, 32, 3))
+                xc = np.broadcast_to(x, (B, 32, 32, 3)).copy()
+                for i, p in enumerate(sel):
+                    full[i, :, y0[p]:y0[p] + h, x0[p]:x0[p] + w] = sc[:, i]
+                    xc[i, y0[p]:y0[p] + h, x0[p]:x0[p] + w] = fill[p]
+                whole = candidates_cpu(full, np.broadcast_to(x, xc.shape), xc, amp)
+                for i, p in enumerate(sel):
+                    cand[i] = whole[i, :, y0[p]:y0[p] + h, x0[p]:x0[p] + w]
+                # Two slots (the tau = 1/2 ones) go to another proposal: the sign corner of mode 1 -- upper end where the score is
+                # positive, lower end where it is negative, the current byte where it is zero -- with a hashed half of its bytes at
+                # the opposite end.  It looks around the first-order optimum where no single flip is rewarded.
+                s = sc[1]
+                base = np.where(s > 0, up[sel], np.where(s < 0, dn[sel], fill[sel]))
+                other = np.where(s > 0, dn[sel], np.where(s < 0, up[sel], fill[sel]))
+                for k in HASH_SLOTS:
+                    inv = hash_corner(sel[:, None], r, HASH_STREAM + k, np.arange(3 * h * w)[None, :]).reshape(B, h, w, 3)
+                    cand[:, k] = np.where(inv, other, base)
+            # ---- their predictions --------------------------------------------------------------------------------------------------
+            sp = spans[sel]
+            nr, nc = int(sp[:, 1].max()), int(sp[:, 3].max())
+            fr, fq = np.minimum(sp[:, 0], POOL - nr), np.minimum(sp[:, 2], POOL - nc)
+            rr = 3 * fr[:, None] + np.arange(3 * nr + 2)[None, :]           # padded rows of the window
+            qq = 3 * fq[:, None] + np.arange(3 * nc + 2)[None, :]
+            win = bpad[rr[:, :, None], qq[:, None, :]]                       # [B, wr, wq, 3]
+            iy, ix = rr - 1 - y0[sel][:, None], qq - 1 - x0[sel][:, None]
+            inside = ((iy >= 0) & (iy < h))[:, :, None] & ((ix >= 0) & (ix < w))[:, None, :]
+            cw = cand[np.arange(B)[:, None, None, None], np.arange(N_CAND)[None, :, None, None],
+                      np.clip(iy, 0, h - 1)[:, None, :, None], np.clip(ix, 0, w - 1)[:, None, None, :]]     # [B, 8, wr, wq, 3]
+            v = np.where(inside[:, None, :, :, None], cw.astype(np.float64), win[:, None])
+            padding = ((rr == 0)[:, :, None] | (qq == 0)[:, None, :])[:, None, :, :, None]
+            xn = np.where(padding, 0.0, (v - tw.off) * tw.a).reshape((B * N_CAND,) + v.shape[2:]).transpose(0, 3, 1, 2)
+            lo, hi = CF._stem_bounds_norm(st, xn, xn, 0)                     # [B * 8, 64, nr, nc]
+            wlo = (lo - tw.slack >= 0).astype(np.uint8).reshape(B, N_CAND, STEM_CH, nr, nc)
+            whi = (hi + tw.slack >= 0).astype(np.uint8).reshape(B, N_CAND, STEM_CH, nr, nc) | wlo
+            c_lo = np.repeat(cur_lo[sel][:, None], N_CAND, axis=1)           # [B, 8, 64, 10, 10]
+            c_un = np.repeat(cur_un[sel][:, None], N_CAND, axis=1)
+            unknown = np.zeros((B, N_CAND), np.int64)
+            for i, (r0, rn, q0, qn) in enumerate(sp):
+                a_, b_ = r0 - fr[i], q0 - fq[i]
+                l_, h_ = wlo[i, :, :, a_:a_ + rn, b_:b_ + qn], whi[i, :, :, a_:a_ + rn, b_:b_ + qn]
+                c_lo[i, :, :, r0:r0 + rn, q0:q0 + qn] = l_
+                c_un[i, :, :, r0:r0 + rn, q0:q0 + qn] = l_ != h_
+                unknown[i] = (l_ != h_).reshape(N_CAND, -1).sum(axis=1)
+            Lp = np.pad(c_lo, ((0, 0), (0, 0), (0, 0), (1, 1), (1, 1)))
+            Up = np.pad(c_un, ((0, 0), (0, 0), (0, 0), (1, 1), (1, 1)))
+            bi = np.arange(B)[:, None, None, None, None]
+            ki = np.arange(N_CAND)[None, :, None, None, None]
+            chi = np.arange(STEM_CH)[None, None, :, None, None]
+            dS, dU = np.zeros((B * N_CAND, 10)), np.zeros((B * N_CAND, 10))
+            for kind in range(4):
+                R0, NR, Q0, NQ = _reached_rect(kind, sp[:, 0], sp[:, 1], sp[:, 2], sp[:, 3])
+                mr, mq = int(NR.max()), int(NQ.max())
+                oy = np.minimum(R0[:, None] + np.arange(mr)[None, :], 10 if kind == 1 else 9)
+                ox = np.minimum(Q0[:, None] + np.arange(mq)[None, :], 10 if kind == 0 else 9)
+                ok = ((np.arange(mr)[None, :] < NR[:, None])[:, :, None] & (np.arange(mq)[None, :] < NQ[:, None])[:, None, :])[:, None, None]
+                oy5, ox5 = oy[:, None, None, :, None], ox[:, None, None, None, :]
+                if kind < 2:
+                    kw = (2, 3)[kind]
+                    l_ = np.stack([Lp[bi, ki, chi, oy5 + q // kw, ox5 + q % kw] for q in range(6)], axis=-1)
+                    u_ = np.stack([Up[bi, ki, chi, oy5 + q // kw, ox5 + q % kw] for q in range(6)], axis=-1)
+                    ylo, yhi = CF.lookup3(tw.T[kind].reshape(1, 1, STEM_CH, 1, 1, 1), l_ & (1 - u_), l_ | u_)
+                elif kind == 2:
+                    grp = (np.arange(STEM_CH) // 8 * 8)[None, None, :, None, None]
+                    l_ = np.stack([Lp[bi, ki, grp + q, oy5 + 1, ox5 + 1] for q in range(8)], axis=-1)
+                    u_ = np.stack([Up[bi, ki, grp + q, oy5 + 1, ox5 + 1] for q in range(8)], axis=-1)
+                    ylo, yhi = CF.lookup3(tw.T[2].reshape(1, 1, STEM_CH, 1, 1, 4), l_ & (1 - u_), l_ | u_)
+                else:
+                    l_, u_ = Lp[bi, ki, chi, oy5 + 1, ox5 + 1], Up[bi, ki, chi, oy5 + 1, ox5 + 1]
+                    ylo, yhi = l_ & (1 - u_), l_ | u_
+                f = np.broadcast_to(((kind * 64 + chi) * SIDE + oy5) * SIDE + ox5, ylo.shape)
+                dl = np.where(ok, ylo.astype(np.int64) - ylo_c[f], 0)
+                du = np.where(ok, (ylo != yhi).astype(np.int64) - unk_c[f], 0)
+                b_, k_, *_ = nz = np.nonzero((dl != 0) | (du != 0))
+                row, fz = b_ * N_CAND + k_, f[nz]
+                for j in range(10):
+                    dS[:, j] += np.bincount(row, weights=D[j, fz] * dl[nz], minlength=B * N_CAND)
+                    dU[:, j] += np.bincount(row, weights=Dm[j, fz] * du[nz], minlength=B * N_CAND)
+            lb = tw.c0[c] - tw.c0 + ((S + dS) + (U + dU))
+            lb[:, c] = np.inf
+            m = lb.min(axis=1).reshape(B, N_CAND)
+            jw = lb.argmin(axis=1).reshape(B, N_CAND)
+            # ---- the smallest prediction wins (ties: the lowest index) and replaces the state if strictly below it --------------------
+            kb = m.argmin(axis=1)
+            mb = m[np.arange(B), kb]
+            for i in range(B):
+                u_ = np.unique(m[i])                                         # the best and the second-best distinct prediction
+                if u_.size > 1 and u_[1] - u_[0] <= tw.tol:
+                    near[sel[i]] = True
+            better = mb < m_cur[sel]
+            ps, ib = sel[better], np.flatnonzero(better)
+            cur_lo[ps], cur_un[ps] = c_lo[ib, kb[ib]], c_un[ib, kb[ib]]
+            fill[ps] = cand[ib, kb[ib]]
+            m_cur[ps], j_cur[ps] = mb[ib], jw[ib, kb[ib]]
+            rec["round"][ps], rec["unknown"][ps] = r, unknown[ib, kb[ib]]
+            active[sel] = ~(m_cur[sel] < -min_margin)                        # (a round that kept its state still gets new hashed corners)
+    rec["m_pred"], rec["worst"] = m_cur, j_cur
+    fills[:, :3 * h * w] = fill.reshape(P, -1)
+    return rec, fills, near
+
+
+def attack_patch_cpu(state, tables, x_u8, classes, patch=(1, 1), stride: int = 1, amp: int = 255, rounds: int = 2,
+                     min_margin: float = 0.0, *, forward: Callable, mean=CIFAR_MEAN, std=CIFAR_STD, confirm: str = "all",
+                     confirm_slack: float = 1e-5) -> PatchAttackResult:
+    """The numpy float64 twin of ``attack_patch_u8``: the gains, scores and candidates in the device's order and bytes (the sums of
+    ``gains_cpu`` / ``scores_cpu`` / ``candidates_cpu`` with ``unknown`` := the position's box planes and the scores kept for the
+    bytes of the patch only), ``m_pred`` as ``certify_box_cpu`` defines ``lb_interval`` for the degenerate box of the pasted image,
+    summed in numpy's order.  ``forward(x_u8) -> (stem bits, feature bits, logits)`` judges the witnesses, as in ``attack_cpu``."""
+    h, w, stride, amp, py, px, rounds = check_patch_attack(patch, stride, amp, rounds, min_margin, confirm)
+    x0 = np.asarray(x_u8)
+    n = x0.shape[0] if x0.ndim else 0
+    classes = np.asarray(classes).astype(np.int64).reshape(-1)
+    if x0.dtype != np.uint8 or x0.shape[1:] != (32, 32, 3) or classes.size != n:
+        raise ValueError(f"expected uint8 images [n, 32, 32, 3] and n classes, got {x0.dtype} {x0.shape}, {classes.size}")
+    tw = _PatchTwin(state, tables, mean, std)
+    P = py * px
+    rec, fills, near = np.zeros((n, P), PATCH_RECORD), np.zeros((n, P, FILL_BYTES), np.uint8), np.zeros((n, P), bool)
+    for i in range(n):
+        rec[i], fills[i], near[i] = _patch_image_cpu(tw, x0[i], int(classes[i]), h, w, stride, amp, rounds, min_margin)
+
+    def judge(images, cls):
+        rows, xcur, worst, active = new_state(len(images))
+        select_cpu(images[:, None], forward(images)[2], 1, cls, min_margin, images, xcur, rows, worst, active, 0)
+        return rows
+    wrong = judge(x0, classes)["status"] == WRONG if n else np.zeros(0, bool)
+    return _patch_result(x0, (h, w), stride, amp, rec.reshape(n, py, px), fills, wrong, confirm, confirm_slack,
+                         lambda tasks: judge(paste_cpu(x0, (h, w), stride, fills, tasks), classes[tasks // P]), near)
+
+
+def _patch_result(x0, patch, stride, amp, rec, fills, wrong, confirm, confirm_slack, judge, near=None) -> PatchAttackResult:
+    """The entry's records ``[n, Py, Px]`` and the forward's verdicts (``judge(tasks)`` -> select records) as a result."""
+    n, py, px = rec.shape
+    maps = np.zeros((n, py * px), dtype=PATCH_MAP)
+    for k in PATCH_RECORD.names:
+        maps[k] = rec.reshape(n, -1)[k]
+    maps["margin"] = np.nan
+    flat = maps.reshape(-1)
+    pred = (flat["round"] > 0) & (flat["m_pred"] < confirm_slack)
+    flat["status"][pred] = PREDICTED
+    tasks = confirm_tasks(rec.reshape(n, -1), confirm, confirm_slack)
+    if tasks.size:
+        rows = judge(tasks)
+        flat["margin"][tasks] = rows["margin0"]
+        flat["status"][tasks] = np.where(rows["status"] == WRONG, FALSIFIED, OPEN)
+    maps = maps.reshape(n, py, px)
+    return PatchAttackResult(x0, patch, stride, amp, maps, patch_rows_from_map(maps, wrong), fills, near)
+
+
+# ---- patches on the device ---------------------------------------------------------------------------------------------------
+
+def patch_search_u8(model, x_u8, classes, patch=(1, 1), stride: int = 1, amp: int = 255, rounds: int = 2, min_margin: float = 0.0,
+                    lane: int = 0):
+    """One ``ttnet_attack_patch_u8`` call on at most ``max_batch`` images: ``(records, fills)`` on the device -- float64
+    ``[n, P, 2]`` holding the 16-byte records (``.cpu().numpy().view(PATCH_RECORD)``) and uint8 ``[n, P, 192]``.  Predictions
+    only: no forward has judged them.  Asynchronous on the current stream."""
+    import torch
+
+    from . import _lib
+    x_u8, classes = CF.checked_inputs(model, x_u8, classes, "attack_patch_u8", "the search needs the certificate's stem planes,")
+    h, w, stride, amp, py, px, rounds = check_patch_attack(patch, stride, amp, rounds, min_margin)
+    n = x_u8.shape[0]
+    plan = model._plan_for(x_u8.device, n)
+    rec = torch.empty((n, py * px, 2), dtype=torch.float64, device=x_u8.device)
+    fills = torch.empty((n, py * px, FILL_BYTES), dtype=torch.uint8, device=x_u8.device)
+    stream = torch.cuda.current_stream(x_u8.device).cuda_stream
+    _lib.check(plan.lib.ttnet_attack_patch_u8(plan.handle, int(lane), C.c_void_p(x_u8.data_ptr()), n, C.c_void_p(classes.data_ptr()), h, w,
+                                              stride, amp, rounds, float(min_margin), C.c_void_p(rec.data_ptr()),
+                                              C.c_void_p(fills.data_ptr()), C.c_void_p(stream)))
+    return rec, fills
+
+
+def paste_u8(model, x_u8, patch, stride: int, fills, tasks):
+    """``ttnet_patch_paste_u8``: uint8 ``[m, 32, 32, 3]``, image ``tasks[k] // P`` of ``x_u8`` with fill ``tasks[k]`` pasted."""
+    import torch
+
+    from . import _lib
+    h, w, stride, _, py, px = CF.check_patch(patch, stride, 1)
+    n, m = x_u8.shape[0], int(tasks.shape[0])
+    tasks = tasks.to(device=x_u8.device, dtype=torch.int64).contiguous()
+    plan = model._plan_for(x_u8.device, n)
+    out = torch.empty((m, 32, 32, 3), dtype=torch.uint8, device=x_u8.device)
+    stream = torch.cuda.current_stream(x_u8.device).cuda_stream
+    _lib.check(plan.lib.ttnet_patch_paste_u8(plan.handle, C.c_void_p(x_u8.data_ptr()), n, h, w, stride, C.c_void_p(fills.data_ptr()),
+                                             C.c_void_p(tasks.data_ptr()), m, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+    return out
+
+
+def _judge_u8(model, images, classes, min_margin: float, lane: int) -> np.ndarray:
+    """The select records (``RECORD``) of round 0 for ``images`` (at most ``FORWARD_ROWS``) through one ``forward_u8``: ``status == 1``
+    means ``margin0 < -min_margin``."""
+    import torch
+    m, dev = images.shape[0], images.device
+    plan = model._plan_for(dev, m)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    logits = torch.empty((m, 10), dtype=torch.float32, device=dev)
+    rows = torch.empty((m, 8), dtype=torch.int32, device=dev)
+    xcur = torch.empty_like(images)
+    worst = torch.empty(m, dtype=torch.int32, device=dev)
+    active = torch.empty(m, dtype=torch.int32, device=dev)
+    _forward_into(plan, lane, images, logits, stream)
+    select_u8(model, images, logits, m, 1, classes, min_margin, images, xcur, rows, worst, active, 0)
+    return rows.cpu().numpy().view(RECORD).reshape(-1)
+
+
+def attack_patch_u8(model, x_u8, classes, patch=(1, 1), stride: int = 1, amp: int = 255, rounds: int = 2, min_margin: float = 0.0,
+                    confirm: str = "all", confirm_slack: float = 1e-5, lane: int = 0) -> PatchAttackResult:
+    """For every position of ``certify_patch_u8`` (the same positions, ``stride`` and ``amp``) search a uint8 fill of the patch on
+    which image i of ``x_u8`` (uint8 HIP tensor ``[N, 32, 32, 3]``) loses ``classes[i]``.  The device predicts (``m_pred``), the
+    forward alone confirms: the positions whose kept fill differs from the clean bytes and whose ``m_pred < confirm_slack`` (the
+    default is the logit tolerance, so near ties get their forward) are pasted, forwarded in chunks of at most ``FORWARD_ROWS``
+    and judged by ``ttnet_attack_select_u8``; ``status == 2`` there means ``margin < -min_margin``.  ``confirm="best"`` forwards
+    only each image's position of smallest ``m_pred`` (enough for the accuracy bracket), ``"none"`` nothing.  More than
+    ``FORWARD_ROWS`` images are searched in parts of that size.  Synchronises: the records come back to choose the forwards."""
+    import torch
+    x0, classes = CF.checked_inputs(model, x_u8, classes, "attack_patch_u8", "the search needs the certificate's stem planes,")
+    h, w, stride, amp, py, px, rounds = check_patch_attack(patch, stride, amp, rounds, min_margin, confirm)
+    n, P = x0.shape[0], py * px
+    parts = [(a, min(n, a + FORWARD_ROWS)) for a in range(0, n, FORWARD_ROWS)]
+    found = [patch_search_u8(model, x0[a:b], classes[a:b], (h, w), stride, amp, rounds, min_margin, lane) for a, b in parts]
+    rec = (np.concatenate([r.cpu().numpy().view(PATCH_RECORD).reshape(-1, P) for r, _ in found]) if found
+           else np.zeros((0, P), PATCH_RECORD))
+    fills = torch.cat([f for _, f in found]) if found else torch.empty((0, P, FILL_BYTES), dtype=torch.uint8, device=x0.device)
+    wrong = np.concatenate([_judge_u8(model, x0[a:b], classes[a:b], min_margin, lane)["status"] == WRONG for a, b in parts] or
+                           [np.zeros(0, bool)])
+
+    def judge(tasks: np.ndarray) -> np.ndarray:
+        out = []
+        for a, b in parts:                                              # (tasks ascend: the parts' answers follow each other)
+            local = tasks[(tasks >= a * P) & (tasks < b * P)] - a * P
+            chunk = min(model._plan_for(x0.device, b - a).max_batch, FORWARD_ROWS)
+            for k in range(0, local.size, chunk):
+                t = torch.from_numpy(local[k:k + chunk]).to(x0.device)
+                images = paste_u8(model, x0[a:b], (h, w), stride, fills[a:b], t)
+                out.append(_judge_u8(model, images, classes[a:b][t // P], min_margin, lane))
+        return np.concatenate(out)
+    return _patch_result(x0, (h, w), stride, amp, rec.reshape(n, py, px), fills, wrong, confirm, confirm_slack, judge)
+
+
+def kept_fills(res: PatchAttackResult) -> Tuple[np.ndarray, np.ndarray]:
+    """``(tasks, fills)`` of the positions a result would ever write out -- status falsified or predicted --: int64 ``[k]``
+    (``image * P + position``) and uint8 ``[k, 3 h w]``, the meaningful bytes of their fill records."""
+    h, w = res.patch
+    tasks = np.flatnonzero(res.map.reshape(-1)["status"] > 0)
+    flat = res.fills.reshape(-1, FILL_BYTES)
+    if isinstance(flat, np.ndarray):
+        return tasks, flat[tasks, :3 * h * w].copy()
+    import torch
+    return tasks, flat[torch.from_numpy(tasks).to(flat.device)][:, :3 * h * w].cpu().numpy()
+
+
+def _summary(patch, stride, amp, rounds, m, rows, tasks, fills) -> dict:
+    return {"patch": tuple(patch), "stride": int(stride), "amp": int(amp), "images": int(rows.size), "wrong": int((rows["status"] == WRONG).sum()),
+            "search": int((rows["status"] == FALSIFIED).sum()), "falsified": int((rows["status"] > 0).sum()),
+            "positions": int(m.size), "positions_falsified": int((m["status"] == FALSIFIED).sum()),
+            "positions_predicted": int((m["status"] == PREDICTED).sum()), "rounds": int(rounds), "rows": rows, "map": m,
+            "fill_tasks": tasks, "fills": fills}
+
+
+def summarise_patch(res: PatchAttackResult, rounds: int) -> dict:
+    """What ``attack_patch_batches`` reports per patch size: counts, ``rows``, ``map``, and the fills of the falsified and predicted
+    positions alone (``fill_tasks``, ``fills``: ``kept_fills``)."""
+    return _summary(res.patch, res.stride, res.amp, rounds, res.map, res.rows, *kept_fills(res))
+
+
+def attack_patch_batches(model, batches: Iterable, patches: Sequence, stride: int = 1, amp: int = 255, rounds: int = 2,
+                         min_margin: float = 0.0, confirm: str = "all", confirm_slack: float = 1e-5, lane: int = 0) -> List[dict]:
+    """``attack_patch_u8`` on the targets of ``batches`` (``cifar.device_batches``) for every patch size of ``patches``: one dict
+    per size (``summarise_patch``) with ``rows`` and ``map`` in dataset order.  Of a batch's fill records only the bytes of the
+    falsified and predicted positions are kept; the records themselves go with the batch."""
+    patches = [tuple(p) for p in patches]
+    parts: List[List[tuple]] = [[] for _ in patches]
+    seen = 0
+    for x, t in batches:
+        for i, p in enumerate(patches):
+            res = attack_patch_u8(model, x, t, p, stride, amp, rounds, min_margin, confirm, confirm_slack, lane)
+            tasks, fills = kept_fills(res)
+            parts[i].append((res.map, res.rows, tasks + seen * res.map.shape[1] * res.map.shape[2], fills))
+        seen += int(x.shape[0])
+    out = []
+    for p, res in zip(patches, parts):
+        h, w, _, _, py, px = CF.check_patch(p, stride, amp)
+        cat = lambda k, empty: np.concatenate([r[k] for r in res]) if res else empty  # noqa: E731
+        out.append(_summary((h, w), stride, amp, rounds, cat(0, np.zeros((0, py, px), PATCH_MAP)), cat(1, np.zeros(0, PATCH_ROW)),
+                            cat(2, np.zeros(0, np.int64)), cat(3, np.zeros((0, 3 * h * w), np.uint8))))
+    return out
+
+
+def patch_robust_bounds(certify_summary: dict, attack_summary: dict) -> dict:
+    """The patch bracket of the same images from ``certify.certify_patch_batches``' and ``attack_patch_batches``' summaries of one
+    size: ``certified, falsified, open`` images and ``positions_certified, positions_falsified, positions_open``.  A position that
+    is both certified (stage > 0) and falsified, or an image that is both, is a bug in one of the two: ``ValueError`` names the
+    first."""
+    cm, am = np.asarray(certify_summary["map"]), np.asarray(attack_summary["map"])
+    if cm.shape != am.shape:
+        raise ValueError(f"certificates {cm.shape} for attack records {am.shape}")
+    cert, fals = cm["stage"] > 0, am["status"] == FALSIFIED
+    both = np.argwhere(cert & fals)
+    if both.size:
+        raise ValueError(f"image {int(both[0][0])}, position {tuple(int(v) for v in both[0][1:])} is both certified and falsified "
+                         f"({len(both)} such positions): a bug in the certificate or in the search")
+    crow, arow = certify_summary["rows"], attack_summary["rows"]
+    icert, ifals = np.asarray(crow["certified"] == crow["positions"]), np.asarray(arow["status"]) > 0
+    ib = np.flatnonzero(icert & ifals)
+    if ib.size:
+        raise ValueError(f"image {int(ib[0])} is both patch-certified and falsified ({ib.size} such images): a bug in the certificate "
+                         "or in the search")
+    return {"images": int(icert.size), "certified": int(icert.sum()), "falsified": int(ifals.sum()),
+            "open": int(icert.size - icert.sum() - ifals.sum()), "wrong": int((arow["status"] == WRONG).sum()),
+            "positions_certified": int(cert.sum()), "positions_falsified": int(fals.sum()),
+            "positions_open": int(cert.size - cert.sum() - fals.sum())}
+
+
+def patch_robust_line(certify_summary: dict, attack_summary: dict) -> str:
+    """``PatchRobust.. size=HxW amp=A stride=S certified a/N <= robust <= b/N (falsified f: wrong at x0 w, by search s; open o;
+    positions certified p, falsified q, open r)``"""
+    b, s = patch_robust_bounds(certify_summary, attack_summary), attack_summary
+    n, f = b["images"], b["falsified"]
+    return (f"PatchRobust.. size={s['patch'][0]}x{s['patch'][1]} amp={s['amp']} stride={s['stride']} certified {b['certified']}/{n} <= robust "
+            f"<= {n - f}/{n} (falsified {f}: wrong at x0 {b['wrong']}, by search {f - b['wrong']}; open {b['open']}; positions certified "
+            f"{b['positions_certified']}, falsified {b['positions_falsified']}, open {b['positions_open']})")
+
+
+def write_patch_witnesses_npz(path: str, summaries: Sequence[dict]):
+    """The falsified positions as .npz: per size ``tasks_HxW`` int64 (``image * P + position``), ``fills_HxW`` uint8 ``[k, 3 h w]``,
+    ``margin_HxW`` float32 (the forward's), ``m_pred_HxW`` float64 and ``geometry_HxW`` int64 ``(h, w, stride, amp, Py, Px)``; a
+    witness is image ``task // P`` with the fill pasted at position ``task % P`` (``paste_cpu``).  Written to a temporary name and
+    renamed."""
+    from .report import replacing
+    arrays = {}
+    for s in summaries:
+        h, w = s["patch"]
+        key = f"{h}x{w}"
+        m = s["map"]
+        flat = m.reshape(-1)
+        tasks = np.flatnonzero(flat["status"] == FALSIFIED)
+        arrays.update({f"tasks_{key}": tasks.astype(np.int64),
+                       f"fills_{key}": s["fills"][np.searchsorted(s["fill_tasks"], tasks)],
+                       f"margin_{key}": flat["margin"][tasks], f"m_pred_{key}": flat["m_pred"][tasks],
+                       f"geometry_{key}": np.array([h, w, s["stride"], s["amp"], m.shape[1], m.shape[2]], dtype=np.int64)})
+    with replacing(path, "wb") as f:
+        np.savez(f, **arrays)

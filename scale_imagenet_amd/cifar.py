@@ -9,7 +9,8 @@ dataset holds, bytes: ``read_cifar10`` transposes the files' planar CHW records 
 tensors there by itself.  ``--certify EPS[,EPS...]`` then certifies the labels against perturbations of up to EPS byte levels
 over the same device-resident bytes (``scale_imagenet_amd.certify``) and prints the verified accuracy per eps; with
 ``--attack`` a search for uint8 counter-examples follows (``scale_imagenet_amd.attack``) and one ``Robust..`` line per eps
-brackets the robust accuracy from both sides.
+brackets the robust accuracy from both sides.  ``--certify_patch HxW[,..]`` sweeps a patch over every image, and with
+``--attack_patch`` a search for a falsifying fill per position follows: one ``PatchRobust..`` line per size.
 
 Both published layouts are read: ``cifar-10-batches-py`` (pickles ``test_batch`` / ``data_batch_1..5``, ``batches.meta``)
 and ``cifar-10-batches-bin`` (``*.bin`` records of 1 label byte + 3072 planar bytes, ``batches.meta.txt``).  The pickles go
@@ -225,6 +226,15 @@ def build_parser() -> argparse.ArgumentParser:
                      help=".npz: per size lb_HxW, stage_HxW, worst_HxW, unknown_stem_HxW, each [N][Py][Px]")
     pat.add_argument("--patch_rows", type=str, default=None, metavar="FILE",
                      help="CSV size,amp,stride,index,class,patch_certified,certified,positions,interval,enumeration,lb_min,pos_min,worst")
+    pat.add_argument("--attack_patch", action="store_true",
+                     help="after each `Patch..` line, search every position for a uint8 fill of the patch on which the image loses its label "
+                          "and print `PatchRobust.. certified a/N <= robust <= b/N`; a witness counts once forward_u8 has judged it "
+                          "(scale_imagenet_amd.attack)")
+    pat.add_argument("--attack_patch_rounds", type=int, default=2, metavar="R", help="rounds of the patch search (1..4)")
+    pat.add_argument("--attack_patch_confirm", choices=("all", "best"), default="all",
+                     help="forward every predicted witness, or only each image's most promising position (enough for the bracket)")
+    pat.add_argument("--patch_witnesses", type=str, default=None, metavar="FILE",
+                     help=".npz of the falsified positions per size: tasks_HxW, fills_HxW, margin_HxW, m_pred_HxW, geometry_HxW")
     att = p.add_argument_group("falsified robustness (with --certify: one more stdout line per eps, after its `Verified..`)")
     att.add_argument("--attack", action="store_true",
                      help="search the box of floor(EPS) byte levels for a uint8 image that loses the label and print `Robust.. eps=E "
@@ -350,8 +360,17 @@ def run(args) -> int:
         from . import certify
         psums = certify.certify_patch_batches(model, batches, patches, args.patch_stride, args.patch_amp, args.certify_enum,
                                               args.certify_min_margin)
-        for s in psums:
+        found = []
+        if args.attack_patch:                                   # the same min_margin for both sides of the bracket
+            from . import attack
+            found = attack.attack_patch_batches(model, batches, patches, args.patch_stride, args.patch_amp, args.attack_patch_rounds,
+                                                args.certify_min_margin, args.attack_patch_confirm)
+        for i, s in enumerate(psums):
             print(certify.patch_line(s))
+            if found:
+                print(attack.patch_robust_line(s, found[i]))
+        if args.patch_witnesses:
+            attack.write_patch_witnesses_npz(args.patch_witnesses, found)
         if args.patch_rows:
             certify.write_patch_rows_csv(args.patch_rows, psums, targets.tolist())
         if args.patch_map:
@@ -379,6 +398,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         raise SystemExit("--patch_amp must be in [1, 255]")
     if (args.patch_map or args.patch_rows) and not args.certify_patch:
         raise SystemExit("--patch_map and --patch_rows need --certify_patch HxW[,HxW...]")
+    if args.attack_patch and not args.certify_patch:
+        raise SystemExit("--attack_patch needs --certify_patch HxW[,HxW...]")
+    if args.patch_witnesses and not args.attack_patch:
+        raise SystemExit("--patch_witnesses needs --attack_patch")
+    if not 1 <= args.attack_patch_rounds <= 4:
+        raise SystemExit("--attack_patch_rounds must be in [1, 4]")
     if (args.attack_rows or args.attack_witnesses) and not args.attack:
         raise SystemExit("--attack_rows and --attack_witnesses need --attack")
     if not 0 <= args.attack_rounds <= 8:

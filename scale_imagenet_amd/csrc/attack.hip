@@ -8,12 +8,20 @@
 //                          at most 256 terms per byte, and the eight candidates
 //   attack_select_kernel   one workgroup per image: the margin of every candidate's logits in float32, the smallest wins
 //                          and becomes x_cur, the record is updated
+//   attack_patch_kernel    the patch search (ttnet_attack_patch_u8): one workgroup per (image, position); the movable stem bits
+//                          are those the position's box leaves unknown, a candidate fill is judged by its predicted margin
+//                          m_pred -- the stem cells of the patch's fields again at radius 0 (certify_stem_cell.inc), the
+//                          features they reach (feature3), the differences against the clean sums in the sweep's order --
+//                          and the gains, pushes and scores of the propose step choose the candidates
+//   patch_paste_kernel     witnesses as images: a fill pasted into its image (ttnet_patch_paste_u8)
 //
 // Float64 sums in a fixed order (the build switches floating-point contraction off for every file), integer work, maxima:
 // the same input gives the same bytes, and the numpy twin (attack.py) the same bytes again.
 
 #include <math.h>
 
+#include "certify_lookup.h"
+#include "partition.h"
 #include "ttnet_common.h"
 #include "va_block.h"
 
@@ -328,6 +336,401 @@ __global__ __launch_bounds__(256) void attack_select_kernel(const uint8_t *__res
   }
 }
 
+// ---- the patch search (include/ttnet.h: ttnet_attack_patch_u8) -------------------------------------------------------------------
+constexpr int kFill = 3 * kPatchMax * kPatchMax;                     // bytes of a fill record
+constexpr int kHashStream = 11;                                      // slot k of a round hashes stream 11 + k (attack.py: HASH_STREAM)
+
+struct PatchRec {       // one (image, position) record, 16 bytes
+  double m_pred;
+  int32_t worst;
+  uint16_t round, unknown;
+};
+static_assert(sizeof(PatchRec) == 16, "record layout of include/ttnet.h");
+
+// bit 16 of a 32-bit integer mix of (position, round, stream, byte): attack.py's hash_corner
+__device__ inline bool hash_corner(uint32_t pos, int rnd, int stream, uint32_t byte) {
+  uint32_t v = pos * 0x9E3779B1u + (uint32_t)(rnd * 8 + stream) * 0x85EBCA6Bu + byte * 0xC2B2AE35u;
+  v ^= v >> 15;
+  v *= 0x2C1B3C6Du;
+  v ^= v >> 12;
+  v *= 0x297A2D39u;
+  v ^= v >> 15;
+  return (v >> 16) & 1u;
+}
+
+// One workgroup per (image, position); task = first_task + blockIdx.x = image * P + position.  Thread (channel, cell row) =
+// tid < 64 * rows of cells owns one touched row of the stem planes, as in certify_patch_kernel; thread = byte of the patch for
+// the scores and the candidates.  s_lo / s_un are the working planes: the clean planes with the touched rows of whatever fill is
+// being judged; the touched rows of the current and of the round's best fill are kept apart (cur_*, best_*: 4 x 64 words each).
+__global__ __launch_bounds__(256, 2) void attack_patch_kernel(
+    const uint8_t *__restrict__ x, CertifyNorm nm, const float *__restrict__ w, const float *__restrict__ bias, const double *__restrict__ bn,
+    const double *__restrict__ slack, const uint64_t *__restrict__ slo, const uint64_t *__restrict__ shi, const uint64_t *__restrict__ ylo,
+    const uint64_t *__restrict__ yhi, const uint32_t *__restrict__ t1, const uint32_t *__restrict__ t2, const uint64_t *__restrict__ t3w,
+    const double *__restrict__ A, const double *__restrict__ c0, const double *__restrict__ wsum, const int32_t *__restrict__ classes,
+    const double *__restrict__ sums, const double *__restrict__ sums_un, PatchGeom g, int rounds, double min_margin,
+    PatchRec *__restrict__ map, uint8_t *__restrict__ fills, long long first_task, long long n_tasks) {
+  __shared__ uint64_t s_lo[kStemRows], s_un[kStemRows];
+  __shared__ uint64_t cur_lo[256], cur_un[256], best_lo[256], best_un[256];
+  __shared__ double win[2][3][kFieldPixels][kFieldPixels];
+  __shared__ double s_wt[kStemCh][kFieldCells][kFieldCells];         // the push of every touched cell in mode 1
+  __shared__ uint16_t s_mov[256], s_neg[256];                        // per touched row: the movable bits, those with g < 0 (bit = cell column of the span)
+  __shared__ uint8_t s_fill[kFill], s_cand[kCand][kFill];
+  __shared__ int s_dup[kCand];
+  __shared__ double part[4][2 * kClasses];
+  __shared__ double s_max[2][4];
+  __shared__ double m_s;
+  __shared__ int j_s, unk_s, unk_pub_s, mov_s;
+  const long long task = first_task + blockIdx.x;
+  if (task >= n_tasks) return;                                       // (whole workgroups)
+  const int P = g.py * g.px, img = (int)(task / P), pos = (int)(task - (long long)img * P), tid = threadIdx.x;
+  const int y0 = (pos / g.px) * g.stride, x0 = (pos % g.px) * g.stride, nbytes = 3 * g.h * g.w;
+  const FieldSpan fr = field_span(y0, g.h), fq = field_span(x0, g.w);
+  const bool touched = fr.count > 0 && fq.count > 0, mine = touched && tid < 64 * fr.count;
+  const int ch = tid & 63, cy = tid >> 6, r = ch * kPool + fr.first + cy;   // (of the threads that own a row)
+  const int c = classes[img];
+  const bool valid = c >= 0 && c < kClasses;
+  const int wr_n = 3 * fr.count + 2, wq_n = 3 * fq.count + 2;        // <= kFieldPixels
+  int b0 = 0;                                                        // the clean byte of this thread's byte of the patch
+  if (tid < nbytes) b0 = x[(size_t)img * kImg + ((y0 + tid / (3 * g.w)) * 32 + x0 + (tid / 3) % g.w) * 3 + tid % 3];
+  if (tid < kFill) s_fill[tid] = (uint8_t)b0;
+  for (int q = tid; q < kStemRows; q += 256) {
+    const uint64_t l = slo[(size_t)img * kStemRows + q];
+    s_lo[q] = l;
+    s_un[q] = (l ^ shi[(size_t)img * kStemRows + q]) & 0x3FFull;
+  }
+  if (tid < 2 * kClasses * 4) (&part[0][0])[tid] = 0.0;
+  if (tid == 0) unk_s = mov_s = 0;
+
+  // the pixels of the fields that meet the patch as centres and radii: the box of the position, or a fill at radius 0
+  auto load_window = [&](bool box, const uint8_t *fill) {
+    if (touched)
+      for (int i = tid; i < 3 * wr_n * wq_n; i += 256) {
+        const int k = i % 3, lq = (i / 3) % wq_n, lr = i / (3 * wq_n), ir = 3 * fr.first - 1 + lr, iq = 3 * fq.first - 1 + lq;   // ir, iq <= 30
+        double centre = 0.0, radius = 0.0;                           // the top / left padding: zero in normalised space
+        if (ir >= 0 && iq >= 0) {
+          const int b = x[(size_t)img * kImg + (ir * 32 + iq) * 3 + k];
+          const bool in = ir >= y0 && ir < y0 + g.h && iq >= x0 && iq < x0 + g.w;
+          int bl = b, bh = b;
+          if (in && box) {
+            bl = b - g.amp > 0 ? b - g.amp : 0;
+            bh = b + g.amp < 255 ? b + g.amp : 255;
+          } else if (in) {
+            bl = bh = fill[((ir - y0) * g.w + (iq - x0)) * 3 + k];
+          }
+          pixel_interval((double)bl, (double)bh, nm, k, centre, radius);
+        }
+        win[0][k][lr][lq] = centre;
+        win[1][k][lr][lq] = radius;
+      }
+  };
+  // lb_j = c0_c - c0_j + ((S_j + dS_j) + (U_j + dU_j)) from the waves' partial sums: thread 0, between two barriers
+  auto combine = [&]() {
+    if (tid == 0) {
+      double best = valid ? INFINITY : -INFINITY;
+      int best_j = -1;
+      for (int j = 0; j < kClasses && valid; ++j) {
+        if (j == c) continue;
+        const double cert = sums[(size_t)img * kClasses + j] + (((part[0][j] + part[1][j]) + part[2][j]) + part[3][j]);
+        const double unk = sums_un[(size_t)img * kClasses + j] + (((part[0][kClasses + j] + part[1][kClasses + j]) + part[2][kClasses + j]) + part[3][kClasses + j]);
+        const double lb = c0[c] - c0[j] + (cert + unk);
+        if (lb < best) {
+          best = lb;
+          best_j = j;
+        }
+      }
+      m_s = best;
+      j_s = best_j;
+      unk_pub_s = unk_s;
+      unk_s = 0;
+    }
+  };
+
+  // ---- the movable bits: the bits that the box of this position leaves unknown; the clean margin ------------------------------------
+  load_window(true, nullptr);
+  __syncthreads();
+  if (mine) {
+    double wr[27];
+#pragma unroll
+    for (int i = 0; i < 27; ++i) wr[i] = (double)w[ch * 27 + i];
+    const double b = (double)bias[ch], sc = bn[ch], sh = bn[64 + ch], sl = slack[ch];
+    uint32_t mov = 0;
+#pragma unroll 1
+    for (int cx = 0; cx < fq.count; ++cx) {
+      // (the included text declares its own loop variables c and r, which shadow the class c and the plane row r inside it)
+#define STEM_AT(k, c, r, q) win[k][c][3 * cy + (r)][3 * cx + (q)]
+#include "certify_stem_cell.inc"
+#undef STEM_AT
+      mov |= (uint32_t)(lo_bit != hi_bit) << cx;
+    }
+    s_mov[tid] = (uint16_t)mov;
+    cur_lo[tid] = s_lo[r];
+    cur_un[tid] = s_un[r];
+    const int k0 = __popcll((s_un[r] >> fq.first) & ((1ull << fq.count) - 1ull));   // round 0: the clean cells of the span within the slack
+    if (k0) atomicAdd(&unk_s, k0);                                   // (integers: any order gives the same sum)
+    if (mov) atomicOr(&mov_s, 1);
+  }
+  __syncthreads();
+  combine();
+  __syncthreads();
+  double m_cur = m_s;
+  int j_cur = j_s, kept_round = 0, kept_unk = unk_pub_s;
+  const bool search = valid && touched && mov_s != 0 && !(m_cur < -min_margin);   // (uniform over the workgroup)
+
+  // the predicted margin of a fill: the touched cells again at radius 0, the features they reach against the clean feature
+  // planes, the sums in certify_patch_kernel's order.  Leaves the fill's rows in the working planes.
+  auto evaluate = [&](const uint8_t *fill, double &m_out, int &j_out, int &unk_out) {
+    load_window(false, fill);
+    __syncthreads();
+    if (mine) {
+      double wr[27];
+#pragma unroll
+      for (int i = 0; i < 27; ++i) wr[i] = (double)w[ch * 27 + i];
+      const double b = (double)bias[ch], sc = bn[ch], sh = bn[64 + ch], sl = slack[ch];
+      uint64_t lo_w = s_lo[r], un_w = s_un[r];
+      int unk = 0;
+#pragma unroll 1
+      for (int cx = 0; cx < fq.count; ++cx) {
+#define STEM_AT(k, c, r, q) win[k][c][3 * cy + (r)][3 * cx + (q)]
+#include "certify_stem_cell.inc"
+#undef STEM_AT
+        const int px = fq.first + cx;
+        lo_w = (lo_w & ~(1ull << px)) | ((uint64_t)lo_bit << px);
+        un_w = (un_w & ~(1ull << px)) | ((uint64_t)(lo_bit != hi_bit) << px);
+        unk += lo_bit != hi_bit;
+      }
+      s_lo[r] = lo_w;
+      s_un[r] = un_w;
+      if (unk) atomicAdd(&unk_s, unk);
+    }
+    __syncthreads();
+    double acc[2 * kClasses];                                        // [j]: the certain part, [10 + j]: the unknown part
+#pragma unroll
+    for (int j = 0; j < 2 * kClasses; ++j) acc[j] = 0.0;
+    for (int kind = 0; kind < 4; ++kind) {
+      const FeatRect rc = reached_rect(kind, fr, fq);
+      for (int e = tid; e < 64 * rc.nr * rc.nc; e += 256) {
+        const int fch = e & 63, cell = e >> 6, oy = rc.r0 + cell / rc.nc, ox = rc.c0 + cell % rc.nc, fc = 64 * kind + fch;
+        bool lo, hi;
+        feature3(s_lo, s_un, kind, fch, oy, ox, t1, t2, t3w, lo, hi);
+        const size_t row = (size_t)img * kFeatRows + fc * kSide + oy;
+        const bool clo = (ylo[row] >> ox) & 1ull, chi = (yhi[row] >> ox) & 1ull;
+        if (lo == clo && hi == chi) continue;
+        const double *af = A + (size_t)(fc * kPlane + oy * kSide + ox) * kClasses;
+        const double ac = af[c];
+#pragma unroll
+        for (int j = 0; j < kClasses; ++j) {
+          const double d = ac - af[j], m = fmin(0.0, d);
+          acc[j] += (lo ? d : 0.0) - (clo ? d : 0.0);
+          acc[kClasses + j] += ((hi && !lo) ? m : 0.0) - ((chi && !clo) ? m : 0.0);
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 2 * kClasses; ++j) {
+      double v = acc[j];
+      for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+      if ((tid & 63) == 0) part[tid >> 6][j] = v;
+    }
+    __syncthreads();
+    combine();
+    __syncthreads();
+    m_out = m_s;
+    j_out = j_s;
+    unk_out = unk_pub_s;
+  };
+
+  for (int rnd = 1; search && rnd <= rounds; ++rnd) {
+    // (here the working planes hold the current fill's rows)
+    if (g.h == 1 && g.w == 1 && rnd == 1) {                          // a 1 x 1 patch has three bytes: its eight corners
+      if (tid < 3) {
+        const uint8_t up = (uint8_t)min(255, b0 + g.amp), dn = (uint8_t)max(0, b0 - g.amp);
+#pragma unroll
+        for (int k = 0; k < kCand; ++k) s_cand[k][tid] = ((k >> tid) & 1) ? up : dn;
+      }
+    } else {
+      // ---- flip gains and pushes of the movable bits, on the current planes: the terms and their order are attack_propose_kernel's
+      if (mine) {
+        const int py = fr.first + cy;
+        auto row1 = [&](int c2, int y) {                             // a stem row of the current planes (known bits), shifted
+          return shifted_row(y, [&](int iy) { return (uint32_t)(s_lo[c2 * kPool + iy] & 0x3FFull); });
+        };
+        const uint64_t T1 = table_word(t1, ch), T2 = table_word(t2, ch);
+        const double sgn = bn[ch] >= 0.0 ? 1.0 : -1.0;
+        const uint32_t bits = (uint32_t)(s_lo[r] & 0x3FFull), mov = s_mov[tid];
+        uint32_t neg = 0;
+        for (int cx = 0; cx < fq.count; ++cx) {
+          const int px = fq.first + cx;
+          double gsum = 0.0, wt = 0.0;
+          if ((mov >> cx) & 1u) {
+            auto term = [&](int fc, int oy, int ox, int ynew, int yold) {  // +D_f, -D_f or nothing
+              if (ynew != yold) {
+                const size_t f = (size_t)(fc * kPlane + oy * kSide + ox) * kClasses;
+                const double d = A[f + c] - A[f + j_cur];
+                gsum += ynew > yold ? d : -d;
+              }
+            };
+            for (int doy = -1; doy <= 1; ++doy) {                    // conv1: rows oy-1..oy+1, columns ox-1..ox; oy <= 9
+              const int oy = py + doy;
+              if (oy < 0 || oy >= kPool) continue;
+              const uint32_t l0 = row1(ch, oy - 1), l1 = row1(ch, oy), l2 = row1(ch, oy + 1);
+              for (int dox = 0; dox <= 1; ++dox) {
+                const int ox = px + dox;
+                const uint32_t at = conv1_index(l0, l1, l2, ox), fl = at ^ (1u << ((1 - doy) * 2 + (1 - dox)));
+                term(ch, oy, ox, (int)((T1 >> fl) & 1ull), (int)((T1 >> at) & 1ull));
+              }
+            }
+            for (int doy = 0; doy <= 1; ++doy) {                     // conv2: rows oy-1..oy, columns ox-1..ox+1; ox <= 9
+              const int oy = py + doy;
+              const uint32_t l0 = row1(ch, oy - 1), l1 = row1(ch, oy);
+              for (int dox = -1; dox <= 1; ++dox) {
+                const int ox = px + dox;
+                if (ox < 0 || ox >= kPool) continue;
+                const uint32_t at = conv2_index(l0, l1, ox), fl = at ^ (1u << ((1 - doy) * 3 + (1 - dox)));
+                term(64 + ch, oy, ox, (int)((T2 >> fl) & 1ull), (int)((T2 >> at) & 1ull));
+              }
+            }
+            uint32_t grp[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) grp[k] = (uint32_t)(s_lo[((ch & ~7) + k) * kPool + py] & 0x3FFull);
+            const uint32_t at = conv3_index(grp, px), fl = at ^ (1u << (ch & 7));
+            for (int o = 0; o < 8; ++o) {                            // conv3: the 8 outputs of the group
+              const int fc = 128 + (ch & ~7) + o;
+              const uint64_t *T3 = t3w + (fc - 128) * 4;
+              term(fc, py, px, (int)((T3[fl >> 6] >> (fl & 63u)) & 1ull), (int)((T3[at >> 6] >> (at & 63u)) & 1ull));
+            }
+            const int bit = (bits >> px) & 1;
+            term(192 + ch, py, px, 1 - bit, bit);                    // out4 carries the bit itself
+            wt = -gsum * (bit == 0 ? 1.0 : -1.0) * sgn;
+            neg |= (uint32_t)(gsum < 0.0) << cx;
+          }
+          s_wt[ch][cy][cx] = wt;
+        }
+        s_neg[tid] = (uint16_t)neg;
+      }
+      __syncthreads();
+      // ---- scores of the bytes of the patch (every other byte scores 0): ch ascending, then py, then px --------------------------------
+      double sc0 = 0.0, sc1 = 0.0;
+      if (tid < nbytes) {
+        const int k = tid % 3;
+        int cyc[2], oyc[2], cxc[2], oxc[2];
+        cells_of(y0 + tid / (3 * g.w), cyc, oyc);
+        cells_of(x0 + (tid / 3) % g.w, cxc, oxc);
+        for (int c2 = 0; c2 < kStemCh; ++c2)
+#pragma unroll
+          for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+              if (oyc[a] < 0 || oxc[b] < 0) continue;
+              const int ly = cyc[a] - fr.first, lx = cxc[b] - fq.first;   // (a cell whose field holds a byte of the patch is in the span)
+              const double w1 = s_wt[c2][ly][lx];
+              if (w1 == 0.0) continue;                               // (a zero term changes no sum: the sums are never -0)
+              const double w0 = ((s_neg[(ly << 6) | c2] >> lx) & 1u) ? w1 : 0.0;
+              const double wk = wsum[(size_t)c2 * 75 + k * 25 + oyc[a] * 5 + oxc[b]];
+              sc0 += w0 * wk;
+              sc1 += w1 * wk;
+            }
+      }
+      double mx[2] = {fabs(sc0), fabs(sc1)};
+#pragma unroll
+      for (int m = 0; m < 2; ++m) {                                  // M = max |score| over the patch, per mode
+        for (int d = 32; d >= 1; d >>= 1) mx[m] = fmax(mx[m], __shfl_xor(mx[m], d));
+        if ((tid & 63) == 0) s_max[m][tid >> 6] = mx[m];
+      }
+      __syncthreads();
+      if (tid < nbytes) {
+        constexpr double kTau[4] = {0.0, 0.125, 0.25, 0.5};
+        const uint8_t keep = s_fill[tid], up = (uint8_t)min(255, b0 + g.amp), dn = (uint8_t)max(0, b0 - g.amp);
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+          const double s = m == 0 ? sc0 : sc1, M = fmax(fmax(s_max[m][0], s_max[m][1]), fmax(s_max[m][2], s_max[m][3]));
+#pragma unroll
+          for (int t = 0; t < 3; ++t) {
+            const bool sel = s != 0.0 && fabs(s) > kTau[t] * M;
+            s_cand[4 * m + t][tid] = sel ? (s > 0.0 ? up : dn) : keep;
+          }
+          // the slot of tau = 1/2: the sign corner of mode 1 with a hashed half of its bytes at the opposite end
+          const uint8_t base = sc1 > 0.0 ? up : (sc1 < 0.0 ? dn : keep), other = sc1 > 0.0 ? dn : (sc1 < 0.0 ? up : keep);
+          s_cand[4 * m + 3][tid] = hash_corner((uint32_t)pos, rnd, kHashStream + 4 * m + 3, (uint32_t)tid) ? other : base;
+        }
+      }
+    }
+    __syncthreads();
+    if (tid < kCand) {                                               // a candidate byte-equal to an earlier one cannot win: skip it
+      int dup = -1;
+      for (int k = 0; k < tid && dup < 0; ++k) {
+        bool same = true;
+        for (int i = 0; i < nbytes && same; ++i) same = s_cand[k][i] == s_cand[tid][i];
+        if (same) dup = k;
+      }
+      s_dup[tid] = dup;
+    }
+    __syncthreads();
+    double best_m = INFINITY;
+    int best_k = -1, best_j = -1, best_unk = 0;
+    for (int k = 0; k < kCand; ++k) {
+      if (s_dup[k] >= 0) continue;                                   // (uniform)
+      double m;
+      int j, unk;
+      evaluate(s_cand[k], m, j, unk);
+      if (m < best_m) {                                              // the smallest prediction; ties: the lowest index
+        best_m = m;
+        best_k = k;
+        best_j = j;
+        best_unk = unk;
+        if (mine) {
+          best_lo[tid] = s_lo[r];
+          best_un[tid] = s_un[r];
+        }
+      }
+    }
+    if (best_k >= 0 && best_m < m_cur) {                             // strictly below the current state: it becomes the state
+      m_cur = best_m;
+      j_cur = best_j;
+      kept_round = rnd;
+      kept_unk = best_unk;
+      if (mine) {
+        cur_lo[tid] = best_lo[tid];
+        cur_un[tid] = best_un[tid];
+      }
+      if (tid < nbytes) s_fill[tid] = s_cand[best_k][tid];
+    }
+    if (mine) {                                                      // the working planes hold the current fill's rows again
+      s_lo[r] = cur_lo[tid];
+      s_un[r] = cur_un[tid];
+    }
+    __syncthreads();
+    if (m_cur < -min_margin) break;
+  }
+  if (tid < kFill) fills[(size_t)task * kFill + tid] = tid < nbytes ? s_fill[tid] : (uint8_t)0;
+  if (tid != 0) return;
+  PatchRec out;
+  out.m_pred = m_cur;
+  out.worst = j_cur;
+  out.round = (uint16_t)kept_round;
+  out.unknown = (uint16_t)(valid ? kept_unk : 0);
+  map[task] = out;
+}
+
+// out[k] = image tasks[k] / P with the fill of task tasks[k] pasted at position tasks[k] % P; zeros for a task out of range
+__global__ __launch_bounds__(256) void patch_paste_kernel(const uint8_t *__restrict__ x, long long n, PatchGeom g, const uint8_t *__restrict__ fills,
+                                                          const int64_t *__restrict__ tasks, uint8_t *__restrict__ out, long long m) {
+  const long long k = blockIdx.x;
+  if (k >= m) return;
+  const long long t = tasks[k], P = (long long)g.py * g.px;
+  uint8_t *dst = out + (size_t)k * kImg;
+  if (t < 0 || t >= n * P) {
+    for (int i = threadIdx.x; i < kImg; i += 256) dst[i] = 0;
+    return;
+  }
+  const int pos = (int)(t % P), y0 = (pos / g.px) * g.stride, x0 = (pos % g.px) * g.stride;
+  const uint8_t *src = x + (size_t)(t / P) * kImg, *fill = fills + (size_t)t * kFill;
+  for (int i = threadIdx.x; i < kImg; i += 256) {
+    const int k3 = i % 3, iq = (i / 3) % 32, ir = i / 96;
+    const bool in = ir >= y0 && ir < y0 + g.h && iq >= x0 && iq < x0 + g.w;
+    dst[i] = in ? fill[((ir - y0) * g.w + (iq - x0)) * 3 + k3] : src[i];
+  }
+}
+
 }  // namespace
 
 int launch_attack_wsum(const float *w, double *wsum, hipStream_t s) {
@@ -347,6 +750,26 @@ int launch_attack_select(const uint8_t *cand, const float *logits, int n, int n_
                          const uint8_t *x0, uint8_t *xcur, void *rows, int32_t *worst, int32_t *active, int round, hipStream_t s) {
   hipLaunchKernelGGL(attack_select_kernel, dim3((unsigned)n), dim3(256), 0, s, cand, logits, n_cand, classes, min_margin, x0, xcur,
                      (Row *)rows, worst, active, round, n);
+  TT_HIP(hipGetLastError());
+  return TTNET_OK;
+}
+
+int launch_attack_patch(const AttackPatchArgs &p, hipStream_t s) {
+  const CertifyArgs &a = p.sweep.clean;
+  const PatchGeom g{p.sweep.patch_h, p.sweep.patch_w, p.sweep.stride, p.sweep.amp, p.sweep.py, p.sweep.px};
+  const long long tasks = (long long)a.n * g.py * g.px;
+  for (long long l = 0; l < part::patch_launches(tasks); ++l)
+    hipLaunchKernelGGL(attack_patch_kernel, dim3((unsigned)part::patch_launch_size(tasks, l)), dim3(256), 0, s, a.x, a.norm, a.w, a.bias, a.stem_bn,
+                       a.slack, a.stem_lo, a.stem_hi, a.feat_lo, a.feat_hi, a.t1, a.t2, a.t3w, a.A, a.c0, p.wsum, a.classes, a.sums, a.sums_un, g,
+                       p.rounds, p.min_margin, (PatchRec *)p.map, p.fills, l * part::kPatchGrid, tasks);
+  TT_HIP(hipGetLastError());
+  return TTNET_OK;
+}
+
+int launch_patch_paste(const uint8_t *x, long long n, int patch_h, int patch_w, int stride, const uint8_t *fills, const int64_t *tasks,
+                       long long m, uint8_t *out, hipStream_t s) {
+  const PatchGeom g{patch_h, patch_w, stride, 0, part::patch_positions(patch_h, stride), part::patch_positions(patch_w, stride)};
+  hipLaunchKernelGGL(patch_paste_kernel, dim3((unsigned)m), dim3(256), 0, s, x, n, g, fills, tasks, out, m);
   TT_HIP(hipGetLastError());
   return TTNET_OK;
 }

@@ -56,6 +56,16 @@ int flat(const FlatGrid &g, I *o) {
   return 0;
 }
 
+// the cut of n * P workgroups that the patch sweep and the patch search share; `key` names the caller in a refusal
+int patch_cut(const char *key, const I *a, I *o) {
+  if (a[1] > ttnet::va::kPatchMax || a[2] > ttnet::va::kPatchMax) return fail(key, "a patch side of %lld is above %lld", a[1] > a[2] ? a[1] : a[2], ttnet::va::kPatchMax);
+  if (a[3] > 32) return fail(key, "stride=%lld is above %lld", a[3], 32);
+  o[0] = patch_positions((int)a[1], (int)a[3]); o[1] = patch_positions((int)a[2], (int)a[3]);
+  const long long tasks = a[0] * o[0] * o[1];
+  o[2] = patch_launches(tasks); o[3] = patch_launch_size(tasks, 0); o[4] = patch_launch_size(tasks, o[2] - 1); o[5] = kPatchGrid;
+  return 0;
+}
+
 const Key kKeys[] = {
     // ---- common
     {"slices_for", 3, {{"n", 'n'}, {"units", 'c'}, {"target", 'c'}}, 1, [](const I *a, I *o) {
@@ -168,15 +178,9 @@ const Key kKeys[] = {
        o[0] = stem_continues((int)a[0], (int)a[1]) ? 1 : 0;
        return 0;
      }},
-    // ---- patch sweep
-    {"patch.sweep", 4, {{"n", 'n'}, {"patch_h", 'd'}, {"patch_w", 'd'}, {"stride", 'd'}}, 6, [](const I *a, I *o) {   // -> positions down, across, launches, workgroups of the first, of the last, at most
-       if (a[1] > ttnet::va::kPatchMax || a[2] > ttnet::va::kPatchMax) return fail("patch.sweep", "a patch side of %lld is above %lld", a[1] > a[2] ? a[1] : a[2], ttnet::va::kPatchMax);
-       if (a[3] > 32) return fail("patch.sweep", "stride=%lld is above %lld", a[3], 32);
-       o[0] = patch_positions((int)a[1], (int)a[3]); o[1] = patch_positions((int)a[2], (int)a[3]);
-       const long long tasks = a[0] * o[0] * o[1];
-       o[2] = patch_launches(tasks); o[3] = patch_launch_size(tasks, 0); o[4] = patch_launch_size(tasks, o[2] - 1); o[5] = kPatchGrid;
-       return 0;
-     }},
+    // ---- patch sweep and patch search: the same cut
+    {"patch.sweep", 4, {{"n", 'n'}, {"patch_h", 'd'}, {"patch_w", 'd'}, {"stride", 'd'}}, 6, [](const I *a, I *o) { return patch_cut("patch.sweep", a, o); }},   // -> positions down, across, launches, workgroups of the first, of the last, at most
+    {"patch.attack", 4, {{"n", 'n'}, {"patch_h", 'd'}, {"patch_w", 'd'}, {"stride", 'd'}}, 6, [](const I *a, I *o) { return patch_cut("patch.attack", a, o); }},
 };
 
 }  // namespace

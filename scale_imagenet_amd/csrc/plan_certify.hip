@@ -1,5 +1,6 @@
 // libttnet.so -- the plan's certificate and attack entries (vAlexnet): ttnet_certify_u8, ttnet_certify_box_u8,
-// ttnet_certify_patch_u8, ttnet_attack_propose_u8, ttnet_attack_select_u8 of include/ttnet.h.
+// ttnet_certify_patch_u8, ttnet_attack_patch_u8, ttnet_patch_paste_u8, ttnet_attack_propose_u8, ttnet_attack_select_u8 of
+// include/ttnet.h.
 //
 // Host code only: argument checks, the state derived once per loaded checkpoint (prepare_certify) and the argument blocks
 // of the kernels in certify.hip and attack.hip.
@@ -177,6 +178,29 @@ int certify_run(ttnet_plan *pl, const CertifyArgs &a, uint64_t *planes_dev, hipS
   return TTNET_OK;
 }
 
+// the ranges the patch entries share, under the entry's name
+int patch_ranges(const char *who, int patch_h, int patch_w, int stride, int amp) {
+  if (patch_h < 1 || patch_h > va::kPatchMax || patch_w < 1 || patch_w > va::kPatchMax || stride < 1 || stride > 32 || amp < 1 || amp > 255)
+    return refused(TTNET_E_INVALID, "%s: patch %d x %d (1..8 each), stride %d (1..32), amp %d (1..255)", who, patch_h, patch_w, stride, amp);
+  return TTNET_OK;
+}
+
+// the argument block of the patch sweep and of the patch search up to their outputs: the clean pass and the geometry
+int patch_fill(ttnet_plan *pl, const CertifyCall &c, ttnet_plan::Lane &L, int patch_h, int patch_w, int stride, int amp, hipStream_t s, PatchArgs &p) {
+  TT_TRY(certify_fill(pl, c, L, s, p.clean));
+  // per image of max_batch: the clean pass's record (4 doubles) and the unknown part of its sums (10)
+  if (!L.patch_base) TT_TRY(dev_alloc(pl, &L.patch_base, (size_t)pl->desc.max_batch * (4 + va::kClasses), false));
+  p.clean.rows = L.patch_base;
+  p.clean.sums_un = L.patch_base + (size_t)pl->desc.max_batch * 4;
+  p.patch_h = patch_h;
+  p.patch_w = patch_w;
+  p.stride = stride;
+  p.amp = amp;
+  p.py = part::patch_positions(patch_h, stride);
+  p.px = part::patch_positions(patch_w, stride);
+  return TTNET_OK;
+}
+
 // what the two attack entries share: the variant, the plan's state and the batch size
 int attack_ready(ttnet_plan *pl, const void *a, int64_t n, const void *b, const char *who) {
   if (pl && pl->path != GatePath::VAlexnet)
@@ -222,27 +246,55 @@ int ttnet_certify_patch_u8(ttnet_plan *pl, int lane, const uint8_t *x_nhwc_dev, 
   const CertifyCall c{"ttnet_certify_patch_u8", lane, x_nhwc_dev, nullptr, n, classes_dev, 0.0, enum_bits, min_margin, rows_dev, map_dev};
   TT_TRY(certify_ready(pl, c));
   if (!classes_dev || !map_dev) return refused(TTNET_E_INVALID, "null argument");
-  if (patch_h < 1 || patch_h > va::kPatchMax || patch_w < 1 || patch_w > va::kPatchMax || stride < 1 || stride > 32 || amp < 1 || amp > 255)
-    return refused(TTNET_E_INVALID, "certify_patch: patch %d x %d (1..8 each), stride %d (1..32), amp %d (1..255)", patch_h, patch_w, stride, amp);
+  TT_TRY(patch_ranges("certify_patch", patch_h, patch_w, stride, amp));
   ttnet_plan::Lane *L = nullptr;
   TT_TRY(certify_check(pl, c, &L));
   PatchArgs p{};
-  TT_TRY(certify_fill(pl, c, *L, s, p.clean));
-  // per image of max_batch: the clean pass's record (4 doubles) and the unknown part of its sums (10)
-  if (!L->patch_base) TT_TRY(dev_alloc(pl, &L->patch_base, (size_t)pl->desc.max_batch * (4 + va::kClasses), false));
-  p.clean.rows = L->patch_base;
-  p.clean.sums_un = L->patch_base + (size_t)pl->desc.max_batch * 4;
-  p.patch_h = patch_h;
-  p.patch_w = patch_w;
-  p.stride = stride;
-  p.amp = amp;
-  p.py = part::patch_positions(patch_h, stride);
-  p.px = part::patch_positions(patch_w, stride);
+  TT_TRY(patch_fill(pl, c, *L, patch_h, patch_w, stride, amp, s, p));
   p.map = map_dev;
   p.rows = rows_dev;
   pl->timing_used = 0;
   TT_TIMED(pl, "patch.base", s, launch_certify_patch(p, kPatchBase, s));
   TT_TIMED(pl, "patch.sweep", s, launch_certify_patch(p, kPatchSweep, s));
+  return TTNET_OK;
+}
+
+int ttnet_attack_patch_u8(ttnet_plan *pl, int lane, const uint8_t *x_nhwc_dev, int64_t n, const int32_t *classes_dev, int patch_h, int patch_w,
+                          int stride, int amp, int rounds, double min_margin, void *map_dev, uint8_t *fills_dev, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const CertifyCall c{"ttnet_attack_patch_u8", lane, x_nhwc_dev, nullptr, n, classes_dev, 0.0, 0, min_margin, map_dev, nullptr};
+  TT_TRY(certify_ready(pl, c));
+  if (!classes_dev || !fills_dev) return refused(TTNET_E_INVALID, "null argument");
+  TT_TRY(patch_ranges("attack_patch", patch_h, patch_w, stride, amp));
+  if (rounds < 1 || rounds > 4) return refused(TTNET_E_INVALID, "attack_patch: rounds = %d (1..4)", rounds);
+  if ((uintptr_t)fills_dev & 3u) return refused(TTNET_E_INVALID, "attack_patch: the fills must be 4-byte aligned");
+  ttnet_plan::Lane *L = nullptr;
+  TT_TRY(certify_check(pl, c, &L));
+  AttackPatchArgs a{};
+  TT_TRY(patch_fill(pl, c, *L, patch_h, patch_w, stride, amp, s, a.sweep));
+  a.rounds = rounds;
+  a.min_margin = min_margin;
+  a.wsum = va_state(pl).wsum;
+  a.map = map_dev;
+  a.fills = fills_dev;
+  pl->timing_used = 0;
+  TT_TIMED(pl, "patch.base", s, launch_certify_patch(a.sweep, kPatchBase, s));
+  TT_TIMED(pl, "patch.attack", s, launch_attack_patch(a, s));
+  return TTNET_OK;
+}
+
+int ttnet_patch_paste_u8(ttnet_plan *pl, const uint8_t *x_nhwc_dev, int64_t n, int patch_h, int patch_w, int stride, const uint8_t *fills_dev,
+                         const int64_t *tasks_dev, int64_t m, uint8_t *out_nhwc_dev, void *stream) {
+  TT_TRY(attack_ready(pl, x_nhwc_dev, n, out_nhwc_dev, "ttnet_patch_paste_u8"));
+  if (!fills_dev || !tasks_dev) return refused(TTNET_E_INVALID, "null argument");
+  TT_TRY(patch_ranges("patch_paste", patch_h, patch_w, stride, 1));
+  if (m < 1 || m > 0x7FFFFFFFll) return refused(TTNET_E_INVALID, "patch_paste: m = %lld (1..2^31 - 1)", (long long)m);
+  if ((((uintptr_t)x_nhwc_dev | (uintptr_t)fills_dev | (uintptr_t)out_nhwc_dev) & 3u) || ((uintptr_t)tasks_dev & 7u))
+    return refused(TTNET_E_INVALID, "patch_paste: the images and fills must be 4-byte aligned, the tasks 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  TT_HIP(hipSetDevice(pl->device));
+  pl->timing_used = 0;
+  TT_TIMED(pl, "patch.paste", s, launch_patch_paste(x_nhwc_dev, n, patch_h, patch_w, stride, fills_dev, tasks_dev, m, out_nhwc_dev, s));
   return TTNET_OK;
 }
 

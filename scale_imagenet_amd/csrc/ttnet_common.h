@@ -437,6 +437,20 @@ int launch_attack_wsum(const float *w, double *wsum, hipStream_t s);
 int launch_attack_propose(const AttackProposeArgs &a, hipStream_t s);
 int launch_attack_select(const uint8_t *cand, const float *logits, int n, int n_cand, const int32_t *classes, float min_margin,
                          const uint8_t *x0, uint8_t *xcur, void *rows, int32_t *worst, int32_t *active, int round, hipStream_t s);
+// the patch search (attack.hip; include/ttnet.h: ttnet_attack_patch_u8).  `sweep.clean` is the per-image pass of the patch
+// sweep ("patch.base", launched by launch_certify_patch); the search reads what it left.  sweep.map / sweep.rows are unused.
+struct AttackPatchArgs {
+  PatchArgs sweep;
+  int rounds;
+  double min_margin;
+  const double *wsum;       // [64][3][5][5]
+  void *map;                // [n][py * px] records of 16 bytes
+  uint8_t *fills;           // [n][py * px][192]
+};
+int launch_attack_patch(const AttackPatchArgs &a, hipStream_t s);
+// out[k] = image tasks[k] / P with fill tasks[k] pasted at position tasks[k] % P; all zero for a task outside [0, n P)
+int launch_patch_paste(const uint8_t *x, long long n, int patch_h, int patch_w, int stride, const uint8_t *fills, const int64_t *tasks,
+                       long long m, uint8_t *out, hipStream_t s);
 int launch_cp_to_rp(const uint16_t *cp, uint64_t *rp, int n, int C, int H, int W, hipStream_t s);
 int launch_rp_to_cp(const uint64_t *rp, uint16_t *cp, int n, int C, int H, int W, hipStream_t s);
 // feature planes (fragment order) -> float32 [n][(16g+k)*PP + pp] (reference Flatten order)

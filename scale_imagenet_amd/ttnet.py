@@ -377,6 +377,13 @@ class _TTNetBase(nn.Module):
         from . import attack
         return attack.attack_u8(self, x_u8, classes, eps, rounds, min_margin, lane, planes)
 
+    def attack_patch_u8(self, x_u8: torch.Tensor, classes, patch=(1, 1), stride: int = 1, amp: int = 255, rounds: int = 2,
+                        min_margin: float = 0.0, confirm: str = "all", confirm_slack: float = 1e-5, lane: int = 0):
+        """Falsified patch robustness (vAlexnet only): per position of ``certify_patch_u8`` a search for a uint8 fill of the patch
+        on which ``forward_u8`` no longer gives ``classes[i]``.  See ``scale_imagenet_amd.attack.attack_patch_u8``."""
+        from . import attack
+        return attack.attack_patch_u8(self, x_u8, classes, patch, stride, amp, rounds, min_margin, confirm, confirm_slack, lane)
+
     def export_truth_tables(self, block_name: str, out_dir: str, block: int = 0, sub_block: int = 0, filters=None,
                             max_expr_bits: int = 9, usage=None, minimiser: str = "sympy", rounds: int = 0,
                             min_count: int = 1):
