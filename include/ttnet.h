@@ -169,7 +169,9 @@ int ttnet_forward_u8(ttnet_plan *plan, int lane, const uint8_t *x_nhwc_dev, int6
  * offsets int(round((size - crop) / 2.0))).  Not bound to a plan.  Asynchronous on `stream` (one kernel; the first call with a
  * geometry uploads its coefficient tables synchronously and keeps them for the life of the process).  src must be 16-byte
  * aligned, dst 4-byte aligned, crop * 3 a multiple of 4, n <= 65535.  Byte-identical to Pillow 12.x on the committed fixture tests/golden/ref_resize.npz
- * (Pillow's own outputs for seeded images of nine geometries); torchvision is not importable where this is
+ * (Pillow's own outputs for seeded images of nine geometries) and on tests/golden/ref_resize_paths.json (every tap-count
+ * instantiation, the buffer's last partial 16-byte piece, short last tiles, other resize / crop pairs, both sides of the size
+ * bound below); torchvision is not importable where this is
  * built, so its output-size and crop-offset rules are restated.
  * Size bound: a workgroup keeps the intermediate rows of its 16 output rows in LDS, so large images are refused
  * (TTNET_E_UNSUPPORTED, beyond about 2650 px on the shorter side at resize 256 / crop 224: 2592 x 3888 is accepted,
@@ -193,8 +195,10 @@ typedef struct ttnet_image_desc {
  *     resize >= crop (no image can then fall short of the crop), 1 <= n <= 65535.
  *   - max_h / max_w bound every image's h / w; they size the LDS of a workgroup (which does not grow with the
  *     scale factor beyond the coefficient tables: about 100 KB at 8192 x 8192, resize 256 / crop 224).  Bounds
- *     the kernel cannot serve are refused here with TTNET_E_UNSUPPORTED (at 256 / 224: beyond about 9200 px on
- *     the shorter of max_h, max_w); an image is never refused on its own.
+ *     the kernel cannot serve are refused here with TTNET_E_UNSUPPORTED (at 256 / 224: min(max_h, max_w) = 9274 is
+ *     accepted and 9275 is not -- a staged input row of the crop must fit 6 x 256 16-byte pieces;
+ *     tests/test_resize_paths_cpu.py derives it); an image is never refused on its own.  Crops other than 224 (up to 684,
+ *     three dword columns per thread) are pinned to Pillow by tests/golden/ref_resize_paths.json.
  *   - a descriptor with h outside [1, max_h], w outside [1, max_w], a negative offset or bytes ending past
  *     src_bytes yields a zero crop and is counted in *bad_dev (int32, device memory, added to, never cleared) when
  *     bad_dev is not NULL.  Whatever the descriptors hold, the kernel reads nothing outside the source buffer and

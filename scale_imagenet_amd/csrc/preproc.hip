@@ -12,7 +12,10 @@
 //
 // Parity: pinned to Pillow 12.x -- tests/golden/ref_resize.npz holds Pillow's own outputs for seeded images of
 // nine geometries (oracle/gen_golden.py resize, run in the build container where Pillow imports) and
-// tests/test_gpu_preprocess.py compares these kernels with it byte for byte.  torchvision is not importable:
+// tests/test_gpu_preprocess.py compares these kernels with it byte for byte; tests/golden/ref_resize_paths.json
+// (tools/gen_resize_paths_fixture.py) holds Pillow's hashes on the geometries that reach every tap-count instantiation, the
+// last partial piece, both sides of the size bounds and the WIDE ragged kernel (tests/test_gpu_resize_paths.py).
+// torchvision is not importable:
 // its output-size and crop-offset rules are restated.
 
 #include <math.h>

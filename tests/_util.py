@@ -75,6 +75,26 @@ def resize_test_images(n: int, h: int, w: int, seed: int) -> np.ndarray:
     return np.clip(img, 0, 255).astype(np.uint8)
 
 
+def oracle_views(img, descs, crop):
+    """The views `descs` ([image, flags, bx, by, bw, bh, nw, nh, x0, y0], all of `img`) by the numpy oracle; a box is
+    resized once however many windows are cut from it."""
+    from oracle import pil_resize as PR
+    resized, out = {}, []
+    for d in descs:
+        _, flags, bx, by, bw, bh, nw, nh, x0, y0 = (int(v) for v in d[:10])
+        key = (bx, by, bw, bh, nw, nh)
+        if key not in resized:
+            r = img[by:by + bh, bx:bx + bw]
+            if nw != bw:
+                r = PR.resample_axis(r, nw, 1)             # horizontal pass first
+            if nh != bh:
+                r = PR.resample_axis(r, nh, 0)
+            resized[key] = r
+        v = resized[key][y0:y0 + crop, x0:x0 + crop]
+        out.append(np.ascontiguousarray(v[:, ::-1] if flags & 1 else v))
+    return out
+
+
 @lru_cache(maxsize=None)
 def golden_resize():
     with np.load(os.path.join(GOLD, "ref_resize.npz")) as z:

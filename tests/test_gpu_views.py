@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from _util import GOLD, args_for, jpeg_bytes, ragged_images, resize_test_images, sha, spec_and_state
+from _util import GOLD, args_for, jpeg_bytes, oracle_views, ragged_images, resize_test_images, sha, spec_and_state
 from oracle import pil_resize as PR
 from scale_imagenet_amd import _lib, jpeg, preprocess, ttnet
 from scale_imagenet_amd.evaluate import evaluate, topk_rows_host
@@ -23,25 +23,6 @@ FAMILIES = (("center", 1), ("flip", 2), ("five", 5), ("ten", 10))
 def _fixture():
     with open(os.path.join(GOLD, "ref_views.json")) as f:
         return json.load(f)
-
-
-def oracle_views(img, descs, crop):
-    """The views `descs` ([image, flags, bx, by, bw, bh, nw, nh, x0, y0], all of `img`) by the numpy oracle; a box is
-    resized once however many windows are cut from it."""
-    resized, out = {}, []
-    for d in descs:
-        _, flags, bx, by, bw, bh, nw, nh, x0, y0 = (int(v) for v in d[:10])
-        key = (bx, by, bw, bh, nw, nh)
-        if key not in resized:
-            r = img[by:by + bh, bx:bx + bw]
-            if nw != bw:
-                r = PR.resample_axis(r, nw, 1)             # horizontal pass first
-            if nh != bh:
-                r = PR.resample_axis(r, nh, 0)
-            resized[key] = r
-        v = resized[key][y0:y0 + crop, x0:x0 + crop]
-        out.append(np.ascontiguousarray(v[:, ::-1] if flags & 1 else v))
-    return out
 
 
 def sizes_of(ims):
