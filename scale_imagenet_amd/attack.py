@@ -278,79 +278,105 @@ def reached_features() -> np.ndarray:
     return np.where(valid != 0, (fc * SIDE + oy) * SIDE + ox, -1)
 
 
+def _table_rows(words):
+    """``(T1 [64], T2 [64], T3 [64, 4])`` of ``words = [table_words(conv1), (conv2), (conv3)]``: a table per output channel."""
+    return words[0][:, 0, 0], words[1][:, 0, 0], words[2].reshape(STEM_CH, 4)
+
+
+def gains_listed(A: np.ndarray, T, pad: np.ndarray, pi, ch, y, x, c, j, feat=None):
+    """Flip gains float64 ``[B]`` of the listed stem bits ``(pi, ch, y, x)`` -- ``pi``: the plane of ``pad`` each lives in; ``pad``:
+    int64 ``[n, 64, 12, 12]``, the stem bits with the zero padding around them -- and bool ``[B, 21]``, which of the 21 features
+    change: for bit s the change of ``logit_c - logit_j`` (``c``, ``j`` per listed bit or scalars, through ``A`` ``[10, 30976]``) when
+    s alone flips.  The sum runs over the at most 21 features whose windows hold s, in the order of ``valexnet_block.reach``: the
+    feature's table (``T = _table_rows(words)``) read at its index with input p flipped against the feature before the flip --
+    ``feat`` ``[n, 256, 11, 11]`` where given (what a forward produced), else the table at the unflipped index -- and every
+    term is +D_f, -D_f or nothing."""
+    def bit(T, i):
+        return ((T >> i.astype(np.uint64)) & np.uint64(1)).astype(np.int64)
+    g = np.zeros(pi.size)
+    changed = np.zeros((pi.size, N_REACH), dtype=bool)
+    for t in range(N_REACH):
+        valid, fc, oy, ox, p = reach(ch, y, x, t)
+        valid = np.broadcast_to(np.asarray(valid, dtype=bool), pi.shape)
+        oy, ox = np.where(valid, oy, 0), np.where(valid, ox, 0)            # (a window outside the plane: any entry, masked below)
+        kind = 0 if t < 6 else 1 if t < 12 else 2 if t < 20 else 3
+        if kind < 2:                                                       # conv1 / conv2: the channel's 64-entry table
+            kw = (2, 3)[kind]
+            idx = sum(pad[pi, ch, oy + q // kw, ox + q % kw] << q for q in range(6))
+            new, old = bit(T[kind][ch], idx ^ (1 << p)), bit(T[kind][ch], idx)
+        elif kind == 2:                                                    # conv3: output fc of the group, four words
+            idx = sum(pad[pi, ch // 8 * 8 + q, y + 1, x + 1] << q for q in range(8))
+            i3 = idx ^ (1 << p)
+            new, old = bit(T[2][fc - 128, i3 >> 6], i3 & 63), bit(T[2][fc - 128, idx >> 6], idx & 63)
+        else:                                                              # out4 carries the bit itself
+            old = pad[pi, ch, y + 1, x + 1]
+            new = 1 - old
+        if feat is not None and kind < 3:
+            old = feat[pi, fc, oy, ox]
+        d = np.where(valid, new - old, 0)
+        f = (fc * SIDE + oy) * SIDE + ox
+        Df = A[c, f] - A[j, f]
+        g = g + np.where(d == 1, Df, np.where(d == -1, -Df, 0.0))
+        changed[:, t] = d != 0
+    return g, changed
+
+
 def gains_cpu(A: np.ndarray, words, stem_bits: np.ndarray, feat_bits: np.ndarray, unknown: np.ndarray, classes, worst,
               return_changed: bool = False):
-    """Flip gains float64 ``[n, 64, 10, 10]``: for every stem bit s marked in ``unknown`` the change of ``logit_c -
-    logit_j`` (c = ``classes[i]``, j = ``worst[i]``, through ``A`` ``[10, 30976]``) when s alone flips, zero elsewhere and
-    for an image whose c or j is no class.  ``stem_bits`` ``[n, 64, 10, 10]``, ``feat_bits`` ``[n, 256, 11, 11]`` (what the
-    forward produced: y before the flip), ``words = [table_words(conv1), (conv2), (conv3)]``.  The sum runs over the at most
-    21 features whose windows hold s, in the order of ``valexnet_block.reach``: the feature's table read at its index with
-    input p flipped, and every term is +D_f, -D_f or nothing.  ``return_changed``: also bool ``[n, 21, 64, 10, 10]``, which of
-    the 21 features change."""
+    """Flip gains float64 ``[n, 64, 10, 10]``: ``gains_listed`` on every stem bit marked in ``unknown`` (c = ``classes[i]``, j =
+    ``worst[i]``), zero elsewhere and for an image whose c or j is no class.  ``stem_bits`` ``[n, 64, 10, 10]``, ``feat_bits``
+    ``[n, 256, 11, 11]`` (what the forward produced: y before the flip), ``words = [table_words(conv1), (conv2), (conv3)]``.
+    ``return_changed``: also bool ``[n, 21, 64, 10, 10]``, which of the 21 features change."""
     stem_bits = np.asarray(stem_bits).astype(np.int64)
-    feat = np.asarray(feat_bits).astype(np.int64)
     n = stem_bits.shape[0]
     classes, worst = np.asarray(classes).astype(np.int64), np.asarray(worst).astype(np.int64)
     ok = (classes >= 0) & (classes < 10) & (worst >= 0) & (worst < 10)
-    c, j = np.where(ok, classes, 0), np.where(ok, worst, 0)
-    D = (A[c] - A[j]).reshape(n, FEAT_CH, SIDE, SIDE)
-    idx = window_indices(stem_bits)                                        # [n, 64, 10, 11], [n, 64, 11, 10], [n, 8, 10, 10]
-    T1, T2, T3 = words[0][:, 0, 0], words[1][:, 0, 0], words[2]              # [64], [64], [8, 8, 4]
-    ch, py, px = np.meshgrid(np.arange(STEM_CH), np.arange(POOL), np.arange(POOL), indexing="ij")
+    pi, ch, y, x = np.nonzero(np.asarray(unknown).astype(bool) & ok[:, None, None, None])
     g = np.zeros((n, STEM_CH, POOL, POOL))
     changed = np.zeros((n, N_REACH, STEM_CH, POOL, POOL), dtype=bool)
+    g[pi, ch, y, x], changed[pi, :, ch, y, x] = gains_listed(A, _table_rows(words), np.pad(stem_bits, ((0, 0), (0, 0), (1, 1), (1, 1))), pi, ch,
+                                                             y, x, classes[pi], worst[pi], np.asarray(feat_bits).astype(np.int64))
+    return (g, changed) if return_changed else g
 
-    def bit(T, i):
-        return ((T >> i.astype(np.uint64)) & np.uint64(1)).astype(np.int64)
-    for t, (valid, fc, oy, ox, p) in enumerate(zip(*reached())):
-        valid = valid != 0
-        oy, ox = np.where(valid, oy, 0), np.where(valid, ox, 0)            # (a window outside the plane: any entry, masked below)
-        kind, old = int(fc[0, 0, 0]) // 64, feat[:, fc, oy, ox]
-        if kind < 2:                                                       # conv1 / conv2: the channel's 64-entry table
-            new = bit((T1, T2)[kind][ch], idx[kind][:, ch, oy, ox] ^ (1 << p))
-        elif kind == 2:                                                    # conv3: output fc of the group, four words
-            i3 = idx[2][:, ch // 8, py, px] ^ (1 << p)
-            w = np.broadcast_to(T3[(fc - 128) // 8, fc % 8], i3.shape + (4,))
-            new = bit(np.take_along_axis(w, (i3 >> 6)[..., None], axis=-1)[..., 0], i3 & 63)
-        else:                                                              # out4 carries the bit itself
-            new, old = 1 - stem_bits, stem_bits
-        d = np.where(valid, new - old, 0)
-        Df = D[:, fc, oy, ox]
-        g = g + np.where(d == 1, Df, np.where(d == -1, -Df, 0.0))
-        changed[:, t] = d != 0
-    keep = np.asarray(unknown).astype(bool) & ok[:, None, None, None]
-    g = np.where(keep, g, 0.0)
-    return (g, changed & keep[:, None]) if return_changed else g
+
+def _cells_of(v: np.ndarray):
+    """The two cells whose 5-wide field may hold row / column v (ascending), v's offset in each, and whether it does."""
+    hi = (v + 1) // 3
+    cells = np.stack([hi - 1, hi], axis=-1)
+    offs = v[..., None] - 3 * cells + 1
+    valid = (cells >= 0) & (cells <= 9) & (offs >= 0) & (offs <= 4)
+    return np.clip(cells, 0, 9), np.clip(offs, 0, 4), valid
+
+
+def scores_rect(wt, Wsum: np.ndarray, y0, x0, h: int, w: int) -> np.ndarray:
+    """Scores float64 ``[2 modes, B, h, w, 3]`` of the bytes of the h x w rectangle at ``(y0[i], x0[i])`` of image i from the pushes
+    ``wt[m]`` ``[B, 64, 10, 10]`` of mode m: ``score[y][x][k] = sum_s wt_s Wsum[ch_s][k][y - 3 py_s + 1][x - 3 px_s + 1]`` over the stem
+    bits whose 5 x 5 field holds the pixel, ch ascending, then py, then px; products and sums rounded one by one.  A cell that does
+    not hold the pixel gets the weight zero; its term is then +-0, which changes no sum (the sums start at +0 and never become
+    -0), and a channel without a push is skipped for the same reason."""
+    B = y0.size
+    cy, oy, vy = _cells_of(y0[:, None] + np.arange(h)[None, :])            # [B, h, 2]
+    cx, ox, vx = _cells_of(x0[:, None] + np.arange(w)[None, :])
+    out = np.zeros((2, B, h, w, 3))
+    b = np.arange(B)[:, None, None]
+    for ch in np.flatnonzero((wt[1] != 0).reshape(B, STEM_CH, -1).any(axis=(0, 2))):
+        for a_ in range(2):
+            for b_ in range(2):
+                v = vy[:, :, a_][:, :, None] & vx[:, :, b_][:, None, :]
+                W = np.where(v[..., None], Wsum[ch][:, oy[:, :, a_][:, :, None], ox[:, :, b_][:, None, :]].transpose(1, 2, 3, 0), 0.0)
+                for m in range(2):
+                    out[m] += wt[m][b, ch, cy[:, :, a_][:, :, None], cx[:, :, b_][:, None, :]][..., None] * W
+    return out
 
 
 def scores_cpu(gains: np.ndarray, stem_bits: np.ndarray, unknown: np.ndarray, bn_scale: np.ndarray, Wsum: np.ndarray) -> np.ndarray:
     """Pixel scores float64 ``[n, 2 modes, 32, 32, 3]``.  The push of stem bit s is ``wt_s = -g_s (bit_s == 0 ? +1 : -1)
     sign(bn_scale[ch])``: in mode 0 for the unknown bits with ``g_s < 0`` (zero elsewhere), in mode 1 for every unknown bit.
-    ``score[y][x][k] = sum_s wt_s Wsum[ch_s][k][y - 3 py_s + 1][x - 3 px_s + 1]`` over the bits whose 5 x 5 field holds the
-    pixel, ch ascending, then py, then px; products and sums rounded one by one."""
-    unknown = np.asarray(unknown).astype(bool)
+    The scores are ``scores_rect`` of the whole image."""
     sgn = np.where(np.asarray(stem_bits) == 0, 1.0, -1.0) * np.where(bn_scale >= 0, 1.0, -1.0)[None, :, None, None]
-    wt1 = np.where(unknown, -gains * sgn, 0.0)
-    wt = (np.where(gains < 0, wt1, 0.0), wt1)
-    n = gains.shape[0]
-    y = np.arange(32)
-    hi = (y + 1) // 3                                                      # the later cell whose field holds row / column y ..
-    cells = np.stack([hi - 1, hi], axis=1)                                 # .. and the one before it, ascending
-    offs = y[:, None] - 3 * cells + 1
-    valid = (cells >= 0) & (cells <= 9) & (offs >= 0) & (offs <= 4)
-    cells, offs = np.clip(cells, 0, 9), np.clip(offs, 0, 4)
-    # per (a, b): the pushes and the kernels gathered to the pixels.  A cell that does not hold the pixel gets the weight
-    # zero; its term is then +-0, which changes no sum (the sums start at +0 and never become -0).
-    ab = [(a, b) for a in range(2) for b in range(2)]
-    W = [np.where((valid[:, a][:, None] & valid[:, b][None, :])[None, :, :, None],
-                  Wsum[:, :, offs[:, a]][:, :, :, offs[:, b]].transpose(0, 2, 3, 1), 0.0) for a, b in ab]      # [64, 32, 32, 3]
-    G = [[w[:, :, cells[:, a]][:, :, :, cells[:, b]] for a, b in ab] for w in wt]                              # [n, 64, 32, 32]
-    out = np.zeros((2, n, 32, 32, 3))
-    for ch in range(64):
-        for q in range(4):
-            for m in range(2):
-                out[m] += G[m][q][:, ch, :, :, None] * W[q][ch][None]
-    return np.ascontiguousarray(out.transpose(1, 0, 2, 3, 4))
+    wt1 = np.where(np.asarray(unknown).astype(bool), -gains * sgn, 0.0)
+    zero = np.zeros(gains.shape[0], dtype=np.int64)
+    return np.ascontiguousarray(scores_rect((np.where(gains < 0, wt1, 0.0), wt1), Wsum, zero, zero, 32, 32).transpose(1, 0, 2, 3, 4))
 
 
 def candidates_cpu(scores: np.ndarray, x0: np.ndarray, xcur: np.ndarray, levels: int, active=None) -> np.ndarray:
@@ -572,15 +598,6 @@ def hash_corner(pos, rnd: int, slot: int, byte) -> np.ndarray:
     return ((v >> np.uint64(16)) & np.uint64(1)).astype(bool)
 
 
-def _cells_of(v: np.ndarray):
-    """The two cells whose 5-wide field may hold row / column v (ascending), v's offset in each, and whether it does."""
-    hi = (v + 1) // 3
-    cells = np.stack([hi - 1, hi], axis=-1)
-    offs = v[..., None] - 3 * cells + 1
-    valid = (cells >= 0) & (cells <= 9) & (offs >= 0) & (offs <= 4)
-    return np.clip(cells, 0, 9), np.clip(offs, 0, 4), valid
-
-
 def _reached_rect(kind: int, r0, rn, q0, qn):
     """``reached_rect`` of csrc/certify_lookup.h on arrays: first row, rows, first column, columns of branch ``kind``."""
     r1, q1 = r0 + rn - 1, q0 + qn - 1
@@ -599,58 +616,20 @@ class _PatchTwin:
         self.A = head_cpu(state)                                           # [10, F]: D_f in the device's bytes
         self.c0 = CF.effective_head(state)[1]
         self.words = _words(tables)
-        self.T = (self.words[0][:, 0, 0], self.words[1][:, 0, 0], self.words[2].reshape(64, 4))
+        self.T = _table_rows(self.words)
         self.Wsum = wsum_cpu(state)
         self.scale = fold_bn(state, "features.2")[0]
         self.slack = CF.stem_slack(state, mean, std)[None, :, None, None]
         self.a, self.off = CF._norm(mean, std)
         self.tol = 1e-9 * float(np.abs(self.A).sum())
 
-    # gains of the listed stem bits (pi: the plane of `pad` each lives in; pad: int64 [B, 64, 12, 12], the definite bits with the
-    # zero padding around them), in gains_cpu's order and bytes
     def gains(self, pad, pi, ch, y, x, c, j):
-        def bit(T, i):
-            return ((T >> i.astype(np.uint64)) & np.uint64(1)).astype(np.int64)
-        g = np.zeros(pi.size)
-        for t in range(N_REACH):
-            valid, fc, oy, ox, p = reach(ch, y, x, t)
-            valid = np.broadcast_to(np.asarray(valid, dtype=bool), pi.shape)
-            oy, ox = np.where(valid, oy, 0), np.where(valid, ox, 0)
-            kind = 0 if t < 6 else 1 if t < 12 else 2 if t < 20 else 3
-            if kind < 2:
-                kw = (2, 3)[kind]
-                idx = sum(pad[pi, ch, oy + q // kw, ox + q % kw] << q for q in range(6))
-                new, old = bit(self.T[kind][ch], idx ^ (1 << p)), bit(self.T[kind][ch], idx)
-            elif kind == 2:
-                idx = sum(pad[pi, ch // 8 * 8 + q, y + 1, x + 1] << q for q in range(8))
-                i3 = idx ^ (1 << p)
-                new, old = bit(self.T[2][fc - 128, i3 >> 6], i3 & 63), bit(self.T[2][fc - 128, idx >> 6], idx & 63)
-            else:
-                old = pad[pi, ch, y + 1, x + 1]
-                new = 1 - old
-            d = np.where(valid, new - old, 0)
-            f = (fc * SIDE + oy) * SIDE + ox
-            Df = self.A[c, f] - self.A[j, f]
-            g = g + np.where(d == 1, Df, np.where(d == -1, -Df, 0.0))
-        return g
+        """``gains_listed`` on the twin's head and tables, the old feature bits from the tables: float64 ``[B]``."""
+        return gains_listed(self.A, self.T, pad, pi, ch, y, x, c, j)[0]
 
-    # scores of the patch bytes [2, B, h, w, 3] from dense pushes wt[m] [B, 64, 10, 10], in scores_cpu's order and bytes
     def scores(self, wt, y0, x0, h, w):
-        B = y0.size
-        cy, oy, vy = _cells_of(y0[:, None] + np.arange(h)[None, :])        # [B, h, 2]
-        cx, ox, vx = _cells_of(x0[:, None] + np.arange(w)[None, :])
-        out = np.zeros((2, B, h, w, 3))
-        b = np.arange(B)[:, None, None]
-        live = np.flatnonzero((wt[1] != 0).reshape(B, STEM_CH, -1).any(axis=(0, 2)))
-        for ch in live:                                                    # (a channel without a push adds zeros only)
-            for a_ in range(2):
-                for b_ in range(2):
-                    v = vy[:, :, a_][:, :, None] & vx[:, :, b_][:, None, :]
-                    W = np.where(v[..., None], self.Wsum[ch][:, oy[:, :, a_][:, :, None], ox[:, :, b_][:, None, :]].transpose(1, 2, 3, 0), 0.0)
-                    for m in range(2):
-                        G = wt[m][b, ch, cy[:, :, a_][:, :, None], cx[:, :, b_][:, None, :]]
-                        out[m] += G[..., None] * W
-        return out
+        """``scores_rect`` on the twin's summed kernels: ``[2, B, h, w, 3]``."""
+        return scores_rect(wt, self.Wsum, y0, x0, h, w)
 
 
 def _patch_image_cpu(tw: _PatchTwin, x: np.ndarray, c: int, h, w, stride, amp, rounds, min_margin, chunk: int = 128):

@@ -34,12 +34,12 @@ def build_lib(force: bool = False, verbose: bool = True) -> str:
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, "ttnet_common.h"), os.path.join(HERE, "..", "include", "ttnet.h")]
-    included = {"gate_full.hip": [os.path.join(CSRC, "erf_table.inc")], "certify.hip": [os.path.join(CSRC, "certify_stem_cell.inc")]}
+    included = {"gate_full.hip": [os.path.join(CSRC, "erf_table.inc")]}
     for src in ("gate_va.hip", "certify.hip", "attack.hip"):
         included[src] = included.get(src, []) + [os.path.join(CSRC, "va_block.h")]
     for src in ("certify.hip", "attack.hip"):
-        included[src] = included[src] + [os.path.join(CSRC, "certify_lookup.h")]
-    included["attack.hip"] = included["attack.hip"] + [os.path.join(CSRC, "certify_stem_cell.inc"), os.path.join(CSRC, "partition.h")]
+        included[src] = included[src] + [os.path.join(CSRC, n) for n in ("certify_lookup.h", "patch_position.h", "certify_stem_cell.inc")]
+    included["attack.hip"] = included["attack.hip"] + [os.path.join(CSRC, "partition.h")]
     for src in ("plan.hip", "plan_tables.hip", "plan_certify.hip"):
         included[src] = [os.path.join(CSRC, "plan.h")]      # (plan.h includes partition.h)
     for src in ("partition.hip", "plan.hip", "plan_tables.hip", "plan_certify.hip", "certify.hip", "stem.hip", "gate.hip", "gate_fused.hip", "gate_xs.hip", "gate_full.hip", "gate_va.hip"):

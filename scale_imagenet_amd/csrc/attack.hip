@@ -10,10 +10,13 @@
 //                          and becomes x_cur, the record is updated
 //   attack_patch_kernel    the patch search (ttnet_attack_patch_u8): one workgroup per (image, position); the movable stem bits
 //                          are those the position's box leaves unknown, a candidate fill is judged by its predicted margin
-//                          m_pred -- the stem cells of the patch's fields again at radius 0 (certify_stem_cell.inc), the
-//                          features they reach (feature3), the differences against the clean sums in the sweep's order --
-//                          and the gains, pushes and scores of the propose step choose the candidates
+//                          m_pred -- the steps of patch_position.h, which the certified sweep takes too, on a fill at radius
+//                          0 -- and the gains, pushes and scores of the propose step choose the candidates
 //   patch_paste_kernel     witnesses as images: a fill pasted into its image (ttnet_patch_paste_u8)
+//
+// The steps of a proposal are written once, for both searches: flip_gain and stem_push, cells_of, and candidate_byte (which states
+// the thresholds).  score_terms and block_max2 serve the propose kernel; the patch search keeps its own score loop and block
+// maximum, one byte per thread: with the shared forms it was 0.8 - 1.5 % slower (profiles/patch_steps_refactor.txt, section 4).
 //
 // Float64 sums in a fixed order (the build switches floating-point contraction off for every file), integer work, maxima:
 // the same input gives the same bytes, and the numpy twin (attack.py) the same bytes again.
@@ -22,6 +25,7 @@
 
 #include "certify_lookup.h"
 #include "partition.h"
+#include "patch_position.h"
 #include "ttnet_common.h"
 #include "va_block.h"
 
@@ -66,6 +70,96 @@ __device__ inline void cells_of(int v, int cell[2], int off[2]) {
   }
 }
 
+// The flip gain of stem bit (ch, py, px): the change of logit_c - logit_j when it alone flips.  row(ch, y) gives the 10 bits of a stem
+// row; old(kind, fc, oy, ox, at) the bit of feature (fc, oy, ox) of branch `kind` before the flip, `at` being its unflipped table
+// index.  The 21 features of va_block.h's reach(), in its order, written out as three nests: one loop over reach(ch, py, px, t)
+// gives the same sums but a propose step 12 - 17 % slower (profiles/va_block_refactor.txt, section 3).
+template <class RowFn, class OldFn>
+__device__ inline double flip_gain(int ch, int py, int px, RowFn row, OldFn old, uint64_t T1, uint64_t T2, const uint64_t *__restrict__ t3w,
+                                   const double *__restrict__ A, int c, int j) {
+  double g = 0.0;
+  auto term = [&](int fc, int oy, int ox, int ynew, int yold) {      // +D_f, -D_f or nothing
+    if (ynew != yold) {
+      const size_t f = (size_t)(fc * kPlane + oy * kSide + ox) * kClasses;
+      const double d = A[f + c] - A[f + j];
+      g += ynew > yold ? d : -d;
+    }
+  };
+  auto row1 = [&](int y) { return shifted_row(y, [&](int iy) { return row(ch, iy); }); };
+  for (int doy = -1; doy <= 1; ++doy) {                              // conv1: rows oy-1..oy+1, columns ox-1..ox; oy <= 9
+    const int oy = py + doy;
+    if (oy < 0 || oy >= kPool) continue;
+    const uint32_t l0 = row1(oy - 1), l1 = row1(oy), l2 = row1(oy + 1);
+    for (int dox = 0; dox <= 1; ++dox) {
+      const int ox = px + dox;
+      const uint32_t at = conv1_index(l0, l1, l2, ox), fl = at ^ (1u << ((1 - doy) * 2 + (1 - dox)));
+      term(ch, oy, ox, (int)((T1 >> fl) & 1ull), old(0, ch, oy, ox, at));
+    }
+  }
+  for (int doy = 0; doy <= 1; ++doy) {                               // conv2: rows oy-1..oy, columns ox-1..ox+1; ox <= 9
+    const int oy = py + doy;
+    const uint32_t l0 = row1(oy - 1), l1 = row1(oy);
+    for (int dox = -1; dox <= 1; ++dox) {
+      const int ox = px + dox;
+      if (ox < 0 || ox >= kPool) continue;
+      const uint32_t at = conv2_index(l0, l1, ox), fl = at ^ (1u << ((1 - doy) * 3 + (1 - dox)));
+      term(64 + ch, oy, ox, (int)((T2 >> fl) & 1ull), old(1, 64 + ch, oy, ox, at));
+    }
+  }
+  uint32_t grp[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) grp[k] = row((ch & ~7) + k, py);
+  const uint32_t at = conv3_index(grp, px), fl = at ^ (1u << (ch & 7));
+  for (int o = 0; o < 8; ++o) {                                      // conv3: the 8 outputs of the group
+    const int fc = 128 + (ch & ~7) + o;
+    term(fc, py, px, (int)((t3w[(fc - 128) * 4 + (fl >> 6)] >> (fl & 63u)) & 1ull), old(2, fc, py, px, at));
+  }
+  const int bit = (row(ch, py) >> px) & 1;
+  term(192 + ch, py, px, 1 - bit, bit);                              // out4 carries the bit itself
+  return g;
+}
+
+// the push of a stem bit of gain g in mode 1: towards the flip where the flip lowers the margin; sgn = the sign of the channel's bn_scale
+__device__ inline double stem_push(double g, int bit, double sgn) { return -g * (bit == 0 ? 1.0 : -1.0) * sgn; }
+
+// The terms of the score of the bytes of pixel (y, x): ch ascending, then the two row cells, then the two column cells.  A cell
+// (ch, py, px) with push(..) = w1 != 0 adds w1 W[25 k] to byte k in mode 1 and, where negative(..), in mode 0 too: add(w0, w1, W)
+// with W = the cell's summed kernel at the pixel's offset in its field.  (A zero term changes no sum: the sums are never -0.)
+template <class PushFn, class NegFn, class AddFn>
+__device__ inline void score_terms(int y, int x, const double *__restrict__ wsum, PushFn push, NegFn negative, AddFn add) {
+  int cy[2], oy[2], cx[2], ox[2];
+  cells_of(y, cy, oy);
+  cells_of(x, cx, ox);
+  for (int ch = 0; ch < kStemCh; ++ch)
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        if (oy[a] < 0 || ox[b] < 0) continue;
+        const double w1 = push(ch, cy[a], cx[b]);
+        if (w1 == 0.0) continue;
+        add(negative(ch, cy[a], cx[b]) ? w1 : 0.0, w1, wsum + (size_t)ch * 75 + oy[a] * 5 + ox[b]);
+      }
+}
+
+// M[m] = the workgroup's maximum of mx[m] (any order gives the same); every thread calls it: it holds a barrier
+__device__ inline void block_max2(double mx[2], double (&s_max)[2][4], int tid, double M[2]) {
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    for (int d = 32; d >= 1; d >>= 1) mx[m] = fmax(mx[m], __shfl_xor(mx[m], d));
+    if ((tid & 63) == 0) s_max[m][tid >> 6] = mx[m];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int m = 0; m < 2; ++m) M[m] = fmax(fmax(s_max[m][0], s_max[m][1]), fmax(s_max[m][2], s_max[m][3]));
+}
+
+// the byte of the candidate of threshold index t: selected when its score is not 0 and |score| > tau M (attack.py: TAUS)
+__device__ inline uint8_t candidate_byte(double s, double M, int t, uint8_t up, uint8_t dn, uint8_t keep) {
+  constexpr double kTau[4] = {0.0, 0.125, 0.25, 0.5};
+  return (s != 0.0 && fabs(s) > kTau[t] * M) ? (s > 0.0 ? up : dn) : keep;
+}
+
 __global__ __launch_bounds__(256) void attack_propose_kernel(
     const uint8_t *__restrict__ x0, const uint8_t *__restrict__ xcur, const int32_t *__restrict__ classes,
     const int32_t *__restrict__ worst, const int32_t *__restrict__ active, const uint64_t *__restrict__ stem,
@@ -100,62 +194,21 @@ __global__ __launch_bounds__(256) void attack_propose_kernel(
   __syncthreads();
   // ---- flip gains: thread = stem row (channel, pooled row) ------------------------------------------------------------------
   const uint64_t *fy = feat + (size_t)img * kFeatRows;
-  auto row1 = [&](int ch, int y) {                                   // a stem row of the forward, shifted
-    return shifted_row(y, [&](int iy) { return (uint32_t)s_bit[ch * kPool + iy]; });
-  };
+  auto row = [&](int ch, int y) { return (uint32_t)s_bit[ch * kPool + y]; };                                     // the forward's stem rows ..
+  auto old = [&](int, int fc, int oy, int ox, uint32_t) { return (int)((fy[fc * kSide + oy] >> ox) & 1ull); };   // .. and its feature planes
   for (int r = tid; r < kStemRows; r += 256) {
     const int ch = r / kPool, py = r - kPool * ch;
     const uint64_t T1 = table_word(t1, ch), T2 = table_word(t2, ch);
     const double sgn = bn_scale[ch] >= 0.0 ? 1.0 : -1.0;
     uint32_t neg = 0;
     for (int px = 0; px < kPool; ++px) {
-      double g = 0.0;
+      double g = 0.0, wt = 0.0;
       if ((s_un[r] >> px) & 1u) {
-        // The 21 features of va_block.h's reach(), in its order, written out as three nests: one loop over reach(ch, py, px, t)
-        // gives the same sums but a propose step 17 % slower (profiles/va_block_refactor.txt).
-        auto term = [&](int fc, int oy, int ox, int ynew, int yold) {  // +D_f, -D_f or nothing
-          if (ynew != yold) {
-            const size_t f = (size_t)(fc * kPlane + oy * kSide + ox) * kClasses;
-            const double d = A[f + c] - A[f + j];
-            g += ynew > yold ? d : -d;
-          }
-        };
-        auto old = [&](int fc, int oy, int ox) { return (int)((fy[fc * kSide + oy] >> ox) & 1ull); };
-        for (int doy = -1; doy <= 1; ++doy) {                        // conv1: rows oy-1..oy+1, columns ox-1..ox; oy <= 9
-          const int oy = py + doy;
-          if (oy < 0 || oy >= kPool) continue;
-          const uint32_t l0 = row1(ch, oy - 1), l1 = row1(ch, oy), l2 = row1(ch, oy + 1);
-          for (int dox = 0; dox <= 1; ++dox) {
-            const int ox = px + dox;
-            const uint32_t fl = conv1_index(l0, l1, l2, ox) ^ (1u << ((1 - doy) * 2 + (1 - dox)));
-            term(ch, oy, ox, (int)((T1 >> fl) & 1ull), old(ch, oy, ox));
-          }
-        }
-        for (int doy = 0; doy <= 1; ++doy) {                         // conv2: rows oy-1..oy, columns ox-1..ox+1; ox <= 9
-          const int oy = py + doy;
-          const uint32_t l0 = row1(ch, oy - 1), l1 = row1(ch, oy);
-          for (int dox = -1; dox <= 1; ++dox) {
-            const int ox = px + dox;
-            if (ox < 0 || ox >= kPool) continue;
-            const uint32_t fl = conv2_index(l0, l1, ox) ^ (1u << ((1 - doy) * 3 + (1 - dox)));
-            term(64 + ch, oy, ox, (int)((T2 >> fl) & 1ull), old(64 + ch, oy, ox));
-          }
-        }
-        uint32_t grp[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) grp[k] = s_bit[((ch & ~7) + k) * kPool + py];
-        const uint32_t fl = conv3_index(grp, px) ^ (1u << (ch & 7));
-        for (int o = 0; o < 8; ++o) {                                // conv3: the 8 outputs of the group
-          const int fc = 128 + (ch & ~7) + o;
-          term(fc, py, px, (int)((t3w[(fc - 128) * 4 + (fl >> 6)] >> (fl & 63u)) & 1ull), old(fc, py, px));
-        }
-        const int bit = (s_bit[r] >> px) & 1;
-        term(192 + ch, py, px, 1 - bit, bit);                        // out4 carries the bit itself
-        s_wt[r * kPool + px] = -g * (bit == 0 ? 1.0 : -1.0) * sgn;
+        g = flip_gain(ch, py, px, row, old, T1, T2, t3w, A, c, j);
+        wt = stem_push(g, (s_bit[r] >> px) & 1, sgn);
         neg |= (uint32_t)(g < 0.0) << px;
-      } else {
-        s_wt[r * kPool + px] = 0.0;
       }
+      s_wt[r * kPool + px] = wt;
       if (gains) gains[(size_t)img * kStemBits + r * kPool + px] = g;
     }
     s_neg[r] = (uint16_t)neg;
@@ -163,50 +216,31 @@ __global__ __launch_bounds__(256) void attack_propose_kernel(
   __syncthreads();
   // ---- pixel scores: thread = pixels tid, tid + 256, ..; both modes and the three colour channels in registers ----------------
   double sc[4][2][3];
-  double mx[2] = {0.0, 0.0};
+  double mx[2] = {0.0, 0.0}, M[2];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int p = tid + 256 * i, y = p >> 5, x = p & 31;
-    int cy[2], oy[2], cx[2], ox[2];
-    cells_of(y, cy, oy);
-    cells_of(x, cx, ox);
+    const int p = tid + 256 * i;
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
       for (int k = 0; k < 3; ++k) sc[i][m][k] = 0.0;
-    for (int ch = 0; ch < kStemCh; ++ch)                             // ch ascending, then py, then px
+    score_terms(p >> 5, p & 31, wsum, [&](int ch, int py, int px) { return s_wt[(ch * kPool + py) * kPool + px]; },
+                [&](int ch, int py, int px) { return (s_neg[ch * kPool + py] >> px) & 1u; },
+                [&](double w0, double w1, const double *W) {
 #pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-          if (oy[a] < 0 || ox[b] < 0) continue;
-          const double w1 = s_wt[(ch * kPool + cy[a]) * kPool + cx[b]];
-          if (w1 == 0.0) continue;                                   // (a zero term changes no sum: the sums are never -0)
-          const double w0 = ((s_neg[ch * kPool + cy[a]] >> cx[b]) & 1u) ? w1 : 0.0;
-          const double *W = wsum + (size_t)ch * 75 + oy[a] * 5 + ox[b];
-#pragma unroll
-          for (int k = 0; k < 3; ++k) {
-            const double wk = W[k * 25];
-            sc[i][0][k] += w0 * wk;
-            sc[i][1][k] += w1 * wk;
-          }
-        }
+                  for (int k = 0; k < 3; ++k) {
+                    const double wk = W[k * 25];
+                    sc[i][0][k] += w0 * wk;
+                    sc[i][1][k] += w1 * wk;
+                  }
+                });
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
       for (int k = 0; k < 3; ++k) mx[m] = fmax(mx[m], fabs(sc[i][m][k]));
   }
-#pragma unroll
-  for (int m = 0; m < 2; ++m) {                                      // M = max |score| of the image and mode (any order gives the same)
-    for (int d = 32; d >= 1; d >>= 1) mx[m] = fmax(mx[m], __shfl_xor(mx[m], d));
-    if ((tid & 63) == 0) s_max[m][tid >> 6] = mx[m];
-  }
-  __syncthreads();
-  double M[2];
-#pragma unroll
-  for (int m = 0; m < 2; ++m) M[m] = fmax(fmax(s_max[m][0], s_max[m][1]), fmax(s_max[m][2], s_max[m][3]));
+  block_max2(mx, s_max, tid, M);                                     // M = max |score| of the image and mode
   // ---- candidates: index 4 mode + tau index ---------------------------------------------------------------------------------------
-  constexpr double kTau[4] = {0.0, 0.125, 0.25, 0.5};
   const uint8_t *org = x0 + (size_t)img * kImg;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -217,14 +251,9 @@ __global__ __launch_bounds__(256) void attack_propose_kernel(
       const int b0 = org[at];
       const uint8_t keep = cur[at], up = (uint8_t)min(255, b0 + levels), dn = (uint8_t)max(0, b0 - levels);
 #pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        const double s = sc[i][m][k];
+      for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const bool sel = s != 0.0 && fabs(s) > kTau[t] * M[m];
-          out[(size_t)(4 * m + t) * kImg + at] = sel ? (s > 0.0 ? up : dn) : keep;
-        }
-      }
+        for (int t = 0; t < 4; ++t) out[(size_t)(4 * m + t) * kImg + at] = candidate_byte(sc[i][m][k], M[m], t, up, dn, keep);
     }
   }
 }
@@ -371,7 +400,7 @@ __global__ __launch_bounds__(256, 2) void attack_patch_kernel(
     PatchRec *__restrict__ map, uint8_t *__restrict__ fills, long long first_task, long long n_tasks) {
   __shared__ uint64_t s_lo[kStemRows], s_un[kStemRows];
   __shared__ uint64_t cur_lo[256], cur_un[256], best_lo[256], best_un[256];
-  __shared__ double win[2][3][kFieldPixels][kFieldPixels];
+  __shared__ PatchWindow win;
   __shared__ double s_wt[kStemCh][kFieldCells][kFieldCells];         // the push of every touched cell in mode 1
   __shared__ uint16_t s_mov[256], s_neg[256];                        // per touched row: the movable bits, those with g < 0 (bit = cell column of the span)
   __shared__ uint8_t s_fill[kFill], s_cand[kCand][kFill];
@@ -382,157 +411,65 @@ __global__ __launch_bounds__(256, 2) void attack_patch_kernel(
   __shared__ int j_s, unk_s, unk_pub_s, mov_s;
   const long long task = first_task + blockIdx.x;
   if (task >= n_tasks) return;                                       // (whole workgroups)
-  const int P = g.py * g.px, img = (int)(task / P), pos = (int)(task - (long long)img * P), tid = threadIdx.x;
-  const int y0 = (pos / g.px) * g.stride, x0 = (pos % g.px) * g.stride, nbytes = 3 * g.h * g.w;
-  const FieldSpan fr = field_span(y0, g.h), fq = field_span(x0, g.w);
-  const bool touched = fr.count > 0 && fq.count > 0, mine = touched && tid < 64 * fr.count;
+  const PatchPos p = patch_pos(task, g);
+  const FieldSpan fr = p.fr, fq = p.fq;
+  const int img = p.img, tid = threadIdx.x, nbytes = 3 * g.h * g.w;
+  const bool mine = p.touched() && tid < 64 * fr.count;
   const int ch = tid & 63, cy = tid >> 6, r = ch * kPool + fr.first + cy;   // (of the threads that own a row)
   const int c = classes[img];
   const bool valid = c >= 0 && c < kClasses;
-  const int wr_n = 3 * fr.count + 2, wq_n = 3 * fq.count + 2;        // <= kFieldPixels
+  const int by = p.y0 + tid / (3 * g.w), bx = p.x0 + (tid / 3) % g.w;       // (of the threads that own a byte of the patch)
   int b0 = 0;                                                        // the clean byte of this thread's byte of the patch
-  if (tid < nbytes) b0 = x[(size_t)img * kImg + ((y0 + tid / (3 * g.w)) * 32 + x0 + (tid / 3) % g.w) * 3 + tid % 3];
+  if (tid < nbytes) b0 = x[(size_t)img * kImg + (by * 32 + bx) * 3 + tid % 3];
   if (tid < kFill) s_fill[tid] = (uint8_t)b0;
-  for (int q = tid; q < kStemRows; q += 256) {
-    const uint64_t l = slo[(size_t)img * kStemRows + q];
-    s_lo[q] = l;
-    s_un[q] = (l ^ shi[(size_t)img * kStemRows + q]) & 0x3FFull;
-  }
+  load_stem_planes(s_lo, s_un, slo, shi, img, tid);
   if (tid < 2 * kClasses * 4) (&part[0][0])[tid] = 0.0;
   if (tid == 0) unk_s = mov_s = 0;
 
-  // the pixels of the fields that meet the patch as centres and radii: the box of the position, or a fill at radius 0
-  auto load_window = [&](bool box, const uint8_t *fill) {
-    if (touched)
-      for (int i = tid; i < 3 * wr_n * wq_n; i += 256) {
-        const int k = i % 3, lq = (i / 3) % wq_n, lr = i / (3 * wq_n), ir = 3 * fr.first - 1 + lr, iq = 3 * fq.first - 1 + lq;   // ir, iq <= 30
-        double centre = 0.0, radius = 0.0;                           // the top / left padding: zero in normalised space
-        if (ir >= 0 && iq >= 0) {
-          const int b = x[(size_t)img * kImg + (ir * 32 + iq) * 3 + k];
-          const bool in = ir >= y0 && ir < y0 + g.h && iq >= x0 && iq < x0 + g.w;
-          int bl = b, bh = b;
-          if (in && box) {
-            bl = b - g.amp > 0 ? b - g.amp : 0;
-            bh = b + g.amp < 255 ? b + g.amp : 255;
-          } else if (in) {
-            bl = bh = fill[((ir - y0) * g.w + (iq - x0)) * 3 + k];
-          }
-          pixel_interval((double)bl, (double)bh, nm, k, centre, radius);
-        }
-        win[0][k][lr][lq] = centre;
-        win[1][k][lr][lq] = radius;
-      }
-  };
-  // lb_j = c0_c - c0_j + ((S_j + dS_j) + (U_j + dU_j)) from the waves' partial sums: thread 0, between two barriers
-  auto combine = [&]() {
+  // the margin of what the planes hold, from the waves' partial sums: thread 0, between two barriers
+  auto margin = [&]() {
     if (tid == 0) {
-      double best = valid ? INFINITY : -INFINITY;
-      int best_j = -1;
-      for (int j = 0; j < kClasses && valid; ++j) {
-        if (j == c) continue;
-        const double cert = sums[(size_t)img * kClasses + j] + (((part[0][j] + part[1][j]) + part[2][j]) + part[3][j]);
-        const double unk = sums_un[(size_t)img * kClasses + j] + (((part[0][kClasses + j] + part[1][kClasses + j]) + part[2][kClasses + j]) + part[3][kClasses + j]);
-        const double lb = c0[c] - c0[j] + (cert + unk);
-        if (lb < best) {
-          best = lb;
-          best_j = j;
-        }
-      }
-      m_s = best;
-      j_s = best_j;
+      patch_margin(part, sums, sums_un, c0, img, c, m_s, j_s);
       unk_pub_s = unk_s;
       unk_s = 0;
     }
   };
+  auto span_bits = [&](uint64_t word) { return __popcll((word >> fq.first) & ((1ull << fq.count) - 1ull)); };
 
   // ---- the movable bits: the bits that the box of this position leaves unknown; the clean margin ------------------------------------
-  load_window(true, nullptr);
+  load_patch_window(win, x, nm, p, g, nullptr, tid);
   __syncthreads();
   if (mine) {
-    double wr[27];
-#pragma unroll
-    for (int i = 0; i < 27; ++i) wr[i] = (double)w[ch * 27 + i];
-    const double b = (double)bias[ch], sc = bn[ch], sh = bn[64 + ch], sl = slack[ch];
     uint32_t mov = 0;
-#pragma unroll 1
-    for (int cx = 0; cx < fq.count; ++cx) {
-      // (the included text declares its own loop variables c and r, which shadow the class c and the plane row r inside it)
-#define STEM_AT(k, c, r, q) win[k][c][3 * cy + (r)][3 * cx + (q)]
-#include "certify_stem_cell.inc"
-#undef STEM_AT
-      mov |= (uint32_t)(lo_bit != hi_bit) << cx;
-    }
+    stem_row_pass(win, ch, cy, fq.count, w, bias, bn, slack, [&](int cx, bool lo_bit, bool hi_bit) { mov |= (uint32_t)(lo_bit != hi_bit) << cx; });
     s_mov[tid] = (uint16_t)mov;
     cur_lo[tid] = s_lo[r];
     cur_un[tid] = s_un[r];
-    const int k0 = __popcll((s_un[r] >> fq.first) & ((1ull << fq.count) - 1ull));   // round 0: the clean cells of the span within the slack
+    const int k0 = span_bits(s_un[r]);                               // round 0: the clean cells of the span within the slack
     if (k0) atomicAdd(&unk_s, k0);                                   // (integers: any order gives the same sum)
     if (mov) atomicOr(&mov_s, 1);
   }
   __syncthreads();
-  combine();
+  margin();
   __syncthreads();
   double m_cur = m_s;
   int j_cur = j_s, kept_round = 0, kept_unk = unk_pub_s;
-  const bool search = valid && touched && mov_s != 0 && !(m_cur < -min_margin);   // (uniform over the workgroup)
+  const bool search = valid && p.touched() && mov_s != 0 && !(m_cur < -min_margin);   // (uniform over the workgroup)
 
   // the predicted margin of a fill: the touched cells again at radius 0, the features they reach against the clean feature
   // planes, the sums in certify_patch_kernel's order.  Leaves the fill's rows in the working planes.
   auto evaluate = [&](const uint8_t *fill, double &m_out, int &j_out, int &unk_out) {
-    load_window(false, fill);
+    load_patch_window(win, x, nm, p, g, fill, tid);
     __syncthreads();
     if (mine) {
-      double wr[27];
-#pragma unroll
-      for (int i = 0; i < 27; ++i) wr[i] = (double)w[ch * 27 + i];
-      const double b = (double)bias[ch], sc = bn[ch], sh = bn[64 + ch], sl = slack[ch];
-      uint64_t lo_w = s_lo[r], un_w = s_un[r];
-      int unk = 0;
-#pragma unroll 1
-      for (int cx = 0; cx < fq.count; ++cx) {
-#define STEM_AT(k, c, r, q) win[k][c][3 * cy + (r)][3 * cx + (q)]
-#include "certify_stem_cell.inc"
-#undef STEM_AT
-        const int px = fq.first + cx;
-        lo_w = (lo_w & ~(1ull << px)) | ((uint64_t)lo_bit << px);
-        un_w = (un_w & ~(1ull << px)) | ((uint64_t)(lo_bit != hi_bit) << px);
-        unk += lo_bit != hi_bit;
-      }
-      s_lo[r] = lo_w;
-      s_un[r] = un_w;
+      rewrite_stem_row(s_lo, s_un, r, win, ch, cy, fq, w, bias, bn, slack);
+      const int unk = span_bits(s_un[r]);
       if (unk) atomicAdd(&unk_s, unk);
     }
     __syncthreads();
-    double acc[2 * kClasses];                                        // [j]: the certain part, [10 + j]: the unknown part
-#pragma unroll
-    for (int j = 0; j < 2 * kClasses; ++j) acc[j] = 0.0;
-    for (int kind = 0; kind < 4; ++kind) {
-      const FeatRect rc = reached_rect(kind, fr, fq);
-      for (int e = tid; e < 64 * rc.nr * rc.nc; e += 256) {
-        const int fch = e & 63, cell = e >> 6, oy = rc.r0 + cell / rc.nc, ox = rc.c0 + cell % rc.nc, fc = 64 * kind + fch;
-        bool lo, hi;
-        feature3(s_lo, s_un, kind, fch, oy, ox, t1, t2, t3w, lo, hi);
-        const size_t row = (size_t)img * kFeatRows + fc * kSide + oy;
-        const bool clo = (ylo[row] >> ox) & 1ull, chi = (yhi[row] >> ox) & 1ull;
-        if (lo == clo && hi == chi) continue;
-        const double *af = A + (size_t)(fc * kPlane + oy * kSide + ox) * kClasses;
-        const double ac = af[c];
-#pragma unroll
-        for (int j = 0; j < kClasses; ++j) {
-          const double d = ac - af[j], m = fmin(0.0, d);
-          acc[j] += (lo ? d : 0.0) - (clo ? d : 0.0);
-          acc[kClasses + j] += ((hi && !lo) ? m : 0.0) - ((chi && !clo) ? m : 0.0);
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 2 * kClasses; ++j) {
-      double v = acc[j];
-      for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-      if ((tid & 63) == 0) part[tid >> 6][j] = v;
-    }
+    reached_sums(s_lo, s_un, p, c, true, ylo, yhi, t1, t2, t3w, A, part, tid);
     __syncthreads();
-    combine();
+    margin();
     __syncthreads();
     m_out = m_s;
     j_out = j_s;
@@ -541,80 +478,43 @@ __global__ __launch_bounds__(256, 2) void attack_patch_kernel(
 
   for (int rnd = 1; search && rnd <= rounds; ++rnd) {
     // (here the working planes hold the current fill's rows)
+    const uint8_t up = (uint8_t)min(255, b0 + g.amp), dn = (uint8_t)max(0, b0 - g.amp);
     if (g.h == 1 && g.w == 1 && rnd == 1) {                          // a 1 x 1 patch has three bytes: its eight corners
-      if (tid < 3) {
-        const uint8_t up = (uint8_t)min(255, b0 + g.amp), dn = (uint8_t)max(0, b0 - g.amp);
+      if (tid < 3)
 #pragma unroll
         for (int k = 0; k < kCand; ++k) s_cand[k][tid] = ((k >> tid) & 1) ? up : dn;
-      }
     } else {
-      // ---- flip gains and pushes of the movable bits, on the current planes: the terms and their order are attack_propose_kernel's
+      // ---- flip gains and pushes of the movable bits, on the current planes (known bits); the old feature bit is the table's
       if (mine) {
         const int py = fr.first + cy;
-        auto row1 = [&](int c2, int y) {                             // a stem row of the current planes (known bits), shifted
-          return shifted_row(y, [&](int iy) { return (uint32_t)(s_lo[c2 * kPool + iy] & 0x3FFull); });
-        };
         const uint64_t T1 = table_word(t1, ch), T2 = table_word(t2, ch);
+        auto row = [&](int c2, int y) { return (uint32_t)(s_lo[c2 * kPool + y] & 0x3FFull); };
+        auto old = [&](int kind, int fc, int, int, uint32_t at) {
+          return (int)(((kind == 0 ? T1 : kind == 1 ? T2 : t3w[(fc - 128) * 4 + (at >> 6)]) >> (at & 63u)) & 1ull);
+        };
         const double sgn = bn[ch] >= 0.0 ? 1.0 : -1.0;
-        const uint32_t bits = (uint32_t)(s_lo[r] & 0x3FFull), mov = s_mov[tid];
+        const uint32_t mov = s_mov[tid];
         uint32_t neg = 0;
         for (int cx = 0; cx < fq.count; ++cx) {
           const int px = fq.first + cx;
-          double gsum = 0.0, wt = 0.0;
+          double wt = 0.0;
           if ((mov >> cx) & 1u) {
-            auto term = [&](int fc, int oy, int ox, int ynew, int yold) {  // +D_f, -D_f or nothing
-              if (ynew != yold) {
-                const size_t f = (size_t)(fc * kPlane + oy * kSide + ox) * kClasses;
-                const double d = A[f + c] - A[f + j_cur];
-                gsum += ynew > yold ? d : -d;
-              }
-            };
-            for (int doy = -1; doy <= 1; ++doy) {                    // conv1: rows oy-1..oy+1, columns ox-1..ox; oy <= 9
-              const int oy = py + doy;
-              if (oy < 0 || oy >= kPool) continue;
-              const uint32_t l0 = row1(ch, oy - 1), l1 = row1(ch, oy), l2 = row1(ch, oy + 1);
-              for (int dox = 0; dox <= 1; ++dox) {
-                const int ox = px + dox;
-                const uint32_t at = conv1_index(l0, l1, l2, ox), fl = at ^ (1u << ((1 - doy) * 2 + (1 - dox)));
-                term(ch, oy, ox, (int)((T1 >> fl) & 1ull), (int)((T1 >> at) & 1ull));
-              }
-            }
-            for (int doy = 0; doy <= 1; ++doy) {                     // conv2: rows oy-1..oy, columns ox-1..ox+1; ox <= 9
-              const int oy = py + doy;
-              const uint32_t l0 = row1(ch, oy - 1), l1 = row1(ch, oy);
-              for (int dox = -1; dox <= 1; ++dox) {
-                const int ox = px + dox;
-                if (ox < 0 || ox >= kPool) continue;
-                const uint32_t at = conv2_index(l0, l1, ox), fl = at ^ (1u << ((1 - doy) * 3 + (1 - dox)));
-                term(64 + ch, oy, ox, (int)((T2 >> fl) & 1ull), (int)((T2 >> at) & 1ull));
-              }
-            }
-            uint32_t grp[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) grp[k] = (uint32_t)(s_lo[((ch & ~7) + k) * kPool + py] & 0x3FFull);
-            const uint32_t at = conv3_index(grp, px), fl = at ^ (1u << (ch & 7));
-            for (int o = 0; o < 8; ++o) {                            // conv3: the 8 outputs of the group
-              const int fc = 128 + (ch & ~7) + o;
-              const uint64_t *T3 = t3w + (fc - 128) * 4;
-              term(fc, py, px, (int)((T3[fl >> 6] >> (fl & 63u)) & 1ull), (int)((T3[at >> 6] >> (at & 63u)) & 1ull));
-            }
-            const int bit = (bits >> px) & 1;
-            term(192 + ch, py, px, 1 - bit, bit);                    // out4 carries the bit itself
-            wt = -gsum * (bit == 0 ? 1.0 : -1.0) * sgn;
-            neg |= (uint32_t)(gsum < 0.0) << cx;
+            const double gain = flip_gain(ch, py, px, row, old, T1, T2, t3w, A, c, j_cur);
+            wt = stem_push(gain, (int)((s_lo[r] >> px) & 1ull), sgn);
+            neg |= (uint32_t)(gain < 0.0) << cx;
           }
           s_wt[ch][cy][cx] = wt;
         }
         s_neg[tid] = (uint16_t)neg;
       }
       __syncthreads();
-      // ---- scores of the bytes of the patch (every other byte scores 0): ch ascending, then py, then px --------------------------------
-      double sc0 = 0.0, sc1 = 0.0;
+      // ---- scores of the bytes of the patch (every other byte scores 0): ch ascending, then py, then px; the kernel's own loop
+      double sc[2] = {0.0, 0.0}, M[2];
       if (tid < nbytes) {
         const int k = tid % 3;
         int cyc[2], oyc[2], cxc[2], oxc[2];
-        cells_of(y0 + tid / (3 * g.w), cyc, oyc);
-        cells_of(x0 + (tid / 3) % g.w, cxc, oxc);
+        cells_of(by, cyc, oyc);
+        cells_of(bx, cxc, oxc);
         for (int c2 = 0; c2 < kStemCh; ++c2)
 #pragma unroll
           for (int a = 0; a < 2; ++a)
@@ -626,31 +526,28 @@ __global__ __launch_bounds__(256, 2) void attack_patch_kernel(
               if (w1 == 0.0) continue;                               // (a zero term changes no sum: the sums are never -0)
               const double w0 = ((s_neg[(ly << 6) | c2] >> lx) & 1u) ? w1 : 0.0;
               const double wk = wsum[(size_t)c2 * 75 + k * 25 + oyc[a] * 5 + oxc[b]];
-              sc0 += w0 * wk;
-              sc1 += w1 * wk;
+              sc[0] += w0 * wk;
+              sc[1] += w1 * wk;
             }
       }
-      double mx[2] = {fabs(sc0), fabs(sc1)};
+      double mx[2] = {fabs(sc[0]), fabs(sc[1])};
 #pragma unroll
       for (int m = 0; m < 2; ++m) {                                  // M = max |score| over the patch, per mode
         for (int d = 32; d >= 1; d >>= 1) mx[m] = fmax(mx[m], __shfl_xor(mx[m], d));
         if ((tid & 63) == 0) s_max[m][tid >> 6] = mx[m];
       }
       __syncthreads();
+#pragma unroll
+      for (int m = 0; m < 2; ++m) M[m] = fmax(fmax(s_max[m][0], s_max[m][1]), fmax(s_max[m][2], s_max[m][3]));
       if (tid < nbytes) {
-        constexpr double kTau[4] = {0.0, 0.125, 0.25, 0.5};
-        const uint8_t keep = s_fill[tid], up = (uint8_t)min(255, b0 + g.amp), dn = (uint8_t)max(0, b0 - g.amp);
+        const uint8_t keep = s_fill[tid];
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
-          const double s = m == 0 ? sc0 : sc1, M = fmax(fmax(s_max[m][0], s_max[m][1]), fmax(s_max[m][2], s_max[m][3]));
 #pragma unroll
-          for (int t = 0; t < 3; ++t) {
-            const bool sel = s != 0.0 && fabs(s) > kTau[t] * M;
-            s_cand[4 * m + t][tid] = sel ? (s > 0.0 ? up : dn) : keep;
-          }
+          for (int t = 0; t < 3; ++t) s_cand[4 * m + t][tid] = candidate_byte(sc[m], M[m], t, up, dn, keep);
           // the slot of tau = 1/2: the sign corner of mode 1 with a hashed half of its bytes at the opposite end
-          const uint8_t base = sc1 > 0.0 ? up : (sc1 < 0.0 ? dn : keep), other = sc1 > 0.0 ? dn : (sc1 < 0.0 ? up : keep);
-          s_cand[4 * m + 3][tid] = hash_corner((uint32_t)pos, rnd, kHashStream + 4 * m + 3, (uint32_t)tid) ? other : base;
+          const uint8_t base = sc[1] > 0.0 ? up : (sc[1] < 0.0 ? dn : keep), other = sc[1] > 0.0 ? dn : (sc[1] < 0.0 ? up : keep);
+          s_cand[4 * m + 3][tid] = hash_corner((uint32_t)p.pos, rnd, kHashStream + 4 * m + 3, (uint32_t)tid) ? other : base;
         }
       }
     }

@@ -13,9 +13,9 @@
 //   ttnet_certify_box_u8 is the same with stage 0's intervals taken from two images (a loader parameter of certify_stem_kernel).
 //   ttnet_certify_patch_u8: all positions of a patch.  Per image the clean planes and sums (the stages above on the degenerate
 //   box), then certify_patch_kernel, one workgroup per (image, position): the stem bounds of the <= 4 x 4 pooled cells whose
-//   field meets the patch (certify_stem_cell.inc, the body stage 0 runs), the features those cells reach, lb_j = clean sums + the changed
-//   features' differences, stage 2 in the workgroup (enumerate_completions, the body of certify_enum_kernel), and
-//   certify_patch_rows_kernel, which folds an image's positions into its record.
+//   field meets the patch, the features those cells reach, lb_j = clean sums + the changed features' differences -- the steps of
+//   patch_position.h, which the patch search (attack.hip) takes too --, stage 2 in the workgroup (enumerate_completions, the body
+//   of certify_enum_kernel), and certify_patch_rows_kernel, which folds an image's positions into its record.
 //
 // Everything is float64 and integer work in a fixed order: no float atomics, the same bytes on every run.
 
@@ -23,6 +23,7 @@
 
 #include "certify_lookup.h"
 #include "partition.h"
+#include "patch_position.h"
 #include "ttnet_common.h"
 #include "va_block.h"
 
@@ -486,14 +487,11 @@ struct PatchRow {       // one image's record, 32 bytes
 static_assert(sizeof(MapRec) == 16 && sizeof(PatchRow) == 32, "record layouts of include/ttnet.h");
 
 
-// One workgroup per (image, position); task = first_task + blockIdx.x = image * P + position.
-//   1. the clean planes of the image into LDS; the pixels of the fields that meet the patch as centres and radii (those of
-//      the patch from [max(0, b - amp), min(255, b + amp)], the others exact): at most 14 x 14 x 3
-//   2. thread (channel, cell row) recomputes that row's cells (certify_stem_cell.inc) and rewrites its word of the planes
-//   3. every feature of the four rectangles those cells reach is looked up on the new planes; where it differs from the clean
-//      feature planes, its contribution changes: thread t sums the differences of the features t, t + 256, .. of a branch
-//      (branches in order), the 64 lanes of a wave meet by shuffles (xor 32, 16, .., 1), the four waves are added in order
-//   4. lb_j = c0_c - c0_j + ((clean certain sum_j + its change) + (clean unknown sum_j + its change)); stage 2 in the workgroup
+// One workgroup per (image, position); task = first_task + blockIdx.x = image * P + position.  The steps are patch_position.h's:
+//   1. the clean planes of the image into LDS; the window of the position's box (load_patch_window): at most 14 x 14 x 3
+//   2. thread (channel, cell row) recomputes that row's cells and rewrites its words of the planes (rewrite_stem_row)
+//   3. the differences of the features those cells reach against the clean feature planes (reached_sums)
+//   4. lb_j from the clean sums and their changes (patch_margin); stage 2 in the workgroup
 __global__ __launch_bounds__(256, 2) void certify_patch_kernel(
     const uint8_t *__restrict__ x, CertifyNorm nm, const float *__restrict__ w, const float *__restrict__ bias,
     const double *__restrict__ bn, const double *__restrict__ slack, const uint64_t *__restrict__ slo, const uint64_t *__restrict__ shi,
@@ -502,113 +500,35 @@ __global__ __launch_bounds__(256, 2) void certify_patch_kernel(
     const double *__restrict__ sums, const double *__restrict__ sums_un, const Row *__restrict__ clean_rows, PatchGeom g, int enum_bits,
     double min_margin, MapRec *__restrict__ map, long long first_task, long long n_tasks) {
   __shared__ uint64_t s_lo[kStemRows], s_un[kStemRows];
-  __shared__ double win[2][3][kFieldPixels][kFieldPixels];
+  __shared__ PatchWindow win;
   __shared__ double part[4][2 * kClasses];
   __shared__ double pos_sums[kClasses];
   __shared__ double lb_s;
   __shared__ int dk_s, worst_s, stage_s;
   const long long task = first_task + blockIdx.x;
   if (task >= n_tasks) return;                                       // (whole workgroups)
-  const int P = g.py * g.px, img = (int)(task / P), pos = (int)(task - (long long)img * P), tid = threadIdx.x;
-  const int y0 = (pos / g.px) * g.stride, x0 = (pos % g.px) * g.stride;
-  const FieldSpan fr = field_span(y0, g.h), fq = field_span(x0, g.w);
-  const bool touched = fr.count > 0 && fq.count > 0;
+  const PatchPos p = patch_pos(task, g);
+  const int img = p.img, tid = threadIdx.x;
   const int c = classes[img];
   const bool valid = c >= 0 && c < kClasses;
-  for (int r = tid; r < kStemRows; r += 256) {
-    const uint64_t l = slo[(size_t)img * kStemRows + r];
-    s_lo[r] = l;
-    s_un[r] = (l ^ shi[(size_t)img * kStemRows + r]) & 0x3FFull;
-  }
+  load_stem_planes(s_lo, s_un, slo, shi, img, tid);
   if (tid == 0) dk_s = 0;
-  const int wr_n = 3 * fr.count + 2, wq_n = 3 * fq.count + 2;        // <= kFieldPixels
-  if (touched)
-    for (int i = tid; i < 3 * wr_n * wq_n; i += 256) {
-      const int ch = i % 3, lq = (i / 3) % wq_n, lr = i / (3 * wq_n), ir = 3 * fr.first - 1 + lr, iq = 3 * fq.first - 1 + lq;   // ir, iq <= 30
-      double centre = 0.0, radius = 0.0;                             // the top / left padding: zero in normalised space
-      if (ir >= 0 && iq >= 0) {
-        const int b = x[(size_t)img * kImg + (ir * 32 + iq) * 3 + ch];
-        const bool in = ir >= y0 && ir < y0 + g.h && iq >= x0 && iq < x0 + g.w;
-        const int bl = in ? (b - g.amp > 0 ? b - g.amp : 0) : b, bh = in ? (b + g.amp < 255 ? b + g.amp : 255) : b;
-        pixel_interval((double)bl, (double)bh, nm, ch, centre, radius);
-      }
-      win[0][ch][lr][lq] = centre;
-      win[1][ch][lr][lq] = radius;
-    }
+  load_patch_window(win, x, nm, p, g, nullptr, tid);
   __syncthreads();
-  if (touched && tid < 64 * fr.count) {
-    const int ch = tid & 63, cy = tid >> 6, r = ch * kPool + fr.first + cy;   // one wave per row of cells
-    double wr[27];
-#pragma unroll
-    for (int i = 0; i < 27; ++i) wr[i] = (double)w[ch * 27 + i];
-    const double b = (double)bias[ch], sc = bn[ch], sh = bn[64 + ch], sl = slack[ch];
-    uint64_t lo_w = s_lo[r], un_w = s_un[r];
-    const int before = __popcll(un_w);
-#pragma unroll 1
-    for (int cx = 0; cx < fq.count; ++cx) {
-      // (the included text declares its own loop variables c and r, which shadow the class c and the plane row r inside it:
-      // STEM_AT's arguments are the text's, and both outer names mean what they meant again after it)
-#define STEM_AT(k, c, r, q) win[k][c][3 * cy + (r)][3 * cx + (q)]
-#include "certify_stem_cell.inc"
-#undef STEM_AT
-      const int px = fq.first + cx;
-      lo_w = (lo_w & ~(1ull << px)) | ((uint64_t)lo_bit << px);
-      un_w = (un_w & ~(1ull << px)) | ((uint64_t)(lo_bit != hi_bit) << px);
-    }
-    s_lo[r] = lo_w;
-    s_un[r] = un_w;
-    const int dk = __popcll(un_w) - before;
+  if (p.touched() && tid < 64 * p.fr.count) {
+    const int ch = tid & 63, cy = tid >> 6, r = ch * kPool + p.fr.first + cy;   // one wave per row of cells
+    const int before = __popcll(s_un[r]);
+    rewrite_stem_row(s_lo, s_un, r, win, ch, cy, p.fq, w, bias, bn, slack);
+    const int dk = __popcll(s_un[r]) - before;
     if (dk) atomicAdd(&dk_s, dk);                                    // (integers: any order gives the same sum)
   }
   __syncthreads();
-  double acc[2 * kClasses];                                          // [j]: the certain part, [10 + j]: the unknown part
-#pragma unroll
-  for (int j = 0; j < 2 * kClasses; ++j) acc[j] = 0.0;
-  if (touched && valid)
-    for (int kind = 0; kind < 4; ++kind) {
-      const FeatRect rc = reached_rect(kind, fr, fq);
-      for (int e = tid; e < 64 * rc.nr * rc.nc; e += 256) {
-        const int ch = e & 63, cell = e >> 6, oy = rc.r0 + cell / rc.nc, ox = rc.c0 + cell % rc.nc, fc = 64 * kind + ch;
-        bool lo, hi;
-        feature3(s_lo, s_un, kind, ch, oy, ox, t1, t2, t3w, lo, hi);
-        const size_t row = (size_t)img * kFeatRows + fc * kSide + oy;
-        const bool clo = (ylo[row] >> ox) & 1ull, chi = (yhi[row] >> ox) & 1ull;
-        if (lo == clo && hi == chi) continue;
-        const double *af = A + (size_t)(fc * kPlane + oy * kSide + ox) * kClasses;
-        const double ac = af[c];
-#pragma unroll
-        for (int j = 0; j < kClasses; ++j) {
-          const double d = ac - af[j], m = fmin(0.0, d);
-          acc[j] += (lo ? d : 0.0) - (clo ? d : 0.0);
-          acc[kClasses + j] += ((hi && !lo) ? m : 0.0) - ((chi && !clo) ? m : 0.0);
-        }
-      }
-    }
-#pragma unroll
-  for (int j = 0; j < 2 * kClasses; ++j) {
-    double v = acc[j];
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    if ((tid & 63) == 0) part[tid >> 6][j] = v;
-  }
+  reached_sums(s_lo, s_un, p, c, p.touched() && valid, ylo, yhi, t1, t2, t3w, A, part, tid);
   __syncthreads();
   const int k = clean_rows[img].unknown_stem + dk_s;
   if (tid == 0) {
-    double best = valid ? INFINITY : -INFINITY;
-    int best_j = -1;
-    for (int j = 0; j < kClasses && valid; ++j) {
-      const double cert = sums[(size_t)img * kClasses + j] + (((part[0][j] + part[1][j]) + part[2][j]) + part[3][j]);
-      const double unk = sums_un[(size_t)img * kClasses + j] + (((part[0][kClasses + j] + part[1][kClasses + j]) + part[2][kClasses + j]) + part[3][kClasses + j]);
-      pos_sums[j] = cert;
-      if (j == c) continue;
-      const double lb = c0[c] - c0[j] + (cert + unk);
-      if (lb < best) {
-        best = lb;
-        best_j = j;
-      }
-    }
-    lb_s = best;
-    worst_s = best_j;
-    stage_s = (valid && best > min_margin) ? 1 : 0;
+    patch_margin(part, sums, sums_un, c0, img, c, lb_s, worst_s, pos_sums);
+    stage_s = (valid && lb_s > min_margin) ? 1 : 0;
   }
   __syncthreads();
   double lb = lb_s;
